@@ -20,11 +20,16 @@ Besides `value` (the contract: t = 0 frames, timed region of K steps) the line c
   other_mesh            the same workload on the other stand-in mesh (N = 1 only)
 """
 import argparse
+import atexit
+import ctypes
 import hashlib
 import json
 import re
 import os
+import shutil
+import subprocess
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -70,7 +75,15 @@ def parse_args(argv=None):
                          "launches of one; one gather per batch).  0 = automatic: 1 on a single GPU (the reference's frame-by-frame loop on 4 frame slots), up to 8 "
                          "when the frame is sharded over N > 1 GPUs (a 1/N shard of ONE frame is eight launches at their latency floors)")
     ap.add_argument("--loopback", action="store_true", help="--host multi only: N LOGICAL devices on cuda:0, shards moved by device copies instead of RCCL (rehearsal on one GPU)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned (rank 0's frame) to DIR as float32 .npy files, at most 64 MB "
+                         "(see dump_outputs); the inputs are fixed, so two builds can be compared output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.host == "multi" and args.gpus > 1:
+        ap.error("--dump-outputs: --host multi keeps its frames on the device (host_copy 0); use --host ranks")
+    return args
 
 
 ARGS = parse_args() if __name__ == "__main__" else None
@@ -85,14 +98,6 @@ if ARGS is not None and ARGS.gpus > 1 and "WORLD_SIZE" not in os.environ and ARG
         rank_cmd = shlex.split(os.environ["RT_BENCH_RANK_CMD"])
     sys.exit(spawn_ranks(ARGS.gpus, rank_cmd))
 
-# A 1/N frame shard is latency-bound (a lone 1/8 shard of cfg3 takes 0.45 ms, 0.16 ms of it the slowest rays of each traversal
-# launch), so a sharded run keeps more frames in flight and gives each of their streams its own hardware queue (HIP maps
-# streams onto 4 by default; read at HIP start-up).  Measured on one GPU (tools/pipeline_cost.py, profiles/r02_shard_ceiling.txt),
-# rank 0's shard of an 8-way split: 0.128 ms per frame with 4 slots, 0.087-0.088 with 16 slots on 16 queues
-# (= 6.2 x the whole frame's 0.541 ms; 4-way: 0.180 / 0.158); a whole frame gains nothing from more than 4, so a single-GPU run keeps the defaults.
-if int(os.environ.get("WORLD_SIZE", "1")) > 1 or (ARGS is not None and ARGS.gpus > 1):
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
-
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
@@ -102,6 +107,7 @@ from vulkan_raytracing_amd import RtContext, host, tiling, workloads  # noqa: E4
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy peak)
 RAY_BYTES, HIT_BYTES = 32, 20
 ANIM_DT = 1.0 / 60.0    # fixed time step of the animated leg (the reference uses the wall clock, src/main.cpp:2798-2800)
+DUMP_MAX_BYTES = 60 << 20   # --dump-outputs: the frame sample stays under 64 MB with the row list and the .npy headers
 
 
 def mark(msg):
@@ -115,6 +121,54 @@ def kernels_sha16():
     for f in ("kernels.hip", "kernels_beam.inc", "kernels_tile.inc", "rt_api.cpp", "bvh_gpu.hip", "bvh_build.cpp", "rt_device.h", "rt_kernels.h"):
         h.update(open(os.path.join(ROOT, "vulkan_raytracing_amd", "csrc", f), "rb").read())
     return h.hexdigest()[:16]
+
+
+def frame_rgba32f(frame):
+    """rank 0's frame as RGBA binary32 on the host: 8-bit frames (--gather-format rgba8) scaled to [0, 1], assembled RGB frames
+    given their constant alpha"""
+    img = frame.cpu().numpy()
+    if img.dtype == np.uint8:
+        img = img.astype(np.float32) / np.float32(255.0)
+    if img.shape[-1] == 3:
+        img = np.concatenate([img, np.ones(img.shape[:2] + (1,), np.float32)], axis=-1)
+    return img
+
+
+def dump_outputs(out_dir, img):
+    """--dump-outputs: frame.npy = the last timed step's frame (H x W x 4 float32, row 0 at the top), or every k-th row of it when
+    the whole frame would exceed DUMP_MAX_BYTES (cfg4); frame_rows.npy = the frame rows it holds"""
+    os.makedirs(out_dir, exist_ok=True)
+    k = -(-img.nbytes // DUMP_MAX_BYTES)
+    rows = np.arange(0, img.shape[0], k)
+    np.save(os.path.join(out_dir, "frame.npy"), np.ascontiguousarray(img[rows], dtype=np.float32))
+    np.save(os.path.join(out_dir, "frame_rows.npy"), rows.astype(np.float64))
+
+
+_SCRATCH = None
+
+
+def scratch_dir():
+    """a private directory outside the tree, removed at exit, for what this process must write when the checkout is read-only"""
+    global _SCRATCH
+    if _SCRATCH is None:
+        _SCRATCH = tempfile.mkdtemp(prefix="rt_bench_")
+        atexit.register(shutil.rmtree, _SCRATCH, True)
+    return _SCRATCH
+
+
+def resources_dir():
+    """resources/ when its generated/ cache of stand-in meshes can be written; in a read-only checkout a mirror in scratch_dir()
+    whose entries link to the tree's files and whose generated/ is its own (host.armadillo_path writes the meshes there)"""
+    res = os.path.join(ROOT, "resources")
+    gen = os.path.join(res, "generated")
+    if os.access(gen if os.path.isdir(gen) else res, os.W_OK):
+        return res
+    mirror = os.path.join(scratch_dir(), "resources")
+    os.makedirs(mirror, exist_ok=True)
+    for name in os.listdir(res):
+        if name != "generated":
+            os.symlink(os.path.join(res, name), os.path.join(mirror, name))
+    return mirror
 
 
 def visible_cores():
@@ -137,6 +191,13 @@ def cpu_baseline(wl, budget_s=14.0):
     whole frames of the same workload on every visible core, plus a 1-thread figure on a band of rows.  Checker code:
     used here ONLY as the reported CPU baseline, never by the product path."""
     from oracle import oracle as orc
+    odir = os.path.join(ROOT, "oracle")
+    if orc._NATIVE is None and not os.access(odir, os.W_OK):
+        # read-only checkout: oracle.lib_native() cannot build in oracle/, so the same Makefile rule builds it in scratch_dir()
+        # (the source found through VPATH) and the module takes that library as its native build
+        subprocess.check_call(["make", "-C", scratch_dir(), "-f", os.path.join(odir, "Makefile"), "VPATH=" + odir, "librt_oracle_native.so"],
+                              stdout=subprocess.DEVNULL)
+        orc._NATIVE = orc._bind(ctypes.CDLL(os.path.join(scratch_dir(), "librt_oracle_native.so")))
     S = orc.OracleScene(native=True)
     geom, inst = wl.geometry, wl.instances
     S.set_geometry(geom.verts, geom.idx, geom.ranges)
@@ -378,7 +439,7 @@ def main_multi(args):
     P = args.frames_in_flight if args.frames_in_flight > 0 else (4 if (n <= 2 or K > 1) else 16)
     if args.loopback:
         P = min(P, max(1, 16 // n))     # all logical devices share one GPU: at most 16 frame slots on it take k_tail's full grid
-    res = os.path.join(ROOT, "resources")
+    res = resources_dir()
     host.armadillo_path(res, kind=args.mesh)
     wl = workloads.make(args.workload, res, mesh=args.mesh)
     W, H = wl.width, wl.height
@@ -516,7 +577,7 @@ def main(args):
     batched = args.batch > 1 or (args.batch == 0 and n > 1 and not args.rehearse_on_one_gpu)
     P = args.frames_in_flight if args.frames_in_flight > 0 else (4 if (n <= 2 or batched) else 16)
 
-    res = os.path.join(ROOT, "resources")
+    res = resources_dir()
     if rank == 0:
         host.armadillo_path(res, kind=args.mesh)  # generate the stand-in once before the other ranks look for it
     if collective:
@@ -536,6 +597,9 @@ def main(args):
     mark("set-up frames done")
     dt = rig.timed(args.steps, args.warmup, animate=args.animate)
     mark("timed region done")
+    dumped = None
+    if args.dump_outputs and rank == 0:   # the last timed step's frame, before the loops below render into its slot again
+        dumped = frame_rgba32f(rig.frames[(rig.counter - 1) % P][:H])
     st = ctx.stats()        # counters of slot 0's last frame + MEAN closest-hit launch time over all its timed frames (every P-th step)
     # the other kernels' live times: a short continuation of the same loop (same frames in flight) with events around every kernel
     k0 = rig.last_k[0]      # frames in slot 0's last pass: its counters are sums over them
@@ -821,11 +885,7 @@ def main(args):
                                                                 "whose outcome cannot change their sample (settled in k_shade)"}
         result["roofline"] = roof
         if last_frame is not None:
-            img = last_frame.cpu().numpy()
-            if img.dtype == np.uint8:   # --gather-format rgba8
-                img = img.astype(np.float32) / np.float32(255.0)
-            if img.shape[-1] == 3:   # assembled multi-rank frame: RGB + the constant alpha
-                img = np.concatenate([img, np.ones(img.shape[:2] + (1,), np.float32)], axis=-1)
+            img = frame_rgba32f(last_frame)
             with open(args.save_image, "wb") as fh:
                 fh.write(b"PF4\n%d %d\n-1.0\n" % (W, H))
                 fh.write(img[::-1].astype("<f4").tobytes())
@@ -882,6 +942,8 @@ def main(args):
             result["cpu_baseline"] = cpu_baseline(wl)
         else:
             result["cpu_baseline"] = None
+        if dumped is not None:
+            dump_outputs(args.dump_outputs, dumped)
         sys.stdout.flush()
         os.dup2(saved_stdout, 1)
         print(json.dumps(result), flush=True)

@@ -17,5 +17,4 @@ python3 -c "from vulkan_raytracing_amd import host; host.armadillo_path('resourc
 for cfg in "--frames-in-flight 1" "--frames-in-flight 4" "--frames-in-flight 6"; do
   echo "rt_headless $cfg: $(./rt_headless --width 1920 --height 1080 --frames 120 --spp 4 --bounce 3 $cfg 2>&1 | grep "ms per frame" | tail -1 | cut -c1-200)" >> gpurun_out/${TAG}_headless.log
 done
-GPU_MAX_HW_QUEUES=8 ./rt_headless --width 1920 --height 1080 --frames 120 --spp 4 --bounce 3 --frames-in-flight 6 2>&1 | grep "ms per frame" | tail -1 | cut -c1-200 | sed 's/^/rt_headless 6 slots, 8 hardware queues: /' >> gpurun_out/${TAG}_headless.log
 bash tools/pmc_ta.sh $TAG > gpurun_out/${TAG}_pmcta.log 2>&1

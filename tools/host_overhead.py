@@ -2,7 +2,7 @@
 """Host-side cost per step of bench.py's sharded loop (rank 0 of an 8-way split: 136 rows), measured on ONE GPU with a
 world-size-1 RCCL group: trace_shard + RGB slice + dist.gather + index_select, P slots in flight.  Prints the time the host
 needs to enqueue a step and the wall time per step; a step whose enqueue takes longer than the GPU needs is host-bound.
-    GPU_MAX_HW_QUEUES=16 P=16 python tools/host_overhead.py"""
+    P=16 python tools/host_overhead.py"""
 import os
 import sys
 import time

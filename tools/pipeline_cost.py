@@ -2,7 +2,7 @@
 """Frames in flight: wall time per frame with P frame slots on P streams, for rank 0's bands of an N-way split of the
 cfg3 frame — the compute side of the N-GPU scaling ceiling (whole frame time / N-way shard time), measurable on one GPU.
     N_LIST=1,2,4,8 P_LIST=1,4,8 [RT_PARAMS=name=value,...] [MESH=standin|limbs] python tools/pipeline_cost.py
-Run with GPU_MAX_HW_QUEUES=8 for P > 4 (bench.py sets it for sharded runs)."""
+P > 4 slots share HIP's hardware queues (the environment's GPU_MAX_HW_QUEUES)."""
 import json
 import os
 import sys

@@ -158,6 +158,23 @@ int rt_build_blas(rt_ctx* ctx, int mesh);
  * allocates buffers and blocks on a fence here every frame, src/main.cpp:672-696, 752-778). */
 int rt_set_instances(rt_ctx* ctx, const rt_instance* instances, int n, int update);
 
+/* createTLAS with a DEVICE instance buffer (src/main.cpp:538-793: the reference's instance buffer is device memory and the TLAS is
+ * built by the device).  d_instances = n rt_instance records (64 B each, same layout and rules as rt_set_instances) in memory of
+ * ctx's GPU, read in stream order on hip_stream (NULL = the context's stream): the library copies them into its own buffer on that
+ * stream, so the caller may overwrite its buffer with work queued on the same stream as soon as the call returns.  Everything else
+ * happens on the device, on a build stream of the context that waits for hip_stream: the instance records (w2o bit-identical to
+ * rt_set_instances'), an LBVH over the instance boxes (update = 0) or a bottom-up refit of the topology of this context's previous
+ * rt_set_instances_device build (update != 0: same n), the quantised TLAS nodes.  The call returns once a small summary of the
+ * build is back on the host (the reference waits on its fence inside createTLAS, :772-778); it does not wait for the frame in
+ * flight: records and TLAS are double-buffered exactly as for rt_set_instances.  Frames and hit records are bit-identical to
+ * those of rt_set_instances with the same records (the closest hit does not depend on the tree).
+ * 1 <= n <= 1048576.  RT_ERR_INVALID_ARGUMENT: a NULL pointer, n out of range, an unknown mesh index, trace_variant != 0, an
+ * update whose previous build came from rt_set_instances / rt_set_batch (and an rt_set_instances update after this call);
+ * RT_ERR_NOT_READY: an instance of a mesh whose BLAS is not built.  After an error the context's TLAS is invalid until the next
+ * successful call.  rt_set_instance_types re-issues the records from the library's copy; frame batches (rt_set_batch) take host
+ * records only, and a later rt_set_batch or rt_set_instances replaces the device instances. */
+int rt_set_instances_device(rt_ctx* ctx, const void* d_instances, int n, int update, void* hip_stream);
+
 /* ---- MTL materials and a per-instance type table -------------------------------------------------
  * The reference's loader parses Kd/Ks/Ns/Ni/illum (include/tiny_obj_loader.h:565 GetMaterials) and its renderer ignores
  * them: src/shader.rgen:51-55 hard-codes ka (.1,.3,.1), kd (.2,1,.2), ks .8, exponent 100, index of refraction 1.52, and

@@ -38,7 +38,7 @@ class RtStats(C.Structure):
         return self.rays_primary + self.rays_secondary + self.rays_shadow
 
 
-EXPORTS = ["rt_create", "rt_create_frame_slot", "rt_destroy", "rt_upload_geometry", "rt_build_blas", "rt_set_instances", "rt_set_materials", "rt_set_instance_types", "rt_set_uniforms", "rt_set_skybox",
+EXPORTS = ["rt_create", "rt_create_frame_slot", "rt_destroy", "rt_upload_geometry", "rt_build_blas", "rt_set_instances", "rt_set_instances_device", "rt_set_materials", "rt_set_instance_types", "rt_set_uniforms", "rt_set_skybox",
            "rt_trace", "rt_trace_async", "rt_trace_wait", "rt_trace_shard", "rt_set_batch", "rt_trace_shard_batch", "rt_assemble_shards", "rt_shard_rows", "rt_synchronize", "rt_get_stats", "rt_set_timing", "rt_intersect",
            "rt_trace_counting", "rt_set_param", "rt_debug_check_builders", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
 
@@ -58,6 +58,7 @@ def lib(variant=None):
         L.rt_upload_geometry.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_int]
         L.rt_build_blas.argtypes = [vp, C.c_int]
         L.rt_set_instances.argtypes = [vp, vp, C.c_int, C.c_int]
+        L.rt_set_instances_device.argtypes = [vp, vp, C.c_int, C.c_int, vp]
         L.rt_set_materials.argtypes = [vp, vp, C.c_int, vp, C.c_size_t]
         L.rt_set_instance_types.argtypes = [vp, vp, C.c_int]
         L.rt_set_uniforms.argtypes = [vp, vp]
@@ -112,6 +113,7 @@ class RtContext:
         if rc:
             raise RtError(rc, "rt_create_frame_slot" if _parent is not None else "rt_create", self.L.rt_last_error(None).decode())
         self.h = h
+        self.device = _parent.device if _parent is not None else device
 
     def frame_slot(self):
         """rt_create_frame_slot: a context for one more frame in flight that shares this context's scene (geometry, BLAS,
@@ -154,6 +156,31 @@ class RtContext:
     def set_instances(self, instances, update=False):
         inst = np.ascontiguousarray(instances, INSTANCE_DTYPE)
         self._chk(self.L.rt_set_instances(self.h, _p(inst), len(inst), int(update)), "rt_set_instances")
+
+    def set_instances_device(self, t, update=False, stream=None):
+        """rt_set_instances_device: the instance records are a contiguous torch tensor on this context's GPU holding n x 64 bytes
+        (uint8 (n, 64), or any dtype whose byte size is a multiple of 64), read in the order of `stream` (default: the current
+        torch stream of that device).  The TLAS is built (update=False) or refitted (update=True) on the GPU."""
+        import torch
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("set_instances_device takes a torch tensor, got %s" % type(t).__name__)
+        if t.device.type != "cuda" or t.device.index != self.device:
+            raise ValueError("instance tensor must live on cuda:%d (the context's GPU), not %s" % (self.device, t.device))
+        if not t.is_contiguous():
+            raise ValueError("instance tensor must be contiguous")
+        nbytes = t.numel() * t.element_size()
+        if t.dtype == torch.uint8 and t.dim() == 2 and t.shape[1] != INSTANCE_DTYPE.itemsize:
+            raise ValueError("a uint8 instance tensor has shape (n, 64), got %s" % (tuple(t.shape),))
+        if nbytes == 0 or nbytes % INSTANCE_DTYPE.itemsize:
+            raise ValueError("instance tensor must hold n x 64 bytes (n >= 1), got %d bytes" % nbytes)
+        if stream is None:
+            stream = torch.cuda.current_stream(t.device)
+        if stream.cuda_stream == 0:
+            # torch's default stream is the null stream, which the C ABI reads as "the context's stream" (a non-blocking stream the
+            # null stream does not order): the records must be complete before the library's copy starts
+            stream.synchronize()
+        self._chk(self.L.rt_set_instances_device(self.h, C.c_void_p(t.data_ptr()), nbytes // INSTANCE_DTYPE.itemsize, int(update),
+                                                 C.c_void_p(stream.cuda_stream)), "rt_set_instances_device")
 
     def set_materials(self, table, prim_material=None):
         """row n4: MTL material table + material id of every triangle of the index buffer; table None/empty removes it"""

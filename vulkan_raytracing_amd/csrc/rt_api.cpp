@@ -21,6 +21,7 @@
 #include "bvh_gpu.h"
 #include "rt_device.h"
 #include "rt_kernels.h"
+#include "tlas_gpu.h"
 
 using namespace rt;
 
@@ -118,7 +119,14 @@ struct Scene {
   uint32_t* d_prim_material = nullptr;
   int n_materials = 0;
   size_t n_prim_material = 0;
+
+  // per-mesh fields of the instance records, for k_inst_records (rt_set_instances_device); uploaded by link_blas
+  TlasMeshDev* d_mesh_table = nullptr;
 };
+
+// which call built a slot's current instances and TLAS
+enum { INST_NONE = 0, INST_HOST = 1, INST_DEVICE = 2 };
+constexpr int MAX_DEVICE_INSTANCES = 1 << 20;
 
 struct rt_ctx {
   int device = 0;
@@ -135,6 +143,13 @@ struct rt_ctx {
   BuiltBvh tlas;
   Bvh4 tlas4;
   bool tlas_valid = false;
+  int inst_source = INST_NONE;   // rt_set_instances / rt_set_batch (host records, h_inst) or rt_set_instances_device (device records, tgpu.d_rec)
+  int n_inst = 0;                // instance records of the current set (all frames of a batch)
+  // rt_set_instances_device: build stream, scratch, the LBVH topology a refit keeps, the library's copy of the records (tlas_gpu.h)
+  TlasGpu tgpu;
+  // far_possible of a device-built TLAS: the object-space test was evaluated by the device at the corners of G (tlas_gpu.hip k_tlas_far)
+  bool dev_far = true;
+  double dev_g_lo[3] = {0, 0, 0}, dev_g_hi[3] = {0, 0, 0};
   // instance records and TLAS nodes are double-buffered (parity): the records of the next frame are written while the
   // frame enqueued before still reads its own, so a per-frame TLAS update never waits for the device
   InstanceDev* d_inst[2] = {nullptr, nullptr};
@@ -499,6 +514,21 @@ int link_blas(rt_ctx* c) {
     HIP_TRY(c, hipMalloc((void**)&S->d_cover_boxes, std::max<size_t>(6, cover.size()) * sizeof(float)));
     if (!cover.empty()) HIP_TRY(c, hipMemcpy(S->d_cover_boxes, cover.data(), cover.size() * sizeof(float), hipMemcpyHostToDevice));
   }
+  {
+    std::vector<TlasMeshDev> tab(std::max<size_t>(1, S->meshes.size()));
+    for (size_t mi = 0; mi < S->meshes.size(); mi++) {
+      const Mesh& m = S->meshes[mi];
+      TlasMeshDev& t = tab[mi];
+      t.blas_root = m.root; t.blas_root4 = m.node_base4;
+      t.first_float = (uint32_t)m.range.first_float; t.first_index = (uint32_t)m.range.first_index;
+      t.cover_first = m.cover_first; t.cover_count = m.cover_count;
+      t.prim_count = m.range.prim_count; t.built = m.built ? 1u : 0u; t.levels = m.levels;
+      for (int k = 0; k < 3; k++) { t.q_lo[k] = m.q_lo[k]; t.q_scale[k] = m.q_scale[k]; t.lo[k] = m.bounds.lo[k]; t.hi[k] = m.bounds.hi[k]; }
+    }
+    if (S->d_mesh_table) { HIP_TRY(c, hipFree(S->d_mesh_table)); S->d_mesh_table = nullptr; }
+    HIP_TRY(c, hipMalloc((void**)&S->d_mesh_table, tab.size() * sizeof(TlasMeshDev)));
+    HIP_TRY(c, hipMemcpy(S->d_mesh_table, tab.data(), tab.size() * sizeof(TlasMeshDev), hipMemcpyHostToDevice));
+  }
   S->variant = c->cfg.variant;
   std::vector<WideNodeQ> wide(S->variant == 2 ? nn : 0);   // only the variant that walks them pays for them
   if (S->variant == 2 && nn) widen_bvh2(nodes.data(), nn, 0, wide.data());
@@ -630,7 +660,7 @@ SceneDev scene_dev(const rt_ctx* c) {
   s.tlas_nodes = c->tlas_node_count[c->parity];
   s.tlas_stride = c->batch_k > 1 ? c->tlas_stride[c->parity] : 0;
   s.blas_nodes = S->d_blas_nodes; s.tlas_root = (int)tlas_base(c); s.tris = S->d_tris; s.inst = c->d_inst[c->parity];
-  s.verts = S->d_verts; s.idx = S->d_idx; s.sky = S->d_sky; s.n_inst = (int)c->h_inst.size();
+  s.verts = S->d_verts; s.idx = S->d_idx; s.sky = S->d_sky; s.n_inst = c->n_inst;
   s.sky_w = S->sky_w; s.sky_h = S->sky_h;
   s.materials = S->d_materials; s.prim_material = S->d_prim_material; s.n_materials = S->n_materials;
   s.cover_boxes = S->d_cover_boxes;
@@ -645,6 +675,10 @@ int collect_stats(rt_ctx* c);
 // the TLAS bounds).  World space: against the TLAS quantisation; object space of every instance: the same points through w2o
 // against the mesh's quantisation — the device's own test (quant_far_o) evaluated at the corners of the box that holds every
 // possible origin.  False for every BASELINE workload, so their frames run the kernels without the far-ray logic.
+// A device-built TLAS (rt_set_instances_device) has no w2o on the host: the device evaluated the object-space test once per build at
+// the 8 corners of G, the TLAS's quantised bounds grown by their own extent on every side (tlas_gpu.hip k_tlas_far).  While the camera
+// is inside G the origin box below lies inside G, and the test is one slab per axis, so G's flag holds for it; with the camera outside
+// G the answer is true (conservative: such frames run the far-ray instantiations, whose results are the same).
 bool far_possible(const rt_ctx* c, const UniformsDev& u) {
   const Scene* S = c->scene;
   const double K = 0.99 * 2097152.0;
@@ -658,6 +692,11 @@ bool far_possible(const rt_ctx* c, const UniformsDev& u) {
   double smin = std::min({(double)c->tlas_q_scale[0], (double)c->tlas_q_scale[1], (double)c->tlas_q_scale[2]});
   for (int k = 0; k < 3; k++)
     if (std::max(std::fabs(c->tlas_q_lo[k] - lo[k]), std::fabs(c->tlas_q_lo[k] - hi[k])) > K * smin) return true;
+  if (c->inst_source == INST_DEVICE) {
+    for (int k = 0; k < 3; k++)
+      if (!((double)u.position[k] >= c->dev_g_lo[k] && (double)u.position[k] <= c->dev_g_hi[k])) return true;
+    return c->dev_far;
+  }
   for (const rt_instance& in : c->h_inst) {
     const Mesh& m = S->meshes[in.mesh];
     if (!m.range.prim_count) continue;
@@ -1294,6 +1333,7 @@ void rt_destroy(rt_ctx* c) {
   if (c->h_stats) hipHostFree(c->h_stats);
   for (int k = 0; k < 2; k++) { if (c->h_stage[k]) hipHostFree(c->h_stage[k]); if (c->ev_frame[k]) hipEventDestroy(c->ev_frame[k]); }
   for (int k = 0; k < 2; k++) if (c->ev_upload[k]) hipEventDestroy(c->ev_upload[k]);
+  tlas_gpu_free(c->tgpu);
   for (auto e : c->ev_pool) hipEventDestroy(e);
   if (c->stream) hipStreamDestroy(c->stream);
   Scene* S = c->scene;
@@ -1301,7 +1341,7 @@ void rt_destroy(rt_ctx* c) {
   S->slot_mask &= ~(1u << c->slot);
   size_traversal_grids(S);
   if (S->members.empty()) {   // the last context of a scene takes the shared arrays with it
-    void* sp[] = {S->d_wide, S->d_nodes4, S->d_verts, S->d_idx, S->d_blas_nodes, S->d_tris, S->d_sky, S->d_materials, S->d_prim_material, S->d_cover_boxes};
+    void* sp[] = {S->d_wide, S->d_nodes4, S->d_verts, S->d_idx, S->d_blas_nodes, S->d_tris, S->d_sky, S->d_materials, S->d_prim_material, S->d_cover_boxes, S->d_mesh_table};
     for (void* p : sp) if (p) hipFree(p);
     for (JitterTable& t : S->jitter_tables) { hipFree(t.d); hipEventDestroy(t.ready); }
     delete S;
@@ -1395,8 +1435,9 @@ static int set_instances_frames(rt_ctx* c, const rt_instance* inst, int n, int u
     if (inst[i].mesh >= S->meshes.size()) return fail(c, RT_ERR_INVALID_ARGUMENT, "instance references an unknown mesh");
     if (!S->meshes[inst[i].mesh].built) return fail(c, RT_ERR_NOT_READY, "instance references a mesh whose BLAS is not built (rt_build_blas)");
   }
-  if (update && (!c->tlas_valid || c->inst_per_frame != n))
-    return fail(c, RT_ERR_INVALID_ARGUMENT, "TLAS update needs a previous build with the same instance count");
+  if (update && (!c->tlas_valid || c->inst_per_frame != n || c->inst_source != INST_HOST))
+    return fail(c, RT_ERR_INVALID_ARGUMENT, c->inst_source == INST_DEVICE && c->tlas_valid ? "TLAS update of a TLAS built by rt_set_instances_device: build with update = 0 first"
+                                                                                          : "TLAS update needs a previous build with the same instance count");
   if (K > 1 && c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, "frame batches need trace_variant 0");
   if (!S->blas_linked) {   // (re)linking moves the shared arrays: every slot of the scene has to be idle
     int q = quiesce_scene(c); if (q) return q;
@@ -1406,6 +1447,7 @@ static int set_instances_frames(rt_ctx* c, const rt_instance* inst, int n, int u
   // has to be called again) instead of half old, half new
   c->tlas_valid = false;
   c->h_inst.assign(inst, inst + total);
+  c->n_inst = total; c->inst_source = INST_HOST;
   std::vector<InstanceDev> inst_dev(total);
   std::vector<Aabb> boxes(total);
   for (int i = 0; i < total; i++) {
@@ -1478,6 +1520,86 @@ int rt_set_batch(rt_ctx* c, int n_frames, const rt_instance* instances, int n, c
   return RT_OK;
 }
 
+// rt_set_instances with the records in device memory: the TLAS is built (LBVH) or refitted on the device (tlas_gpu.hip).  The records
+// are copied into the context's own buffer in the caller's stream order; the build runs on the context's build stream and the call
+// returns when its summary (dequantisation, depth, error and far flags) is back.  Like rt_set_instances it waits only for the frame
+// before the last: the records and the TLAS region are double-buffered by parity.  d_instances == tgpu.d_rec re-issues the kept records.
+static int set_instances_device(rt_ctx* c, const void* d_instances, int n, int update, hipStream_t src_stream) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  if (!d_instances || n <= 0) return fail(c, RT_ERR_INVALID_ARGUMENT, "no instances");
+  if (n > MAX_DEVICE_INSTANCES) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_set_instances_device takes 1.." + std::to_string(MAX_DEVICE_INSTANCES) + " instances");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, "device instances need trace_variant 0");
+  if (update && (!c->tlas_valid || c->inst_source != INST_DEVICE || c->n_inst != n))
+    return fail(c, RT_ERR_INVALID_ARGUMENT, c->inst_source == INST_HOST && c->tlas_valid ? "TLAS update of a TLAS built on the host (rt_set_instances / rt_set_batch): build with update = 0 first"
+                                                                                        : "TLAS update needs a previous rt_set_instances_device build with the same instance count");
+  HIP_TRY(c, hipSetDevice(c->device));
+  Scene* S = c->scene;
+  const int next_parity = c->parity ^ 1;
+  if (c->ev_frame_valid[next_parity]) { HIP_TRY(c, hipEventSynchronize(c->ev_frame[next_parity])); c->ev_frame_valid[next_parity] = false; }
+  if (c->upload_inflight[next_parity]) { HIP_TRY(c, hipEventSynchronize(c->ev_upload[next_parity])); c->upload_inflight[next_parity] = false; }
+  if (!S->blas_linked) {   // (re)linking moves the shared arrays: every slot of the scene has to be idle
+    int q = quiesce_scene(c); if (q) return q;
+    int r = link_blas(c); if (r) return r;
+  }
+  // the records and the TLAS region of next_parity are rewritten from here on: an error leaves the slot's TLAS invalid
+  c->tlas_valid = false;
+  c->inst_gen[next_parity]++;
+  const size_t n_nodes = n >= 2 ? (size_t)n - 1 : 1;   // known from n: no readback sizes the region
+  if (n_nodes > S->tlas_cap) {
+    if (S->members.size() > 1)
+      return fail(c, RT_ERR_INVALID_ARGUMENT, "TLAS of " + std::to_string(n_nodes) + " nodes exceeds the " + std::to_string(S->tlas_cap) +
+                                                 " a frame slot of a shared scene can hold: set the instances before creating frame slots");
+    S->tlas_cap = (uint32_t)((n_nodes + 1023) & ~(size_t)1023);
+    int r = alloc_scene_arrays(c); if (r) return r;
+  }
+  if ((size_t)n > c->cap_inst[next_parity]) {
+    if (c->d_inst[next_parity]) HIP_TRY(c, hipFree(c->d_inst[next_parity]));
+    c->d_inst[next_parity] = nullptr; c->cap_inst[next_parity] = 0;
+    HIP_TRY(c, hipMalloc((void**)&c->d_inst[next_parity], (size_t)n * sizeof(InstanceDev)));
+    c->cap_inst[next_parity] = (size_t)n;
+  }
+  const size_t base = S->n_blas_nodes + (size_t)(2 * c->slot + next_parity) * S->tlas_cap;
+  TlasBuildArgs a{};
+  a.d_src = d_instances; a.src_stream = src_stream ? src_stream : c->stream; a.n = n; a.refit = update != 0;
+  a.meshes = S->d_mesh_table; a.n_meshes = (int)S->meshes.size();
+  a.h_types = c->inst_types.data(); a.n_types = (int)std::min<size_t>(c->inst_types.size(), (size_t)n);
+  a.d_inst = c->d_inst[next_parity]; a.d_nodes = S->d_blas_nodes + base; a.node_base = (int32_t)base;
+  std::string err;
+  if (tlas_gpu_build(c->tgpu, a, err)) return fail(c, RT_ERR_DEVICE, err);
+  const TlasSummary& sm = *c->tgpu.h_sum;
+  // the host path's checks, reported by k_inst_records: the first offending instance decides, as in set_instances_frames
+  if (sm.bad_mesh != 0xFFFFFFFFu && (sm.unbuilt == 0xFFFFFFFFu || sm.bad_mesh < sm.unbuilt))
+    return fail(c, RT_ERR_INVALID_ARGUMENT, "instance references an unknown mesh");
+  if (sm.unbuilt != 0xFFFFFFFFu) return fail(c, RT_ERR_NOT_READY, "instance references a mesh whose BLAS is not built (rt_build_blas)");
+  if (getenv("RT_BUILD_TIMING")) fprintf(stderr, "[tlas_gpu] %d instances, %s, depth %d\n", n, update ? "refit" : "LBVH build", sm.depth);
+  {
+    // the traversal stack as set_instances_frames sizes it, from the depth the LBVH reports
+    const int tl = sm.depth + 1, blas_levels = sm.blas_levels;
+    const int need2 = 2 + tl + blas_levels, needw = 2 + 3 * ((tl + 1) / 2) + 3 * ((blas_levels + 1) / 2);
+    c->ovf_stride = (uint32_t)std::max<int>(STACK_OVF, (std::max(need2, needw) + 7) & ~7);
+    c->stack_need = need2 + ENTRY_WORDS + 2;
+  }
+  for (int k = 0; k < 3; k++) {
+    c->tlas_q_lo[k] = sm.q_lo[k]; c->tlas_q_scale[k] = sm.q_scale[k];
+    const double tlo = sm.q_lo[k], thi = (double)sm.q_lo[k] + 65535.0 * (double)sm.q_scale[k];
+    c->dev_g_lo[k] = tlo - (thi - tlo); c->dev_g_hi[k] = thi + (thi - tlo);   // G (far_possible), as k_tlas_far took it
+  }
+  c->dev_far = sm.far != 0;
+  c->parity = next_parity;
+  c->inst_per_frame = n; c->batch_k = 1; c->n_inst = n; c->inst_source = INST_DEVICE;
+  c->h_inst.clear();
+  c->tlas_node_count[next_parity] = (int)n_nodes; c->tlas_stride[next_parity] = 0;
+  // (the build is complete: frames on any stream find ev_upload already passed)
+  if (!c->ev_upload[next_parity]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_upload[next_parity], hipEventDisableTiming));
+  HIP_TRY(c, hipEventRecord(c->ev_upload[next_parity], c->tgpu.stream));
+  c->upload_pending = true; c->upload_inflight[next_parity] = true;
+  c->tlas_valid = true;
+  return RT_OK;
+}
+
+int rt_set_instances_device(rt_ctx* c, const void* d_instances, int n, int update, void* hip_stream) {
+  return set_instances_device(c, d_instances, n, update, (hipStream_t)hip_stream);
+}
 
 // Row n4: the MTL materials the reference's loader parses and its renderer ignores (src/shader.rgen:51-55
 // hard-codes kd, ks, 100, 1.52).  table[prim_material[g]] shades triangle g of the index buffer (g = first_index / 3 +
@@ -1524,6 +1646,8 @@ int rt_set_instance_types(rt_ctx* c, const uint32_t* types, int n) {
   if (n < 0 || (n > 0 && !types)) return fail(c, RT_ERR_INVALID_ARGUMENT, "bad rt_set_instance_types arguments");
   for (int i = 0; i < n; i++) if (types[i] > 2u) return fail(c, RT_ERR_INVALID_ARGUMENT, "instance type must be 0, 1 or 2");
   c->inst_types.assign(types, types + n);
+  if (c->tlas_valid && c->inst_source == INST_DEVICE)   // re-issue the records from the library's device copy
+    return set_instances_device(c, c->tgpu.d_rec, c->n_inst, 1, nullptr);
   if (c->tlas_valid && !c->h_inst.empty()) {   // re-issue the instance records with the new types
     std::vector<rt_instance> keep = c->h_inst;
     return rt_set_instances(c, keep.data(), (int)keep.size(), 1);
@@ -1589,9 +1713,15 @@ int rt_set_param(rt_ctx* c, const char* name, int value) {
       // slots that had a TLAS get it back (same instances, fresh build) once the arrays are linked again
       for (rt_ctx* m : S->members) {
         if (!m->tlas_valid) continue;
-        std::vector<rt_instance> keep = m->h_inst;
-        m->tlas_valid = false;
-        int r = rt_set_instances(m, keep.data(), (int)keep.size(), 0);
+        int r;
+        if (m->inst_source == INST_DEVICE) {   // (from the library's device copy of the records)
+          m->tlas_valid = false;
+          r = set_instances_device(m, m->tgpu.d_rec, m->n_inst, 0, nullptr);
+        } else {
+          std::vector<rt_instance> keep = m->h_inst;
+          m->tlas_valid = false;
+          r = rt_set_instances(m, keep.data(), (int)keep.size(), 0);
+        }
         if (r) { if (m != c) c->error = m->error; return r; }
       }
     }

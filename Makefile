@@ -13,7 +13,7 @@ all: $(PKG)/librt_mi355x.so oracle
 
 # one object per source, so that a change to one file recompiles that file only (kernels.hip alone is ~25 s)
 OBJDIR   := build/obj
-DEVHDRS  := $(CSRC)/rt_device.h $(CSRC)/rt_kernels.h $(CSRC)/bvh_build.h $(CSRC)/bvh_gpu.h $(CSRC)/lbvh_kernels.h $(CSRC)/tlas_gpu.h include/rt_api.h
+DEVHDRS  := $(CSRC)/rt_device.h $(CSRC)/rt_kernels.h $(CSRC)/bvh_build.h $(CSRC)/bvh_gpu.h $(CSRC)/lbvh_kernels.h $(CSRC)/tlas_gpu.h $(CSRC)/blas_quant.h $(CSRC)/blas_refit.h include/rt_api.h
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(DEVHDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
@@ -21,7 +21,7 @@ $(OBJDIR)/%.o: $(CSRC)/%.cpp $(DEVHDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 $(OBJDIR)/kernels.o: $(CSRC)/kernels_tile.inc $(CSRC)/kernels_beam.inc
-PRODUCT_OBJS := $(OBJDIR)/kernels.o $(OBJDIR)/bvh_gpu.o $(OBJDIR)/tlas_gpu.o $(OBJDIR)/rt_api.o $(OBJDIR)/bvh_build.o
+PRODUCT_OBJS := $(OBJDIR)/kernels.o $(OBJDIR)/bvh_gpu.o $(OBJDIR)/tlas_gpu.o $(OBJDIR)/blas_refit.o $(OBJDIR)/rt_api.o $(OBJDIR)/bvh_build.o
 $(PKG)/librt_mi355x.so: $(PRODUCT_OBJS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(PRODUCT_OBJS)
 
@@ -30,7 +30,7 @@ $(PKG)/librt_mi355x.so: $(PRODUCT_OBJS)
 $(OBJDIR)/kernels_alt.o: $(CSRC)/kernels.hip $(CSRC)/kernels_alt.inc $(CSRC)/kernels_tile.inc $(CSRC)/kernels_beam.inc $(DEVHDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -DRT_ALT_KERNELS -c -o $@ $(CSRC)/kernels.hip
-$(PKG)/librt_mi355x_alt.so: $(OBJDIR)/kernels_alt.o $(OBJDIR)/bvh_gpu.o $(OBJDIR)/tlas_gpu.o $(OBJDIR)/rt_api.o $(OBJDIR)/bvh_build.o
+$(PKG)/librt_mi355x_alt.so: $(OBJDIR)/kernels_alt.o $(OBJDIR)/bvh_gpu.o $(OBJDIR)/tlas_gpu.o $(OBJDIR)/blas_refit.o $(OBJDIR)/rt_api.o $(OBJDIR)/bvh_build.o
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $^
 alt: $(PKG)/librt_mi355x_alt.so
 all: alt
@@ -44,10 +44,13 @@ resource-usage:
 # the same report for the device TLAS builder's TU (tests/test_device_tlas.py holds its per-frame kernels to no scratch)
 resource-usage-tlas:
 	$(HIPCC) $(HIPFLAGS) -c -Rpass-analysis=kernel-resource-usage -o /dev/null $(CSRC)/tlas_gpu.hip
+# ... and for the BLAS refit's TU (tests/test_blas_refit.py holds every refit kernel to no scratch and no spills)
+resource-usage-blas-refit:
+	$(HIPCC) $(HIPFLAGS) -c -Rpass-analysis=kernel-resource-usage -o /dev/null $(CSRC)/blas_refit.hip
 
 clean:
 	rm -f $(PKG)/*.so; rm -rf $(OBJDIR); $(MAKE) -C oracle clean
-.PHONY: all oracle clean resource-usage resource-usage-tlas alt
+.PHONY: all oracle clean resource-usage resource-usage-tlas resource-usage-blas-refit alt
 
 # host-side library (OBJ/MTL ingest, camera, animation, stand-in mesh, JPEG decode) — g++ only
 HOSTSRC := $(CSRC)/host_shim.cpp host/fly_camera.cpp host/standin.cpp host/standin_limbs.cpp $(wildcard host/jpeg_decode.cpp)
@@ -66,4 +69,4 @@ rt_headless: host/rt_headless.cpp host/fly_camera.cpp host/standin.cpp host/stan
 
 # kernel experiments: make exp EXP_NAME=<suffix> EXP_FLAGS="-DRT_EXP_..."  -> librt_mi355x_<suffix>.so (load with RT_LIB_VARIANT)
 exp:
-	$(HIPCC) $(HIPFLAGS) $(EXP_FLAGS) -shared -o $(PKG)/librt_mi355x_$(EXP_NAME).so $(CSRC)/kernels.hip $(CSRC)/bvh_gpu.hip $(CSRC)/tlas_gpu.hip $(CSRC)/rt_api.cpp $(CSRC)/bvh_build.cpp
+	$(HIPCC) $(HIPFLAGS) $(EXP_FLAGS) -shared -o $(PKG)/librt_mi355x_$(EXP_NAME).so $(CSRC)/kernels.hip $(CSRC)/bvh_gpu.hip $(CSRC)/tlas_gpu.hip $(CSRC)/blas_refit.hip $(CSRC)/rt_api.cpp $(CSRC)/bvh_build.cpp

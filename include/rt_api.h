@@ -175,6 +175,23 @@ int rt_set_instances(rt_ctx* ctx, const rt_instance* instances, int n, int updat
  * records only, and a later rt_set_batch or rt_set_instances replaces the device instances. */
 int rt_set_instances_device(rt_ctx* ctx, const void* d_instances, int n, int update, void* hip_stream);
 
+/* BLAS update (Vulkan: a BLAS built with ALLOW_UPDATE, rebuilt with mode = UPDATE, src = dst) for deforming meshes: skinning, cloth,
+ * morph targets.  d_verts6 = the mesh's new vertices in the rt_upload_geometry layout (interleaved px py pz nx ny nz) in memory of
+ * ctx's GPU, covering the mesh's vertex span: from its first_float, 6 x (largest index the mesh references + 1) floats, which
+ * n_floats must equal.  Positions and normals are replaced; indices, triangle count and materials stay.  The call waits for the
+ * frames of every slot of the scene (the vertex buffer and the BLAS are shared and not double-buffered), copies the vertices into
+ * the scene's vertex buffer in stream order on hip_stream (NULL = the context's stream: the caller may overwrite its buffer as soon
+ * as the call returns), refits the BLAS on the device (same topology, new boxes and quantisation) and returns after one small
+ * readback (the new root box).  Every slot's TLAS is then stale: its next frame needs rt_set_instances, rt_set_instances_device or
+ * rt_set_batch first (update = 1 is accepted), else RT_ERR_NOT_READY.  Frames and hit records equal those of a fresh
+ * rt_upload_geometry + rt_build_blas + rt_set_instances over the same vertices.  A later relink keeps the refit; a later
+ * rt_build_blas of the mesh builds over the refitted vertices; rt_upload_geometry drops it.
+ * RT_ERR_INVALID_ARGUMENT: a NULL pointer, a mesh index out of range, a wrong n_floats, a mesh without triangles or whose vertex
+ * span overlaps another mesh's, trace_variant != 0, or a position that is not finite (the vertices are replaced by then: the mesh
+ * counts as not built until a refit with finite positions or rt_build_blas); RT_ERR_NOT_READY: the mesh has no built BLAS, or a
+ * frame of the scene submitted with rt_trace_async is pending. */
+int rt_refit_blas_device(rt_ctx* ctx, int mesh, const void* d_verts6, size_t n_floats, void* hip_stream);
+
 /* ---- MTL materials and a per-instance type table -------------------------------------------------
  * The reference's loader parses Kd/Ks/Ns/Ni/illum (include/tiny_obj_loader.h:565 GetMaterials) and its renderer ignores
  * them: src/shader.rgen:51-55 hard-codes ka (.1,.3,.1), kd (.2,1,.2), ks .8, exponent 100, index of refraction 1.52, and

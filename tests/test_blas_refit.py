@@ -1,0 +1,549 @@
+"""rt_refit_blas_device: a mesh's BLAS refitted on the GPU from device-resident vertices (deforming meshes).
+
+A refit keeps the tree and recomputes its boxes; the closest hit does not depend on the tree.  So every frame and every
+closest-hit record after a refit must be bit-identical to those of a fresh context built on the host from the same vertices
+(rt_upload_geometry + rt_build_blas + rt_set_instances).  Any-hit records name whichever blocker a walk meets first, which depends on
+the tree: against a fresh build they are compared by whether the segment is blocked, against the same tree byte for byte."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import scenes
+from vulkan_raytracing_amd import RtContext, api, host, workloads
+from vulkan_raytracing_amd.api import INSTANCE_DTYPE, RtError
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RES = scenes.RES
+PATHS = [os.path.join(RES, "teapot.obj"), os.path.join(RES, "cube.obj")]
+TOL = 1e-3
+FRAC = 0.999
+RT_ERR_INVALID_ARGUMENT, RT_ERR_NOT_READY = 1, 2
+W, H = 200, 112
+
+
+def check_image(gpu, ref):
+    """the bar of tests/test_gpu_parity.py: max-abs <= 1e-3 and bit-exact on >= 99.9 % of pixels"""
+    diff = np.abs(gpu - ref).max(axis=2)
+    r = {"max": float(diff.max()), "frac_within_tol": float((diff <= TOL).mean()), "frac_bit_exact": float((diff == 0).mean())}
+    assert r["frac_within_tol"] >= FRAC, r
+    assert r["frac_bit_exact"] >= FRAC, r
+    return r
+
+
+# ---- CPU ----------------------------------------------------------------------------------------------------------------------
+
+def test_product_library_exports_refit_blas_device():
+    assert "rt_refit_blas_device" in api.EXPORTS
+    hdr = open(os.path.join(ROOT, "include", "rt_api.h")).read()
+    assert re.search(r"^int rt_refit_blas_device\(rt_ctx\* ctx, int mesh, const void\* d_verts6, size_t n_floats, void\* hip_stream\);", hdr, re.M)
+    L = api.lib()
+    assert hasattr(L, "rt_refit_blas_device")
+    assert L.rt_abi_version() == 7
+
+
+def test_null_context_is_rejected_without_a_device():
+    L = api.lib()
+    assert L.rt_refit_blas_device(None, 0, None, 6, None) == RT_ERR_INVALID_ARGUMENT
+    assert L.rt_refit_blas_device(None, -1, None, 0, None) == RT_ERR_INVALID_ARGUMENT
+
+
+def test_refit_kernels_use_no_scratch():
+    """`make resource-usage-blas-refit` (a cross-compile of blas_refit.hip with the resource-usage remarks): no refit kernel uses
+    scratch or spills a register."""
+    out = subprocess.run(["make", "-C", ROOT, "resource-usage-blas-refit"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, check=True).stdout
+    kernels, cur = {}, None
+    for line in out.splitlines():
+        m = re.search(r"remark: Function Name: (\S+)", line)
+        if m:
+            cur = kernels.setdefault(m.group(1), {})
+            continue
+        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\S+) \[-Rpass", line)
+        if m and cur is not None:
+            cur[m.group(1).strip()] = m.group(2)
+    for short in ("k_refit_parents", "k_refit_check", "k_refit_leaves", "k_refit_quant", "k_refit_emit", "k_refit_cover"):
+        found = [(n, r) for n, r in kernels.items() if short in n]
+        assert found, (short, list(kernels))
+        for name, r in found:
+            assert int(r["ScratchSize"]) == 0 and int(r["VGPRs Spill"]) == 0 and int(r["SGPRs Spill"]) == 0, (name, r)
+
+
+# ---- GPU ----------------------------------------------------------------------------------------------------------------------
+
+def span(geom, m):
+    """first float and length of mesh m's vertex span: 6 x (largest index + 1)"""
+    ff, fi, pc = geom.ranges[m]
+    return ff, 6 * (int(geom.idx[fi:fi + 3 * pc].max()) + 1)
+
+
+def deform(geom, m, amp=0.15, phase=0.0, scale=(1.0, 1.0, 1.0), collapse=False):
+    """mesh m's vertices displaced along their normals by a sine field, optionally scaled per axis and with every third triangle
+    collapsed to a point, normals recomputed: a float32 (nv, 6) tensor on the GPU"""
+    import torch
+    ff, n = span(geom, m)
+    _, fi, pc = geom.ranges[m]
+    v = torch.from_numpy(geom.verts[ff:ff + n].reshape(-1, 6).copy()).to("cuda:0")
+    tri = torch.from_numpy(geom.idx[fi:fi + 3 * pc].astype(np.int64).reshape(-1, 3)).to("cuda:0")
+    p, nrm = v[:, :3], v[:, 3:]
+    ext = (p.max(0).values - p.min(0).values).max()
+    f = torch.sin(6.0 * p[:, 0] / ext + phase) * torch.cos(5.0 * p[:, 1] / ext + 2.0 * phase) * torch.sin(7.0 * p[:, 2] / ext + 0.5)
+    p = (p + amp * ext * f[:, None] * nrm) * torch.tensor(scale, dtype=torch.float32, device="cuda:0")
+    if collapse:
+        t = tri[::3]
+        p = p.clone()
+        p[t[:, 1]] = p[t[:, 0]]
+        p[t[:, 2]] = p[t[:, 0]]
+    fn = torch.cross(p[tri[:, 1]] - p[tri[:, 0]], p[tri[:, 2]] - p[tri[:, 0]], dim=1)
+    vn = torch.zeros_like(p).index_add_(0, tri.reshape(-1), fn.repeat_interleave(3, dim=0))
+    vn = vn / vn.norm(dim=1, keepdim=True).clamp_min(1e-30)
+    return torch.cat([p, vn], dim=1).contiguous()
+
+
+def with_mesh(geom, verts, m, t):
+    """a host copy of the whole vertex buffer with mesh m's span replaced by tensor t"""
+    ff, n = span(geom, m)
+    out = np.array(verts, np.float32, copy=True)
+    out[ff:ff + n] = t.detach().cpu().numpy().reshape(-1)
+    return out
+
+
+def refit(ctx, m, t):
+    import torch
+    torch.cuda.current_stream().synchronize()
+    ctx.refit_blas_device(m, t)
+
+
+def two_objects(geom, max_bounce=3):
+    u = host.default_uniforms(max_bounce_count=max_bounce, samples_per_pixel=1, center_object_type=1, orbiting_object_type=0,
+                              orbiting_object_primitive_offset=geom.orbiting_primitive_offset, orbiting_object_vertex_offset=geom.orbiting_vertex_offset)
+    return host.SceneAnimation().instances((0, 1)), u
+
+
+def setup(ctx, geom, verts, inst, u, sky, builder=1):
+    ctx.set_param("blas_builder", builder)
+    ctx.upload_geometry(verts, geom.idx, geom.ranges)
+    ctx.set_instances(inst)
+    ctx.set_uniforms(u)
+    ctx.set_skybox(sky)
+
+
+def ring(mesh, n, radius=8.0, scale=0.12):
+    inst = np.zeros(n, INSTANCE_DTYPE)
+    for k in range(n):
+        a = 2.0 * np.pi * k / n
+        y = 0.9 * np.sin(7.0 * a)
+        M = np.array([[scale * np.cos(a), 0, scale * np.sin(a), radius * np.cos(a)], [0, scale, 0, y], [-scale * np.sin(a), 0, scale * np.cos(a), radius * np.sin(a)]], np.float32)
+        inst[k] = host.make_instance(M.reshape(12), 1, mesh)
+    return inst
+
+
+def rays_of(seed):
+    r = np.concatenate([scenes.random_rays(20_000, seed=seed), scenes.grazing_rays(20_000, seed=seed + 1)])
+    sh = r.copy()
+    sh[:, 7] = 12.0
+    return r, sh
+
+
+def assert_like_fresh(ctx, geom, verts, inst, u, sky, seed=5, builder=1, same_tree=False):
+    """ctx's frame and hit records equal those of a fresh context built on the host from `verts`; returns the frame"""
+    img, _ = ctx.trace(W, H)
+    r, sh = rays_of(seed)
+    g, _ = ctx.intersect(r)
+    a, _ = ctx.intersect(sh, any_hit=True)
+    f = RtContext(0)
+    try:
+        setup(f, geom, verts, inst, u, sky, builder)
+        img_f, _ = f.trace(W, H)
+        g_f, _ = f.intersect(r)
+        a_f, _ = f.intersect(sh, any_hit=True)
+    finally:
+        f.close()
+    assert (img != img[0, 0]).any()
+    assert np.array_equal(img.view(np.uint32), img_f.view(np.uint32))
+    assert (g["inst"] >= 0).mean() > 0.05
+    assert g.tobytes() == g_f.tobytes()
+    if same_tree:
+        assert a.tobytes() == a_f.tobytes()
+    else:
+        assert np.array_equal(a["inst"] >= 0, a_f["inst"] >= 0)
+    return img
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = RtContext(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def geom():
+    return host.SceneGeometry(PATHS)
+
+
+@pytest.fixture(scope="module")
+def sky():
+    return scenes.synthetic_skybox(64)
+
+
+@pytest.mark.gpu
+def test_identity_refit(ctx, geom, sky):
+    import torch
+    inst, u = two_objects(geom)
+    setup(ctx, geom, geom.verts, inst, u, sky)
+    img0, st0 = ctx.trace(W, H, counting=True)
+    r, sh = rays_of(11)
+    g0, _ = ctx.intersect(r)
+    a0, _ = ctx.intersect(sh, any_hit=True)
+    for m in (0, 1):
+        ff, n = span(geom, m)
+        refit(ctx, m, torch.from_numpy(geom.verts[ff:ff + n].copy()).to("cuda:0"))
+    ctx.set_instances(inst, update=True)
+    img1, st1 = ctx.trace(W, H, counting=True)
+    g1, _ = ctx.intersect(r)
+    a1, _ = ctx.intersect(sh, any_hit=True)
+    assert np.array_equal(img1.view(np.uint32), img0.view(np.uint32))
+    # the device builder's boxes are exact unions: the refit reproduces its planes, so the walks are the same
+    assert (st1.node_visits, st1.tri_tests) == (st0.node_visits, st0.tri_tests)
+    assert g1.tobytes() == g0.tobytes() and a1.tobytes() == a0.tobytes()
+    # the host builder (leaves of several triangles, its own quantisation): the frame is the same
+    try:
+        setup(ctx, geom, geom.verts, inst, u, sky, builder=0)
+        img_h, _ = ctx.trace(W, H)
+        ff, n = span(geom, 0)
+        refit(ctx, 0, torch.from_numpy(geom.verts[ff:ff + n].copy()).to("cuda:0"))
+        ctx.set_instances(inst, update=True)
+        img_h1, _ = ctx.trace(W, H)
+        assert np.array_equal(img_h1.view(np.uint32), img_h.view(np.uint32))
+        assert np.array_equal(img_h1.view(np.uint32), img0.view(np.uint32))
+    finally:
+        ctx.set_param("blas_builder", 1)
+
+
+@pytest.mark.gpu
+def test_deformed_two_objects_both_instance_sources_and_oracle(ctx, geom, sky):
+    import torch
+    inst, u = two_objects(geom)
+    setup(ctx, geom, geom.verts, inst, u, sky)
+    t0 = deform(geom, 0, amp=0.12)
+    t1 = deform(geom, 1, amp=0.2, phase=1.0)
+    refit(ctx, 0, t0)
+    refit(ctx, 1, t1)
+    verts = with_mesh(geom, with_mesh(geom, geom.verts, 0, t0), 1, t1)
+    ctx.set_instances(inst, update=True)
+    img = assert_like_fresh(ctx, geom, verts, inst, u, sky, seed=21)
+    sp = scenes.ScenePair(PATHS, inst, u, sky=sky)
+    sp.orc.set_geometry(verts, geom.idx, geom.ranges)
+    ref, _ = sp.orc.render(W, H)
+    check_image(img, ref)
+    # device instance records: a build, a refit of the mesh, an update of the device TLAS
+    dev = torch.from_numpy(np.ascontiguousarray(inst, INSTANCE_DTYPE).view(np.uint8).reshape(-1, 64).copy()).to("cuda:0")
+    torch.cuda.synchronize()
+    ctx.set_instances_device(dev)
+    t2 = deform(geom, 0, amp=0.25, phase=2.0)
+    refit(ctx, 0, t2)
+    ctx.set_instances_device(dev, update=True)
+    assert_like_fresh(ctx, geom, with_mesh(geom, verts, 0, t2), inst, u, sky, seed=23)
+
+
+@pytest.mark.gpu
+def test_ring_of_4096_refitted_instances(ctx, geom, sky):
+    inst = ring(0, 4096)
+    _, u = two_objects(geom, max_bounce=2)
+    u["position"][0][:3] = (0.0, 6.0, 16.0)
+    setup(ctx, geom, geom.verts, inst, u, sky)
+    t = deform(geom, 0, amp=0.3, phase=0.7)
+    refit(ctx, 0, t)
+    ctx.set_instances(inst, update=True)
+    img, _ = ctx.trace(W, H)
+    f = RtContext(0)
+    try:
+        setup(f, geom, with_mesh(geom, geom.verts, 0, t), inst, u, sky)
+        img_f, _ = f.trace(W, H)
+    finally:
+        f.close()
+    assert (img != img[0, 0]).any()
+    assert np.array_equal(img.view(np.uint32), img_f.view(np.uint32))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", ["grown_x3", "flat_y", "collapsed_third"])
+def test_extreme_shapes(ctx, geom, sky, shape):
+    inst, u = two_objects(geom)
+    setup(ctx, geom, geom.verts, inst, u, sky)
+    kw = {"grown_x3": dict(amp=0.1, scale=(3.0, 3.0, 3.0)), "flat_y": dict(amp=0.0, scale=(1.0, 0.0, 1.0)),
+          "collapsed_third": dict(amp=0.1, collapse=True)}[shape]
+    t = deform(geom, 0, **kw)
+    refit(ctx, 0, t)
+    ctx.set_instances(inst, update=True)
+    assert_like_fresh(ctx, geom, with_mesh(geom, geom.verts, 0, t), inst, u, sky, seed=31)
+
+
+@pytest.mark.gpu
+def test_animation_two_slots_in_flight(ctx, geom, sky):
+    """8 frames, each after a refit and a TLAS update, alternating between two frame slots: the refit waits for the frame still in
+    flight on the other slot, and every frame equals its fresh build"""
+    import torch
+    inst, u = two_objects(geom, max_bounce=2)
+    setup(ctx, geom, geom.verts, inst, u, sky)
+    slot = ctx.frame_slot()
+    try:
+        slot.set_instances(inst)
+        slot.set_uniforms(u)
+        slots = (ctx, slot)
+        outs, verts = [], []
+        for k in range(8):
+            t = deform(geom, 0, amp=0.05 * (k + 1), phase=0.4 * k)
+            refit(ctx if k % 2 else slot, 0, t)   # (through either slot: the scene is shared)
+            verts.append(with_mesh(geom, geom.verts, 0, t))
+            s = slots[k % 2]
+            a = inst.copy()
+            tr = a["transform"]
+            tr[1, 3] += np.float32(0.1 * k)
+            a["transform"] = tr
+            s.set_instances(a, update=True)
+            out = torch.empty((H, W, 4), dtype=torch.float32, device="cuda:0")
+            s.trace_shard(W, H, H, 0, 1, out.data_ptr(), out.numel() * 4)
+            outs.append((out, a))
+        ctx.synchronize()
+        slot.synchronize()
+        for k, (out, a) in enumerate(outs):
+            f = RtContext(0)
+            try:
+                setup(f, geom, verts[k], a, u, sky)
+                img_f, _ = f.trace(W, H)
+            finally:
+                f.close()
+            assert np.array_equal(out.cpu().numpy().view(np.uint32), img_f.view(np.uint32)), k
+    finally:
+        slot.close()
+
+
+@pytest.mark.gpu
+def test_cfg3_standin_full_size(sky):
+    w = workloads.make("cfg3", RES)
+    g = host.SceneGeometry(w.paths)
+    big = int(np.argmax([r[2] for r in g.ranges]))
+    assert g.ranges[big][2] > 300_000
+    c = RtContext(0)
+    try:
+        setup(c, g, g.verts, w.instances, w.uniforms, sky)
+        t = deform(g, big, amp=0.08, phase=0.3)
+        refit(c, big, t)
+        c.set_instances(w.instances, update=True)
+        img, _ = c.trace(320, 180)
+        f = RtContext(0)
+        try:
+            setup(f, g, with_mesh(g, g.verts, big, t), w.instances, w.uniforms, sky)
+            img_f, _ = f.trace(320, 180)
+        finally:
+            f.close()
+        assert np.array_equal(img.view(np.uint32), img_f.view(np.uint32))
+    finally:
+        c.close()
+
+
+@pytest.mark.gpu
+def test_stream_order_and_ownership(ctx, geom, sky):
+    import torch
+    inst, u = two_objects(geom)
+    setup(ctx, geom, geom.verts, inst, u, sky)
+    expect = deform(geom, 0, amp=0.2, phase=1.3)
+    ref_verts = with_mesh(geom, geom.verts, 0, expect)
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        # a queue of work in front of the vertices, then the vertices themselves produced by torch ops on that stream
+        a = torch.randn(2048, 2048, device="cuda:0")
+        for _ in range(8):
+            a = a @ a / 64.0
+        v = (expect * 2.0 - expect + (a[0, 0] != a[0, 0]).to(torch.float32) * 0).contiguous()
+        ctx.refit_blas_device(0, v, stream=s)   # no synchronisation by the caller
+        v.zero_()                               # overwritten right after the call, on the same stream
+    ctx.set_instances(inst, update=True)
+    assert_like_fresh(ctx, geom, ref_verts, inst, u, sky, seed=41)
+    torch.cuda.synchronize()
+
+
+@pytest.mark.gpu
+def test_state_rules(ctx, geom, sky):
+    inst, u = two_objects(geom)
+    setup(ctx, geom, geom.verts, inst, u, sky)
+    n_prims = len(geom.idx) // 3
+    table = np.zeros(3, api.MATERIAL_DTYPE)
+    for k in range(3):
+        table[k] = ((0.1, 0.1, 0.1), 10.0 + 40 * k, (0.9 - 0.3 * k, 0.3 + 0.2 * k, 0.5), 1.5, (0.2, 0.2, 0.2), k)
+    pm = (np.arange(n_prims) % 3).astype(np.uint32)
+    ctx.set_materials(table, pm)
+    t = deform(geom, 0, amp=0.2, phase=0.5)
+    refit(ctx, 0, t)
+    verts = with_mesh(geom, geom.verts, 0, t)
+    # the TLAS is stale: no frame, no ray query before a re-set
+    with pytest.raises(RtError) as e:
+        ctx.trace(W, H)
+    assert e.value.code == RT_ERR_NOT_READY
+    with pytest.raises(RtError) as e:
+        ctx.intersect(rays_of(1)[0][:16])
+    assert e.value.code == RT_ERR_NOT_READY
+    ctx.set_instances(inst, update=True)   # an update is accepted
+    img, _ = ctx.trace(W, H)
+    f = RtContext(0)
+    try:
+        setup(f, geom, verts, inst, u, sky)
+        f.set_materials(table, pm)
+        img_f, _ = f.trace(W, H)
+    finally:
+        f.close()
+    assert np.array_equal(img.view(np.uint32), img_f.view(np.uint32))   # materials survive the refit
+    ctx.set_materials(None)
+    # the relink trap: a build of the OTHER mesh relinks the arrays from the host mirrors, the refit must survive it
+    ctx.build_blas(1)
+    ctx.set_instances(inst)
+    assert_like_fresh(ctx, geom, verts, inst, u, sky, seed=51)
+    # a build of the refitted mesh builds over its refitted vertices (device builder, then host builder)
+    ctx.build_blas(0)
+    ctx.set_instances(inst)
+    assert_like_fresh(ctx, geom, verts, inst, u, sky, seed=52)
+    t2 = deform(geom, 0, amp=0.3, phase=2.5)
+    refit(ctx, 0, t2)
+    verts2 = with_mesh(geom, geom.verts, 0, t2)
+    try:
+        ctx.set_param("blas_builder", 0)
+        ctx.build_blas(0)
+        ctx.set_instances(inst)
+        assert_like_fresh(ctx, geom, verts2, inst, u, sky, seed=53)
+    finally:
+        ctx.set_param("blas_builder", 1)
+    # rt_upload_geometry resets everything
+    ctx.upload_geometry(geom.verts, geom.idx, geom.ranges)
+    ctx.set_instances(inst)
+    assert_like_fresh(ctx, geom, geom.verts, inst, u, sky, seed=54, same_tree=True)
+
+
+@pytest.mark.gpu
+def test_kept_shadow_records_do_not_survive_a_refit(ctx, geom, sky):
+    inst, u = two_objects(geom)
+    setup(ctx, geom, geom.verts, inst, u, sky)
+    ctx.set_param("shadow_entry", 2)
+    for _ in range(3):   # light and instances stand still: the light-side records are built and kept
+        ctx.trace(W, H)
+    t = deform(geom, 1, amp=0.35, phase=0.9)
+    refit(ctx, 1, t)
+    ctx.set_instances(inst, update=True)   # identical records
+    assert_like_fresh(ctx, geom, with_mesh(geom, geom.verts, 1, t), inst, u, sky, seed=61)
+
+
+@pytest.mark.gpu
+def test_errors(ctx, geom, sky):
+    import torch
+    inst, u = two_objects(geom)
+    setup(ctx, geom, geom.verts, inst, u, sky)
+    ff, n = span(geom, 0)
+    good = torch.from_numpy(geom.verts[ff:ff + n].copy()).to("cuda:0")
+    torch.cuda.synchronize()
+    L, h = ctx.L, ctx.h
+    assert L.rt_refit_blas_device(h, 0, None, n, None) == RT_ERR_INVALID_ARGUMENT
+    assert L.rt_refit_blas_device(h, 2, good.data_ptr(), n, None) == RT_ERR_INVALID_ARGUMENT
+    assert L.rt_refit_blas_device(h, -1, good.data_ptr(), n, None) == RT_ERR_INVALID_ARGUMENT
+    for bad_n in (n - 6, n + 6, 0):
+        assert L.rt_refit_blas_device(h, 0, good.data_ptr(), bad_n, None) == RT_ERR_INVALID_ARGUMENT
+        assert "n_floats" in L.rt_last_error(h).decode()
+    with pytest.raises(ValueError):
+        ctx.refit_blas_device(0, good.double())
+    with pytest.raises(ValueError):
+        ctx.refit_blas_device(0, good.cpu())
+    with pytest.raises(ValueError):
+        ctx.refit_blas_device(0, good.reshape(-1, 3))
+    # none of those touched the scene: the frame is still there
+    ctx.trace(W, H)
+    # a pending rt_trace_async frame
+    ctx.trace_async(W, H)
+    assert L.rt_refit_blas_device(h, 0, good.data_ptr(), n, None) == RT_ERR_NOT_READY
+    ctx.trace_wait()
+    # a mesh without a built BLAS
+    ctx.upload_geometry(geom.verts, geom.idx, geom.ranges, build=False)
+    ctx.build_blas(1)
+    assert L.rt_refit_blas_device(h, 0, good.data_ptr(), n, None) == RT_ERR_NOT_READY
+    ctx.build_blas(0)
+    ctx.set_instances(inst)
+    # a position that is not finite: an error, and the mesh counts as not built until a good refit
+    bad = good.clone()
+    bad[7 * 6 + 1] = float("nan")
+    bad[40 * 6 + 2] = float("inf")
+    bad[60 * 6:90 * 6].view(-1, 6)[:, :3] = float("nan")   # (and whole vertices: test_good_refit_repairs_whole_non_finite_vertices)
+    torch.cuda.synchronize()
+    with pytest.raises(RtError) as e:
+        ctx.refit_blas_device(0, bad)
+    assert e.value.code == RT_ERR_INVALID_ARGUMENT and "not finite" in str(e.value)
+    with pytest.raises(RtError) as e:
+        ctx.trace(W, H)
+    assert e.value.code == RT_ERR_NOT_READY
+    with pytest.raises(RtError) as e:
+        ctx.set_instances(inst, update=True)
+    assert e.value.code == RT_ERR_NOT_READY
+    dev = torch.from_numpy(np.ascontiguousarray(inst, INSTANCE_DTYPE).view(np.uint8).reshape(-1, 64).copy()).to("cuda:0")
+    torch.cuda.synchronize()
+    with pytest.raises(RtError) as e:
+        ctx.set_instances_device(dev)
+    assert e.value.code == RT_ERR_NOT_READY
+    t = deform(geom, 0, amp=0.1)
+    refit(ctx, 0, t)
+    ctx.set_instances(inst)
+    assert_like_fresh(ctx, geom, with_mesh(geom, geom.verts, 0, t), inst, u, sky, seed=71)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("builder", [1, 0])
+@pytest.mark.parametrize("part", ["first_third", "all"])
+def test_good_refit_repairs_whole_non_finite_vertices(ctx, geom, sky, part, builder):
+    """every position of a range of vertices (or of all of them) NaN: the refit fails, and a later refit with good vertices restores
+    the mesh completely — an empty leaf box of the bad refit must not be taken for an absent child afterwards"""
+    import torch
+    inst, u = two_objects(geom)
+    try:
+        setup(ctx, geom, geom.verts, inst, u, sky, builder)
+        img0, st0 = ctx.trace(W, H, counting=True)
+        ff, n = span(geom, 0)
+        good = torch.from_numpy(geom.verts[ff:ff + n].copy()).to("cuda:0")
+        bad = good.clone().reshape(-1, 6)
+        rows = bad.shape[0] // 3 if part == "first_third" else bad.shape[0]
+        bad[:rows, :3] = float("nan")
+        bad = bad.contiguous()
+        torch.cuda.synchronize()
+        with pytest.raises(RtError) as e:
+            ctx.refit_blas_device(0, bad)
+        assert e.value.code == RT_ERR_INVALID_ARGUMENT and "not finite" in str(e.value)
+        with pytest.raises(RtError) as e:
+            ctx.set_instances(inst, update=True)
+        assert e.value.code == RT_ERR_NOT_READY
+        refit(ctx, 0, good)   # the uploaded vertices again
+        ctx.set_instances(inst, update=True)
+        img1, st1 = ctx.trace(W, H, counting=True)
+        assert np.array_equal(img1.view(np.uint32), img0.view(np.uint32))
+        if builder == 1:   # the device builder's planes are reproduced exactly: the same walks
+            assert (st1.node_visits, st1.tri_tests) == (st0.node_visits, st0.tri_tests)
+        t = deform(geom, 0, amp=0.2, phase=1.1)
+        refit(ctx, 0, t)
+        ctx.set_instances(inst, update=True)
+        assert_like_fresh(ctx, geom, with_mesh(geom, geom.verts, 0, t), inst, u, sky, seed=81, builder=builder)
+    finally:
+        ctx.set_param("blas_builder", 1)
+
+
+@pytest.mark.gpu
+def test_trace_variant_other_than_0_is_refused(geom, sky):
+    import torch
+    c = RtContext(0, variant="alt")
+    try:
+        inst, u = two_objects(geom)
+        setup(c, geom, geom.verts, inst, u, sky)
+        c.set_param("trace_variant", 2)
+        ff, n = span(geom, 0)
+        good = torch.from_numpy(geom.verts[ff:ff + n].copy()).to("cuda:0")
+        torch.cuda.synchronize()
+        assert c.L.rt_refit_blas_device(c.h, 0, good.data_ptr(), n, None) == RT_ERR_INVALID_ARGUMENT
+        assert "trace_variant" in c.L.rt_last_error(c.h).decode()
+    finally:
+        c.close()

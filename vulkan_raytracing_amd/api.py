@@ -38,7 +38,7 @@ class RtStats(C.Structure):
         return self.rays_primary + self.rays_secondary + self.rays_shadow
 
 
-EXPORTS = ["rt_create", "rt_create_frame_slot", "rt_destroy", "rt_upload_geometry", "rt_build_blas", "rt_set_instances", "rt_set_instances_device", "rt_set_materials", "rt_set_instance_types", "rt_set_uniforms", "rt_set_skybox",
+EXPORTS = ["rt_create", "rt_create_frame_slot", "rt_destroy", "rt_upload_geometry", "rt_build_blas", "rt_set_instances", "rt_set_instances_device", "rt_refit_blas_device", "rt_set_materials", "rt_set_instance_types", "rt_set_uniforms", "rt_set_skybox",
            "rt_trace", "rt_trace_async", "rt_trace_wait", "rt_trace_shard", "rt_set_batch", "rt_trace_shard_batch", "rt_assemble_shards", "rt_shard_rows", "rt_synchronize", "rt_get_stats", "rt_set_timing", "rt_intersect",
            "rt_trace_counting", "rt_set_param", "rt_debug_check_builders", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
 
@@ -59,6 +59,7 @@ def lib(variant=None):
         L.rt_build_blas.argtypes = [vp, C.c_int]
         L.rt_set_instances.argtypes = [vp, vp, C.c_int, C.c_int]
         L.rt_set_instances_device.argtypes = [vp, vp, C.c_int, C.c_int, vp]
+        L.rt_refit_blas_device.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
         L.rt_set_materials.argtypes = [vp, vp, C.c_int, vp, C.c_size_t]
         L.rt_set_instance_types.argtypes = [vp, vp, C.c_int]
         L.rt_set_uniforms.argtypes = [vp, vp]
@@ -181,6 +182,32 @@ class RtContext:
             stream.synchronize()
         self._chk(self.L.rt_set_instances_device(self.h, C.c_void_p(t.data_ptr()), nbytes // INSTANCE_DTYPE.itemsize, int(update),
                                                  C.c_void_p(stream.cuda_stream)), "rt_set_instances_device")
+
+    def refit_blas_device(self, mesh, t, stream=None):
+        """rt_refit_blas_device: mesh `mesh`'s new vertices, a contiguous float32 torch tensor on this context's GPU of shape (nv, 6) or
+        (6 * nv,) in the upload layout (px py pz nx ny nz), covering the mesh's vertex span; read in the order of `stream` (default: the
+        current torch stream of that device).  The BLAS is refitted on the GPU; every frame slot then needs its instances set again."""
+        import torch
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("refit_blas_device takes a torch tensor, got %s" % type(t).__name__)
+        if t.device.type != "cuda" or t.device.index != self.device:
+            raise ValueError("vertex tensor must live on cuda:%d (the context's GPU), not %s" % (self.device, t.device))
+        if t.dtype != torch.float32:
+            raise ValueError("vertex tensor must be float32, not %s" % t.dtype)
+        if not t.is_contiguous():
+            raise ValueError("vertex tensor must be contiguous")
+        if not ((t.dim() == 2 and t.shape[1] == 6) or (t.dim() == 1 and t.shape[0] % 6 == 0)):
+            raise ValueError("vertex tensor has shape (nv, 6) or (6 * nv,), got %s" % (tuple(t.shape),))
+        if t.numel() == 0:
+            raise ValueError("vertex tensor is empty")
+        if stream is None:
+            stream = torch.cuda.current_stream(t.device)
+        if stream.cuda_stream == 0:
+            # torch's default stream is the null stream, which the C ABI reads as "the context's stream" (a non-blocking stream the
+            # null stream does not order): the vertices must be complete before the library's copy starts
+            stream.synchronize()
+        self._chk(self.L.rt_refit_blas_device(self.h, int(mesh), C.c_void_p(t.data_ptr()), t.numel(), C.c_void_p(stream.cuda_stream)),
+                  "rt_refit_blas_device")
 
     def set_materials(self, table, prim_material=None):
         """row n4: MTL material table + material id of every triangle of the index buffer; table None/empty removes it"""

@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <string>
 
+#include "blas_quant.h"
 #include "bvh_gpu.h"
 #include "lbvh_kernels.h"
 
@@ -136,18 +137,8 @@ __global__ void k_quant_params(const Box* node_boxes, float* qparams /* lo[3], s
   if (threadIdx.x >= 3) return;
   const int k = threadIdx.x;
   const float lo = node_boxes[0].lo[k], hi = node_boxes[0].hi[k];
-  const float ext = hi - lo;
-  const float scale = ext > 0.f ? ext * 1.00001f / 65520.0f : 1e-30f;
-  qparams[k] = lo - 4.0f * scale;       // quanta 0..3 stay below every stored plane
-  qparams[3 + k] = scale;
+  blas_quant_axis_params(lo, hi, &qparams[k], &qparams[3 + k]);   // (blas_quant.h, shared with the refit)
   qparams[6 + k] = lo; qparams[9 + k] = hi;
-}
-
-__device__ __forceinline__ uint32_t quant_box_axis(float lo, float hi, float base, float scale) {
-  // two quanta of margin on each side cover the float rounding of the division
-  float ql = floorf((lo - base) / scale) - 2.0f, qh = ceilf((hi - base) / scale) + 2.0f;
-  ql = fminf(fmaxf(ql, 0.0f), 65535.0f); qh = fminf(fmaxf(qh, 0.0f), 65535.0f);
-  return (uint32_t)ql | ((uint32_t)qh << 16);
 }
 
 // emit: internal node i with more than 4 triangles becomes BvhNodeQ[i]; children with <= 4 triangles become leaves
@@ -277,10 +268,7 @@ __global__ void k_quant_params_ploc(const PlocNode* nodes, int root, float* qpar
   if (threadIdx.x >= 3) return;
   const int k = threadIdx.x;
   const float lo = fminf(nodes[root].b0.lo[k], nodes[root].b1.lo[k]), hi = fmaxf(nodes[root].b0.hi[k], nodes[root].b1.hi[k]);
-  const float ext = hi - lo;
-  const float scale = ext > 0.f ? ext * 1.00001f / 65520.0f : 1e-30f;
-  qparams[k] = lo - 4.0f * scale;
-  qparams[3 + k] = scale;
+  blas_quant_axis_params(lo, hi, &qparams[k], &qparams[3 + k]);
   qparams[6 + k] = lo; qparams[9 + k] = hi;
 }
 

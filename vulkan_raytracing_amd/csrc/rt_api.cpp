@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "blas_refit.h"
 #include "bvh_build.h"
 #include "bvh_gpu.h"
 #include "rt_device.h"
@@ -58,6 +59,15 @@ struct Mesh {
   int32_t root = 0;                        // index of the mesh's root node in the linked quantized array
   uint32_t tri_base = 0;
   uint32_t cover_first = 0, cover_count = 0;   // the mesh's frontier boxes in Scene::d_cover_boxes (primary-ray coverage mask)
+  uint32_t laid_count = 0;        // slots of the mesh's nodes in the linked array (treelet layout)
+  // rt_refit_blas_device (blas_refit.hip): the device is the truth for a refitted mesh — the host mirrors (bvh, qnodes, tris, h_blasq,
+  // h_verts) keep the vertices of its last build, and every relink re-applies the refit from d_verts
+  uint32_t span_floats = 0;       // floats of the vertex span [first_float, first_float + span_floats): 6 x (largest index + 1)
+  int span_shared_with = -1;      // another mesh whose vertex span overlaps this one's (such a mesh cannot be refitted)
+  bool refitted = false;          // the linked arrays hold a refit of d_verts, not the mirrors
+  bool verts_on_device = false;   // h_verts is stale over the span (downloaded before a host build)
+  bool poisoned = false;          // the last refit met a non-finite position: not usable until a good refit or rt_build_blas
+  bool parents_ready = false;     // the refit's parent links of the linked layout are on the device
 };
 
 struct TimedSpan { int cat; hipEvent_t a, b; };
@@ -122,6 +132,9 @@ struct Scene {
 
   // per-mesh fields of the instance records, for k_inst_records (rt_set_instances_device); uploaded by link_blas
   TlasMeshDev* d_mesh_table = nullptr;
+  // rt_refit_blas_device: the frontier cut link_blas chose, (parent node << 1) | child per box of d_cover_boxes, and the refit's scratch
+  uint32_t* d_cover_src = nullptr;
+  BlasRefitScratch refit;
 };
 
 // which call built a slot's current instances and TLAS
@@ -143,6 +156,7 @@ struct rt_ctx {
   BuiltBvh tlas;
   Bvh4 tlas4;
   bool tlas_valid = false;
+  bool tlas_stale = false;       // a BLAS was refitted since the TLAS was set (Vulkan: the TLAS must be updated): frames wait for a re-set, update = 1 is allowed
   int inst_source = INST_NONE;   // rt_set_instances / rt_set_batch (host records, h_inst) or rt_set_instances_device (device records, tgpu.d_rec)
   int n_inst = 0;                // instance records of the current set (all frames of a batch)
   // rt_set_instances_device: build stream, scratch, the LBVH topology a refit keeps, the library's copy of the records (tlas_gpu.h)
@@ -400,6 +414,9 @@ static std::vector<BvhNodeQ> treelet_layout(const std::vector<BvhNodeQ>& in) {
   return out;
 }
 
+// refit mesh mi from the vertices at src (device, m.span_floats floats, read in src_stream's order), or from d_verts as it is (src NULL)
+int refit_mesh(rt_ctx* c, int mi, const float* src, hipStream_t src_stream);
+
 int link_blas(rt_ctx* c) {
   Scene* S = c->scene;
   size_t nn = 0, nt = 0, nn4 = 0;
@@ -415,6 +432,7 @@ int link_blas(rt_ctx* c) {
     gap_from[mi] = nn;
     nn = (nn + 3u) & ~(size_t)3u;   // every mesh starts on a line
     m.node_base = (int32_t)nn; m.tri_base = (uint32_t)nt; m.node_base4 = (int32_t)nn4;
+    m.laid_count = (uint32_t)laid[mi].size(); m.parents_ready = false;
     nn += laid[mi].size(); nt += m.tris.size(); nn4 += m.bvh4.nodes.size();
   }
   std::vector<BvhNodeQ> nodes(nn);
@@ -456,13 +474,15 @@ int link_blas(rt_ctx* c) {
   // boxes with two quanta of margin) in object space.  A leaf met on the way contributes its box as it is.
   {
     std::vector<float> cover;
+    std::vector<uint32_t> cover_src;   // where each box came from: a refit re-emits it from the new planes (blas_refit.hip k_refit_cover)
     S->max_cover_count = 0;
     size_t target = COVER_TARGET_BOXES;
     if (const char* e = getenv("RT_COVER_BOXES")) { const long v = atol(e); if (v >= 2 && v <= (1 << 20)) target = (size_t)v; }   // experiments
     for (auto& m : S->meshes) {
       m.cover_first = (uint32_t)(cover.size() / 6); m.cover_count = 0;
       if (!m.built || m.qnodes.empty()) continue;
-      auto emit = [&](const BvhNodeQ& q, int k) {
+      auto emit = [&](int32_t parent, int k) {
+        const BvhNodeQ& q = nodes[parent];
         float lo[3], hi[3];
         for (int ax = 0; ax < 3; ax++) {
           const uint32_t w = q.w[3 * k + ax];
@@ -473,6 +493,7 @@ int link_blas(rt_ctx* c) {
           lo[ax] -= pad; hi[ax] += pad;
         }
         cover.insert(cover.end(), lo, lo + 3); cover.insert(cover.end(), hi, hi + 3);
+        cover_src.push_back(((uint32_t)parent << 1) | (uint32_t)k);
       };
       // open the LARGEST box first (object-space surface area) until `target` boxes are open: boxes of even size hug the
       // silhouette better than the boxes of one tree level
@@ -505,14 +526,17 @@ int link_blas(rt_ctx* c) {
         const Open o = open.top(); open.pop();
         push_children(o.ref);
       }
-      for (const Open& o : closed) emit(nodes[o.parent], o.k);
-      while (!open.empty()) { emit(nodes[open.top().parent], open.top().k); open.pop(); }
+      for (const Open& o : closed) emit(o.parent, o.k);
+      while (!open.empty()) { emit(open.top().parent, open.top().k); open.pop(); }
       m.cover_count = (uint32_t)(cover.size() / 6) - m.cover_first;
       S->max_cover_count = std::max(S->max_cover_count, m.cover_count);
     }
     if (S->d_cover_boxes) { HIP_TRY(c, hipFree(S->d_cover_boxes)); S->d_cover_boxes = nullptr; }
     HIP_TRY(c, hipMalloc((void**)&S->d_cover_boxes, std::max<size_t>(6, cover.size()) * sizeof(float)));
     if (!cover.empty()) HIP_TRY(c, hipMemcpy(S->d_cover_boxes, cover.data(), cover.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (S->d_cover_src) { HIP_TRY(c, hipFree(S->d_cover_src)); S->d_cover_src = nullptr; }
+    HIP_TRY(c, hipMalloc((void**)&S->d_cover_src, std::max<size_t>(1, cover_src.size()) * sizeof(uint32_t)));
+    if (!cover_src.empty()) HIP_TRY(c, hipMemcpy(S->d_cover_src, cover_src.data(), cover_src.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   }
   {
     std::vector<TlasMeshDev> tab(std::max<size_t>(1, S->meshes.size()));
@@ -522,7 +546,7 @@ int link_blas(rt_ctx* c) {
       t.blas_root = m.root; t.blas_root4 = m.node_base4;
       t.first_float = (uint32_t)m.range.first_float; t.first_index = (uint32_t)m.range.first_index;
       t.cover_first = m.cover_first; t.cover_count = m.cover_count;
-      t.prim_count = m.range.prim_count; t.built = m.built ? 1u : 0u; t.levels = m.levels;
+      t.prim_count = m.range.prim_count; t.built = (m.built && !m.poisoned) ? 1u : 0u; t.levels = m.levels;
       for (int k = 0; k < 3; k++) { t.q_lo[k] = m.q_lo[k]; t.q_scale[k] = m.q_scale[k]; t.lo[k] = m.bounds.lo[k]; t.hi[k] = m.bounds.hi[k]; }
     }
     if (S->d_mesh_table) { HIP_TRY(c, hipFree(S->d_mesh_table)); S->d_mesh_table = nullptr; }
@@ -541,6 +565,13 @@ int link_blas(rt_ctx* c) {
   if (nt) HIP_TRY(c, hipMemcpy(S->d_tris, tris.data(), nt * sizeof(TriPacket), hipMemcpyHostToDevice));
   S->arrays_ready = false;
   int r = alloc_scene_arrays(c); if (r) return r;
+  // the arrays were linked from the host mirrors, which keep a refitted mesh's last build: the device is the truth for such a mesh,
+  // so its refit is applied again from d_verts (which nothing here touches)
+  for (size_t mi = 0; mi < S->meshes.size(); mi++) {
+    const Mesh& m = S->meshes[mi];
+    if (!m.built || !m.refitted || m.poisoned) continue;
+    r = refit_mesh(c, (int)mi, nullptr, nullptr); if (r) return r;
+  }
   S->blas_linked = true;
   return RT_OK;
 }
@@ -562,6 +593,45 @@ int alloc_scene_arrays(rt_ctx* c) {
     if (S->n_blas_nodes) HIP_TRY(c, hipMemcpy(S->d_wide, S->h_wide.data(), S->n_blas_nodes * sizeof(WideNodeQ), hipMemcpyHostToDevice));
   }
   S->arrays_ready = true;
+  return RT_OK;
+}
+
+int refit_mesh(rt_ctx* c, int mi, const float* src, hipStream_t src_stream) {
+  Scene* S = c->scene;
+  Mesh& m = S->meshes[mi];
+  std::string err;
+  bool grown = false;
+  if (blas_refit_reserve(S->refit, S->n_blas_nodes, &grown, err)) return fail(c, RT_ERR_OUT_OF_MEMORY, err);
+  if (grown) for (Mesh& o : S->meshes) o.parents_ready = false;   // (the kept parents went with the old array)
+  BlasRefitArgs a{};
+  a.d_src = src; a.src_stream = src_stream; a.stream = c->stream;
+  a.d_verts = S->d_verts; a.d_idx = S->d_idx;
+  a.first_float = (uint32_t)m.range.first_float; a.first_index = (uint32_t)m.range.first_index; a.span_floats = m.span_floats; a.prim_count = m.range.prim_count;
+  a.d_nodes = S->d_blas_nodes; a.node_base = m.node_base; a.node_count = m.laid_count;
+  a.d_tris = S->d_tris; a.tri_base = m.tri_base;
+  a.d_cover_src = S->d_cover_src; a.d_cover_boxes = S->d_cover_boxes; a.cover_first = m.cover_first; a.cover_count = m.cover_count;
+  a.d_mesh_entry = S->d_mesh_table + mi;
+  a.derive_parents = !m.parents_ready;
+  if (blas_refit(S->refit, a, err)) return fail(c, RT_ERR_DEVICE, err);
+  const RefitSummary& sm = *S->refit.h_sum;
+  m.parents_ready = true;
+  m.refitted = true; m.verts_on_device = true;   // (from here on d_verts, not h_verts, holds the mesh's vertices)
+  if (sm.bad || !sm.root_done) { m.poisoned = true; return fail(c, RT_ERR_DEVICE, "BLAS refit of mesh " + std::to_string(mi) + ": the linked tree is inconsistent"); }
+  if (sm.nonfinite) {
+    m.poisoned = true;
+    return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_refit_blas_device: mesh " + std::to_string(mi) + " has a position that is not finite; it counts as not built until a refit with finite positions or rt_build_blas");
+  }
+  m.poisoned = false;
+  for (int k = 0; k < 3; k++) { m.bounds.lo[k] = sm.root_lo[k]; m.bounds.hi[k] = sm.root_hi[k]; m.q_lo[k] = sm.q_lo[k]; m.q_scale[k] = sm.q_scale[k]; }
+  return RT_OK;
+}
+
+// a host-side build reads h_verts: bring the span of a mesh whose vertices were replaced on the device back first
+int sync_host_verts(rt_ctx* c, Mesh& m) {
+  if (!m.verts_on_device) return RT_OK;
+  Scene* S = c->scene;
+  HIP_TRY(c, hipMemcpy(S->h_verts.data() + m.range.first_float, S->d_verts + m.range.first_float, (size_t)m.span_floats * sizeof(float), hipMemcpyDeviceToHost));
+  m.verts_on_device = false;
   return RT_OK;
 }
 
@@ -733,11 +803,12 @@ int quiesce_scene(rt_ctx* c) {
   return RT_OK;
 }
 // the linked arrays changed: every slot has to set its instances again
-void invalidate_tlas(Scene* S) { for (rt_ctx* m : S->members) m->tlas_valid = false; }
+void invalidate_tlas(Scene* S) { for (rt_ctx* m : S->members) { m->tlas_valid = false; m->tlas_stale = false; } }
 
 int ready_to_trace(rt_ctx* c, bool batch = false) {
   if (!c->scene->d_verts) return fail(c, RT_ERR_NOT_READY, "rt_upload_geometry has not been called");
   if (!c->tlas_valid) return fail(c, RT_ERR_NOT_READY, "rt_set_instances has not been called");
+  if (c->tlas_stale) return fail(c, RT_ERR_NOT_READY, "a BLAS was refitted (rt_refit_blas_device) since the TLAS was set: update it with rt_set_instances, rt_set_instances_device or rt_set_batch first");
   if (!batch && c->batch_k != 1) return fail(c, RT_ERR_NOT_READY, "the context holds a frame batch (rt_set_batch): render it with rt_trace_shard_batch, or call rt_set_instances for a single frame");
   return RT_OK;
 }
@@ -1341,8 +1412,10 @@ void rt_destroy(rt_ctx* c) {
   S->slot_mask &= ~(1u << c->slot);
   size_traversal_grids(S);
   if (S->members.empty()) {   // the last context of a scene takes the shared arrays with it
-    void* sp[] = {S->d_wide, S->d_nodes4, S->d_verts, S->d_idx, S->d_blas_nodes, S->d_tris, S->d_sky, S->d_materials, S->d_prim_material, S->d_cover_boxes, S->d_mesh_table};
+    void* sp[] = {S->d_wide, S->d_nodes4, S->d_verts, S->d_idx, S->d_blas_nodes, S->d_tris, S->d_sky, S->d_materials, S->d_prim_material, S->d_cover_boxes, S->d_mesh_table,
+                  S->d_cover_src};
     for (void* p : sp) if (p) hipFree(p);
+    blas_refit_free(S->refit);
     for (JitterTable& t : S->jitter_tables) { hipFree(t.d); hipEventDestroy(t.ready); }
     delete S;
   }
@@ -1378,7 +1451,19 @@ int rt_upload_geometry(rt_ctx* c, const float* verts6, size_t n_floats, const ui
   HIP_TRY(c, hipMemcpy(S->d_verts, verts6, n_floats * sizeof(float), hipMemcpyHostToDevice));
   HIP_TRY(c, hipMemcpy(S->d_idx, idx, n_idx * sizeof(uint32_t), hipMemcpyHostToDevice));
   S->meshes.assign(n_meshes, Mesh{});
-  for (int m = 0; m < n_meshes; m++) S->meshes[m].range = ranges[m];
+  for (int m = 0; m < n_meshes; m++) {
+    Mesh& mm = S->meshes[m];
+    mm.range = ranges[m];
+    uint64_t top = 0;   // largest index + 1: the vertex span rt_refit_blas_device replaces
+    for (uint64_t k = 0; k < 3ull * mm.range.prim_count; k++) top = std::max<uint64_t>(top, (uint64_t)idx[mm.range.first_index + k] + 1);
+    mm.span_floats = (uint32_t)(6 * top);
+  }
+  for (int a = 0; a < n_meshes; a++)
+    for (int b = 0; b < n_meshes && S->meshes[a].span_shared_with < 0; b++) {
+      const Mesh &ma = S->meshes[a], &mb = S->meshes[b];
+      if (a != b && ma.span_floats && mb.span_floats && ma.range.first_float < mb.range.first_float + mb.span_floats && mb.range.first_float < ma.range.first_float + ma.span_floats)
+        S->meshes[a].span_shared_with = b;
+    }
   S->blas_linked = false; invalidate_tlas(S);
   // the per-triangle material ids belong to the old index buffer
   if (S->d_materials) { HIP_TRY(c, hipFree(S->d_materials)); S->d_materials = nullptr; }
@@ -1394,6 +1479,8 @@ int rt_build_blas(rt_ctx* c, int mesh) {
   { int q = quiesce_scene(c); if (q) return q; }
   Mesh& m = S->meshes[mesh];
   m.gpu_built = false;
+  // (a refitted mesh is built over its refitted vertices: the device builder reads d_verts, the host builder h_verts once synchronised)
+  m.refitted = false; m.poisoned = false;
   if (c->blas_builder == 1 && c->cfg.variant != 1 && m.range.prim_count >= 8) {
     // device build straight from the uploaded vertex/index buffers; the result is downloaded once so that the
     // linker treats every mesh alike
@@ -1410,6 +1497,7 @@ int rt_build_blas(rt_ctx* c, int mesh) {
     m.bvh = BuiltBvh{}; m.bvh4 = Bvh4{};
     m.gpu_built = true;
   } else {
+    { int r = sync_host_verts(c, m); if (r) return r; }
     build_blas(S->h_verts.data() + m.range.first_float, S->h_idx.data() + m.range.first_index, m.range.prim_count, m.bvh, m.tris);
     collapse_bvh4(m.bvh, true, false, m.bvh4);
     m.bounds = m.bvh.bounds;
@@ -1433,7 +1521,7 @@ static int set_instances_frames(rt_ctx* c, const rt_instance* inst, int n, int u
   const int total = n * K;
   for (int i = 0; i < total; i++) {
     if (inst[i].mesh >= S->meshes.size()) return fail(c, RT_ERR_INVALID_ARGUMENT, "instance references an unknown mesh");
-    if (!S->meshes[inst[i].mesh].built) return fail(c, RT_ERR_NOT_READY, "instance references a mesh whose BLAS is not built (rt_build_blas)");
+    if (!S->meshes[inst[i].mesh].built || S->meshes[inst[i].mesh].poisoned) return fail(c, RT_ERR_NOT_READY, "instance references a mesh whose BLAS is not built (rt_build_blas)");
   }
   if (update && (!c->tlas_valid || c->inst_per_frame != n || c->inst_source != INST_HOST))
     return fail(c, RT_ERR_INVALID_ARGUMENT, c->inst_source == INST_DEVICE && c->tlas_valid ? "TLAS update of a TLAS built by rt_set_instances_device: build with update = 0 first"
@@ -1498,7 +1586,7 @@ static int set_instances_frames(rt_ctx* c, const rt_instance* inst, int n, int u
   c->inst_gen[next_parity]++;
   c->inst_per_frame = n; c->batch_k = K;
   int r = upload_instances(c, inst_dev, K > 1 ? &frame_trees : nullptr); if (r) return r;
-  c->tlas_valid = true;
+  c->tlas_valid = true; c->tlas_stale = false;
   return RT_OK;
 }
 
@@ -1593,12 +1681,37 @@ static int set_instances_device(rt_ctx* c, const void* d_instances, int n, int u
   if (!c->ev_upload[next_parity]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_upload[next_parity], hipEventDisableTiming));
   HIP_TRY(c, hipEventRecord(c->ev_upload[next_parity], c->tgpu.stream));
   c->upload_pending = true; c->upload_inflight[next_parity] = true;
-  c->tlas_valid = true;
+  c->tlas_valid = true; c->tlas_stale = false;
   return RT_OK;
 }
 
 int rt_set_instances_device(rt_ctx* c, const void* d_instances, int n, int update, void* hip_stream) {
   return set_instances_device(c, d_instances, n, update, (hipStream_t)hip_stream);
+}
+
+// Vulkan's BLAS update (mode = UPDATE, src = dst) over a device vertex buffer: the mesh's vertices are replaced in stream order and its
+// BLAS is refitted on the device (blas_refit.hip) — same topology and layout, new packets, boxes, quantisation and frontier boxes.  The
+// vertex buffer and the BLAS are scene state that every slot's frames read and that is not double-buffered, so the call waits for the
+// frames of every slot first (quiesce_scene).  Afterwards every slot's TLAS is stale: its next frame needs a re-set, which may be an update.
+int rt_refit_blas_device(rt_ctx* c, int mesh, const void* d_verts6, size_t n_floats, void* hip_stream) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  if (!d_verts6) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_refit_blas_device: d_verts6 is NULL");
+  Scene* S = c->scene;
+  if (mesh < 0 || mesh >= (int)S->meshes.size()) return fail(c, RT_ERR_INVALID_ARGUMENT, "mesh index out of range");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_refit_blas_device needs trace_variant 0 (the BVH4 and 4-ary records are derived on the host)");
+  Mesh& m = S->meshes[mesh];
+  if (m.range.prim_count == 0) return fail(c, RT_ERR_INVALID_ARGUMENT, "mesh " + std::to_string(mesh) + " has no triangles");
+  if (n_floats != m.span_floats)
+    return fail(c, RT_ERR_INVALID_ARGUMENT, "n_floats must be the mesh's vertex span, 6 x (largest index + 1) = " + std::to_string(m.span_floats) + ", got " + std::to_string(n_floats));
+  if (m.span_shared_with >= 0)
+    return fail(c, RT_ERR_INVALID_ARGUMENT, "the vertex span of mesh " + std::to_string(mesh) + " overlaps that of mesh " + std::to_string(m.span_shared_with) + ": its vertices cannot be replaced alone");
+  if (!m.built) return fail(c, RT_ERR_NOT_READY, "mesh " + std::to_string(mesh) + " has no built BLAS (rt_build_blas)");
+  { int q = quiesce_scene(c); if (q) return q; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (!S->blas_linked) { int r = link_blas(c); if (r) return r; }
+  // from here on the vertex buffer is being replaced: whatever the outcome, no slot renders from its TLAS before a re-set
+  for (rt_ctx* o : S->members) if (o->tlas_valid) o->tlas_stale = true;
+  return refit_mesh(c, mesh, (const float*)d_verts6, hip_stream ? (hipStream_t)hip_stream : c->stream);
 }
 
 // Row n4: the MTL materials the reference's loader parses and its renderer ignores (src/shader.rgen:51-55
@@ -1698,11 +1811,14 @@ int rt_set_param(rt_ctx* c, const char* name, int value) {
     const int before = c->cfg.variant;
     for (rt_ctx* m : S->members) m->cfg.variant = value;   // the linked arrays are per scene: every slot walks the same ones
     bool relink = (value == 2 && before != 2 && S->blas_linked);   // the 4-ary records are derived from the linked BVH2 on demand
-    if (value == 1) {
-      // the quad kernel walks the BVH4 that only the host builder produces: rebuild device-built meshes on the host
+    if (value != 0) {
+      // the quad kernel walks the BVH4 that only the host builder produces: rebuild device-built meshes on the host; the BVH4 and the
+      // 4-ary records are derived from the host mirrors, which a refitted mesh does not keep current: rebuild those too, over their refitted vertices
       for (size_t mi = 0; mi < S->meshes.size(); mi++) {
         Mesh& m = S->meshes[mi];
-        if (!m.built || !m.gpu_built) continue;
+        if (!m.built || !((value == 1 && m.gpu_built) || m.refitted)) continue;
+        { int r = sync_host_verts(c, m); if (r) return r; }
+        m.refitted = false; m.poisoned = false;
         build_blas(S->h_verts.data() + m.range.first_float, S->h_idx.data() + m.range.first_index, m.range.prim_count, m.bvh, m.tris);
         collapse_bvh4(m.bvh, true, false, m.bvh4);
         m.bounds = m.bvh.bounds; m.gpu_built = false; relink = true;

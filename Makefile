@@ -20,13 +20,14 @@ $(OBJDIR)/%.o: $(CSRC)/%.hip $(DEVHDRS)
 $(OBJDIR)/%.o: $(CSRC)/%.cpp $(DEVHDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-$(OBJDIR)/kernels.o: $(CSRC)/kernels_tile.inc $(CSRC)/kernels_beam.inc
+$(OBJDIR)/kernels.o: $(CSRC)/kernels_beam.inc
 PRODUCT_OBJS := $(OBJDIR)/kernels.o $(OBJDIR)/bvh_gpu.o $(OBJDIR)/tlas_gpu.o $(OBJDIR)/blas_refit.o $(OBJDIR)/rt_api.o $(OBJDIR)/bvh_build.o
 $(PKG)/librt_mi355x.so: $(PRODUCT_OBJS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(PRODUCT_OBJS)
 
-# the traversal alternatives that measured slower (k_packet, the quad/BVH4 kernel, 4-ary records: csrc/kernels_alt.inc) are NOT in the
-# product library; `make alt` builds librt_mi355x_alt.so with them for the identity tests (RtContext(variant="alt") / RT_LIB_VARIANT=alt)
+# the alternatives that measured slower (k_packet, the quad/BVH4 kernel, 4-ary records: csrc/kernels_alt.inc; tile blobs: csrc/kernels_tile.inc;
+# shadow beams: k_beam_shadow in csrc/kernels_beam.inc) are NOT in the product library; `make alt` builds librt_mi355x_alt.so with them
+# (-DRT_ALT_KERNELS) for the identity tests (RtContext(variant="alt") / RT_LIB_VARIANT=alt)
 $(OBJDIR)/kernels_alt.o: $(CSRC)/kernels.hip $(CSRC)/kernels_alt.inc $(CSRC)/kernels_tile.inc $(CSRC)/kernels_beam.inc $(DEVHDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -DRT_ALT_KERNELS -c -o $@ $(CSRC)/kernels.hip
@@ -41,6 +42,9 @@ oracle:
 # registers, scratch, LDS and occupancy of every kernel of the product TU (tests/test_host.py holds the shipped traversal kernels to their budget)
 resource-usage:
 	$(HIPCC) $(HIPFLAGS) -c -Rpass-analysis=kernel-resource-usage -o /dev/null $(CSRC)/kernels.hip
+# ... and for the alt TU (tests/test_host.py holds the tile-blob kernels to theirs)
+resource-usage-alt:
+	$(HIPCC) $(HIPFLAGS) -DRT_ALT_KERNELS -c -Rpass-analysis=kernel-resource-usage -o /dev/null $(CSRC)/kernels.hip
 # the same report for the device TLAS builder's TU (tests/test_device_tlas.py holds its per-frame kernels to no scratch)
 resource-usage-tlas:
 	$(HIPCC) $(HIPFLAGS) -c -Rpass-analysis=kernel-resource-usage -o /dev/null $(CSRC)/tlas_gpu.hip
@@ -50,7 +54,7 @@ resource-usage-blas-refit:
 
 clean:
 	rm -f $(PKG)/*.so; rm -rf $(OBJDIR); $(MAKE) -C oracle clean
-.PHONY: all oracle clean resource-usage resource-usage-tlas resource-usage-blas-refit alt
+.PHONY: all oracle clean resource-usage resource-usage-alt resource-usage-tlas resource-usage-blas-refit alt
 
 # host-side library (OBJ/MTL ingest, camera, animation, stand-in mesh, JPEG decode) — g++ only
 HOSTSRC := $(CSRC)/host_shim.cpp host/fly_camera.cpp host/standin.cpp host/standin_limbs.cpp $(wildcard host/jpeg_decode.cpp)

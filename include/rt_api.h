@@ -297,9 +297,11 @@ int rt_set_timing(rt_ctx* ctx, int enabled);
  * per ray; frames without far rays), 0 = one walk per ray; "camera_records" 0 = no entry records for the primary rays (the light-side records stay);
  * "dead_shadow_rays" 1 (default) = a shadow ray whose outcome cannot change its sample (diffuse and specular exactly 0: the same bits lit or
  * shadowed) is settled when it is made and not walked — it still counts in rt_stats::rays_shadow, rays_shadow_untraced says how many — 0 = every
- * shadow ray is walked; "shadow_beams" 1 = the shadow rays of the primary hits in beams as well (k_beam_shadow; default 0: measured slower);
+ * shadow ray is walked; "shadow_beams" 1 = the shadow rays of the primary hits in beams as well (k_beam_shadow; default 0: measured slower;
+ * librt_mi355x_alt.so only — the product library refuses 1 with RT_ERR_INVALID_ARGUMENT);
  * "jitter_table" 1 (default) = k_raygen reads the sample positions of a frame size from a table made once, 0 = evaluates the hash per sample and frame;
- * "tile_blobs" 1 = the nodes and triangle packets of a screen tile staged through LDS (k_blob / k_tile; default 0: measured slower).
+ * "tile_blobs" 1 = the nodes and triangle packets of a screen tile staged through LDS (k_blob / k_tile; default 0: measured slower;
+ * librt_mi355x_alt.so only, like "shadow_beams").  In the product library the tile-blob fields of rt_stats are always 0.
  * Results do not depend on any of them. */
 int rt_set_param(rt_ctx* ctx, const char* name, int value);
 

@@ -30,7 +30,8 @@ def ctx():
 @pytest.fixture(scope="module")
 def ctx_alt():
     """A context of librt_mi355x_alt.so: the product sources compiled with -DRT_ALT_KERNELS, i.e. WITH the traversal kernels that
-    measured slower and are not shipped (k_packet, the quad/BVH4 kernel, 4-ary records).  Loaded next to the product library."""
+    measured slower and are not shipped (k_packet, the quad/BVH4 kernel, 4-ary records, tile blobs, shadow beams).  Loaded next to the
+    product library."""
     c = RtContext(0, variant="alt")
     yield c
     c.close()
@@ -319,6 +320,10 @@ def test_trace_variants_are_result_identical(ctx, ctx_alt):
         ctx.set_param("trace_variant", 2)
     with pytest.raises(RtError):
         ctx.set_param("packet_trace", 1)
+    for name in ("tile_blobs", "shadow_beams"):
+        with pytest.raises(RtError):
+            ctx.set_param(name, 1)
+        ctx.set_param(name, 0)
     arm, _ = host.armadillo_path(RES)
     scenes.two_object_scene(os.path.join(RES, "teapot.obj"), arm, 2, 1, 4, 2, sky=scenes.synthetic_skybox(64), ctx=ctx, time_param=0.6)
     product_img, product_st = ctx.trace(256, 144)
@@ -1476,7 +1481,7 @@ def test_frame_batches_equal_the_frames_rendered_one_by_one(ctx):
     ctx.set_instances(inst0)
 
 
-def test_tile_blobs_are_result_identical(ctx):
+def test_tile_blobs_are_result_identical(ctx_alt):
     """VERDICT r3 item 1 / north_star "BVH nodes and triangle packets staged through LDS": for every 8x8-pixel tile whose entry record
     names an instance k_blob writes the nodes and triangle packets the tile's beam can touch as one blob, and k_tile generates the
     tile's primary rays and walks them through it in LDS (rt_set_param "tile_blobs"; off by default: it measured slower); rays that may still hit another instance of their
@@ -1484,8 +1489,10 @@ def test_tile_blobs_are_result_identical(ctx):
     frames and ray counts are identical with it on and off, the frame equals the oracle's, and the statistics show the path was taken.
     Cameras: the start-up one, inside an instance's box, sheared, partly off screen and very close (blobs that do not fit), far away
     (the whole scene in a few tiles: refused blobs), behind the camera; band shards; overlapping instances (rays handed on: the
-    mirror teapot behind and beside the orbiting mesh); 17 instances; a one-instance scene; odd sample counts."""
+    mirror teapot behind and beside the orbiting mesh); 17 instances; a one-instance scene; odd sample counts.  Tile blobs are in the
+    alt library only."""
     import torch
+    ctx = ctx_alt
     arm, _ = host.armadillo_path(RES)
     sp = scenes.two_object_scene(os.path.join(RES, "teapot.obj"), arm, 1, 0, 2, 2, sky=scenes.synthetic_skybox(64), ctx=ctx, time_param=0.45)
     W, H = 408, 232
@@ -1556,31 +1563,28 @@ def test_tile_blobs_are_result_identical(ctx):
     assert o1[1][3].blob_tiles > 0 and o1[1][3].tile_rays_handed_on == 0
 
 
-def test_pixel_beams_are_result_identical(ctx):
-    """One walk per PIXEL for the primary rays (csrc/kernels_beam.inc, rt_set_param "pixel_beams", default on): the samples of a pixel
-    share the camera as origin, so one lane walks the tree once for all of them — boxes against the beam of the pixel's live rays
-    (conservative), triangles against every ray with the canonical test and tie rule.  Frames, ray counts and the rays that enter
-    traversal are identical with it on and off, the frame equals the oracle's, and the node visits show the path was taken.
-    The same for the SHADOW rays of the primary hits (k_beam_shadow, "shadow_beams", default off — it measured slower): a beam seen from
-    the light, the rays' end points measured against a common one, a pixel's rays walked in groups of like direction; every frame of
-    this test is rendered three ways (both beams, neither, primary only).
-    Cameras: the start-up one, inside an instance's box, sheared, partly off screen and very close, far away, behind the camera, axis
-    aligned (directions that straddle an axis plane inside a pixel); band shards; overlapping instances; 17 instances; a one-instance
-    scene; sample counts 1, 3, 7 (a second, partly filled sample row group); a frame size that does not fill its last tiles."""
+def _pixel_beam_sweep(ctx, arms):
+    """Every frame of the pixel-beam tests rendered in each of `arms` — 0: one walk per ray, 1: beams for the primary rays and for the
+    shadow rays of the primary hits, 2: beams for the primary rays only — with identical frames, ray counts and rays entering traversal.
+    The first arm (the one with the most beams) is also checked against the oracle and against band shards, and its node visits show
+    that the beams ran.  Cameras: the start-up one, inside an instance's box, sheared, partly off screen and very close, far away, behind
+    the camera, axis aligned (directions that straddle an axis plane inside a pixel); band shards; overlapping instances; 17 instances;
+    a one-instance scene; sample counts 1, 3, 7 (a second, partly filled sample row group); a frame size that does not fill its last tiles."""
     import torch
+    top = arms[0]
     arm, _ = host.armadillo_path(RES)
     sp = scenes.two_object_scene(os.path.join(RES, "teapot.obj"), arm, 1, 0, 2, 2, sky=scenes.synthetic_skybox(64), ctx=ctx, time_param=0.45)
     W, H = 408, 232
 
     def both(w=W, h=H):
         out = {}
-        for on in (1, 0, 2):          # 2: pixel beams for the primary rays only, one walk per shadow ray
+        for on in arms:
             ctx.set_param("pixel_beams", 1 if on else 0)
-            ctx.set_param("shadow_beams", 1 if on == 1 else 0)
+            ctx.set_param("shadow_beams", 1 if on == 1 else 0)   # (arm 1 runs on the alt library only)
             img, st = ctx.trace(w, h, counting=True)
             out[on] = (img, (st.rays_primary, st.rays_secondary, st.rays_shadow), st.closest_rays, st)
         ctx.set_param("pixel_beams", 1); ctx.set_param("shadow_beams", 0)
-        for k in (1, 2):
+        for k in arms:
             assert np.array_equal(out[k][0], out[0][0]) and out[k][1] == out[0][1] and out[k][2] == out[0][2], (k, out[k][1], out[0][1], out[k][2], out[0][2])
         return out
 
@@ -1588,11 +1592,12 @@ def test_pixel_beams_are_result_identical(ctx):
     try:
         out = both()
         # (the beams' node visits are counted per pixel: fewer than one walk per ray, even with two samples in pixels this coarse)
-        assert 0 < out[1][3].node_visits < 0.9 * out[0][3].node_visits, (out[1][3].node_visits, out[0][3].node_visits)
-        assert 0 < out[1][3].node_visits_shadow != out[2][3].node_visits_shadow, (out[1][3].node_visits_shadow, out[2][3].node_visits_shadow)   # (the shadow beams ran)
+        assert 0 < out[top][3].node_visits < 0.9 * out[0][3].node_visits, (out[top][3].node_visits, out[0][3].node_visits)
+        if 1 in arms:
+            assert 0 < out[1][3].node_visits_shadow != out[2][3].node_visits_shadow, (out[1][3].node_visits_shadow, out[2][3].node_visits_shadow)   # (the shadow beams ran)
         ref, rc = sp.orc.render(W, H)
-        check_image(out[1][0], ref)
-        assert out[1][1] == (int(rc[0]), int(rc[1]), int(rc[2]))
+        check_image(out[top][0], ref)
+        assert out[top][1] == (int(rc[0]), int(rc[1]), int(rc[2]))
         for band, n in ((8, 3), (16, 2)):
             rows_max = tiling.max_shard_rows(H, band, n)
             shards = []
@@ -1601,7 +1606,7 @@ def test_pixel_beams_are_result_identical(ctx):
                 ctx.trace_shard(W, H, band, s, n, buf.data_ptr(), buf.numel() * 4, torch.cuda.current_stream().cuda_stream)
                 ctx.synchronize()
                 shards.append(buf.cpu().numpy())
-            assert np.array_equal(tiling.assemble(shards, H, W, band), out[1][0])
+            assert np.array_equal(tiling.assemble(shards, H, W, band), out[top][0])
         for pos, extra in (((0.3, 0.2, 5.2), {}), ((3.5, 0.5, 9.0), {}), ((0.0, 0.0, 2000.0), {}), ((6.0, 1.0, 14.0), {}), ((-4.0, 3.0, 12.0), {"center_object_type": 2, "max_bounce_count": 5}),
                            ((0.0, 0.0, 20.0), {"forward": (0.0, 0.0, 1.0)}), ((0.0, 0.0, 20.0), {}), ((0.0, 0.0, 20.0), {"samples_per_pixel": 3}), ((1.0, 0.4, 16.0), {"samples_per_pixel": 7}),
                            ((1.0, 0.4, 16.0), {"samples_per_pixel": 1})):
@@ -1619,7 +1624,7 @@ def test_pixel_beams_are_result_identical(ctx):
         u[0]["right"][:3] = (1.3, 0.2, 0.1); u[0]["up"][:3] = (0.15, 0.8, -0.1); u[0]["forward"][:3] = (0.1, -0.05, -1.4)
         sp.set_uniforms(u); o2 = both()
         ref, rc = sp.orc.render(W, H)
-        check_image(o2[1][0], ref)
+        check_image(o2[top][0], ref)
     finally:
         ctx.set_param("pixel_beams", 1); ctx.set_param("shadow_beams", 0)
         sp.set_uniforms(base_u)
@@ -1631,6 +1636,22 @@ def test_pixel_beams_are_result_identical(ctx):
     wl1 = workloads.make("cfg1", RES)
     wl1.apply(ctx)
     both(256, 256)
+
+
+def test_pixel_beams_are_result_identical(ctx):
+    """One walk per PIXEL for the primary rays (csrc/kernels_beam.inc, rt_set_param "pixel_beams", default on): the samples of a pixel
+    share the camera as origin, so one lane walks the tree once for all of them — boxes against the beam of the pixel's live rays
+    (conservative), triangles against every ray with the canonical test and tie rule.  Frames, ray counts and the rays that enter
+    traversal are identical with it on and off, the frame equals the oracle's, and the node visits show the path was taken
+    (_pixel_beam_sweep: every frame rendered with pixel beams and without)."""
+    _pixel_beam_sweep(ctx, (2, 0))
+
+
+def test_shadow_beams_are_result_identical(ctx_alt):
+    """The same for the SHADOW rays of the primary hits (k_beam_shadow, "shadow_beams", default off — it measured slower; alt library
+    only): a beam seen from the light, the rays' end points measured against a common one, a pixel's rays walked in groups of like
+    direction; every frame of _pixel_beam_sweep is rendered three ways (both beams, neither, primary only)."""
+    _pixel_beam_sweep(ctx_alt, (1, 0, 2))
 
 
 def test_pixel_beams_and_settled_shadow_rays_on_random_scenes(ctx):
@@ -1693,28 +1714,33 @@ def test_pixel_beams_and_settled_shadow_rays_on_random_scenes(ctx):
         ctx.set_param("pixel_beams", 1); ctx.set_param("dead_shadow_rays", 1)
 
 
+def _settled_shadow_frames(ctx, tag, W, H):
+    """A frame with "dead_shadow_rays" on and off: identical frames and ray counts, some (not all) shadow rays settled, fewer walked."""
+    out = {}
+    ctx.trace(W, H)      # (so that both frames below find the light-side entry records of this scene kept)
+    for on in (1, 0):
+        ctx.set_param("dead_shadow_rays", on)
+        img, st = ctx.trace(W, H, counting=True)
+        out[on] = (img, (st.rays_primary, st.rays_secondary, st.rays_shadow), st.rays_shadow_untraced, st.node_visits_shadow)
+    ctx.set_param("dead_shadow_rays", 1)
+    assert np.array_equal(out[1][0], out[0][0]) and out[1][1] == out[0][1], (tag, out[1][1], out[0][1])
+    assert out[0][2] == 0 and 0 < out[1][2] < out[1][1][2], (tag, out[1][2], out[1][1])
+    assert out[1][3] < out[0][3], (tag, out[1][3], out[0][3])       # fewer shadow rays walked
+    return out
+
+
 def test_shadow_rays_that_cannot_change_their_sample_are_settled_in_k_shade(ctx):
     """src/shader.rgen:107-128 traces a shadow ray for every diffuse hit and adds `pow(0.9, i) * (diffuse + specular)` if the light is
     visible.  Where the surface AND the half vector face away from the light both terms are exactly 0: tmpColor stays Iamb*ka whether the
     ray reaches the light or not, bit for bit — k_shade writes the sample and does not queue the ray (rt_set_param "dead_shadow_rays",
     default on; rt_stats.rays_shadow still counts it, rays_shadow_untraced says how many).  Frames and ray counts are identical with the
     parameter on and off and equal the oracle's, with and without a material table (Iamb*ka of the hit's material), with the shadow
-    rays in beams, on the kernels of the alternative library's default path, and in the bounce loop (mirror teapot: k_tail)."""
+    rays in beams (alt library: test_settled_shadow_rays_with_shadow_beams), and in the bounce loop (mirror teapot: k_tail)."""
     arm, _ = host.armadillo_path(RES)
     W, H = 408, 232
 
     def both(tag):
-        out = {}
-        ctx.trace(W, H)      # (so that both frames below find the light-side entry records of this scene kept)
-        for on in (1, 0):
-            ctx.set_param("dead_shadow_rays", on)
-            img, st = ctx.trace(W, H, counting=True)
-            out[on] = (img, (st.rays_primary, st.rays_secondary, st.rays_shadow), st.rays_shadow_untraced, st.node_visits_shadow)
-        ctx.set_param("dead_shadow_rays", 1)
-        assert np.array_equal(out[1][0], out[0][0]) and out[1][1] == out[0][1], (tag, out[1][1], out[0][1])
-        assert out[0][2] == 0 and 0 < out[1][2] < out[1][1][2], (tag, out[1][2], out[1][1])
-        assert out[1][3] < out[0][3], (tag, out[1][3], out[0][3])       # fewer shadow rays walked
-        return out
+        return _settled_shadow_frames(ctx, tag, W, H)
 
     try:
         sp = scenes.two_object_scene(os.path.join(RES, "teapot.obj"), arm, 1, 0, 2, 3, sky=scenes.synthetic_skybox(64), ctx=ctx, time_param=0.45)
@@ -1722,9 +1748,6 @@ def test_shadow_rays_that_cannot_change_their_sample_are_settled_in_k_shade(ctx)
         ref, rc = sp.orc.render(W, H)
         check_image(o[1][0], ref)
         assert o[1][1] == (int(rc[0]), int(rc[1]), int(rc[2]))
-        ctx.set_param("shadow_beams", 1)
-        both("shadow beams")
-        ctx.set_param("shadow_beams", 0)
         # the light on the far side: most visible surfaces face away from it
         u = sp.uniforms.copy(); u[0]["light_position"][:3] = (-6.0, -3.0, -20.0)
         sp.set_uniforms(u)
@@ -1744,8 +1767,21 @@ def test_shadow_rays_that_cannot_change_their_sample_are_settled_in_k_shade(ctx)
         check_image(om[1][0], ref)
         assert om[1][1] == (int(rc[0]), int(rc[1]), int(rc[2]))
     finally:
-        ctx.set_param("dead_shadow_rays", 1); ctx.set_param("shadow_beams", 0)
+        ctx.set_param("dead_shadow_rays", 1)
         ctx.set_materials(None)
+
+
+def test_settled_shadow_rays_with_shadow_beams(ctx_alt):
+    """The frame of test_shadow_rays_that_cannot_change_their_sample_are_settled_in_k_shade with the shadow rays of the primary hits in
+    beams (k_beam_shadow, "shadow_beams", alt library only): settling still gives the same frame, and fewer rays are walked."""
+    ctx = ctx_alt
+    arm, _ = host.armadillo_path(RES)
+    try:
+        scenes.two_object_scene(os.path.join(RES, "teapot.obj"), arm, 1, 0, 2, 3, sky=scenes.synthetic_skybox(64), ctx=ctx, time_param=0.45)
+        ctx.set_param("shadow_beams", 1)
+        _settled_shadow_frames(ctx, "shadow beams", 408, 232)
+    finally:
+        ctx.set_param("dead_shadow_rays", 1); ctx.set_param("shadow_beams", 0)
 
 
 def test_jitter_table_is_bit_identical_to_evaluating_the_hash(ctx):

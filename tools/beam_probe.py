@@ -1,5 +1,6 @@
 """Pixel beams (csrc/kernels_beam.inc) against one walk per ray on a workload: node visits and triangle tests of the closest-hit kernels
-(counting build), identity of the frames, lone-frame time by kernel category.  Usage: python3 tools/beam_probe.py [workload] [mesh]"""
+(counting build), identity of the frames, lone-frame time by kernel category.
+The shadow rays' beams (k_beam_shadow) are in the alt library only: the probe loads it (`make alt`).  Usage: python3 tools/beam_probe.py [workload] [mesh]"""
 import os
 import sys
 
@@ -11,7 +12,7 @@ from vulkan_raytracing_amd import RtContext, workloads
 RES = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "resources")
 name = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
 mesh = sys.argv[2] if len(sys.argv) > 2 else "standin"
-ctx = RtContext(0)
+ctx = RtContext(0, variant="alt")
 wl = workloads.make(name, RES, mesh=mesh)
 wl.apply(ctx)
 imgs = {}

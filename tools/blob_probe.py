@@ -1,5 +1,5 @@
 """Tile-blob statistics and lone kernel times of a workload with the tile path on and off (one context, frames one at a time).
-Usage: python3 tools/blob_probe.py [cfg3|cfg4|cfg5] [standin|limbs]"""
+Tile blobs are in the alt library only (`make alt`).  Usage: python3 tools/blob_probe.py [cfg3|cfg4|cfg5] [standin|limbs]"""
 import os
 import sys
 
@@ -11,7 +11,7 @@ from vulkan_raytracing_amd import RtContext, workloads
 RES = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "resources")
 name = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
 mesh = sys.argv[2] if len(sys.argv) > 2 else "standin"
-ctx = RtContext(0)
+ctx = RtContext(0, variant="alt")
 wl = workloads.make(name, RES, mesh=mesh)
 wl.apply(ctx)
 W, H = wl.width, wl.height

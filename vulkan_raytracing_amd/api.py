@@ -47,7 +47,7 @@ _LIBS = {}
 
 def lib(variant=None):
     """librt_mi355x.so, or librt_mi355x_<variant>.so (variant "alt": the build that also holds the traversal kernels which
-    measured slower — k_packet, the quad/BVH4 kernel, 4-ary records; `make alt`).  RT_LIB_VARIANT names the default."""
+    measured slower — k_packet, the quad/BVH4 kernel, 4-ary records, tile blobs, shadow beams; `make alt`).  RT_LIB_VARIANT names the default."""
     if variant not in _LIBS:
         L = _native.load_rt(variant)
         vp = C.c_void_p

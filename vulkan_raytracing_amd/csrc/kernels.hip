@@ -17,7 +17,6 @@
 // -ffp-contract=off so nothing fuses unless written as __builtin_fmaf.  Box tests are the one
 // exception — they only have to be conservative, so they use v_rcp_f32 and a slack factor.
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 
 #include "rt_kernels.h"
 
@@ -756,8 +755,10 @@ __global__ __launch_bounds__(256) void k_raygen(SceneDev sc, FrameDev f, Uniform
   const uint32_t tile = blockIdx.y * gridDim.x + blockIdx.x;   // (over all frames of a batch: the records of frame k follow those of frame k - 1)
   const uint32_t tile1 = by * gridDim.x + blockIdx.x;          // within its frame
   if (f.entry != nullptr && covered && (uint32_t)f.entry[tile].w[0] == ENTRY_EMPTY) covered = false;
-  // tile blobs (k_blob): the rays of a tile that has one are walked in LDS by k_trace_tile
+#ifdef RT_ALT_KERNELS
+  // tile blobs (k_blob, alt library only): the rays of a tile that has one are walked in LDS by k_tile
   if (f.tile_blob != nullptr && covered && f.tile_blob[tile] != BLOB_NONE) return;   // (uniform over the workgroup) k_tile generates and walks this tile's rays
+#endif
   bool survive = false;
   F3 d = mk3(0.f, 0.f, 1.f);
   uint32_t sid = 0;
@@ -1425,11 +1426,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_WAVES_PE
 template <int MODE, bool ANY, bool WIDE, bool ENTRY = false, bool FAR = true, bool CONT = false>
 __global__ __launch_bounds__(256) void k_trace_count(TraceArgs a) { trace_body<MODE, ANY, true, WIDE, ENTRY, FAR, CONT>(a); }
 
-#include "kernels_tile.inc"   // k_blob, k_trace_tile: the tile's nodes and triangle packets staged through LDS
-#include "kernels_beam.inc"   // k_beam: the primary rays of a pixel walked together
+#include "kernels_beam.inc"   // k_beam: the primary rays of a pixel walked together (and, in the alt library, k_beam_shadow: their shadow rays)
 
 #ifdef RT_ALT_KERNELS
-#include "kernels_alt.inc"   // k_packet, k_trace4: alternatives measured slower, only in librt_mi355x_alt.so
+// alternatives measured slower, only in librt_mi355x_alt.so
+#include "kernels_alt.inc"    // k_packet, k_trace4
+#include "kernels_tile.inc"   // k_blob, k_tile: the tile's nodes and triangle packets staged through LDS
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -1444,9 +1446,10 @@ struct ShadeArgs {
   BatchTab bt;
 };
 
-// TILE: bounce 0 of a frame with tile blobs — the hit records lie in two regions per shard (kernels_tile.inc)
+// TILE: bounce 0 of a frame with tile blobs — the hit records lie in two regions per shard (kernels_tile.inc; alt library only)
 // BATCH: the frame is one of a frame batch — the light is the one of the sample's frame (the single-frame instantiations are untouched)
-// RUNS: bounce 0 of a frame with shadow runs (kernels_beam.inc) — the shadow ray of a primary hit goes into the slot of its primary ray
+// RUNS: bounce 0 of a frame with shadow runs (k_beam_shadow, kernels_beam.inc; alt library only) — the shadow ray of a primary hit goes
+// into the slot of its primary ray
 template <bool TILE = false, bool BATCH = false, bool RUNS = false>
 __device__ __forceinline__ void shade_body(const ShadeArgs& a, const int bounce) {
   const FrameDev& f = a.f;
@@ -1879,43 +1882,19 @@ void launch_trace_closest(const SceneDev& sc, const FrameDev& f, int bounce, boo
     a.entry = f.entry;
     a.rays_per_lane = (uint32_t)cfg.rays_per_lane; a.min_blocks = (uint32_t)cfg.min_blocks;
     const dim3 g(cfg.trace_blocks), b(256);
-
+#ifdef RT_ALT_KERNELS
     if (f.tile_blob != nullptr) {   // queue 0 may hold rays k_tile handed on (tile blobs are off in frames with far rays)
       if (counting) hipLaunchKernelGGL((k_trace_count<MODE_CLOSEST, false, false, true, false, true>), g, b, 0, s, a);
       else hipLaunchKernelGGL((k_trace<MODE_CLOSEST, false, false, true, false, true>), g, b, 0, s, a);
       return;
     }
+#endif
     if (counting) hipLaunchKernelGGL((k_trace_count<MODE_CLOSEST, false, false, true>), g, b, 0, s, a);
     else if (cfg.far) hipLaunchKernelGGL((k_trace<MODE_CLOSEST, false, false, true, true>), g, b, 0, s, a);
     else hipLaunchKernelGGL((k_trace<MODE_CLOSEST, false, false, true, false>), g, b, 0, s, a);
     return;
   }
   launch_trace<MODE_CLOSEST, false>(a, counting, cfg, s);
-}
-
-void launch_blob(const SceneDev& sc, const EntryArgs& e, const FrameDev& f, bool counting, hipStream_t s) {
-  const uint32_t n = (uint32_t)(e.tiles_x * e.tile_rows);
-  if (n == 0 || f.tile_blob == nullptr) return;
-  BlobArgs a{sc, e, f.tile_blob, f.blob_arena, f.blob_slots / N_SHARDS, f.blob_list, f.counters};
-  if (counting) hipLaunchKernelGGL((k_blob<true>), dim3(n), dim3(64), 0, s, a);
-  else hipLaunchKernelGGL((k_blob<false>), dim3(n), dim3(64), 0, s, a);
-}
-
-template <int CLS>
-static void launch_tile_class(const TileArgs& t, uint32_t blocks, bool counting, hipStream_t s) {
-  if (counting) hipLaunchKernelGGL((k_tile<CLS, true>), dim3(blocks), dim3(256), 0, s, t);
-  else hipLaunchKernelGGL((k_tile<CLS, false>), dim3(blocks), dim3(256), 0, s, t);
-}
-void launch_tile(const SceneDev& sc, const FrameDev& f, const UniformsDev& u, bool counting, hipStream_t s) {
-  if (f.tile_blob == nullptr) return;
-  TileArgs t{};
-  t.sc = sc; t.f = f; t.u = u; t.sub_slots = f.blob_slots / N_SHARDS; t.tmin = 0.001f;   // src/shader.rgen:87
-  const uint32_t blocks = f.blob_slots / N_SHARDS * N_SHARDS;
-  launch_tile_class<0>(t, blocks, counting, s);
-  launch_tile_class<1>(t, blocks, counting, s);
-  launch_tile_class<2>(t, blocks, counting, s);
-  static const bool twice = getenv("RT_EXP_TILE_TWICE") != nullptr;   // experiment: the same launches again (warm TLB / caches): how much of k_tile is cold misses?
-  if (twice) { launch_tile_class<0>(t, blocks, counting, s); launch_tile_class<1>(t, blocks, counting, s); launch_tile_class<2>(t, blocks, counting, s); }
 }
 
 void launch_entry(const SceneDev& sc, const EntryViews& a, hipStream_t s) {
@@ -1959,6 +1938,33 @@ void launch_trace_shadow(const SceneDev& sc, const FrameDev& f, bool counting, c
   launch_trace<MODE_SHADOW, true>(a, counting, cfg, s);
 }
 
+// tile blobs and shadow beams: alternatives measured slower, only in librt_mi355x_alt.so.  The product library keeps empty launchers
+// (rt_api.o is shared by both libraries); rt_set_param refuses the two parameters there, so FrameDev::tile_blob stays NULL and
+// shadow_runs 0 and rt_api never calls them.
+#ifdef RT_ALT_KERNELS
+void launch_blob(const SceneDev& sc, const EntryArgs& e, const FrameDev& f, bool counting, hipStream_t s) {
+  const uint32_t n = (uint32_t)(e.tiles_x * e.tile_rows);
+  if (n == 0 || f.tile_blob == nullptr) return;
+  BlobArgs a{sc, e, f.tile_blob, f.blob_arena, f.blob_slots / N_SHARDS, f.blob_list, f.counters};
+  if (counting) hipLaunchKernelGGL((k_blob<true>), dim3(n), dim3(64), 0, s, a);
+  else hipLaunchKernelGGL((k_blob<false>), dim3(n), dim3(64), 0, s, a);
+}
+
+template <int CLS>
+static void launch_tile_class(const TileArgs& t, uint32_t blocks, bool counting, hipStream_t s) {
+  if (counting) hipLaunchKernelGGL((k_tile<CLS, true>), dim3(blocks), dim3(256), 0, s, t);
+  else hipLaunchKernelGGL((k_tile<CLS, false>), dim3(blocks), dim3(256), 0, s, t);
+}
+void launch_tile(const SceneDev& sc, const FrameDev& f, const UniformsDev& u, bool counting, hipStream_t s) {
+  if (f.tile_blob == nullptr) return;
+  TileArgs t{};
+  t.sc = sc; t.f = f; t.u = u; t.sub_slots = f.blob_slots / N_SHARDS; t.tmin = 0.001f;   // src/shader.rgen:87
+  const uint32_t blocks = f.blob_slots / N_SHARDS * N_SHARDS;
+  launch_tile_class<0>(t, blocks, counting, s);
+  launch_tile_class<1>(t, blocks, counting, s);
+  launch_tile_class<2>(t, blocks, counting, s);
+}
+
 // the shadow rays of the primary hits, one walk per pixel (kernels_beam.inc): the runs of bounce queue 0 in the shadow arrays
 void launch_beam_shadow(const SceneDev& sc, const FrameDev& f, const UniformsDev& u, bool counting, const LaunchCfg& cfg, hipStream_t s) {
   if (!f.shadow_runs || !f.pixel_runs) return;
@@ -1974,6 +1980,11 @@ void launch_beam_shadow(const SceneDev& sc, const FrameDev& f, const UniformsDev
   if (counting) hipLaunchKernelGGL(k_beam_shadow_count, g, b, 0, s, A);
   else hipLaunchKernelGGL(k_beam_shadow, g, b, 0, s, A);
 }
+#else
+void launch_blob(const SceneDev&, const EntryArgs&, const FrameDev&, bool, hipStream_t) {}
+void launch_tile(const SceneDev&, const FrameDev&, const UniformsDev&, bool, hipStream_t) {}
+void launch_beam_shadow(const SceneDev&, const FrameDev&, const UniformsDev&, bool, const LaunchCfg&, hipStream_t) {}
+#endif
 
 void launch_trace_raw(const SceneDev& sc, const float4* ray_o, const float4* ray_d, HitRec* out, uint32_t shard_cap,
                       int32_t* ovf_stack, uint32_t* counters, bool any_hit, bool counting, const LaunchCfg& cfg, hipStream_t s) {
@@ -2036,8 +2047,10 @@ void launch_tail(const SceneDev& sc, const FrameDev& f, const UniformsDev& u, co
 void launch_shade(const SceneDev& sc, const FrameDev& f, const UniformsDev& u, const BatchTab& bt, int bounce, const LaunchCfg& cfg, hipStream_t s) {
   ShadeArgs a{sc, f, u, bounce, bt};
   if (f.batch_k > 1) hipLaunchKernelGGL((k_shade<false, true>), dim3(cfg.shade_blocks), dim3(256), 0, s, a);
+#ifdef RT_ALT_KERNELS
   else if (bounce == 0 && f.shadow_runs) hipLaunchKernelGGL((k_shade<false, false, true>), dim3(cfg.shade_blocks), dim3(256), 0, s, a);
   else if (bounce == 0 && f.tile_blob != nullptr) hipLaunchKernelGGL((k_shade<true, false>), dim3(cfg.shade_blocks), dim3(256), 0, s, a);
+#endif
   else hipLaunchKernelGGL((k_shade<false, false>), dim3(cfg.shade_blocks), dim3(256), 0, s, a);
 }
 

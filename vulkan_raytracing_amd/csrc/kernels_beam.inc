@@ -327,6 +327,7 @@ __device__ __forceinline__ void beam_body(const TraceArgs& a, const uint32_t run
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_BEAM_WAVES, RT_BEAM_WAVES))) void k_beam(TraceArgs a, uint32_t run) { beam_body<false>(a, run); }
 __global__ __launch_bounds__(256) void k_beam_count(TraceArgs a, uint32_t run) { beam_body<true>(a, run); }
 
+#ifdef RT_ALT_KERNELS   // k_beam_shadow measured slower: only in librt_mi355x_alt.so
 // ------------------------------------------------------------------------------------------------
 // k_beam_shadow: the SHADOW rays of a pixel's samples walked together (src/shader.rgen:107-129, any hit).
 // The shadow rays of a frame all END at the light — within 0.01 of it: a ray starts 0.01 N off its surface point P and runs parallel
@@ -648,3 +649,4 @@ __device__ __forceinline__ void beam_shadow_body(const BeamShadowArgs& A) {
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_BEAM_WAVES, RT_BEAM_WAVES))) void k_beam_shadow(BeamShadowArgs a) { beam_shadow_body<false>(a); }
 __global__ __launch_bounds__(256) void k_beam_shadow_count(BeamShadowArgs a) { beam_shadow_body<true>(a); }
+#endif  // RT_ALT_KERNELS

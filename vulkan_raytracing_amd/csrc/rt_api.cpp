@@ -234,14 +234,15 @@ struct rt_ctx {
   int light_tiles = LIGHT_TILES_DEFAULT;   // tiles per side of a face of that cube
   EntryRec* d_entry = nullptr;   // one record per 8x8 tile of this slot's largest frame so far
   size_t entry_alloc_tiles = 0;
-  // tile blobs (rt_device.h; kernels_tile.inc): 1 = k_blob writes, for every tile whose record names an instance, the nodes and triangle packets the tile's beam
-  // can touch as one blob, and k_trace_tile walks the tile's primary rays through it in LDS (result-identical; needs entry_points)
   int camera_records = 1;   // entry records for the primary rays (k_entry's camera view); 0: their walks start at the TLAS root (the light-side records are not affected)
   int dead_shadow_rays = 1; // a shadow ray whose outcome cannot change its sample (diffuse and specular exactly 0) is settled in k_shade; 0: walked like the others
   int shadow_beams = 0; // ... and the shadow rays of the primary hits (k_beam_shadow): result-identical, a third of the node visits, and SLOWER (the rays of a pixel end
-                        // at very different times — the first hit ends a ray — so most lanes of a wave wait: profiles/r04_experiments.txt); rt_set_param("shadow_beams", 1)
-  bool sh_double = false;   // the shadow arrays of this context's frame have room for the shadow runs beside the compact queue
+                        // at very different times — the first hit ends a ray — so most lanes of a wave wait: profiles/r04_experiments.txt); rt_set_param("shadow_beams", 1),
+                        // alt library only (alt_kernels_built())
+  bool sh_double = false;   // the shadow arrays of this context's frame have room for the shadow runs beside the compact queue (shadow_beams only)
   int pixel_beams = 1;  // the primary rays of a pixel walked together (kernels_beam.inc): result-identical; rt_set_param("pixel_beams", 0) restores one walk per ray
+  // tile blobs (rt_device.h; kernels_tile.inc): 1 = k_blob writes, for every tile whose record names an instance, the nodes and triangle packets the tile's beam
+  // can touch as one blob, and k_tile walks the tile's primary rays through it in LDS (result-identical; needs entry_points; alt library only: alt_kernels_built())
   int tile_blobs = 0;   // OFF by default: result-identical and measured slower (profiles/r04_experiments.txt: a wave of k_tile spends two thirds of its life
                         // fetching its blob and storing its results, the walk itself is 2.6 x faster than the global one)
   uint32_t* d_tile_blob = nullptr;   // directory, one word per tile (allocated with d_entry)
@@ -1310,7 +1311,8 @@ int collect_stats(rt_ctx* c) {
 // ================================================================================================
 extern "C" {
 
-int rt_abi_version(void) { return 7; }   // 2: rt_trace_async / rt_trace_wait; 3: rt_stats::tail_faults, rt_debug_sizing; 4: frame slots, rt_assemble_shards, materials; 5: rt_stats::frames_rerendered, entry records, BGRA8
+int rt_abi_version(void) { return 7; }   // 2: rt_trace_async / rt_trace_wait; 3: rt_stats::tail_faults, rt_debug_sizing; 4: frame slots, rt_assemble_shards, materials; 5: rt_stats::frames_rerendered, entry records, BGRA8;
+                                         // 6: rt_stats tile-blob fields (blob_tiles .. tile_diag); 7: rt_stats::rays_shadow_untraced
 
 // Persistent traversal grid, workgroups per CU.  A lone context renders one frame at a time: the kernels are latency-bound and
 // 5 workgroups per CU (all the LDS admits) are fastest (cfg3: 1.00 ms vs 1.03 at 4, 1.28 at 2).  With several frame slots the
@@ -1864,11 +1866,17 @@ int rt_set_param(rt_ctx* c, const char* name, int value) {
   }
   if (k == "primary_cover") { c->primary_cover = value != 0; return RT_OK; }
   if (k == "jitter_table") { c->jitter_table = value != 0; return RT_OK; }
-  if (k == "tile_blobs") { c->tile_blobs = value != 0; return RT_OK; }
+  if (k == "tile_blobs") {
+    if (value != 0 && !alt_kernels_built()) return fail(c, RT_ERR_INVALID_ARGUMENT, "tile_blobs is not in the product library (measured slower): build librt_mi355x_alt.so with `make alt` and load it (RT_LIB_VARIANT=alt)");
+    c->tile_blobs = value != 0; return RT_OK;
+  }
   if (k == "pixel_beams") { c->pixel_beams = value != 0; return RT_OK; }
   if (k == "camera_records") { c->camera_records = value != 0; return RT_OK; }
   if (k == "dead_shadow_rays") { c->dead_shadow_rays = value != 0; return RT_OK; }
-  if (k == "shadow_beams") { c->shadow_beams = value != 0; return RT_OK; }
+  if (k == "shadow_beams") {
+    if (value != 0 && !alt_kernels_built()) return fail(c, RT_ERR_INVALID_ARGUMENT, "shadow_beams is not in the product library (measured slower): build librt_mi355x_alt.so with `make alt` and load it (RT_LIB_VARIANT=alt)");
+    c->shadow_beams = value != 0; return RT_OK;
+  }
 
   if (k == "entry_points") { c->entry_points = value != 0; return RT_OK; }
   if (k == "packet_trace") {
@@ -1996,9 +2004,8 @@ int rt_trace_shard(rt_ctx* c, int W, int H, int band_rows, int shard, int n_shar
   return enqueue_frame(c, W, H, band_rows, shard, n_shards, (float4*)d_out, s);
 }
 
-// Root-side step of a multi-GPU frame: n_shards compact shards (as rt_trace_shard writes them, each padded to
-// shard_stride_bytes) lie back to back in d_gathered after the gather; this writes the width x height frame to d_frame on
-// hip_stream (NULL = the context's stream).  Pixel format = the context's ("output_rgba8").  Asynchronous.
+// rt_trace_shard for the frame batch of rt_set_batch: frame k's compact shard lands frame_stride_bytes behind frame k - 1's
+// (0: back to back).
 int rt_trace_shard_batch(rt_ctx* c, int W, int H, int band_rows, int shard, int n_shards, void* d_out, size_t frame_stride_bytes, size_t out_capacity_bytes, void* hip_stream) {
   if (!c) return RT_ERR_INVALID_ARGUMENT;
   if (W <= 0 || H <= 0 || band_rows <= 0 || n_shards <= 0 || shard < 0 || shard >= n_shards || !d_out)
@@ -2021,6 +2028,9 @@ int rt_trace_shard_batch(rt_ctx* c, int W, int H, int band_rows, int shard, int 
   return r;
 }
 
+// Root-side step of a multi-GPU frame: n_shards compact shards (as rt_trace_shard writes them, each padded to
+// shard_stride_bytes) lie back to back in d_gathered after the gather; this writes the width x height frame to d_frame on
+// hip_stream (NULL = the context's stream).  Pixel format = the context's ("output_rgba8").  Asynchronous.
 int rt_assemble_shards(rt_ctx* c, const void* d_gathered, int n_shards, size_t shard_stride_bytes, int W, int H, int band_rows,
                        void* d_frame, size_t frame_capacity_bytes, void* hip_stream) {
   if (!c) return RT_ERR_INVALID_ARGUMENT;

@@ -152,7 +152,7 @@ constexpr int ENTRY_VIEWS = 7;                       // camera + 6 light faces
 constexpr int BATCH_MAX = 8;
 constexpr int MAX_VIEWS = 8;                         // >= ENTRY_VIEWS, >= BATCH_MAX
 constexpr int LIGHT_TILES_DEFAULT = 256;             // tiles per side of a light face (rt_set_param "light_tiles")
-// Tile blobs (k_blob / k_tile, round 4): "BVH nodes and triangle packets staged through LDS".  For every 8x8-pixel tile whose entry
+// Tile blobs (k_blob / k_tile, round 4; alt library only): "BVH nodes and triangle packets staged through LDS".  For every 8x8-pixel tile whose entry
 // record names an instance, k_blob continues the beam search of k_entry down to the leaves and writes what the tile's beam can touch of
 // that instance's BLAS as ONE compact blob: the nodes in breadth-first order with blob-local links, then their triangle packets.  The
 // workgroup that owns the tile in k_tile copies the blob into LDS with coalesced loads, generates the tile's primary rays

@@ -76,7 +76,8 @@ struct FrameDev {
   int batch_k;                 // 1: a single frame
   uint32_t out_frame_stride;   // pixels between the shard images of consecutive frames of a batch in `out` (>= rows * width)
   uint32_t cover_view_words;   // words of ONE view's coverage mask (frame k's camera mask starts k * cover_view_words into `cover`)
-  // Tile blobs (rt_device.h; NULL: off).  tile_blob[local tile] = arena slot of the tile's blob or BLOB_NONE (k_blob): k_raygen leaves
+  // Tile blobs (rt_device.h; NULL: off — always in the product library, which has no tile-blob kernels; the fields stay so that
+  // rt_api.o, linked into both libraries, sees one layout).  tile_blob[local tile] = arena slot of the tile's blob or BLOB_NONE (k_blob): k_raygen leaves
   // the tiles that have one to k_tile, which generates their rays itself, walks them in LDS, puts them (ray direction + hit record) at the
   // TOP of their shard's region of bounce queue 0 (Q_TILE_RAYS; k_shade reads both ends) and appends the few that may still hit
   // another instance to queue 0 proper for the global walk.
@@ -89,7 +90,8 @@ struct FrameDev {
   // pixel together; a slot without a ray has a zero direction and gets HIT_DEAD as its hit record.
   int pixel_runs;
   // ... and the shadow ray of a primary hit takes the slot of its primary ray in sh_o / sh_d / sh_c / sh_e (zero direction: none), for
-  // k_beam_shadow; the compact shadow queue of the later bounces then starts sh_base entries up in the same arrays (0: no shadow runs)
+  // k_beam_shadow; the compact shadow queue of the later bounces then starts sh_base entries up in the same arrays (0: no shadow runs;
+  // always in the product library, which has no k_beam_shadow)
   uint32_t shadow_runs;        // 0 / 1
   uint32_t sh_base;
 };
@@ -154,6 +156,7 @@ void launch_jitter_table(const FrameDev& f, uint32_t spp, float2* table, hipStre
 void launch_trace_closest(const SceneDev& sc, const FrameDev& f, int bounce, bool counting, const LaunchCfg& cfg, hipStream_t s);
 // one lane per tile of the shard: the record of every tile the coverage mask marks
 void launch_entry(const SceneDev& sc, const EntryViews& a, hipStream_t s);
+// tile blobs and shadow beams (alt library only; empty in the product library, whose frames never have tile_blob / shadow_runs):
 // one wavefront per tile of the camera view `e` (the view the records were made for): the tile's blob
 void launch_blob(const SceneDev& sc, const EntryArgs& e, const FrameDev& f, bool counting, hipStream_t s);
 // the tiles with a blob: their primary rays generated and walked in LDS, one launch per size class
@@ -161,6 +164,7 @@ void launch_tile(const SceneDev& sc, const FrameDev& f, const UniformsDev& u, bo
 // bounces first_bounce..maxBounceCount (traversal + shading) in one launch of TAIL_BLOCKS workgroups
 void launch_tail(const SceneDev& sc, const FrameDev& f, const UniformsDev& u, const BatchTab& bt, int first_bounce, bool counting, const LaunchCfg& cfg, int tail_blocks, hipStream_t s);
 void launch_shade(const SceneDev& sc, const FrameDev& f, const UniformsDev& u, const BatchTab& bt, int bounce, const LaunchCfg& cfg, hipStream_t s);
+// the shadow rays of the primary hits, one walk per pixel (alt library only, like launch_blob / launch_tile)
 void launch_beam_shadow(const SceneDev& sc, const FrameDev& f, const UniformsDev& u, bool counting, const LaunchCfg& cfg, hipStream_t s);
 void launch_trace_shadow(const SceneDev& sc, const FrameDev& f, bool counting, const LaunchCfg& cfg, hipStream_t s);
 void launch_resolve(const FrameDev& f, const UniformsDev& u, hipStream_t s);
@@ -174,7 +178,8 @@ void launch_trace_raw(const SceneDev& sc, const float4* ray_o, const float4* ray
 // de-interleave n_shards gathered compact shards (shard_stride_px pixels apart) into the width x height frame
 void launch_assemble(const void* gathered, void* out, int width, int height, int band_rows, int n_shards, size_t shard_stride_px, bool rgba8, hipStream_t s);
 int trace_threads_per_block();
-// true in librt_mi355x_alt.so (-DRT_ALT_KERNELS): trace_variant 1 / 2 and packet_trace exist; the product library has the one-lane BVH2 kernels only
+// true in librt_mi355x_alt.so (-DRT_ALT_KERNELS): trace_variant 1 / 2, packet_trace, tile_blobs and shadow_beams exist; the product library
+// has the one-lane BVH2 kernels only
 bool alt_kernels_built();
 // resident workgroups of k_tail per CU (occupancy query; <= 0 on failure)
 int tail_blocks_per_cu();

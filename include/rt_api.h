@@ -311,6 +311,28 @@ int rt_set_param(rt_ctx* ctx, const char* name, int value);
 int rt_intersect(rt_ctx* ctx, size_t n, const float* rays8_host, int any_hit, rt_hit* out_host, int counting,
                  rt_stats* stats);
 
+/* Surface of a closest hit: what src/shader.rchit:50-96 computes before it shades (32 B, 16-B aligned in rt_intersect_device's output). */
+typedef struct rt_hit_attr {
+  float position[3];    /* P = o2w * (barycentric interpolation of the triangle's three positions) */
+  int32_t object_index; /* gl_InstanceCustomIndexEXT; -1 on a miss */
+  float normal[3];      /* N = normalize(interpolated normal * w2o), as the closest-hit shading takes it */
+  uint32_t reserved;    /* 0 */
+} rt_hit_attr;
+
+/* Ray queries in device memory (VK_KHR_ray_query: rayQueryEXT from any shader), ordered on hip_stream (NULL = the context's stream).
+ * d_rays8 = n rays in rt_intersect's layout (o.xyz, tmin, d.xyz, tmax: 32 B each, 16-B aligned); d_hits receives n rt_hit (4-B
+ * aligned); d_attr, optional and for closest-hit queries only, n rt_hit_attr (16-B aligned; a miss gives zeros and object_index -1).
+ * All three are memory of ctx's GPU.  Hits equal rt_intersect's bit for bit for both any_hit values.  Fully asynchronous: the rays are
+ * read and the results written in stream order; no host copy, no host synchronisation, no wait for a frame in flight (a query has its
+ * own counter block and spill area, allocated at the first query).  A query sees the TLAS of the last rt_set_instances* call before it
+ * and the scene as it was at the call: later calls that rewrite that TLAS parity or the shared scene wait for it, rt_destroy too.  Queries
+ * of one context from different streams run one after the other (stream waits, not host waits).  n == 0 enqueues nothing.  The quantised
+ * BVH2 is always walked (packet_trace does not apply).
+ * RT_ERR_INVALID_ARGUMENT: a NULL or misaligned pointer, a pointer that is not memory of ctx's GPU, n >= 0xFFFFFF00, d_attr with
+ * any_hit != 0 (Vulkan's any hit here is SkipClosestHit), trace_variant != 0; RT_ERR_NOT_READY: as for a frame (no geometry, no TLAS,
+ * a TLAS stale after rt_refit_blas_device, a frame batch held by the context). */
+int rt_intersect_device(rt_ctx* ctx, size_t n, const void* d_rays8, int any_hit, void* d_hits, void* d_attr, void* hip_stream);
+
 /* Same frame as rt_trace but through the instrumented traversal kernels (visit counters). */
 int rt_trace_counting(rt_ctx* ctx, int width, int height, float* out_rgba32f_host, rt_stats* stats);
 

@@ -40,7 +40,7 @@ class RtStats(C.Structure):
 
 EXPORTS = ["rt_create", "rt_create_frame_slot", "rt_destroy", "rt_upload_geometry", "rt_build_blas", "rt_set_instances", "rt_set_instances_device", "rt_refit_blas_device", "rt_set_materials", "rt_set_instance_types", "rt_set_uniforms", "rt_set_skybox",
            "rt_trace", "rt_trace_async", "rt_trace_wait", "rt_trace_shard", "rt_set_batch", "rt_trace_shard_batch", "rt_assemble_shards", "rt_shard_rows", "rt_synchronize", "rt_get_stats", "rt_set_timing", "rt_intersect",
-           "rt_trace_counting", "rt_set_param", "rt_debug_check_builders", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
+           "rt_trace_counting", "rt_intersect_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
 
 _LIBS = {}
 
@@ -80,6 +80,7 @@ def lib(variant=None):
         L.rt_debug_check_builders.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp]
         L.rt_debug_sizing.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, vp]
         L.rt_intersect.argtypes = [vp, C.c_size_t, vp, C.c_int, vp, C.c_int, C.POINTER(RtStats)]
+        L.rt_intersect_device.argtypes = [vp, C.c_size_t, vp, C.c_int, vp, vp, vp]
         L.rt_last_error.argtypes = [vp]
         L.rt_last_error.restype = C.c_char_p
         L.rt_device_info.argtypes = [vp]
@@ -301,6 +302,84 @@ class RtContext:
         st = RtStats()
         self._chk(self.L.rt_intersect(self.h, len(rays8), _p(rays8), int(any_hit), _p(out), int(counting), C.byref(st)), "rt_intersect")
         return out, st
+
+    def intersect_device(self, rays, any_hit=False, attributes=False, stream=None, out=None):
+        """rt_intersect_device: ray queries in device memory.  `rays` is a contiguous float32 torch tensor (n, 8) on this context's GPU
+        (o.xyz, tmin, d.xyz, tmax per row), read in the order of `stream` (default: the current torch stream of that device); the
+        results are written in that order too, and the call never waits on the host.  Returns a RayQuery of zero-copy views over one
+        int32 (n, 5) hits buffer (rt_hit: t, u, v, prim, inst) and, with attributes=True (closest-hit queries only), one int32 (n, 8)
+        attribute buffer (rt_hit_attr: position, object_index, normal, reserved).  out = (hits, attr) reuses such buffers."""
+        import torch
+        if not isinstance(rays, torch.Tensor):
+            raise TypeError("intersect_device takes a torch tensor, got %s" % type(rays).__name__)
+        if rays.device.type != "cuda" or rays.device.index != self.device:
+            raise ValueError("ray tensor must live on cuda:%d (the context's GPU), not %s" % (self.device, rays.device))
+        if rays.dtype != torch.float32:
+            raise ValueError("ray tensor must be float32, not %s" % rays.dtype)
+        if not rays.is_contiguous():
+            raise ValueError("ray tensor must be contiguous")
+        if rays.dim() != 2 or rays.shape[1] != 8:
+            raise ValueError("ray tensor has shape (n, 8), got %s" % (tuple(rays.shape),))
+        n = rays.shape[0]
+        cur = torch.cuda.current_stream(rays.device)
+        if stream is None:
+            stream = cur
+        if out is None:
+            hits = torch.empty((n, 5), dtype=torch.int32, device=rays.device)
+            attr = torch.empty((n, 8), dtype=torch.int32, device=rays.device) if attributes else None
+            if stream != cur:   # (allocated for the current stream, written on `stream`)
+                hits.record_stream(stream)
+                if attr is not None:
+                    attr.record_stream(stream)
+        else:
+            hits, attr = out
+            if hits.dtype != torch.int32 or tuple(hits.shape) != (n, 5) or not hits.is_contiguous() or hits.device != rays.device:
+                raise ValueError("out hits must be a contiguous int32 (n, 5) tensor on the rays' device")
+            if attributes and (attr is None or attr.dtype != torch.int32 or tuple(attr.shape) != (n, 8) or not attr.is_contiguous() or attr.device != rays.device):
+                raise ValueError("out attributes must be a contiguous int32 (n, 8) tensor on the rays' device")
+            attr = attr if attributes else None
+        if n:
+            run = stream
+            if stream.cuda_stream == 0:
+                # torch's default stream is the null stream, which the C ABI reads as "the context's stream" (a non-blocking stream the
+                # null stream does not order): the query goes through a side stream that waits for the default stream and that the
+                # default stream waits for in turn — no host synchronisation
+                if getattr(self, "_query_stream", None) is None:
+                    self._query_stream = torch.cuda.Stream(rays.device)
+                run = self._query_stream
+                run.wait_stream(stream)
+                for t in (rays, hits, attr):
+                    if t is not None:
+                        t.record_stream(run)
+            self._chk(self.L.rt_intersect_device(self.h, n, C.c_void_p(rays.data_ptr()), int(any_hit), C.c_void_p(hits.data_ptr()),
+                                                 C.c_void_p(attr.data_ptr()) if attr is not None else None, C.c_void_p(run.cuda_stream)),
+                      "rt_intersect_device")
+            if run is not stream:
+                stream.wait_stream(run)
+        return RayQuery(hits, attr)
+
+
+class RayQuery:
+    """Results of RtContext.intersect_device: views over the hits buffer (int32 (n, 5), rt_hit) and the optional attribute buffer
+    (int32 (n, 8), rt_hit_attr).  Misses have prim = inst = -1, and zero position / normal with object_index -1."""
+
+    def __init__(self, hits, attr):
+        import torch
+        self.hits, self.attr = hits, attr
+        f = hits[:, 0:3].view(torch.float32)
+        self.t, self.u, self.v = f[:, 0], f[:, 1], f[:, 2]
+        self.prim, self.inst = hits[:, 3], hits[:, 4]
+        if attr is not None:
+            self.position = attr[:, 0:3].view(torch.float32)
+            self.object_index = attr[:, 3]
+            self.normal = attr[:, 4:7].view(torch.float32)
+        else:
+            self.position = self.normal = self.object_index = None
+
+    def numpy(self):
+        """the hit records as rt_intersect returns them (HIT_DTYPE), and the attributes as (n, 8) int32 (or None); synchronises"""
+        h = self.hits.cpu().numpy().view(HIT_DTYPE).reshape(-1)
+        return h, (self.attr.cpu().numpy() if self.attr is not None else None)
 
 
 def check_builders(verts6, idx):

@@ -898,6 +898,7 @@ struct TraceArgs {
 constexpr int MODE_CLOSEST = 0;  // pipeline closest hit: o.w = tmax, d.w = sid
 constexpr int MODE_SHADOW = 1;   // pipeline any hit + shading epilogue
 constexpr int MODE_RAW = 2;      // o.w = tmin, d.w = tmax; writes HitRec
+constexpr int MODE_QUERY = 3;    // MODE_RAW on the caller's rays as they are (rt_intersect_device): ray i is the float4 pair ray_o[2i], ray_o[2i + 1]
 
 
 // ---- variant 0: BVH2, ONE LANE PER RAY, persistent threads with per-lane refill.
@@ -952,6 +953,7 @@ constexpr uint32_t REFILL_MIN = RT_REFILL_MIN;
 // their ray can still reach (mask in o.w).
 template <int MODE, bool ANY, bool COUNT, bool WIDE, bool ENTRY = false, bool FAR = true, bool CONT = false>
 __device__ __forceinline__ void trace_body(const TraceArgs& a) {
+  constexpr bool RAYS8 = MODE == MODE_RAW || MODE == MODE_QUERY;   // record-level rays: per-ray tmin and tmax, HitRec results
   __shared__ int s_stack[4][STACK2_LDS + 1][64];   // + one scratch row: lanes that do not push write there (fast_step)
   __shared__ float4 s_rays[4][2][64];
   __shared__ float4 s_out[4][64];
@@ -1005,7 +1007,12 @@ __device__ __forceinline__ void trace_body(const TraceArgs& a) {
       shard = (shard + 1u) & (N_SHARDS - 1); tried++;
     }
     if (lane < pf_count) {
-      pf_o = ld_stream(&a.ray_o[pf_base + lane]); pf_d = ld_stream(&a.ray_d[pf_base + lane]);
+      if constexpr (MODE == MODE_QUERY) {   // (o.xyz, tmin, d.xyz, tmax): 32 bytes per ray, read where the caller left them
+        const size_t r = 2u * (size_t)(pf_base + lane);
+        pf_o = ld_stream(&a.ray_o[r]); pf_d = ld_stream(&a.ray_o[r + 1u]);
+      } else {
+        pf_o = ld_stream(&a.ray_o[pf_base + lane]); pf_d = ld_stream(&a.ray_d[pf_base + lane]);
+      }
       if (ENTRY && MODE == MODE_SHADOW) pf_e = (uint32_t)ld_stream(reinterpret_cast<const int*>(a.sh_e) + pf_base + lane);
     }
   };
@@ -1100,7 +1107,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& a) {
           const uint32_t ci = chunk_pos + rank;
           q = chunk_base + ci;
           const float4 ro = s_rays[wave][0][ci], rd = s_rays[wave][1][ci];
-          if (MODE == MODE_RAW) { tmin_ray = ro.w; tmax = rd.w; }
+          if (RAYS8) { tmin_ray = ro.w; tmax = rd.w; }
           else { tmax = ro.w; sid = __float_as_uint(rd.w); }
           wo = mk3(ro.x, ro.y, ro.z); wd = mk3(rd.x, rd.y, rd.z);
           co = wo; cd = wd;
@@ -1167,7 +1174,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& a) {
             quant_space(co, cd, a.sc.tlas_q_lo, a.sc.tlas_q_scale, qs, qb, rot); far = FAR && quant_far_o(co, a.sc.tlas_q_lo, a.sc.tlas_q_scale);
             sp = 1;
             cur = a.sc.tlas_root;   // TLAS root (always interior); in a frame batch: the root of the ray's frame
-            if (MODE != MODE_RAW && a.sc.batch_samples) cur += (int)frame_of(sid, a.sc.batch_samples) * a.sc.tlas_stride;
+            if (!RAYS8 && a.sc.batch_samples) cur += (int)frame_of(sid, a.sc.batch_samples) * a.sc.tlas_stride;
           }
           if (!(CONT && handed_on)) { best_t = (ENTRY && MODE == MODE_CLOSEST) ? 10000.0f : tmax; best_u = 0.f; best_v = 0.f; best_prim = -1; best_inst = -1; }
           need = false;
@@ -1188,10 +1195,10 @@ __device__ __forceinline__ void trace_body(const TraceArgs& a) {
           const uint4 X = np[0], Y = np[1], Z = np[2], R = np[3];
           if (COUNT) cnt_nodes++;
           float t0, t1, t2, t3;
-          bool h0 = far ? slab_q_far(X.x, Y.x, Z.x, qs, qb, rot, (MODE == MODE_RAW ? tmin_ray : a.tmin), best_t, t0) : slab_q(X.x, Y.x, Z.x, qs, qb, rot, (MODE == MODE_RAW ? tmin_ray : a.tmin), best_t, t0);
-          bool h1 = far ? slab_q_far(X.y, Y.y, Z.y, qs, qb, rot, (MODE == MODE_RAW ? tmin_ray : a.tmin), best_t, t1) : slab_q(X.y, Y.y, Z.y, qs, qb, rot, (MODE == MODE_RAW ? tmin_ray : a.tmin), best_t, t1);
-          bool h2 = far ? slab_q_far(X.z, Y.z, Z.z, qs, qb, rot, (MODE == MODE_RAW ? tmin_ray : a.tmin), best_t, t2) : slab_q(X.z, Y.z, Z.z, qs, qb, rot, (MODE == MODE_RAW ? tmin_ray : a.tmin), best_t, t2);
-          bool h3 = far ? slab_q_far(X.w, Y.w, Z.w, qs, qb, rot, (MODE == MODE_RAW ? tmin_ray : a.tmin), best_t, t3) : slab_q(X.w, Y.w, Z.w, qs, qb, rot, (MODE == MODE_RAW ? tmin_ray : a.tmin), best_t, t3);
+          bool h0 = far ? slab_q_far(X.x, Y.x, Z.x, qs, qb, rot, (RAYS8 ? tmin_ray : a.tmin), best_t, t0) : slab_q(X.x, Y.x, Z.x, qs, qb, rot, (RAYS8 ? tmin_ray : a.tmin), best_t, t0);
+          bool h1 = far ? slab_q_far(X.y, Y.y, Z.y, qs, qb, rot, (RAYS8 ? tmin_ray : a.tmin), best_t, t1) : slab_q(X.y, Y.y, Z.y, qs, qb, rot, (RAYS8 ? tmin_ray : a.tmin), best_t, t1);
+          bool h2 = far ? slab_q_far(X.z, Y.z, Z.z, qs, qb, rot, (RAYS8 ? tmin_ray : a.tmin), best_t, t2) : slab_q(X.z, Y.z, Z.z, qs, qb, rot, (RAYS8 ? tmin_ray : a.tmin), best_t, t2);
+          bool h3 = far ? slab_q_far(X.w, Y.w, Z.w, qs, qb, rot, (RAYS8 ? tmin_ray : a.tmin), best_t, t3) : slab_q(X.w, Y.w, Z.w, qs, qb, rot, (RAYS8 ? tmin_ray : a.tmin), best_t, t3);
           if (far && cur_inst < 0) { h0 = h1 = h2 = h3 = true; t0 = t1 = t2 = t3 = 0.0f; }   // far ray in world space: the TLAS does not cull (see the BVH2 visit below)
           // entry distance with the entry number in its two low mantissa bits; a miss sorts last
           uint32_t k0 = h0 ? (__float_as_uint(t0) & ~3u) : 0xFFFFFFFFu;
@@ -1230,8 +1237,8 @@ __device__ __forceinline__ void trace_body(const TraceArgs& a) {
         // more than the padding of the instance boxes, so the TLAS is not allowed to cull for it — every instance is entered and
         // the BLAS tests, made on the object-space ray itself with the widened slabs, decide.
         const bool open_all = far && cur_inst < 0;
-        bool h0 = open_all ? (Q0.x & 0xFFFFu) <= (Q0.x >> 16) : (far ? slab_q_far(Q0.x, Q0.y, Q0.z, qs, qb, rot, (MODE == MODE_RAW ? tmin_ray : a.tmin), best_t, t0) : slab_q(Q0.x, Q0.y, Q0.z, qs, qb, rot, (MODE == MODE_RAW ? tmin_ray : a.tmin), best_t, t0));
-        bool h1 = open_all ? (Q0.w & 0xFFFFu) <= (Q0.w >> 16) : (far ? slab_q_far(Q0.w, Q1.x, Q1.y, qs, qb, rot, (MODE == MODE_RAW ? tmin_ray : a.tmin), best_t, t1) : slab_q(Q0.w, Q1.x, Q1.y, qs, qb, rot, (MODE == MODE_RAW ? tmin_ray : a.tmin), best_t, t1));
+        bool h0 = open_all ? (Q0.x & 0xFFFFu) <= (Q0.x >> 16) : (far ? slab_q_far(Q0.x, Q0.y, Q0.z, qs, qb, rot, (RAYS8 ? tmin_ray : a.tmin), best_t, t0) : slab_q(Q0.x, Q0.y, Q0.z, qs, qb, rot, (RAYS8 ? tmin_ray : a.tmin), best_t, t0));
+        bool h1 = open_all ? (Q0.w & 0xFFFFu) <= (Q0.w >> 16) : (far ? slab_q_far(Q0.w, Q1.x, Q1.y, qs, qb, rot, (RAYS8 ? tmin_ray : a.tmin), best_t, t1) : slab_q(Q0.w, Q1.x, Q1.y, qs, qb, rot, (RAYS8 ? tmin_ray : a.tmin), best_t, t1));
         if (open_all) { t0 = 0.0f; t1 = 0.0f; }
         if (h0 && h1) {
           const bool swap = t1 < t0;
@@ -1266,8 +1273,8 @@ __device__ __forceinline__ void trace_body(const TraceArgs& a) {
         const int2 ch = make_int2((int)Q1.z, (int)Q1.w);
         if (COUNT) cnt_nodes++;
         float t0, t1;
-        const bool h0 = slab_q(Q0.x, Q0.y, Q0.z, qs, qb, rot, (MODE == MODE_RAW ? tmin_ray : a.tmin), best_t, t0);
-        const bool h1 = slab_q(Q0.w, Q1.x, Q1.y, qs, qb, rot, (MODE == MODE_RAW ? tmin_ray : a.tmin), best_t, t1);
+        const bool h0 = slab_q(Q0.x, Q0.y, Q0.z, qs, qb, rot, (RAYS8 ? tmin_ray : a.tmin), best_t, t0);
+        const bool h1 = slab_q(Q0.w, Q1.x, Q1.y, qs, qb, rot, (RAYS8 ? tmin_ray : a.tmin), best_t, t1);
         const bool both = h0 && h1, none = !(h0 || h1), swap = t1 < t0;
         const uint32_t pm = 0u - (uint32_t)both;
         stk_lds[(((uint32_t)sp & pm) | ((uint32_t)STACK2_LDS & ~pm)) * 64u] = swap ? ch.x : ch.y;
@@ -1291,8 +1298,8 @@ __device__ __forceinline__ void trace_body(const TraceArgs& a) {
         const int2 ch = make_int2((int)Q1.z, (int)Q1.w);
         if (COUNT) cnt_nodes++;
         float t0, t1;
-        const bool h0 = slab_q(Q0.x, Q0.y, Q0.z, qs, qb, rot, (MODE == MODE_RAW ? tmin_ray : a.tmin), best_t, t0);
-        const bool h1 = slab_q(Q0.w, Q1.x, Q1.y, qs, qb, rot, (MODE == MODE_RAW ? tmin_ray : a.tmin), best_t, t1);
+        const bool h0 = slab_q(Q0.x, Q0.y, Q0.z, qs, qb, rot, (RAYS8 ? tmin_ray : a.tmin), best_t, t0);
+        const bool h1 = slab_q(Q0.w, Q1.x, Q1.y, qs, qb, rot, (RAYS8 ? tmin_ray : a.tmin), best_t, t1);
         const bool both = h0 && h1, none = !(h0 || h1), swap = t1 < t0;
         const uint32_t pm = 0u - (uint32_t)both;   // all ones when pushing
         stk_lds[(((uint32_t)sp & pm) | ((uint32_t)STACK2_LDS & ~pm)) * 64u] = swap ? ch.x : ch.y;   // the far child: one store, no branch
@@ -1338,7 +1345,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& a) {
           if (COUNT) cnt_tris++;
           float tt, uu, vv;
           // (the closest-hit pipeline's primary rays all have tmax 10000, src/shader.rgen:87: a constant for the ENTRY kernel, not a register)
-          if (tri_test(T0, T1, T2, co, cd, (MODE == MODE_RAW ? tmin_ray : a.tmin), (ANY ? best_t : ((ENTRY && MODE == MODE_CLOSEST) ? 10000.0f : tmax)), tt, uu, vv)) {
+          if (tri_test(T0, T1, T2, co, cd, (RAYS8 ? tmin_ray : a.tmin), (ANY ? best_t : ((ENTRY && MODE == MODE_CLOSEST) ? 10000.0f : tmax)), tt, uu, vv)) {
             if (ANY && MODE == MODE_SHADOW) best_inst = cur_inst;   // the shadow pipeline only asks WHETHER something was hit: no record to keep
             else {
               const int prim = (int)__float_as_uint(T2.y);
@@ -1446,6 +1453,23 @@ struct ShadeArgs {
   BatchTab bt;
 };
 
+// src/shader.rchit:50-96 up to the shading: the world position P and the shading normal N of the hit (u, v) on triangle `prim` of
+// instance I.  The one copy of this arithmetic: k_shade and k_tail shade with it, k_hit_attr hands it to ray queries.
+struct Surface { F3 P, N; };
+__device__ __forceinline__ Surface hit_surface(const SceneDev& sc, const InstanceDev* I, uint32_t prim, float hu, float hv) {
+  const uint32_t* ix = sc.idx + I->first_index + 3u * prim;
+  const uint32_t ia = ix[0], ib = ix[1], ic = ix[2];
+  const float* vb = sc.verts + I->first_float;
+  const float bx = (1.0f - hu) - hv, by = hu, bz = hv;
+  const float* pa = vb + 6u * ia; const float* pb = vb + 6u * ib; const float* pc = vb + 6u * ic;
+  const F3 pos = fma3(bz, mk3(pc[0], pc[1], pc[2]), fma3(by, mk3(pb[0], pb[1], pb[2]), mul3(mk3(pa[0], pa[1], pa[2]), bx)));
+  const F3 nrm = fma3(bz, mk3(pc[3], pc[4], pc[5]), fma3(by, mk3(pb[3], pb[4], pb[5]), mul3(mk3(pa[3], pa[4], pa[5]), bx)));
+  Surface s;
+  s.P = xform_point(I->o2w, pos);
+  s.N = normalize3(xform_normal(I->w2o, nrm));
+  return s;
+}
+
 // TILE: bounce 0 of a frame with tile blobs — the hit records lie in two regions per shard (kernels_tile.inc; alt library only)
 // BATCH: the frame is one of a frame batch — the light is the one of the sample's frame (the single-frame instantiations are untouched)
 // RUNS: bounce 0 of a frame with shadow runs (k_beam_shadow, kernels_beam.inc; alt library only) — the shadow ray of a primary hit goes
@@ -1499,15 +1523,9 @@ __device__ __forceinline__ void shade_body(const ShadeArgs& a, const int bounce)
         const float4 h = ld_stream(&f.hit_a[q]);
         const InstanceDev* I = a.sc.inst + inst;
         const uint32_t prim = __float_as_uint(h.w);
-        const uint32_t* ix = a.sc.idx + I->first_index + 3u * prim;
-        const uint32_t ia = ix[0], ib = ix[1], ic = ix[2];
-        const float* vb = a.sc.verts + I->first_float;
-        const float bx = (1.0f - h.y) - h.z, by = h.y, bz = h.z;
-        const float* pa = vb + 6u * ia; const float* pb = vb + 6u * ib; const float* pc = vb + 6u * ic;
-        const F3 pos = fma3(bz, mk3(pc[0], pc[1], pc[2]), fma3(by, mk3(pb[0], pb[1], pb[2]), mul3(mk3(pa[0], pa[1], pa[2]), bx)));
-        const F3 nrm = fma3(bz, mk3(pc[3], pc[4], pc[5]), fma3(by, mk3(pb[3], pb[4], pb[5]), mul3(mk3(pa[3], pa[4], pa[5]), bx)));
-        const F3 P = xform_point(I->o2w, pos);
-        F3 N = normalize3(xform_normal(I->w2o, nrm));
+        const Surface S = hit_surface(a.sc, I, prim, h.y, h.z);
+        const F3 P = S.P;
+        F3 N = S.N;
         const int objectIndex = I->custom_index;
         // src/shader.rgen:96, generalised (row n4): a per-instance type replaces the two-way switch when the host set one,
         // and an MTL material may fix its own type (illum)
@@ -2001,6 +2019,46 @@ void launch_trace_raw(const SceneDev& sc, const float4* ray_o, const float4* ray
 #endif
   if (any_hit) launch_trace<MODE_RAW, true>(a, counting, cfg, s);
   else launch_trace<MODE_RAW, false>(a, counting, cfg, s);
+}
+
+// ---- ray queries (rt_intersect_device): the caller's rays, hits and surfaces stay in device memory
+// The query's own counter block gets the ray count (shard 0 of queue 0) and fresh chunk cursors in stream order: k_trace reads
+// nothing else of it.
+__global__ __launch_bounds__(64) void k_query_init(uint32_t* counters, uint32_t n) {
+  const uint32_t t = threadIdx.x;
+  if (t < (uint32_t)N_SHARDS) { counters[cnt_tail(0, (int)t)] = t == 0u ? n : 0u; counters[cnt_work(0, (int)t)] = 0u; }
+}
+
+void launch_query(const SceneDev& sc, const float4* rays, HitRec* out, uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool any_hit,
+                  const LaunchCfg& cfg, hipStream_t s) {
+  hipLaunchKernelGGL(k_query_init, dim3(1), dim3(64), 0, s, counters, n);
+  TraceArgs a = make_args(sc, counters, 0, n, ovf_stack);
+  a.ray_o = rays; a.raw_out = out;
+  a.rays_per_lane = (uint32_t)cfg.rays_per_lane; a.min_blocks = (uint32_t)cfg.min_blocks;
+  // the persistent grid and the far-ray logic of the record-level entry point (query rays start anywhere)
+  const dim3 g(cfg.trace_blocks), b(256);
+  if (any_hit) hipLaunchKernelGGL((k_trace<MODE_QUERY, true, false, false, true>), g, b, 0, s, a);
+  else hipLaunchKernelGGL((k_trace<MODE_QUERY, false, false, false, true>), g, b, 0, s, a);
+}
+
+// rt_hit_attr of every closest hit: what src/shader.rchit:50-96 computes before it shades (hit_surface), objectIndex = the instance's
+// custom index; a miss gives zeros and objectIndex -1.  A kernel of its own: the traversal's register budget stays what it is.
+__global__ __launch_bounds__(256) void k_hit_attr(SceneDev sc, const HitRec* __restrict__ hits, float4* __restrict__ attr, uint32_t n) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const HitRec h = hits[i];
+  float4 a0 = make_float4(0.f, 0.f, 0.f, __int_as_float(-1)), a1 = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (h.inst >= 0) {
+    const InstanceDev* I = sc.inst + h.inst;
+    const Surface S = hit_surface(sc, I, (uint32_t)h.prim, h.u, h.v);
+    a0 = make_float4(S.P.x, S.P.y, S.P.z, __int_as_float(I->custom_index));
+    a1 = make_float4(S.N.x, S.N.y, S.N.z, 0.f);
+  }
+  attr[2u * (size_t)i] = a0; attr[2u * (size_t)i + 1u] = a1;
+}
+
+void launch_hit_attr(const SceneDev& sc, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s) {
+  hipLaunchKernelGGL(k_hit_attr, dim3((n + 255u) / 256u), dim3(256), 0, s, sc, hits, attr, n);
 }
 
 int tail_blocks_per_cu() {

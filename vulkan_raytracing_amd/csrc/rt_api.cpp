@@ -32,6 +32,7 @@ static_assert(sizeof(rt_uniforms) == sizeof(UniformsDev), "uniform mirrors out o
 static_assert(sizeof(rt_hit) == sizeof(HitRec), "hit mirrors out of sync");
 static_assert(sizeof(rt_mesh_range) == 24, "rt_mesh_range layout");
 static_assert(sizeof(rt_material) == sizeof(MaterialDev), "material mirrors out of sync");
+static_assert(sizeof(rt_hit_attr) == 2 * sizeof(float4), "rt_hit_attr is the two float4 k_hit_attr writes");
 
 namespace {
 
@@ -291,6 +292,15 @@ struct rt_ctx {
   bool debug_force_tail_fault = false;   // rt_set_param "debug_force_tail_fault": treat the next k_tail frame as faulted (tests the fallback)
   uint32_t last_max_bounce = 0;
   uint64_t last_primary = 0;
+  // rt_intersect_device: the query workspace — a counter block and a spill area of its own, so that a query never touches what a
+  // pending frame uses — and the completion event of the last query that read each TLAS parity.  Queries of this context run one
+  // after the other (each one's stream waits for the previous one's event), so the event of the last query covers all of them.
+  uint32_t* d_q_counters = nullptr;
+  int32_t* d_q_ovf = nullptr;
+  size_t q_ovf_alloc = 0;          // int32 entries of d_q_ovf
+  hipEvent_t ev_query[2] = {nullptr, nullptr};
+  bool ev_query_valid[2] = {false, false};
+  int query_last = -1;             // parity of the last query (-1: none since the last host wait)
 };
 
 namespace {
@@ -368,6 +378,7 @@ namespace {
 // concatenate every built mesh into one node array / one packet array with global references (host side), then
 // (re)allocate the device arrays: BLAS part + MAX_SLOTS TLAS regions, and upload the BLAS part
 int alloc_scene_arrays(rt_ctx* c);
+int wait_queries(rt_ctx* c, rt_ctx* m, int parity = -1);
 
 // Cache-line layout of a mesh's quantized nodes: four 32-byte nodes share a 128-byte line of the vector L1, and the step a walk takes
 // most often is parent -> child.  Nodes are laid out in TREELETS of a node and its interior children (1-3 nodes, never split across a
@@ -579,6 +590,7 @@ int link_blas(rt_ctx* c) {
 
 int alloc_scene_arrays(rt_ctx* c) {
   Scene* S = c->scene;
+  for (rt_ctx* m : S->members) { int q = wait_queries(c, m); if (q) return q; }   // (pending queries read the arrays freed here)
   const size_t regions = (size_t)2 * MAX_SLOTS * S->tlas_cap;
   if (S->d_blas_nodes) { HIP_TRY(c, hipFree(S->d_blas_nodes)); S->d_blas_nodes = nullptr; }
   if (S->d_nodes4) { HIP_TRY(c, hipFree(S->d_nodes4)); S->d_nodes4 = nullptr; }
@@ -792,9 +804,20 @@ int quiesce(rt_ctx* c) {
   if (c->frame_pending) return collect_stats(c);
   return RT_OK;
 }
-// Calls that rewrite the SHARED scene wait for the frames of every slot that renders from it.
+// Ray queries (rt_intersect_device) of context m: the host waits for the last query that read TLAS parity `parity` (-1: for the last
+// query of all, which, queries being serialised, covers every one).  Reports on c.
+int wait_queries(rt_ctx* c, rt_ctx* m, int parity) {
+  const int p = parity < 0 ? m->query_last : parity;
+  if (p < 0 || !m->ev_query_valid[p]) return RT_OK;
+  HIP_TRY(c, hipEventSynchronize(m->ev_query[p]));
+  m->ev_query_valid[p] = false;
+  if (parity < 0 || p == m->query_last) { m->ev_query_valid[0] = m->ev_query_valid[1] = false; m->query_last = -1; }   // (what ran before it is done too)
+  return RT_OK;
+}
+// Calls that rewrite the SHARED scene wait for the frames and the ray queries of every slot that renders from it.
 int quiesce_scene(rt_ctx* c) {
   for (rt_ctx* m : c->scene->members) {
+    { int q = wait_queries(c, m); if (q) return q; }
     if (m->async_pending) return fail(c, RT_ERR_NOT_READY, "a frame slot of this scene has a frame pending (rt_trace_async): collect it with rt_trace_wait first");
     if (m->frame_pending) { int r = collect_stats(m); if (r) { if (m != c) c->error = m->error; return r; } }
     for (int k = 0; k < 2; k++)
@@ -1396,6 +1419,7 @@ void rt_destroy(rt_ctx* c) {
   if (!c) return;
   live_slots_add(c->device, -1);
   hipSetDevice(c->device);
+  wait_queries(c, c);   // the query workspace is freed below
   hipDeviceSynchronize();
   FrameDev& f = c->frame;
   void* ptrs[] = {c->d_inst[0], c->d_inst[1], c->d_out_own, c->d_counters, c->d_ovf, c->d_cover_mask, c->d_entry, c->d_light_entry, f.sh_e, c->d_fault_total, c->d_tile_blob, c->d_blob_arena, c->d_blob_list,
@@ -1406,6 +1430,9 @@ void rt_destroy(rt_ctx* c) {
   if (c->h_stats) hipHostFree(c->h_stats);
   for (int k = 0; k < 2; k++) { if (c->h_stage[k]) hipHostFree(c->h_stage[k]); if (c->ev_frame[k]) hipEventDestroy(c->ev_frame[k]); }
   for (int k = 0; k < 2; k++) if (c->ev_upload[k]) hipEventDestroy(c->ev_upload[k]);
+  if (c->d_q_counters) hipFree(c->d_q_counters);
+  if (c->d_q_ovf) hipFree(c->d_q_ovf);
+  for (int k = 0; k < 2; k++) if (c->ev_query[k]) hipEventDestroy(c->ev_query[k]);
   tlas_gpu_free(c->tgpu);
   for (auto e : c->ev_pool) hipEventDestroy(e);
   if (c->stream) hipStreamDestroy(c->stream);
@@ -1519,6 +1546,7 @@ static int set_instances_frames(rt_ctx* c, const rt_instance* inst, int n, int u
   // before that one (usually long finished) — a per-frame update never stalls the host on the frame in flight.
   const int next_parity = c->parity ^ 1;
   if (c->ev_frame_valid[next_parity]) { HIP_TRY(c, hipEventSynchronize(c->ev_frame[next_parity])); c->ev_frame_valid[next_parity] = false; }
+  { int q = wait_queries(c, c, next_parity); if (q) return q; }   // ... and for the ray queries that read it
   if (c->upload_inflight[next_parity]) { HIP_TRY(c, hipEventSynchronize(c->ev_upload[next_parity])); c->upload_inflight[next_parity] = false; }   // its staging buffer is rewritten
   const int total = n * K;
   for (int i = 0; i < total; i++) {
@@ -1626,6 +1654,7 @@ static int set_instances_device(rt_ctx* c, const void* d_instances, int n, int u
   Scene* S = c->scene;
   const int next_parity = c->parity ^ 1;
   if (c->ev_frame_valid[next_parity]) { HIP_TRY(c, hipEventSynchronize(c->ev_frame[next_parity])); c->ev_frame_valid[next_parity] = false; }
+  { int q = wait_queries(c, c, next_parity); if (q) return q; }   // ... and for the ray queries that read it
   if (c->upload_inflight[next_parity]) { HIP_TRY(c, hipEventSynchronize(c->ev_upload[next_parity])); c->upload_inflight[next_parity] = false; }
   if (!S->blas_linked) {   // (re)linking moves the shared arrays: every slot of the scene has to be idle
     int q = quiesce_scene(c); if (q) return q;
@@ -2184,6 +2213,59 @@ int rt_intersect(rt_ctx* c, size_t n, const float* rays8, int any_hit, rt_hit* o
     stats->closest_rays = any_hit ? 0 : n; stats->rays_shadow = any_hit ? n : 0;
     stats->bvh_node_bytes = c->cfg.variant == 1 ? sizeof(Bvh4Node) : c->cfg.variant == 2 ? sizeof(WideNodeQ) : sizeof(BvhNodeQ); stats->bvh_tri_bytes = sizeof(TriPacket);
   }
+  return RT_OK;
+}
+
+// VK_KHR_ray_query for device-resident rays: rt_intersect's traversal (k_trace<MODE_QUERY>: the one-lane BVH2 walk with the far-ray logic)
+// on the caller's rays, hits and surfaces, ordered on the caller's stream.  Nothing is copied, nothing waits on the host, and no frame
+// is waited for: the query has its own counter block and spill area.  What it reads of the context — the TLAS of the current parity
+// and the shared scene — is kept alive by its event: set_instances_* wait for it before they rewrite that parity, quiesce_scene and
+// rt_destroy before the scene or the workspace go.
+int rt_intersect_device(rt_ctx* c, size_t n, const void* d_rays8, int any_hit, void* d_hits, void* d_attr, void* hip_stream) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, "too many rays for one call");
+  if (any_hit && d_attr) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device: hit attributes are for closest-hit queries only (any_hit skips the closest-hit shader)");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device needs trace_variant 0");
+  if (n) {
+    if (!d_rays8 || !d_hits) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device: null ray/hit pointers");
+    if (((uintptr_t)d_rays8 & 15u) || ((uintptr_t)d_hits & 3u) || ((uintptr_t)d_attr & 15u))
+      return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device: rays and attributes must be 16-byte aligned, hits 4-byte aligned");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const void* ptrs[3] = {d_rays8, d_hits, d_attr};
+    for (const void* p : ptrs) {
+      if (!p) continue;
+      hipPointerAttribute_t at{};
+      const bool ok = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == c->device;
+      (void)hipGetLastError();   // (a host pointer leaves an error behind)
+      if (!ok) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device: rays, hits and attributes must be device memory of the context's GPU (" + std::to_string(c->device) + ")");
+    }
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  int r = ready_to_trace(c); if (r) return r;
+  if (n == 0) return RT_OK;
+  const hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+  // the workspace: allocated at the first query; the spill area re-sized (after the last query is done) when the trees grew
+  if (!c->d_q_counters) HIP_TRY(c, hipMalloc((void**)&c->d_q_counters, CNT_WORDS * sizeof(uint32_t)));
+  const size_t ovf_need = ovf_elems(c->cfg.trace_blocks, c->tail_blocks, c->ovf_stride);
+  if (ovf_need > c->q_ovf_alloc) {
+    { int q = wait_queries(c, c); if (q) return q; }
+    if (c->d_q_ovf) HIP_TRY(c, hipFree(c->d_q_ovf));
+    c->d_q_ovf = nullptr; c->q_ovf_alloc = 0;
+    HIP_TRY(c, hipMalloc((void**)&c->d_q_ovf, ovf_need * sizeof(int32_t)));
+    c->q_ovf_alloc = ovf_need;
+  }
+  for (int k = 0; k < 2; k++)
+    if (!c->ev_query[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_query[k], hipEventDisableTiming));
+  // device-side ordering: behind the previous query of this context (its workspace), and behind the copies or the build of the TLAS
+  if (c->query_last >= 0) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_query[c->query_last], 0));
+  if (c->upload_inflight[c->parity]) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_upload[c->parity], 0));
+  const SceneDev sc = scene_dev(c);
+  launch_query(sc, (const float4*)d_rays8, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, any_hit != 0, c->cfg, s);
+  if (d_attr) launch_hit_attr(sc, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipEventRecord(c->ev_query[c->parity], s));
+  c->ev_query_valid[c->parity] = true;
+  c->query_last = c->parity;
   return RT_OK;
 }
 

@@ -174,6 +174,12 @@ void launch_cover(const SceneDev& sc, const CoverViews& a, uint32_t max_boxes_pe
 // counters must hold the ray count in cnt_tail(0, 0) and zeros elsewhere; rays form shard 0 of capacity shard_cap
 void launch_trace_raw(const SceneDev& sc, const float4* ray_o, const float4* ray_d, HitRec* out, uint32_t shard_cap,
                       int32_t* ovf_stack, uint32_t* counters, bool any_hit, bool counting, const LaunchCfg& cfg, hipStream_t s);
+// rt_intersect_device: the same traversal on the caller's rays, 8 floats each (o.xyz, tmin, d.xyz, tmax), in stream order; counters is a
+// counter block of its own (k_query_init writes the ray count into it) and ovf_stack a spill area sized like the context's
+void launch_query(const SceneDev& sc, const float4* rays, HitRec* out, uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool any_hit,
+                  const LaunchCfg& cfg, hipStream_t s);
+// rt_hit_attr (two float4) of every closest hit of `hits`
+void launch_hit_attr(const SceneDev& sc, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s);
 
 // de-interleave n_shards gathered compact shards (shard_stride_px pixels apart) into the width x height frame
 void launch_assemble(const void* gathered, void* out, int width, int height, int band_rows, int n_shards, size_t shard_stride_px, bool rgba8, hipStream_t s);

@@ -53,8 +53,9 @@ typedef struct rt_mesh_range {
 typedef struct rt_instance {
   float transform[12];              /* row-major 3x4 object->world (glmToVulkan, src/main.cpp:245-249) */
   uint32_t custom_index_and_mask;   /* instanceCustomIndex:24 (low) | mask:8 (high) */
-  uint32_t sbt_offset_and_flags;    /* instanceShaderBindingTableRecordOffset:24 | flags:8 (ignored: the
-                                       reference always uses offset 0 / TRIANGLE_FACING_CULL_DISABLE) */
+  uint32_t sbt_offset_and_flags;    /* instanceShaderBindingTableRecordOffset:24 | flags:8 (RT_INSTANCE_FLAG_*: read by
+                                       rt_intersect_device_flags only; frames ignore them, as the reference, which always uses
+                                       offset 0 / TRIANGLE_FACING_CULL_DISABLE) */
   uint64_t mesh;                    /* index into rt_mesh_range[] — replaces accelerationStructureReference.
                                        RULE: the closest-hit stage reads the index/vertex range of THIS mesh.  The reference
                                        picks the range from instanceCustomIndex instead (src/shader.rchit:52-58: index 0 -> no
@@ -332,6 +333,52 @@ typedef struct rt_hit_attr {
  * any_hit != 0 (Vulkan's any hit here is SkipClosestHit), trace_variant != 0; RT_ERR_NOT_READY: as for a frame (no geometry, no TLAS,
  * a TLAS stale after rt_refit_blas_device, a frame batch held by the context). */
 int rt_intersect_device(rt_ctx* ctx, size_t n, const void* d_rays8, int any_hit, void* d_hits, void* d_attr, void* hip_stream);
+
+/* Ray flags and cull masks per query (rayQueryInitializeEXT(rq, tlas, rayFlags, cullMask, origin, tMin, direction, tMax)).  The values
+ * are those of gl_RayFlags*EXT / SPIR-V RayFlags; the reference traces with Opaque (primary rays) and Opaque | TerminateOnFirstHit |
+ * SkipClosestHit = 13 (shadow rays), cull mask 0xFF (src/shader.rgen:66-67). */
+#define RT_RAY_FLAG_OPAQUE                 0x001u
+#define RT_RAY_FLAG_NO_OPAQUE              0x002u
+#define RT_RAY_FLAG_TERMINATE_ON_FIRST_HIT 0x004u
+#define RT_RAY_FLAG_SKIP_CLOSEST_HIT       0x008u   /* no effect on a query */
+#define RT_RAY_FLAG_CULL_BACK_FACING       0x010u
+#define RT_RAY_FLAG_CULL_FRONT_FACING      0x020u
+#define RT_RAY_FLAG_CULL_OPAQUE            0x040u
+#define RT_RAY_FLAG_CULL_NO_OPAQUE         0x080u
+#define RT_RAY_FLAG_SKIP_TRIANGLES         0x100u
+#define RT_RAY_FLAG_SKIP_AABBS             0x200u   /* no effect: there are no AABB geometries */
+/* VkGeometryInstanceFlagBitsKHR, in the high byte of rt_instance::sbt_offset_and_flags */
+#define RT_INSTANCE_FLAG_FACING_CULL_DISABLE 0x1u
+#define RT_INSTANCE_FLAG_FLIP_FACING         0x2u
+#define RT_INSTANCE_FLAG_FORCE_OPAQUE        0x4u
+#define RT_INSTANCE_FLAG_FORCE_NO_OPAQUE     0x8u
+/* hit kinds in rt_hit_attr::reserved (gl_HitKindFrontFacingTriangleEXT / BackFacing), 0 on a miss */
+#define RT_HIT_KIND_FRONT_FACING 0xFEu
+#define RT_HIT_KIND_BACK_FACING  0xFFu
+
+/* rt_intersect_device with per-ray flags and cull masks.  Rays, hits, attributes, stream, ordering, workspace and RT_ERR_NOT_READY are
+ * those of rt_intersect_device.  d_ray_words, optional, is n uint32 in device memory of ctx's GPU (4-B aligned), read in stream order
+ * like the rays: bits 0-9 are ray flags, bits 24-31 the ray's cull mask, bits 10-23 are ignored.  Ray i traces with
+ * flags = ray_flags | (word & 0x3FF) and cull mask = cull_mask & (word >> 24); a NULL array acts as words of 0xFF000000.
+ *  - cull mask: an instance with (mask & cull) == 0 is not entered;
+ *  - opacity: every geometry is opaque (the reference builds them with VK_GEOMETRY_OPAQUE_BIT_KHR, src/main.cpp:330).  The ray's
+ *    OPAQUE / NO_OPAQUE decides first (OPAQUE if a word sets both), then the instance's FORCE_OPAQUE / FORCE_NO_OPAQUE (FORCE_OPAQUE
+ *    first).  SKIP_TRIANGLES, CULL_OPAQUE on opaque and CULL_NO_OPAQUE on non-opaque triangles skip the instance.  There is no
+ *    candidate / confirm loop: a non-opaque triangle is committed as if the caller confirmed every candidate;
+ *  - facing, decided in object space (an instance transform, mirroring included, does not change it): a triangle is FRONT-FACING when
+ *    det = dot(e1, cross(d, e2)) < 0 (e1 = v1 - v0, e2 = v2 - v0, d the object-space direction), i.e. its vertices appear clockwise
+ *    from the ray origin in a right-handed object space (the DXR / VK_NV_ray_tracing default; VK_KHR's FLIP_FACING is aliased
+ *    TRIANGLE_FRONT_COUNTERCLOCKWISE).  FLIP_FACING inverts it.  CULL_BACK_FACING / CULL_FRONT_FACING reject triangles before they can be
+ *    accepted, unless the instance has FACING_CULL_DISABLE (rt_host.hpp's make_instance sets it on every instance, as the reference);
+ *  - TERMINATE_ON_FIRST_HIT: the ray stops at its first accepted hit (rt_intersect_device's any_hit = 1); closest-hit and first-hit
+ *    rays may be mixed in one call.
+ * d_attr (optional, also for first-hit rays) receives rt_intersect_device's P, N and objectIndex, and the hit kind in `reserved`
+ * (RT_HIT_KIND_*, 0 on a miss).
+ * RT_ERR_INVALID_ARGUMENT: as for rt_intersect_device, and d_ray_words misaligned or not memory of ctx's GPU; ray_flags with bits
+ * outside 0x3FF, cull_mask > 0xFF, more than one of OPAQUE, NO_OPAQUE, CULL_OPAQUE and CULL_NO_OPAQUE, both facing culls, or
+ * SKIP_TRIANGLES with SKIP_AABBS or a facing cull (Vulkan's valid-usage rules).  Per-ray words are not validated (that would need a
+ * host round trip): they follow the formulas above as written. */
+int rt_intersect_device_flags(rt_ctx* ctx, size_t n, const void* d_rays8, const void* d_ray_words, uint32_t ray_flags, uint32_t cull_mask, void* d_hits, void* d_attr, void* hip_stream);
 
 /* Same frame as rt_trace but through the instrumented traversal kernels (visit counters). */
 int rt_trace_counting(rt_ctx* ctx, int width, int height, float* out_rgba32f_host, rt_stats* stats);

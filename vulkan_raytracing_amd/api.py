@@ -38,9 +38,29 @@ class RtStats(C.Structure):
         return self.rays_primary + self.rays_secondary + self.rays_shadow
 
 
+# rt_intersect_device_flags (include/rt_api.h): gl_RayFlags*EXT values, VkGeometryInstanceFlagBitsKHR (high byte of sbt_offset_and_flags),
+# and the hit kinds RayQuery.hit_kind reports
+RAY_FLAG_NONE = 0x000
+RAY_FLAG_OPAQUE = 0x001
+RAY_FLAG_NO_OPAQUE = 0x002
+RAY_FLAG_TERMINATE_ON_FIRST_HIT = 0x004
+RAY_FLAG_SKIP_CLOSEST_HIT = 0x008
+RAY_FLAG_CULL_BACK_FACING = 0x010
+RAY_FLAG_CULL_FRONT_FACING = 0x020
+RAY_FLAG_CULL_OPAQUE = 0x040
+RAY_FLAG_CULL_NO_OPAQUE = 0x080
+RAY_FLAG_SKIP_TRIANGLES = 0x100
+RAY_FLAG_SKIP_AABBS = 0x200
+INSTANCE_FLAG_FACING_CULL_DISABLE = 0x1
+INSTANCE_FLAG_FLIP_FACING = 0x2
+INSTANCE_FLAG_FORCE_OPAQUE = 0x4
+INSTANCE_FLAG_FORCE_NO_OPAQUE = 0x8
+HIT_KIND_FRONT_FACING = 0xFE
+HIT_KIND_BACK_FACING = 0xFF
+
 EXPORTS = ["rt_create", "rt_create_frame_slot", "rt_destroy", "rt_upload_geometry", "rt_build_blas", "rt_set_instances", "rt_set_instances_device", "rt_refit_blas_device", "rt_set_materials", "rt_set_instance_types", "rt_set_uniforms", "rt_set_skybox",
            "rt_trace", "rt_trace_async", "rt_trace_wait", "rt_trace_shard", "rt_set_batch", "rt_trace_shard_batch", "rt_assemble_shards", "rt_shard_rows", "rt_synchronize", "rt_get_stats", "rt_set_timing", "rt_intersect",
-           "rt_trace_counting", "rt_intersect_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
+           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_set_param", "rt_debug_check_builders", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
 
 _LIBS = {}
 
@@ -81,6 +101,7 @@ def lib(variant=None):
         L.rt_debug_sizing.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, vp]
         L.rt_intersect.argtypes = [vp, C.c_size_t, vp, C.c_int, vp, C.c_int, C.POINTER(RtStats)]
         L.rt_intersect_device.argtypes = [vp, C.c_size_t, vp, C.c_int, vp, vp, vp]
+        L.rt_intersect_device_flags.argtypes = [vp, C.c_size_t, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
         L.rt_last_error.argtypes = [vp]
         L.rt_last_error.restype = C.c_char_p
         L.rt_device_info.argtypes = [vp]
@@ -309,6 +330,36 @@ class RtContext:
         results are written in that order too, and the call never waits on the host.  Returns a RayQuery of zero-copy views over one
         int32 (n, 5) hits buffer (rt_hit: t, u, v, prim, inst) and, with attributes=True (closest-hit queries only), one int32 (n, 8)
         attribute buffer (rt_hit_attr: position, object_index, normal, reserved).  out = (hits, attr) reuses such buffers."""
+        def call(run, hits, attr):
+            return self.L.rt_intersect_device(self.h, rays.shape[0], C.c_void_p(rays.data_ptr()), int(any_hit), C.c_void_p(hits.data_ptr()),
+                                              C.c_void_p(attr.data_ptr()) if attr is not None else None, C.c_void_p(run.cuda_stream))
+        hits, attr = self._device_query(rays, attributes, stream, out, (), call, "rt_intersect_device")
+        return RayQuery(hits, attr)
+
+    def intersect_device_flags(self, rays, ray_flags=0, cull_mask=0xFF, words=None, attributes=False, stream=None, out=None):
+        """rt_intersect_device_flags: intersect_device with rayQueryInitializeEXT's rayFlags and cullMask, for the whole call and per ray.
+        `words`, optional, is an int32 or uint32 (n,) tensor on the context's GPU: bits 0-9 ray flags, bits 24-31 the ray's cull mask
+        (ray i traces with ray_flags | (word & 0x3FF) and cull_mask & (word >> 24)).  Attributes are allowed for first-hit rays too, and
+        RayQuery.hit_kind holds the hit kind (HIT_KIND_FRONT_FACING / HIT_KIND_BACK_FACING, 0 on a miss).  See include/rt_api.h."""
+        import torch
+        n = rays.shape[0] if isinstance(rays, torch.Tensor) else 0
+        if words is not None:
+            if not isinstance(words, torch.Tensor):
+                raise TypeError("words must be a torch tensor, got %s" % type(words).__name__)
+            if words.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+                raise ValueError("words must be int32 or uint32, not %s" % words.dtype)
+            if words.device != getattr(rays, "device", None) or not words.is_contiguous() or tuple(words.shape) != (n,):
+                raise ValueError("words must be a contiguous (n,) tensor on the rays' device")
+
+        def call(run, hits, attr):
+            return self.L.rt_intersect_device_flags(self.h, n, C.c_void_p(rays.data_ptr()), C.c_void_p(words.data_ptr()) if words is not None and n else None,
+                                                    int(ray_flags) & 0xFFFFFFFF, int(cull_mask) & 0xFFFFFFFF, C.c_void_p(hits.data_ptr()),
+                                                    C.c_void_p(attr.data_ptr()) if attr is not None else None, C.c_void_p(run.cuda_stream))
+        hits, attr = self._device_query(rays, attributes, stream, out, (words,), call, "rt_intersect_device_flags")
+        return RayQuery(hits, attr, hit_kind=True)
+
+    def _device_query(self, rays, attributes, stream, out, inputs, call, name):
+        """the common part of intersect_device*: checks, output buffers, the null-stream detour; call(run_stream, hits, attr) -> status"""
         import torch
         if not isinstance(rays, torch.Tensor):
             raise TypeError("intersect_device takes a torch tensor, got %s" % type(rays).__name__)
@@ -348,22 +399,20 @@ class RtContext:
                     self._query_stream = torch.cuda.Stream(rays.device)
                 run = self._query_stream
                 run.wait_stream(stream)
-                for t in (rays, hits, attr):
+                for t in (rays, hits, attr) + tuple(inputs):
                     if t is not None:
                         t.record_stream(run)
-            self._chk(self.L.rt_intersect_device(self.h, n, C.c_void_p(rays.data_ptr()), int(any_hit), C.c_void_p(hits.data_ptr()),
-                                                 C.c_void_p(attr.data_ptr()) if attr is not None else None, C.c_void_p(run.cuda_stream)),
-                      "rt_intersect_device")
+            self._chk(call(run, hits, attr), name)
             if run is not stream:
                 stream.wait_stream(run)
-        return RayQuery(hits, attr)
+        return hits, attr
 
 
 class RayQuery:
     """Results of RtContext.intersect_device: views over the hits buffer (int32 (n, 5), rt_hit) and the optional attribute buffer
     (int32 (n, 8), rt_hit_attr).  Misses have prim = inst = -1, and zero position / normal with object_index -1."""
 
-    def __init__(self, hits, attr):
+    def __init__(self, hits, attr, hit_kind=False):
         import torch
         self.hits, self.attr = hits, attr
         f = hits[:, 0:3].view(torch.float32)
@@ -375,6 +424,8 @@ class RayQuery:
             self.normal = attr[:, 4:7].view(torch.float32)
         else:
             self.position = self.normal = self.object_index = None
+        # intersect_device_flags with attributes: the hit kind (HIT_KIND_FRONT_FACING / HIT_KIND_BACK_FACING, 0 on a miss); None otherwise
+        self.hit_kind = attr[:, 7] if (hit_kind and attr is not None) else None
 
     def numpy(self):
         """the hit records as rt_intersect returns them (HIT_DTYPE), and the attributes as (n, 8) int32 (or None); synchronises"""

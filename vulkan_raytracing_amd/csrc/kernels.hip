@@ -256,6 +256,54 @@ __device__ __forceinline__ bool tri_test(const float4 T0, const float4 T1, const
   t = tt; u = un * inv; v = vn * inv;
   return true;
 }
+// tri_test with a facing cull (ray queries, MODE_QUERY_FLAGS): facing_cull & QF_CULL_NEG rejects the triangle when det < 0,
+// & QF_CULL_POS when det > 0, before it can be accepted.  The arithmetic is tri_test's, operation for operation, so t, u, v of an
+// accepted triangle are bit-identical to it.  (A copy rather than tri_test calling it with 0: the extra branch, folded away or not,
+// reschedules the kernels that call tri_test.)
+__device__ __forceinline__ bool tri_test_facing(const float4 T0, const float4 T1, const float4 T2, F3 co, F3 cd, float tmin, float tmax, uint32_t facing_cull,
+                                                float& t, float& u, float& v) {
+  const F3 v0 = mk3(T0.x, T0.y, T0.z), e1 = mk3(T0.w, T1.x, T1.y), e2 = mk3(T1.z, T1.w, T2.x);
+  const F3 p = cross3(cd, e2);
+  const float det = dot3(e1, p);
+  const F3 s = sub3(co, v0);
+  float un = dot3(s, p);
+  const F3 qv = cross3(s, e1);
+  float vn = dot3(cd, qv);
+  float tn = dot3(e2, qv);
+  const float da = __builtin_fabsf(det);
+  if (det < 0.0f) { un = -un; vn = -vn; tn = -tn; }
+  if (!((un >= 0.0f) && (vn >= 0.0f) && (un + vn <= da) && (da > 0.0f))) return false;
+  if ((facing_cull & (det < 0.0f ? QF_CULL_NEG : QF_CULL_POS)) != 0u) return false;
+  const float inv = 1.0f / da;
+  const float tt = tn * inv;
+  if (!((tt > tmin) && (tt < tmax))) return false;
+  t = tt; u = un * inv; v = vn * inv;
+  return true;
+}
+
+// Ray query flags (MODE_QUERY_FLAGS) where a ray reaches an instance: does the ray with query word w enter the instance with mask word
+// imask (mask | flags << 8, InstanceDev::mask)?  If it does, `cull` gets the facing its triangles reject (QF_CULL_NEG / QF_CULL_POS).
+//  * cull mask: (instance mask & the ray's) == 0 hides the instance;
+//  * opacity: every geometry is built opaque (src/main.cpp:330); the ray's OPAQUE / NO_OPAQUE decides first, then the instance's
+//    FORCE_OPAQUE / FORCE_NO_OPAQUE.  SkipTriangles, CullOpaque on opaque and CullNoOpaque on non-opaque triangles skip the instance
+//    (there are no AABB geometries, and every triangle of an instance has the same opacity);
+//  * facing, in object space: front-facing <=> (det < 0) == FRONT_IS_DET_NEGATIVE, inverted by FLIP_FACING; FACING_CULL_DISABLE
+//    turns the ray's facing culls off.
+constexpr bool FRONT_IS_DET_NEGATIVE = true;   // det = dot(e1, cross(d, e2)) < 0: clockwise seen from the origin (right-handed object space)
+__device__ __forceinline__ bool query_enters(uint32_t w, uint32_t imask, uint32_t& cull) {
+  const uint32_t f = imask >> 8;
+  cull = 0u;
+  if ((imask & (w >> 24) & 0xFFu) == 0u) return false;
+  const bool opaque = (w & QF_OPAQUE) ? true : (w & QF_NO_OPAQUE) ? false : (f & INST_FLAG_FORCE_OPAQUE) ? true : (f & INST_FLAG_FORCE_NO_OPAQUE) == 0u;
+  if ((w & QF_SKIP_TRIANGLES) != 0u || (w & (opaque ? QF_CULL_OPAQUE : QF_CULL_NO_OPAQUE)) != 0u) return false;
+  if ((f & INST_FLAG_FACING_CULL_DISABLE) == 0u) {
+    const bool neg_front = FRONT_IS_DET_NEGATIVE != ((f & INST_FLAG_FLIP_FACING) != 0u);
+    const bool cull_front = (w & QF_CULL_FRONT) != 0u, cull_back = (w & QF_CULL_BACK) != 0u;
+    if (neg_front ? cull_front : cull_back) cull |= QF_CULL_NEG;
+    if (neg_front ? cull_back : cull_front) cull |= QF_CULL_POS;
+  }
+  return true;
+}
 
 // x / 255.0f without the ten-instruction IEEE division sequence: q = x*rc, one fma for the exact remainder, one fma
 // to correct q (rc = RN(1/255)).  The result equals the IEEE quotient — which is what the canonical definition and
@@ -888,17 +936,24 @@ struct TraceArgs {
   HitRec* raw_out;             // raw mode
   int32_t* ovf_stack;
   uint32_t* counters;
-  float tmin;
+  union {
+    float tmin;                // the pipeline's one tmin (record-level rays carry their own)
+    uint32_t query_word;       // MODE_QUERY_FLAGS: the call's ray flags | cull mask << 24
+  };
   uint32_t rays_per_lane;      // device-side grid sizing (variant 0): blocks beyond total/(256*rays_per_lane) exit
   uint32_t min_blocks;
   const EntryRec* entry;       // ENTRY kernels: the tile records of k_entry (closest hit: the ray carries its tile in o.w;
-  const uint32_t* sh_e;        // shadow: record index | ENTRY_REVERSE of every shadow-queue entry, written by k_shade)
+  union {
+    const uint32_t* sh_e;      // shadow: record index | ENTRY_REVERSE of every shadow-queue entry, written by k_shade)
+    const uint32_t* ray_words; // MODE_QUERY_FLAGS: the caller's per-ray words (flags | cull mask << 24), or null: every word 0xFF000000
+  };
 };
 
 constexpr int MODE_CLOSEST = 0;  // pipeline closest hit: o.w = tmax, d.w = sid
 constexpr int MODE_SHADOW = 1;   // pipeline any hit + shading epilogue
 constexpr int MODE_RAW = 2;      // o.w = tmin, d.w = tmax; writes HitRec
 constexpr int MODE_QUERY = 3;    // MODE_RAW on the caller's rays as they are (rt_intersect_device): ray i is the float4 pair ray_o[2i], ray_o[2i + 1]
+constexpr int MODE_QUERY_FLAGS = 4;   // MODE_QUERY with ray flags and a cull mask per ray (rt_intersect_device_flags): any hit is a per-ray bit
 
 
 // ---- variant 0: BVH2, ONE LANE PER RAY, persistent threads with per-lane refill.
@@ -953,12 +1008,14 @@ constexpr uint32_t REFILL_MIN = RT_REFILL_MIN;
 // their ray can still reach (mask in o.w).
 template <int MODE, bool ANY, bool COUNT, bool WIDE, bool ENTRY = false, bool FAR = true, bool CONT = false>
 __device__ __forceinline__ void trace_body(const TraceArgs& a) {
-  constexpr bool RAYS8 = MODE == MODE_RAW || MODE == MODE_QUERY;   // record-level rays: per-ray tmin and tmax, HitRec results
+  constexpr bool QUERY = MODE == MODE_QUERY || MODE == MODE_QUERY_FLAGS;   // the caller's 32-byte rays
+  constexpr bool RAYS8 = MODE == MODE_RAW || QUERY;   // record-level rays: per-ray tmin and tmax, HitRec results
+  constexpr bool QF = MODE == MODE_QUERY_FLAGS;
   __shared__ int s_stack[4][STACK2_LDS + 1][64];   // + one scratch row: lanes that do not push write there (fast_step)
   __shared__ float4 s_rays[4][2][64];
   __shared__ float4 s_out[4][64];
   __shared__ int2 s_outq[4][64];
-  __shared__ uint32_t s_ent[(ENTRY && MODE == MODE_SHADOW) ? 4 : 1][64];   // entry record of every ray of the current chunk
+  __shared__ uint32_t s_ent[((ENTRY && MODE == MODE_SHADOW) || QF) ? 4 : 1][64];   // entry record (query word) of every ray of the current chunk
   // Instance records staged through LDS: what "enter the instance" reads (world->object rows, dequantisation, root, mask)
   // for the first LDS_INSTANCES instances, 80 bytes each.  That phase runs for a quarter of the lanes at a time and was
   // spending ~1200 cycles per pass on the global-memory latency of these few, shared records.
@@ -1007,9 +1064,13 @@ __device__ __forceinline__ void trace_body(const TraceArgs& a) {
       shard = (shard + 1u) & (N_SHARDS - 1); tried++;
     }
     if (lane < pf_count) {
-      if constexpr (MODE == MODE_QUERY) {   // (o.xyz, tmin, d.xyz, tmax): 32 bytes per ray, read where the caller left them
+      if constexpr (QUERY) {   // (o.xyz, tmin, d.xyz, tmax): 32 bytes per ray, read where the caller left them
         const size_t r = 2u * (size_t)(pf_base + lane);
         pf_o = ld_stream(&a.ray_o[r]); pf_d = ld_stream(&a.ray_o[r + 1u]);
+        if (QF) {   // the ray's effective word: the call's flags | the ray's, the call's cull mask & the ray's
+          const uint32_t w = a.ray_words ? (uint32_t)ld_stream(reinterpret_cast<const int*>(a.ray_words) + pf_base + lane) : 0xFF000000u;
+          pf_e = ((a.query_word | w) & QF_FLAGS) | (a.query_word & w & 0xFF000000u);
+        }
       } else {
         pf_o = ld_stream(&a.ray_o[pf_base + lane]); pf_d = ld_stream(&a.ray_d[pf_base + lane]);
       }
@@ -1018,7 +1079,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& a) {
   };
   auto promote = [&]() {
     s_rays[wave][0][lane] = pf_o; s_rays[wave][1][lane] = pf_d;
-    if (ENTRY && MODE == MODE_SHADOW) s_ent[wave][lane] = pf_e;
+    if ((ENTRY && MODE == MODE_SHADOW) || QF) s_ent[wave][lane] = pf_e;
     chunk_base = pf_base; chunk_count = pf_count; chunk_pos = 0;
     prefetch();
   };
@@ -1052,6 +1113,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& a) {
   bool need = true;
   uint32_t q = 0, sid = 0;
   float tmin_ray = 0.f, tmax = 0.f;   // tmin is a per-ray value only in the raw mode; the pipeline uses one constant
+  uint32_t qword = 0;   // QF: the ray's query word (QF_*), with the facing cull of its current instance in bits 10-11
   F3 wo = mk3(0, 0, 0), wd = mk3(0, 0, 1), co = wo, cd = wd, qs = mk3(1, 1, 1), qb = mk3(0, 0, 0);
   uint3 rot = make_uint3(0u, 0u, 0u);
   bool far = false;   // quant_far() of the current space: this lane's visits take the generic path with the widened slab test
@@ -1109,6 +1171,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& a) {
           const float4 ro = s_rays[wave][0][ci], rd = s_rays[wave][1][ci];
           if (RAYS8) { tmin_ray = ro.w; tmax = rd.w; }
           else { tmax = ro.w; sid = __float_as_uint(rd.w); }
+          if (QF) qword = s_ent[wave][ci];
           wo = mk3(ro.x, ro.y, ro.z); wd = mk3(rd.x, rd.y, rd.z);
           co = wo; cd = wd;
           cur_inst = -1;
@@ -1336,6 +1399,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& a) {
       // BLAS leaf: Moller-Trumbore on 48-byte packets.  The entry popped after a leaf is often a leaf again (the far child of a
       // bottom node whose two children were both hit): up to RT_LEAF_CHAIN leaves are tested in one visit of this phase, instead of
       // one outer pass each — passes, not node visits, are what a ray's life is counted in.
+      const bool any_ray = ANY || (QF && (qword & QF_TERMINATE) != 0u);   // (QF: TerminateOnFirstHit, a per-ray bit)
       for (int chain = 0; chain < RT_LEAF_CHAIN; chain++) {
         const uint32_t ref = (uint32_t)(~cur);
         const uint32_t first = ref >> 3, count = (ref & 7u) + 1u;
@@ -1345,7 +1409,10 @@ __device__ __forceinline__ void trace_body(const TraceArgs& a) {
           if (COUNT) cnt_tris++;
           float tt, uu, vv;
           // (the closest-hit pipeline's primary rays all have tmax 10000, src/shader.rgen:87: a constant for the ENTRY kernel, not a register)
-          if (tri_test(T0, T1, T2, co, cd, (RAYS8 ? tmin_ray : a.tmin), (ANY ? best_t : ((ENTRY && MODE == MODE_CLOSEST) ? 10000.0f : tmax)), tt, uu, vv)) {
+          bool acc;
+          if constexpr (QF) acc = tri_test_facing(T0, T1, T2, co, cd, tmin_ray, any_ray ? best_t : tmax, qword, tt, uu, vv);
+          else acc = tri_test(T0, T1, T2, co, cd, (RAYS8 ? tmin_ray : a.tmin), (ANY ? best_t : ((ENTRY && MODE == MODE_CLOSEST) ? 10000.0f : tmax)), tt, uu, vv);
+          if (acc) {
             if (ANY && MODE == MODE_SHADOW) best_inst = cur_inst;   // the shadow pipeline only asks WHETHER something was hit: no record to keep
             else {
               const int prim = (int)__float_as_uint(T2.y);
@@ -1355,7 +1422,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& a) {
             }
           }
         }
-        if (ANY && best_inst >= 0) { cur = REF_DONE; break; }   // any hit ends the ray (flags 13, src/shader.rgen:67)
+        if (any_ray && best_inst >= 0) { cur = REF_DONE; break; }   // any hit ends the ray (flags 13, src/shader.rgen:67)
         pop();
         if (!(cur < 0 && cur > REF_MARK)) break;
       }
@@ -1376,8 +1443,14 @@ __device__ __forceinline__ void trace_body(const TraceArgs& a) {
       const int ii = ~cur;
       int root; uint32_t imask;
       to_instance(ii, root, imask);
-      if ((imask & 0xFFu) == 0u) {
-        pop();   // invisible to the ray mask 0xFF; the ray space may still be that of the instance left before
+      bool skip = (imask & 0xFFu) == 0u;
+      if (QF) {   // the ray's cull mask and opacity rules; the facing cull the leaves of this instance apply
+        uint32_t cull;
+        skip = !query_enters(qword, imask, cull);
+        qword = (qword & ~(QF_CULL_NEG | QF_CULL_POS)) | cull;
+      }
+      if (skip) {
+        pop();   // invisible to the ray mask (0xFF, or the query's); the ray space may still be that of the instance left before
         if (cur >= 0) { quant_space(wo, wd, a.sc.tlas_q_lo, a.sc.tlas_q_scale, qs, qb, rot); far = FAR && quant_far_o(wo, a.sc.tlas_q_lo, a.sc.tlas_q_scale); }
       } else {
         push(REF_MARK);
@@ -2059,6 +2132,46 @@ __global__ __launch_bounds__(256) void k_hit_attr(SceneDev sc, const HitRec* __r
 
 void launch_hit_attr(const SceneDev& sc, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s) {
   hipLaunchKernelGGL(k_hit_attr, dim3((n + 255u) / 256u), dim3(256), 0, s, sc, hits, attr, n);
+}
+
+// rt_intersect_device_flags: k_query_init, then the walk with per-ray flags and cull masks.  One instantiation: terminate-on-first-hit
+// is a bit of the ray's word (closest-hit and first-hit rays share a launch), FAR as for every record-level walk.
+void launch_query_flags(const SceneDev& sc, const float4* rays, const uint32_t* words, uint32_t query_word, HitRec* out, uint32_t n,
+                        int32_t* ovf_stack, uint32_t* counters, const LaunchCfg& cfg, hipStream_t s) {
+  hipLaunchKernelGGL(k_query_init, dim3(1), dim3(64), 0, s, counters, n);
+  TraceArgs a = make_args(sc, counters, 0, n, ovf_stack);
+  a.ray_o = rays; a.raw_out = out; a.ray_words = words; a.query_word = query_word;
+  a.rays_per_lane = (uint32_t)cfg.rays_per_lane; a.min_blocks = (uint32_t)cfg.min_blocks;
+  hipLaunchKernelGGL((k_trace<MODE_QUERY_FLAGS, false, false, false, true>), dim3(cfg.trace_blocks), dim3(256), 0, s, a);
+}
+
+// The hit kind of every hit (gl_HitKindFrontFacingTriangleEXT 0xFE / BackFacing 0xFF, 0 on a miss) into word 7 of its rt_hit_attr, after
+// k_hit_attr.  det is recomputed with the walk's own arithmetic: the object-space direction is xform_vec of the instance's w2o rows, and
+// e1 = v1 - v0, e2 = v2 - v0 are rounded once from the vertex buffer as every packet writer rounds them (bvh_build.cpp, k_emit_tris,
+// the BLAS refit), so the reported facing is the one the facing cull judged.
+__global__ __launch_bounds__(256) void k_hit_kind(SceneDev sc, const float4* __restrict__ rays, const HitRec* __restrict__ hits, uint32_t* __restrict__ attr,
+                                                 uint32_t n) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const HitRec h = hits[i];
+  uint32_t kind = 0u;
+  if (h.inst >= 0) {
+    const InstanceDev* I = sc.inst + h.inst;
+    const float4 rd = rays[2u * (size_t)i + 1u];
+    const F3 cd = xform_vec(I->w2o, mk3(rd.x, rd.y, rd.z));
+    const uint32_t* ix = sc.idx + I->first_index + 3u * (uint32_t)h.prim;
+    const float* vb = sc.verts + I->first_float;
+    const float* p0 = vb + 6u * ix[0]; const float* p1 = vb + 6u * ix[1]; const float* p2 = vb + 6u * ix[2];
+    const F3 e1 = mk3(p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]), e2 = mk3(p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]);
+    const float det = dot3(e1, cross3(cd, e2));
+    const bool front = ((det < 0.0f) == FRONT_IS_DET_NEGATIVE) != (((I->mask >> 8) & INST_FLAG_FLIP_FACING) != 0u);
+    kind = front ? 0xFEu : 0xFFu;
+  }
+  attr[8u * (size_t)i + 7u] = kind;
+}
+
+void launch_hit_kind(const SceneDev& sc, const float4* rays, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s) {
+  hipLaunchKernelGGL(k_hit_kind, dim3((n + 255u) / 256u), dim3(256), 0, s, sc, rays, hits, reinterpret_cast<uint32_t*>(attr), n);
 }
 
 int tail_blocks_per_cu() {

@@ -1575,7 +1575,7 @@ static int set_instances_frames(rt_ctx* c, const rt_instance* inst, int n, int u
     invert_affine(d.o2w, d.w2o);
     d.blas_root = m.root;
     d.blas_root4 = m.node_base4;
-    d.mask = m.range.prim_count ? (inst[i].custom_index_and_mask >> 24) : 0u;   // an empty mesh is never entered
+    d.mask = m.range.prim_count ? instance_mask_word(inst[i].custom_index_and_mask, inst[i].sbt_offset_and_flags) : 0u;   // an empty mesh is never entered
     for (int k = 0; k < 3; k++) { d.q_lo[k] = m.q_lo[k]; d.q_scale[k] = m.q_scale[k]; }
     d.custom_index = (int32_t)(inst[i].custom_index_and_mask & 0xFFFFFFu);
     d.first_float = (uint32_t)m.range.first_float;
@@ -2216,28 +2216,26 @@ int rt_intersect(rt_ctx* c, size_t n, const float* rays8, int any_hit, rt_hit* o
   return RT_OK;
 }
 
-// VK_KHR_ray_query for device-resident rays: rt_intersect's traversal (k_trace<MODE_QUERY>: the one-lane BVH2 walk with the far-ray logic)
-// on the caller's rays, hits and surfaces, ordered on the caller's stream.  Nothing is copied, nothing waits on the host, and no frame
-// is waited for: the query has its own counter block and spill area.  What it reads of the context — the TLAS of the current parity
-// and the shared scene — is kept alive by its event: set_instances_* wait for it before they rewrite that parity, quiesce_scene and
-// rt_destroy before the scene or the workspace go.
-int rt_intersect_device(rt_ctx* c, size_t n, const void* d_rays8, int any_hit, void* d_hits, void* d_attr, void* hip_stream) {
-  if (!c) return RT_ERR_INVALID_ARGUMENT;
-  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, "too many rays for one call");
-  if (any_hit && d_attr) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device: hit attributes are for closest-hit queries only (any_hit skips the closest-hit shader)");
-  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device needs trace_variant 0");
+namespace {
+// The body of rt_intersect_device and rt_intersect_device_flags (their own argument checks come first).  flags: the flag-aware
+// walk (MODE_QUERY_FLAGS) with the ray words `words` (or none) and the call's query word; otherwise the plain query with any_hit.
+int intersect_device(rt_ctx* c, size_t n, const void* d_rays8, bool any_hit, bool flags, const void* words, uint32_t query_word, void* d_hits,
+                     void* d_attr, void* hip_stream) {
+  const char* const name = flags ? "rt_intersect_device_flags" : "rt_intersect_device";
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + " needs trace_variant 0");
   if (n) {
-    if (!d_rays8 || !d_hits) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device: null ray/hit pointers");
+    if (!d_rays8 || !d_hits) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null ray/hit pointers");
     if (((uintptr_t)d_rays8 & 15u) || ((uintptr_t)d_hits & 3u) || ((uintptr_t)d_attr & 15u))
-      return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device: rays and attributes must be 16-byte aligned, hits 4-byte aligned");
+      return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": rays and attributes must be 16-byte aligned, hits 4-byte aligned");
     HIP_TRY(c, hipSetDevice(c->device));
-    const void* ptrs[3] = {d_rays8, d_hits, d_attr};
+    const void* ptrs[4] = {d_rays8, d_hits, d_attr, words};
     for (const void* p : ptrs) {
       if (!p) continue;
       hipPointerAttribute_t at{};
       const bool ok = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == c->device;
       (void)hipGetLastError();   // (a host pointer leaves an error behind)
-      if (!ok) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device: rays, hits and attributes must be device memory of the context's GPU (" + std::to_string(c->device) + ")");
+      if (!ok) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + (flags ? ": rays, ray words, hits and attributes" : ": rays, hits and attributes") +
+                                                           " must be device memory of the context's GPU (" + std::to_string(c->device) + ")");
     }
   }
   HIP_TRY(c, hipSetDevice(c->device));
@@ -2260,13 +2258,48 @@ int rt_intersect_device(rt_ctx* c, size_t n, const void* d_rays8, int any_hit, v
   if (c->query_last >= 0) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_query[c->query_last], 0));
   if (c->upload_inflight[c->parity]) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_upload[c->parity], 0));
   const SceneDev sc = scene_dev(c);
-  launch_query(sc, (const float4*)d_rays8, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, any_hit != 0, c->cfg, s);
+  if (flags) launch_query_flags(sc, (const float4*)d_rays8, (const uint32_t*)words, query_word, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, c->cfg, s);
+  else launch_query(sc, (const float4*)d_rays8, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, any_hit, c->cfg, s);
   if (d_attr) launch_hit_attr(sc, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
+  if (d_attr && flags) launch_hit_kind(sc, (const float4*)d_rays8, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipEventRecord(c->ev_query[c->parity], s));
   c->ev_query_valid[c->parity] = true;
   c->query_last = c->parity;
   return RT_OK;
+}
+}  // namespace
+
+// VK_KHR_ray_query for device-resident rays: rt_intersect's traversal (k_trace<MODE_QUERY>: the one-lane BVH2 walk with the far-ray logic)
+// on the caller's rays, hits and surfaces, ordered on the caller's stream.  Nothing is copied, nothing waits on the host, and no frame
+// is waited for: the query has its own counter block and spill area.  What it reads of the context — the TLAS of the current parity
+// and the shared scene — is kept alive by its event: set_instances_* wait for it before they rewrite that parity, quiesce_scene and
+// rt_destroy before the scene or the workspace go.
+int rt_intersect_device(rt_ctx* c, size_t n, const void* d_rays8, int any_hit, void* d_hits, void* d_attr, void* hip_stream) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, "too many rays for one call");
+  if (any_hit && d_attr) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device: hit attributes are for closest-hit queries only (any_hit skips the closest-hit shader)");
+  return intersect_device(c, n, d_rays8, any_hit != 0, false, nullptr, 0u, d_hits, d_attr, hip_stream);
+}
+
+// rt_intersect_device with ray flags and cull masks, per call and per ray (rayQueryInitializeEXT's rayFlags and cullMask): the same
+// checks, workspace and ordering (intersect_device), the walk k_trace<MODE_QUERY_FLAGS>, and k_hit_kind after k_hit_attr.
+int rt_intersect_device_flags(rt_ctx* c, size_t n, const void* d_rays8, const void* d_ray_words, uint32_t ray_flags, uint32_t cull_mask, void* d_hits,
+                              void* d_attr, void* hip_stream) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, "too many rays for one call");
+  // Vulkan's valid-usage rules for rayQueryInitializeEXT's flags (the per-ray words cannot be checked without a host round trip)
+  if ((ray_flags & ~0x3FFu) != 0u || cull_mask > 0xFFu)
+    return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device_flags: ray_flags has bits outside 0x3FF or cull_mask is above 0xFF");
+  const uint32_t opacity = ray_flags & (RT_RAY_FLAG_OPAQUE | RT_RAY_FLAG_NO_OPAQUE | RT_RAY_FLAG_CULL_OPAQUE | RT_RAY_FLAG_CULL_NO_OPAQUE);
+  if ((opacity & (opacity - 1u)) != 0u)
+    return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device_flags: at most one of OPAQUE, NO_OPAQUE, CULL_OPAQUE and CULL_NO_OPAQUE");
+  const uint32_t facing = RT_RAY_FLAG_CULL_BACK_FACING | RT_RAY_FLAG_CULL_FRONT_FACING;
+  if ((ray_flags & facing) == facing) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device_flags: CULL_BACK_FACING with CULL_FRONT_FACING");
+  if ((ray_flags & RT_RAY_FLAG_SKIP_TRIANGLES) && (ray_flags & (RT_RAY_FLAG_SKIP_AABBS | facing)))
+    return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device_flags: SKIP_TRIANGLES with SKIP_AABBS or a facing cull");
+  if (n && ((uintptr_t)d_ray_words & 3u)) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device_flags: ray words must be 4-byte aligned");
+  return intersect_device(c, n, d_rays8, false, true, n ? d_ray_words : nullptr, (cull_mask << 24) | ray_flags, d_hits, d_attr, hip_stream);
 }
 
 }  // extern "C"

@@ -81,7 +81,7 @@ struct alignas(16) InstanceDev {
   float w2o[12];        // gl_WorldToObjectEXT, row-major 3x4 (inverse evaluated in binary64, rounded once)
   float o2w[12];        // gl_ObjectToWorldEXT, row-major 3x4 (rt_instance::transform)
   int32_t blas_root;    // global index of the mesh's root node in blas_nodes
-  uint32_t mask;        // instance mask (ray mask is 0xFF)
+  uint32_t mask;        // bits 0-7: instance mask (frames trace with the ray mask 0xFF); bits 8-11: instance flags (INST_FLAG_*, for ray queries only)
   int32_t custom_index; // gl_InstanceCustomIndexEXT
   uint32_t first_float; // vertexOffset of src/shader.rchit:55 (floats)
   uint32_t first_index; // 3*primitive offset of src/shader.rchit:54 (uint32s)
@@ -114,6 +114,18 @@ struct MaterialDev {
   float ks[3]; uint32_t type;   // 0 diffuse, 1 mirror, 2 refractive, TYPE_BY_INSTANCE: the instance decides
 };
 static_assert(sizeof(MaterialDev) == 48, "MaterialDev must be 48 bytes");
+// InstanceDev::mask >> 8: VkGeometryInstanceFlagBitsKHR (rt_instance::sbt_offset_and_flags >> 24, low 4 bits).  Only the flag-aware ray
+// query (MODE_QUERY_FLAGS) reads them; every other reader masks the word with 0xFF, so frames ignore them as the reference's pipeline does.
+constexpr uint32_t INST_FLAG_FACING_CULL_DISABLE = 0x1u, INST_FLAG_FLIP_FACING = 0x2u, INST_FLAG_FORCE_OPAQUE = 0x4u, INST_FLAG_FORCE_NO_OPAQUE = 0x8u;
+constexpr uint32_t instance_mask_word(uint32_t custom_index_and_mask, uint32_t sbt_offset_and_flags) {   // (constexpr: host and device code)
+  return (custom_index_and_mask >> 24) | (((sbt_offset_and_flags >> 24) & 0xFu) << 8);
+}
+// The per-ray word of MODE_QUERY_FLAGS (rt_intersect_device_flags): bits 0-9 the ray flags (RT_RAY_FLAG_*, the SPIR-V RayFlags values),
+// bits 24-31 the cull mask.  Bits 10-11 hold the facing cull of the instance the ray is in, set when the ray enters it.
+constexpr uint32_t QF_OPAQUE = 0x1u, QF_NO_OPAQUE = 0x2u, QF_TERMINATE = 0x4u, QF_CULL_BACK = 0x10u, QF_CULL_FRONT = 0x20u, QF_CULL_OPAQUE = 0x40u,
+                   QF_CULL_NO_OPAQUE = 0x80u, QF_SKIP_TRIANGLES = 0x100u, QF_FLAGS = 0x3FFu;
+constexpr uint32_t QF_CULL_NEG = 0x400u, QF_CULL_POS = 0x800u;   // reject triangles with det < 0 / det > 0 (tri_test_facing)
+
 constexpr uint32_t TYPE_BY_OBJECT_INDEX = 0xFFFFFFFFu;   // InstanceDev::type: objectIndex == 0 ? centerObjectType : orbitingObjectType
 constexpr uint32_t TYPE_BY_INSTANCE = 0xFFFFFFFFu;       // MaterialDev::type
 constexpr uint32_t MATERIAL_NONE = 0xFFFFFFFFu;          // shadow-queue tag: the reference's constant ambient term

@@ -180,6 +180,12 @@ void launch_query(const SceneDev& sc, const float4* rays, HitRec* out, uint32_t 
                   const LaunchCfg& cfg, hipStream_t s);
 // rt_hit_attr (two float4) of every closest hit of `hits`
 void launch_hit_attr(const SceneDev& sc, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s);
+// rt_intersect_device_flags: launch_query with per-ray flags and cull masks; words (n uint32, or null: every word 0xFF000000) and
+// query_word (the call's flags | cull mask << 24) combine as the header documents
+void launch_query_flags(const SceneDev& sc, const float4* rays, const uint32_t* words, uint32_t query_word, HitRec* out, uint32_t n,
+                        int32_t* ovf_stack, uint32_t* counters, const LaunchCfg& cfg, hipStream_t s);
+// the hit kind (0xFE front, 0xFF back, 0 miss) of every hit of `hits` into word 7 of its rt_hit_attr (after launch_hit_attr)
+void launch_hit_kind(const SceneDev& sc, const float4* rays, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s);
 
 // de-interleave n_shards gathered compact shards (shard_stride_px pixels apart) into the width x height frame
 void launch_assemble(const void* gathered, void* out, int width, int height, int band_rows, int n_shards, size_t shard_stride_px, bool rgba8, hipStream_t s);

@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void k_inst_records(const RecDev* rec, int n, 
       }
       d.blas_root = m.blas_root;
       d.blas_root4 = m.blas_root4;
-      d.mask = m.prim_count ? (r.custom_index_and_mask >> 24) : 0u;   // an empty mesh is never entered
+      d.mask = m.prim_count ? instance_mask_word(r.custom_index_and_mask, r.sbt_offset_and_flags) : 0u;   // an empty mesh is never entered
       for (int k = 0; k < 3; k++) { d.q_lo[k] = m.q_lo[k]; d.q_scale[k] = m.q_scale[k]; }
       d.custom_index = (int32_t)(r.custom_index_and_mask & 0xFFFFFFu);
       d.first_float = m.first_float;

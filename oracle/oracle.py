@@ -28,6 +28,8 @@ def _bind(L):
     L.orc_set_skybox.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int]
     L.orc_intersect.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.orc_hit_attributes.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.orc_intersect_query.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
+    L.orc_query_candidate.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5
     L.orc_render.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.orc_jitter.argtypes = [C.c_float, C.c_float, C.c_float]
     L.orc_jitter.restype = C.c_float
@@ -135,6 +137,35 @@ class OracleScene:
         vc = np.zeros(2, np.uint64)
         self.L.orc_intersect(self.h, len(rays8), _ptr(rays8), int(any_hit), int(use_bvh), _ptr(out), _ptr(vc) if counts else None)
         return (out, vc) if counts else out
+
+    def _query_inputs(self, rays8, words):
+        rays8 = np.ascontiguousarray(rays8, np.float32).reshape(-1, 8)
+        if words is not None:
+            words = np.ascontiguousarray(words, np.uint32).reshape(-1)
+            assert len(words) == len(rays8)
+        return rays8, words
+
+    def intersect_query(self, rays8, words=None, ray_flags=0, cull_mask=0xFF, use_bvh=True):
+        """rt_intersect_device_flags' rules (orc_intersect_query): (HIT_DTYPE records, uint32 hit kinds: 0xFE, 0xFF, 0 on a miss)"""
+        rays8, words = self._query_inputs(rays8, words)
+        out = np.zeros(len(rays8), HIT_DTYPE)
+        kind = np.zeros(len(rays8), np.uint32)
+        self.L.orc_intersect_query(self.h, len(rays8), _ptr(rays8), _ptr(words) if words is not None else None, int(ray_flags) & 0xFFFFFFFF,
+                                   int(cull_mask) & 0xFFFFFFFF, int(use_bvh), _ptr(out), _ptr(kind))
+        return out, kind
+
+    def query_candidate(self, rays8, inst, prim, words=None, ray_flags=0, cull_mask=0xFF):
+        """may ray i accept triangle prim[i] of instance inst[i] under its word?  (bool ok, HIT_DTYPE records, uint32 hit kinds)"""
+        rays8, words = self._query_inputs(rays8, words)
+        inst = np.ascontiguousarray(inst, np.int32)
+        prim = np.ascontiguousarray(prim, np.int32)
+        assert len(inst) == len(prim) == len(rays8)
+        ok = np.zeros(len(rays8), np.uint8)
+        out = np.zeros(len(rays8), HIT_DTYPE)
+        kind = np.zeros(len(rays8), np.uint32)
+        self.L.orc_query_candidate(self.h, len(rays8), _ptr(rays8), _ptr(words) if words is not None else None, int(ray_flags) & 0xFFFFFFFF,
+                                   int(cull_mask) & 0xFFFFFFFF, _ptr(inst), _ptr(prim), _ptr(ok), _ptr(out), _ptr(kind))
+        return ok.astype(bool), out, kind
 
     def hit_attributes(self, hits):
         hits = np.ascontiguousarray(hits)

@@ -167,6 +167,7 @@ struct Instance {
   int32_t custom_index;
   uint32_t mask;
   uint32_t mesh;
+  uint32_t flags;   // VkGeometryInstanceFlagBitsKHR (sbt_and_flags >> 24): read by the ray-query rules only (trace_query)
 };
 
 // Row n4: one MTL material; 48 bytes, same layout as the product's rt_material.
@@ -407,6 +408,103 @@ static bool trace(const Scene& s, V3 o, V3 d, float tmin, float tmax, bool any_h
       if (!box_test(nd, oo, id, slack, tmin, found ? best.t : tmax)) continue;
       if (nd.count) {
         for (uint32_t k = 0; k < nd.count; k++) { consider(m.order[nd.first + k]); if (any_hit && found) return true; }
+      } else { stack[sp++] = nd.right; stack[sp++] = nd.left; }
+    }
+  }
+  return found;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Ray queries with flags and cull masks (rt_intersect_device_flags, include/rt_api.h; Vulkan's ray-traversal chapter).  A separate
+// path: trace / tri_test above, and with them the frames, the golden hashes and the cpu_baseline, are not touched.
+//   * ray i traces with flags = call | (word & 0x3FF) and cull mask = call_cull & (word >> 24) (no words: 0xFF000000);
+//   * an instance is entered only if (its mask & the cull mask) != 0;
+//   * opacity: the ray's OPAQUE, then its NO_OPAQUE, then the instance's FORCE_OPAQUE, then FORCE_NO_OPAQUE, then the geometry
+//     (built opaque); SKIP_TRIANGLES, CULL_OPAQUE on opaque and CULL_NO_OPAQUE on non-opaque geometry skip the instance;
+//   * facing, in object space: front-facing <=> det < 0 (det of tri_test), inverted by FLIP_FACING.  CULL_BACK / CULL_FRONT reject
+//     the triangle unless the instance has FACING_CULL_DISABLE, which does not change the reported kind;
+//   * TERMINATE_ON_FIRST_HIT: the first accepted candidate ends the ray; otherwise the closest hit with tri_test's tie rule.
+enum : uint32_t {
+  RF_OPAQUE = 0x1, RF_NO_OPAQUE = 0x2, RF_TERMINATE = 0x4, RF_CULL_BACK = 0x10, RF_CULL_FRONT = 0x20, RF_CULL_OPAQUE = 0x40,
+  RF_CULL_NO_OPAQUE = 0x80, RF_SKIP_TRIANGLES = 0x100,
+  IF_FACING_CULL_DISABLE = 0x1, IF_FLIP_FACING = 0x2, IF_FORCE_OPAQUE = 0x4, IF_FORCE_NO_OPAQUE = 0x8,
+  KIND_FRONT = 0xFE, KIND_BACK = 0xFF
+};
+struct QueryRay { uint32_t flags, cull; };
+static inline QueryRay query_ray(const uint32_t* words, uint64_t i, uint32_t call_flags, uint32_t call_cull) {
+  const uint32_t w = words ? words[i] : 0xFF000000u;
+  return QueryRay{call_flags | (w & 0x3FFu), call_cull & (w >> 24)};
+}
+static inline bool query_instance_visible(const QueryRay& r, const Instance& in) {
+  if ((in.mask & r.cull & 0xFFu) == 0) return false;
+  bool opaque;
+  if (r.flags & RF_OPAQUE) opaque = true;
+  else if (r.flags & RF_NO_OPAQUE) opaque = false;
+  else if (in.flags & IF_FORCE_OPAQUE) opaque = true;
+  else if (in.flags & IF_FORCE_NO_OPAQUE) opaque = false;
+  else opaque = true;   // VK_GEOMETRY_OPAQUE_BIT_KHR (src/main.cpp:330)
+  if (r.flags & RF_SKIP_TRIANGLES) return false;
+  if (opaque && (r.flags & RF_CULL_OPAQUE)) return false;
+  if (!opaque && (r.flags & RF_CULL_NO_OPAQUE)) return false;
+  return true;
+}
+// tri_test's arithmetic, with the facing decided from the sign of the same det after the inside test.  kind: the hit kind.
+static inline bool tri_test_query(V3 o, V3 d, V3 v0, V3 e1, V3 e2, float tmin, float tmax, const QueryRay& r, uint32_t iflags,
+                                  float& t, float& u, float& v, uint32_t& kind) {
+  V3 p = cross(d, e2);
+  float det = dot3(e1, p);
+  V3 s = o - v0;
+  float un = dot3(s, p);
+  V3 q = cross(s, e1);
+  float vn = dot3(d, q);
+  float tn = dot3(e2, q);
+  float da = fabsf(det);
+  if (det < 0.0f) { un = -un; vn = -vn; tn = -tn; }
+  if (!(un >= 0.0f) || !(vn >= 0.0f) || !(un + vn <= da) || !(da > 0.0f)) return false;
+  bool front = det < 0.0f;
+  if (iflags & IF_FLIP_FACING) front = !front;
+  if (!(iflags & IF_FACING_CULL_DISABLE)) {
+    if (front && (r.flags & RF_CULL_FRONT)) return false;
+    if (!front && (r.flags & RF_CULL_BACK)) return false;
+  }
+  float inv = 1.0f / da;
+  float tt = tn * inv;
+  if (!(tt > tmin) || !(tt < tmax)) return false;
+  t = tt; u = un * inv; v = vn * inv; kind = front ? KIND_FRONT : KIND_BACK;
+  return true;
+}
+
+// trace() under a query's flags and cull mask; kind = 0 on a miss.
+static bool trace_query(const Scene& s, V3 o, V3 d, float tmin, float tmax, const QueryRay& r, bool use_bvh, Hit& best, uint32_t& kind) {
+  best.t = tmax; best.u = best.v = 0.f; best.prim = -1; best.inst = -1; kind = 0;
+  const bool first_hit = (r.flags & RF_TERMINATE) != 0;
+  bool found = false;
+  for (size_t ii = 0; ii < s.inst.size(); ii++) {
+    const Instance& in = s.inst[ii];
+    if (!query_instance_visible(r, in)) continue;
+    const Mesh& m = s.meshes[in.mesh];
+    V3 oo = xform_point(in.w2o, o), od = xform_vec(in.w2o, d);
+    auto consider = [&](uint32_t prim) {
+      const uint32_t* ix = &s.idx[m.first_index + 3ull * prim];
+      V3 v0 = vert_pos(s, m, ix[0]), v1 = vert_pos(s, m, ix[1]), v2 = vert_pos(s, m, ix[2]);
+      float t, u, v; uint32_t k;
+      if (!tri_test_query(oo, od, v0, v1 - v0, v2 - v0, tmin, tmax, r, in.flags, t, u, v, k)) return;
+      bool better = !found || t < best.t || (t == best.t && ((int32_t)ii < best.inst || ((int32_t)ii == best.inst && (int32_t)prim < best.prim)));
+      if (better) { best.t = t; best.u = u; best.v = v; best.prim = (int32_t)prim; best.inst = (int32_t)ii; kind = k; found = true; }
+    };
+    if (!use_bvh) {
+      for (uint32_t p = 0; p < m.prim_count; p++) { consider(p); if (first_hit && found) return true; }
+      continue;
+    }
+    if (m.nodes.empty()) continue;
+    V3 id = mk(safe_inv(od.x), safe_inv(od.y), safe_inv(od.z));
+    const V3 slack = mk(1e-5f * fabsf(oo.x) * fabsf(id.x), 1e-5f * fabsf(oo.y) * fabsf(id.y), 1e-5f * fabsf(oo.z) * fabsf(id.z));
+    int32_t stack[128]; int sp = 0; stack[sp++] = 0;
+    while (sp) {
+      const BNode& nd = m.nodes[stack[--sp]];
+      if (!box_test(nd, oo, id, slack, tmin, found ? best.t : tmax)) continue;
+      if (nd.count) {
+        for (uint32_t k = 0; k < nd.count; k++) { consider(m.order[nd.first + k]); if (first_hit && found) return true; }
       } else { stack[sp++] = nd.right; stack[sp++] = nd.left; }
     }
   }
@@ -678,6 +776,7 @@ int orc_set_instances(void* p, const InstanceIn* in, int n) {
     invert_affine(I.o2w, I.w2o);
     I.custom_index = (int32_t)(in[i].custom_index_and_mask & 0xFFFFFFu);
     I.mask = in[i].custom_index_and_mask >> 24;
+    I.flags = in[i].sbt_and_flags >> 24;
     I.mesh = (uint32_t)in[i].mesh;
     if (I.mesh >= s.meshes.size()) return 1;
     s.inst.push_back(I);
@@ -707,6 +806,48 @@ int orc_intersect(void* p, uint64_t n, const float* rays, int any_hit, int use_b
     out[i] = h;
   }
   if (visit_counts) { visit_counts[0] = c.nodes; visit_counts[1] = c.tris; }
+  return 0;
+}
+
+// rt_intersect_device_flags' semantics: rays as orc_intersect, words (n uint32: flags | cull mask << 24) or null, the call's flags and
+// cull mask.  out: n Hit records (a miss as orc_intersect's), out_kind: n hit kinds (0xFE front, 0xFF back, 0 on a miss).
+int orc_intersect_query(void* p, uint64_t n, const float* rays, const uint32_t* words, uint32_t call_flags, uint32_t call_cull, int use_bvh,
+                        Hit* out, uint32_t* out_kind) {
+  Scene& s = *(Scene*)p;
+  for (uint64_t i = 0; i < n; i++) {
+    const float* r = rays + 8 * i;
+    Hit h; uint32_t kind;
+    bool f = trace_query(s, mk(r[0], r[1], r[2]), mk(r[4], r[5], r[6]), r[3], r[7], query_ray(words, i, call_flags, call_cull), use_bvh != 0, h, kind);
+    if (!f) { h.t = r[7]; h.u = h.v = 0.f; h.prim = -1; h.inst = -1; kind = 0; }
+    out[i] = h;
+    out_kind[i] = kind;
+  }
+  return 0;
+}
+
+// May ray i accept triangle prim[i] of instance inst[i] under its word (a first-hit ray may report any such triangle)?  ok[i] = 1 and
+// out[i] = (t, u, v, prim, inst), out_kind[i] = the hit kind if it may; ok[i] = 0 otherwise (also for an instance or prim out of range).
+int orc_query_candidate(void* p, uint64_t n, const float* rays, const uint32_t* words, uint32_t call_flags, uint32_t call_cull,
+                        const int32_t* inst, const int32_t* prim, uint8_t* ok, Hit* out, uint32_t* out_kind) {
+  Scene& s = *(Scene*)p;
+  for (uint64_t i = 0; i < n; i++) {
+    const float* r = rays + 8 * i;
+    ok[i] = 0; out_kind[i] = 0;
+    out[i].t = r[7]; out[i].u = out[i].v = 0.f; out[i].prim = -1; out[i].inst = -1;
+    if (inst[i] < 0 || (size_t)inst[i] >= s.inst.size()) continue;
+    const Instance& in = s.inst[inst[i]];
+    const Mesh& m = s.meshes[in.mesh];
+    if (prim[i] < 0 || (uint32_t)prim[i] >= m.prim_count) continue;
+    const QueryRay qr = query_ray(words, i, call_flags, call_cull);
+    if (!query_instance_visible(qr, in)) continue;
+    V3 oo = xform_point(in.w2o, mk(r[0], r[1], r[2])), od = xform_vec(in.w2o, mk(r[4], r[5], r[6]));
+    const uint32_t* ix = &s.idx[m.first_index + 3ull * (uint32_t)prim[i]];
+    V3 v0 = vert_pos(s, m, ix[0]), v1 = vert_pos(s, m, ix[1]), v2 = vert_pos(s, m, ix[2]);
+    float t, u, v; uint32_t k;
+    if (!tri_test_query(oo, od, v0, v1 - v0, v2 - v0, r[3], r[7], qr, in.flags, t, u, v, k)) continue;
+    ok[i] = 1; out_kind[i] = k;
+    out[i].t = t; out[i].u = u; out[i].v = v; out[i].prim = prim[i]; out[i].inst = inst[i];
+  }
   return 0;
 }
 

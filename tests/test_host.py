@@ -101,7 +101,7 @@ def test_shipped_traversal_kernels_keep_their_register_budget():
         if m:
             mode, _, wide, _, far, cont = (int(x) for x in m.groups())
             assert wide == 0 and cont == 0, name
-            (hot if (far == 0 and mode != 2) else other).append((name, r))
+            (hot if (far == 0 and mode < 3) else other).append((name, r))   # (modes 3 and 4: record-level rays)
         elif re.match(r"_ZN2rt6k_tailILb0E", name):      # (the shipped, non-counting instantiation)
             other.append((name, r))
         elif name == "_ZN2rt6k_beamENS_9TraceArgsEj":

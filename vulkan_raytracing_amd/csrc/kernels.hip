@@ -933,7 +933,7 @@ struct TraceArgs {
   int32_t* hit_inst;
   const float4* sh_c;          // shadow pipeline
   float4* sample_color;
-  HitRec* raw_out;             // raw mode
+  HitRec* raw_out;             // record-level rays
   int32_t* ovf_stack;
   uint32_t* counters;
   union {
@@ -951,8 +951,9 @@ struct TraceArgs {
 
 constexpr int MODE_CLOSEST = 0;  // pipeline closest hit: o.w = tmax, d.w = sid
 constexpr int MODE_SHADOW = 1;   // pipeline any hit + shading epilogue
-constexpr int MODE_RAW = 2;      // o.w = tmin, d.w = tmax; writes HitRec
-constexpr int MODE_QUERY = 3;    // MODE_RAW on the caller's rays as they are (rt_intersect_device): ray i is the float4 pair ray_o[2i], ray_o[2i + 1]
+// (the record-level modes keep the numbers 3 and 4: the tests find their kernels by symbol)
+constexpr int MODE_QUERY = 3;    // record-level rays (rt_intersect, rt_intersect_device): ray i is the float4 pair ray_o[2i] = (o.xyz, tmin),
+                                 // ray_o[2i + 1] = (d.xyz, tmax), read where the caller left them; writes HitRec
 constexpr int MODE_QUERY_FLAGS = 4;   // MODE_QUERY with ray flags and a cull mask per ray (rt_intersect_device_flags): any hit is a per-ray bit
 
 
@@ -1008,8 +1009,7 @@ constexpr uint32_t REFILL_MIN = RT_REFILL_MIN;
 // their ray can still reach (mask in o.w).
 template <int MODE, bool ANY, bool COUNT, bool WIDE, bool ENTRY = false, bool FAR = true, bool CONT = false>
 __device__ __forceinline__ void trace_body(const TraceArgs& a) {
-  constexpr bool QUERY = MODE == MODE_QUERY || MODE == MODE_QUERY_FLAGS;   // the caller's 32-byte rays
-  constexpr bool RAYS8 = MODE == MODE_RAW || QUERY;   // record-level rays: per-ray tmin and tmax, HitRec results
+  constexpr bool RAYS8 = MODE == MODE_QUERY || MODE == MODE_QUERY_FLAGS;   // record-level rays: 32 bytes each, per-ray tmin and tmax, HitRec results
   constexpr bool QF = MODE == MODE_QUERY_FLAGS;
   __shared__ int s_stack[4][STACK2_LDS + 1][64];   // + one scratch row: lanes that do not push write there (fast_step)
   __shared__ float4 s_rays[4][2][64];
@@ -1064,7 +1064,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& a) {
       shard = (shard + 1u) & (N_SHARDS - 1); tried++;
     }
     if (lane < pf_count) {
-      if constexpr (QUERY) {   // (o.xyz, tmin, d.xyz, tmax): 32 bytes per ray, read where the caller left them
+      if constexpr (RAYS8) {   // (o.xyz, tmin, d.xyz, tmax): 32 bytes per ray, read where the caller left them
         const size_t r = 2u * (size_t)(pf_base + lane);
         pf_o = ld_stream(&a.ray_o[r]); pf_d = ld_stream(&a.ray_o[r + 1u]);
         if (QF) {   // the ray's effective word: the call's flags | the ray's, the call's cull mask & the ray's
@@ -1112,7 +1112,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs& a) {
   // ---- per-lane ray state
   bool need = true;
   uint32_t q = 0, sid = 0;
-  float tmin_ray = 0.f, tmax = 0.f;   // tmin is a per-ray value only in the raw mode; the pipeline uses one constant
+  float tmin_ray = 0.f, tmax = 0.f;   // tmin is a per-ray value only for record-level rays; the pipeline uses one constant
   uint32_t qword = 0;   // QF: the ray's query word (QF_*), with the facing cull of its current instance in bits 10-11
   F3 wo = mk3(0, 0, 0), wd = mk3(0, 0, 1), co = wo, cd = wd, qs = mk3(1, 1, 1), qb = mk3(0, 0, 0);
   uint3 rot = make_uint3(0u, 0u, 0u);
@@ -1928,8 +1928,10 @@ static void launch_trace(const TraceArgs& a_in, bool counting, const LaunchCfg& 
   }
 #endif
   // (the product library has the one-lane BVH2 kernel only; rt_set_param refuses the other variants there: alt_kernels_built())
+  // Record-level rays start anywhere: they always take the far-ray logic, and no FAR = false kernel is instantiated for them.
   if (counting) hipLaunchKernelGGL((k_trace_count<MODE, ANY, false>), g, b, 0, s, a);
-  else if (cfg.far || MODE == MODE_RAW) hipLaunchKernelGGL((k_trace<MODE, ANY, false, false, true>), g, b, 0, s, a);
+  else if constexpr (MODE == MODE_QUERY) hipLaunchKernelGGL((k_trace<MODE, ANY, false, false, true>), g, b, 0, s, a);
+  else if (cfg.far) hipLaunchKernelGGL((k_trace<MODE, ANY, false, false, true>), g, b, 0, s, a);
   else hipLaunchKernelGGL((k_trace<MODE, ANY, false, false, false>), g, b, 0, s, a);
 }
 
@@ -2077,24 +2079,7 @@ void launch_tile(const SceneDev&, const FrameDev&, const UniformsDev&, bool, hip
 void launch_beam_shadow(const SceneDev&, const FrameDev&, const UniformsDev&, bool, const LaunchCfg&, hipStream_t) {}
 #endif
 
-void launch_trace_raw(const SceneDev& sc, const float4* ray_o, const float4* ray_d, HitRec* out, uint32_t shard_cap,
-                      int32_t* ovf_stack, uint32_t* counters, bool any_hit, bool counting, const LaunchCfg& cfg, hipStream_t s) {
-  TraceArgs a = make_args(sc, counters, 0, shard_cap, ovf_stack);
-  a.ray_o = ray_o; a.ray_d = ray_d; a.raw_out = out;
-#ifdef RT_ALT_KERNELS
-  if (cfg.packet >= 2 && cfg.variant == 0) {
-    a.rays_per_lane = (uint32_t)cfg.rays_per_lane; a.min_blocks = (uint32_t)cfg.min_blocks;
-    const dim3 g(cfg.packet_blocks), b(256);
-    if (any_hit) { if (counting) hipLaunchKernelGGL((k_packet<MODE_RAW, true, true, false>), g, b, 0, s, a); else hipLaunchKernelGGL((k_packet<MODE_RAW, true, false, false>), g, b, 0, s, a); }
-    else { if (counting) hipLaunchKernelGGL((k_packet<MODE_RAW, false, true, false>), g, b, 0, s, a); else hipLaunchKernelGGL((k_packet<MODE_RAW, false, false, false>), g, b, 0, s, a); }
-    return;
-  }
-#endif
-  if (any_hit) launch_trace<MODE_RAW, true>(a, counting, cfg, s);
-  else launch_trace<MODE_RAW, false>(a, counting, cfg, s);
-}
-
-// ---- ray queries (rt_intersect_device): the caller's rays, hits and surfaces stay in device memory
+// ---- ray queries (rt_intersect, rt_intersect_device): the record-level walk on the rays where they lie
 // The query's own counter block gets the ray count (shard 0 of queue 0) and fresh chunk cursors in stream order: k_trace reads
 // nothing else of it.
 __global__ __launch_bounds__(64) void k_query_init(uint32_t* counters, uint32_t n) {
@@ -2103,15 +2088,21 @@ __global__ __launch_bounds__(64) void k_query_init(uint32_t* counters, uint32_t 
 }
 
 void launch_query(const SceneDev& sc, const float4* rays, HitRec* out, uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool any_hit,
-                  const LaunchCfg& cfg, hipStream_t s) {
+                  bool counting, const LaunchCfg& cfg, hipStream_t s) {
   hipLaunchKernelGGL(k_query_init, dim3(1), dim3(64), 0, s, counters, n);
   TraceArgs a = make_args(sc, counters, 0, n, ovf_stack);
   a.ray_o = rays; a.raw_out = out;
-  a.rays_per_lane = (uint32_t)cfg.rays_per_lane; a.min_blocks = (uint32_t)cfg.min_blocks;
-  // the persistent grid and the far-ray logic of the record-level entry point (query rays start anywhere)
-  const dim3 g(cfg.trace_blocks), b(256);
-  if (any_hit) hipLaunchKernelGGL((k_trace<MODE_QUERY, true, false, false, true>), g, b, 0, s, a);
-  else hipLaunchKernelGGL((k_trace<MODE_QUERY, false, false, false, true>), g, b, 0, s, a);
+#ifdef RT_ALT_KERNELS
+  if (cfg.packet >= 2 && cfg.variant == 0) {
+    a.rays_per_lane = (uint32_t)cfg.rays_per_lane; a.min_blocks = (uint32_t)cfg.min_blocks;
+    const dim3 g(cfg.packet_blocks), b(256);
+    if (any_hit) { if (counting) hipLaunchKernelGGL((k_packet<MODE_QUERY, true, true, false>), g, b, 0, s, a); else hipLaunchKernelGGL((k_packet<MODE_QUERY, true, false, false>), g, b, 0, s, a); }
+    else { if (counting) hipLaunchKernelGGL((k_packet<MODE_QUERY, false, true, false>), g, b, 0, s, a); else hipLaunchKernelGGL((k_packet<MODE_QUERY, false, false, false>), g, b, 0, s, a); }
+    return;
+  }
+#endif
+  if (any_hit) launch_trace<MODE_QUERY, true>(a, counting, cfg, s);
+  else launch_trace<MODE_QUERY, false>(a, counting, cfg, s);
 }
 
 // rt_hit_attr of every closest hit: what src/shader.rchit:50-96 computes before it shades (hit_surface), objectIndex = the instance's

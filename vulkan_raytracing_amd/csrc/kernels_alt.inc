@@ -67,9 +67,12 @@ __global__ __launch_bounds__(256) void k_packet(TraceArgs a) {
     const bool on = lane < count;
     const uint32_t q = base + lane;
     float4 ro = make_float4(0, 0, 0, 0), rd = make_float4(0, 0, 1, 0);
-    if (on) { ro = a.ray_o[q]; rd = a.ray_d[q]; }
-    const float tmin = MODE == MODE_RAW ? ro.w : a.tmin;
-    const float tmax = MODE == MODE_RAW ? rd.w : ((ENTRY && MODE == MODE_CLOSEST) ? 10000.0f : ro.w);   // (ENTRY closest: o.w carries the tile)
+    if (on) {
+      if (MODE == MODE_QUERY) { ro = a.ray_o[2u * (size_t)q]; rd = a.ray_o[2u * (size_t)q + 1u]; }   // (o.xyz, tmin, d.xyz, tmax): 32 bytes per ray
+      else { ro = a.ray_o[q]; rd = a.ray_d[q]; }
+    }
+    const float tmin = MODE == MODE_QUERY ? ro.w : a.tmin;
+    const float tmax = MODE == MODE_QUERY ? rd.w : ((ENTRY && MODE == MODE_CLOSEST) ? 10000.0f : ro.w);   // (ENTRY closest: o.w carries the tile)
     const F3 wo = mk3(ro.x, ro.y, ro.z), wd = mk3(rd.x, rd.y, rd.z);
     float best_t = tmax, best_u = 0.f, best_v = 0.f;
     int best_prim = -1, best_inst = -1;
@@ -323,7 +326,11 @@ __global__ __launch_bounds__(256) void k_trace4(TraceArgs a) {
       shard = (shard + 1u) & (N_SHARDS - 1); tried++;
     }
     if (lane < pf_count) {
-      pf_o = a.ray_o[pf_base + lane]; pf_d = a.ray_d[pf_base + lane];
+      if (MODE == MODE_QUERY) {   // (o.xyz, tmin, d.xyz, tmax): 32 bytes per ray
+        pf_o = a.ray_o[2u * (size_t)(pf_base + lane)]; pf_d = a.ray_o[2u * (size_t)(pf_base + lane) + 1u];
+      } else {
+        pf_o = a.ray_o[pf_base + lane]; pf_d = a.ray_d[pf_base + lane];
+      }
       if (MODE == MODE_SHADOW) pf_c = a.sh_c[pf_base + lane];
     }
   };
@@ -375,7 +382,7 @@ __global__ __launch_bounds__(256) void k_trace4(TraceArgs a) {
           q = chunk_base + ci;
           const float4 ro = s_rays[wave][0][ci], rd = s_rays[wave][1][ci];
           if (MODE == MODE_SHADOW) shc = s_rays[wave][2][ci];
-          if (MODE == MODE_RAW) { tmin = ro.w; tmax = rd.w; }
+          if (MODE == MODE_QUERY) { tmin = ro.w; tmax = rd.w; }
           else { tmin = a.tmin; tmax = ro.w; sid = __float_as_uint(rd.w); }
           if (sub == 0) { s_world[wave][0][ray] = ro; s_world[wave][1][ray] = rd; }
           co = mk3(ro.x, ro.y, ro.z); cd = mk3(rd.x, rd.y, rd.z);

@@ -292,8 +292,8 @@ struct rt_ctx {
   bool debug_force_tail_fault = false;   // rt_set_param "debug_force_tail_fault": treat the next k_tail frame as faulted (tests the fallback)
   uint32_t last_max_bounce = 0;
   uint64_t last_primary = 0;
-  // rt_intersect_device: the query workspace — a counter block and a spill area of its own, so that a query never touches what a
-  // pending frame uses — and the completion event of the last query that read each TLAS parity.  Queries of this context run one
+  // ray queries (rt_intersect, rt_intersect_device*): the query workspace — a counter block and a spill area of its own, so that a
+  // query never touches what a pending frame uses — and the completion event of the last query that read each TLAS parity.  Queries of this context run one
   // after the other (each one's stream waits for the previous one's event), so the event of the last query covers all of them.
   uint32_t* d_q_counters = nullptr;
   int32_t* d_q_ovf = nullptr;
@@ -804,8 +804,8 @@ int quiesce(rt_ctx* c) {
   if (c->frame_pending) return collect_stats(c);
   return RT_OK;
 }
-// Ray queries (rt_intersect_device) of context m: the host waits for the last query that read TLAS parity `parity` (-1: for the last
-// query of all, which, queries being serialised, covers every one).  Reports on c.
+// Ray queries (rt_intersect, rt_intersect_device*) of context m: the host waits for the last query that read TLAS parity `parity` (-1:
+// for the last query of all, which, queries being serialised, covers every one).  Reports on c.
 int wait_queries(rt_ctx* c, rt_ctx* m, int parity) {
   const int p = parity < 0 ? m->query_last : parity;
   if (p < 0 || !m->ev_query_valid[p]) return RT_OK;
@@ -2160,54 +2160,79 @@ int rt_trace_wait(rt_ctx* c, const void** pixels, rt_stats* stats) {
 }
 int rt_trace_counting(rt_ctx* c, int W, int H, float* out, rt_stats* stats) { return trace_host(c, W, H, out, stats, true); }
 
+namespace {
+// The enqueue of every ray query (rt_intersect, rt_intersect_device, rt_intersect_device_flags) on stream s, after the caller's checks.
+// flags: the flag-aware walk (MODE_QUERY_FLAGS) with the ray words `words` (or none) and the call's query word; otherwise the plain
+// walk with any_hit, instrumented when counting (its counts start from a zeroed counter block).  d_attr (optional): the hit attributes.
+// t0 / t1 (optional): events recorded around the walk.
+int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, size_t n, const void* d_rays8, bool any_hit, bool counting, bool flags,
+                  const void* words, uint32_t query_word, void* d_hits, void* d_attr, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
+  // the workspace: allocated at the first query; the spill area re-sized (after the last query is done) when the trees grew
+  if (!c->d_q_counters) HIP_TRY(c, hipMalloc((void**)&c->d_q_counters, CNT_WORDS * sizeof(uint32_t)));
+  const size_t ovf_need = ovf_elems(c->cfg.trace_blocks, c->tail_blocks, c->ovf_stride);
+  if (ovf_need > c->q_ovf_alloc) {
+    { int q = wait_queries(c, c); if (q) return q; }
+    if (c->d_q_ovf) HIP_TRY(c, hipFree(c->d_q_ovf));
+    c->d_q_ovf = nullptr; c->q_ovf_alloc = 0;
+    HIP_TRY(c, hipMalloc((void**)&c->d_q_ovf, ovf_need * sizeof(int32_t)));
+    c->q_ovf_alloc = ovf_need;
+  }
+  for (int k = 0; k < 2; k++)
+    if (!c->ev_query[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_query[k], hipEventDisableTiming));
+  // device-side ordering: behind the previous query of this context (its workspace), and behind the copies or the build of the TLAS
+  if (c->query_last >= 0) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_query[c->query_last], 0));
+  if (c->upload_inflight[c->parity]) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_upload[c->parity], 0));
+  if (counting) HIP_TRY(c, hipMemsetAsync(c->d_q_counters, 0, CNT_WORDS * sizeof(uint32_t), s));
+  const SceneDev sc = scene_dev(c);
+  if (t0) HIP_TRY(c, hipEventRecord(t0, s));
+  if (flags) launch_query_flags(sc, (const float4*)d_rays8, (const uint32_t*)words, query_word, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, cfg, s);
+  else launch_query(sc, (const float4*)d_rays8, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, any_hit, counting, cfg, s);
+  if (t1) HIP_TRY(c, hipEventRecord(t1, s));
+  if (d_attr) launch_hit_attr(sc, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
+  if (d_attr && flags) launch_hit_kind(sc, (const float4*)d_rays8, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipEventRecord(c->ev_query[c->parity], s));
+  c->ev_query_valid[c->parity] = true;
+  c->query_last = c->parity;
+  return RT_OK;
+}
+}  // namespace
+
+// A blocking ray query from host memory: the rays are copied to the device as they are, walked on the context's stream like a device
+// query (its workspace and ordering) and the hits copied back.
 int rt_intersect(rt_ctx* c, size_t n, const float* rays8, int any_hit, rt_hit* out, int counting, rt_stats* stats) {
   if (!c) return RT_ERR_INVALID_ARGUMENT;
   if ((!rays8 || !out) && n) return fail(c, RT_ERR_INVALID_ARGUMENT, "null ray/hit pointers");
   if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, "too many rays for one call");
   HIP_TRY(c, hipSetDevice(c->device));
-  { int q = quiesce(c); if (q) return q; }   // the counters and spill stacks below are the pending frame's
+  { int q = quiesce(c); if (q) return q; }   // not beside a frame of rt_trace_async; a finished pending frame is collected
   int r = ready_to_trace(c); if (r) return r;
-  r = ensure_common(c); if (r) return r;
   if (stats) memset(stats, 0, sizeof(*stats));
   if (n == 0) return RT_OK;
-  std::vector<float4> ho(n), hd(n);
-  for (size_t i = 0; i < n; i++) {
-    const float* p = rays8 + 8 * i;
-    ho[i] = make_float4(p[0], p[1], p[2], p[3]);
-    hd[i] = make_float4(p[4], p[5], p[6], p[7]);
-  }
-  float4 *d_o = nullptr, *d_d = nullptr; HitRec* d_h = nullptr;
+  // one allocation: the rays (32 B each), then the hits
+  const size_t ray_bytes = n * 8 * sizeof(float);
+  char* d_buf = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   struct Guard {   // every exit path below releases the temporaries
-    float4 *&o, *&d; HitRec*& h; hipEvent_t &a, &b;
-    ~Guard() { if (o) hipFree(o); if (d) hipFree(d); if (h) hipFree(h); if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
-  } guard{d_o, d_d, d_h, e0, e1};
-  HIP_TRY(c, hipMalloc((void**)&d_o, n * sizeof(float4)));
-  HIP_TRY(c, hipMalloc((void**)&d_d, n * sizeof(float4)));
-  HIP_TRY(c, hipMalloc((void**)&d_h, n * sizeof(HitRec)));
-  HIP_TRY(c, hipMemcpy(d_o, ho.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(d_d, hd.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, CNT_WORDS * sizeof(uint32_t), c->stream));
-  uint32_t n32 = (uint32_t)n;
-  HIP_TRY(c, hipMemcpyAsync(c->d_counters + cnt_tail(0, 0), &n32, sizeof(n32), hipMemcpyHostToDevice, c->stream));
+    char*& buf; hipEvent_t &a, &b;
+    ~Guard() { if (buf) hipFree(buf); if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
+  } guard{d_buf, e0, e1};
+  HIP_TRY(c, hipMalloc((void**)&d_buf, ray_bytes + n * sizeof(HitRec)));
+  HitRec* const d_h = (HitRec*)(d_buf + ray_bytes);
+  HIP_TRY(c, hipMemcpy(d_buf, rays8, ray_bytes, hipMemcpyHostToDevice));
   HIP_TRY(c, hipEventCreate(&e0)); HIP_TRY(c, hipEventCreate(&e1));
-  hipEventRecord(e0, c->stream);
-  LaunchCfg raw_cfg = c->cfg;
-  if (c->stack_need > 120) raw_cfg.packet = 0;   // (see enqueue_frame)
-  launch_trace_raw(scene_dev(c), d_o, d_d, d_h, n32, c->d_ovf, c->d_counters, any_hit != 0, counting != 0, raw_cfg, c->stream);
-  hipEventRecord(e1, c->stream);
+  LaunchCfg cfg = c->cfg;
+  if (c->stack_need > 120) cfg.packet = 0;   // (see enqueue_frame)
+  r = enqueue_query(c, c->stream, cfg, n, d_buf, any_hit != 0, counting != 0, false, nullptr, 0u, d_h, nullptr, e0, e1); if (r) return r;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpy(out, d_h, n * sizeof(HitRec), hipMemcpyDeviceToHost));
-  struct Rezero {   // frames expect both counter blocks zeroed, on whatever stream they are enqueued next
-    rt_ctx* c;
-    ~Rezero() { (void)hipMemsetAsync(c->d_counters, 0, 2 * CNT_WORDS * sizeof(uint32_t), c->stream); (void)hipStreamSynchronize(c->stream); c->cnt_parity = 0; }
-  } rezero{c};
   if (stats) {
-    uint32_t cnt[CNT_TAILS];
-    HIP_TRY(c, hipMemcpy(cnt, c->d_counters, sizeof(cnt), hipMemcpyDeviceToHost));
-    memcpy(&stats->node_visits, &cnt[any_hit ? CNT_NODE_VISITS_SH : CNT_NODE_VISITS], 8);
-    memcpy(&stats->tri_tests, &cnt[any_hit ? CNT_TRI_TESTS_SH : CNT_TRI_TESTS], 8);
+    if (counting) {
+      uint32_t cnt[CNT_TAILS];
+      HIP_TRY(c, hipMemcpy(cnt, c->d_q_counters, sizeof(cnt), hipMemcpyDeviceToHost));
+      memcpy(&stats->node_visits, &cnt[any_hit ? CNT_NODE_VISITS_SH : CNT_NODE_VISITS], 8);
+      memcpy(&stats->tri_tests, &cnt[any_hit ? CNT_TRI_TESTS_SH : CNT_TRI_TESTS], 8);
+    }
     float ms = 0.f; hipEventElapsedTime(&ms, e0, e1);
     if (any_hit) stats->ms_trace_shadow = ms; else stats->ms_trace_closest = ms;
     stats->closest_rays = any_hit ? 0 : n; stats->rays_shadow = any_hit ? n : 0;
@@ -2217,8 +2242,8 @@ int rt_intersect(rt_ctx* c, size_t n, const float* rays8, int any_hit, rt_hit* o
 }
 
 namespace {
-// The body of rt_intersect_device and rt_intersect_device_flags (their own argument checks come first).  flags: the flag-aware
-// walk (MODE_QUERY_FLAGS) with the ray words `words` (or none) and the call's query word; otherwise the plain query with any_hit.
+// The body of rt_intersect_device and rt_intersect_device_flags (their own argument checks come first): the checks of a device call,
+// then the query on the caller's stream.  packet_trace does not apply to device queries.
 int intersect_device(rt_ctx* c, size_t n, const void* d_rays8, bool any_hit, bool flags, const void* words, uint32_t query_word, void* d_hits,
                      void* d_attr, void* hip_stream) {
   const char* const name = flags ? "rt_intersect_device_flags" : "rt_intersect_device";
@@ -2241,32 +2266,9 @@ int intersect_device(rt_ctx* c, size_t n, const void* d_rays8, bool any_hit, boo
   HIP_TRY(c, hipSetDevice(c->device));
   int r = ready_to_trace(c); if (r) return r;
   if (n == 0) return RT_OK;
-  const hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-  // the workspace: allocated at the first query; the spill area re-sized (after the last query is done) when the trees grew
-  if (!c->d_q_counters) HIP_TRY(c, hipMalloc((void**)&c->d_q_counters, CNT_WORDS * sizeof(uint32_t)));
-  const size_t ovf_need = ovf_elems(c->cfg.trace_blocks, c->tail_blocks, c->ovf_stride);
-  if (ovf_need > c->q_ovf_alloc) {
-    { int q = wait_queries(c, c); if (q) return q; }
-    if (c->d_q_ovf) HIP_TRY(c, hipFree(c->d_q_ovf));
-    c->d_q_ovf = nullptr; c->q_ovf_alloc = 0;
-    HIP_TRY(c, hipMalloc((void**)&c->d_q_ovf, ovf_need * sizeof(int32_t)));
-    c->q_ovf_alloc = ovf_need;
-  }
-  for (int k = 0; k < 2; k++)
-    if (!c->ev_query[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_query[k], hipEventDisableTiming));
-  // device-side ordering: behind the previous query of this context (its workspace), and behind the copies or the build of the TLAS
-  if (c->query_last >= 0) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_query[c->query_last], 0));
-  if (c->upload_inflight[c->parity]) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_upload[c->parity], 0));
-  const SceneDev sc = scene_dev(c);
-  if (flags) launch_query_flags(sc, (const float4*)d_rays8, (const uint32_t*)words, query_word, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, c->cfg, s);
-  else launch_query(sc, (const float4*)d_rays8, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, any_hit, c->cfg, s);
-  if (d_attr) launch_hit_attr(sc, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
-  if (d_attr && flags) launch_hit_kind(sc, (const float4*)d_rays8, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipEventRecord(c->ev_query[c->parity], s));
-  c->ev_query_valid[c->parity] = true;
-  c->query_last = c->parity;
-  return RT_OK;
+  LaunchCfg cfg = c->cfg;
+  cfg.packet = 0;
+  return enqueue_query(c, hip_stream ? (hipStream_t)hip_stream : c->stream, cfg, n, d_rays8, any_hit, false, flags, words, query_word, d_hits, d_attr);
 }
 }  // namespace
 

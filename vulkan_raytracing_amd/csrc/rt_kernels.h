@@ -170,14 +170,12 @@ void launch_trace_shadow(const SceneDev& sc, const FrameDev& f, bool counting, c
 void launch_resolve(const FrameDev& f, const UniformsDev& u, hipStream_t s);
 // marks the tiles of `mask` (FrameDev::cover layout) that the frontier boxes of the instances project onto
 void launch_cover(const SceneDev& sc, const CoverViews& a, uint32_t max_boxes_per_instance, uint32_t* mask_block, hipStream_t s);
-// record-level traceRayEXT on raw rays: o = (o.xyz, tmin), d = (d.xyz, tmax); writes HitRec[n]
-// counters must hold the ray count in cnt_tail(0, 0) and zeros elsewhere; rays form shard 0 of capacity shard_cap
-void launch_trace_raw(const SceneDev& sc, const float4* ray_o, const float4* ray_d, HitRec* out, uint32_t shard_cap,
-                      int32_t* ovf_stack, uint32_t* counters, bool any_hit, bool counting, const LaunchCfg& cfg, hipStream_t s);
-// rt_intersect_device: the same traversal on the caller's rays, 8 floats each (o.xyz, tmin, d.xyz, tmax), in stream order; counters is a
-// counter block of its own (k_query_init writes the ray count into it) and ovf_stack a spill area sized like the context's
+// record-level traceRayEXT (rt_intersect, rt_intersect_device) on the caller's rays, 8 floats each (o.xyz, tmin, d.xyz, tmax), in stream
+// order; writes HitRec[n].  counters is a counter block of the query's own (k_query_init writes the ray count and fresh chunk cursors
+// into it; counting adds node visits and triangle tests to it, so the caller zeroes it first) and ovf_stack a spill area sized like the
+// context's.  cfg.variant and cfg.packet >= 2 choose the alt library's kernels; the product library walks the one-lane BVH2.
 void launch_query(const SceneDev& sc, const float4* rays, HitRec* out, uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool any_hit,
-                  const LaunchCfg& cfg, hipStream_t s);
+                  bool counting, const LaunchCfg& cfg, hipStream_t s);
 // rt_hit_attr (two float4) of every closest hit of `hits`
 void launch_hit_attr(const SceneDev& sc, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s);
 // rt_intersect_device_flags: launch_query with per-ray flags and cull masks; words (n uint32, or null: every word 0xFF000000) and

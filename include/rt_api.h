@@ -380,6 +380,32 @@ int rt_intersect_device(rt_ctx* ctx, size_t n, const void* d_rays8, int any_hit,
  * host round trip): they follow the formulas above as written. */
 int rt_intersect_device_flags(rt_ctx* ctx, size_t n, const void* d_rays8, const void* d_ray_words, uint32_t ray_flags, uint32_t cull_mask, void* d_hits, void* d_attr, void* hip_stream);
 
+/* Custom ray generation: the frame's shading of the caller's primary rays.  The caller's rays replace the pinhole camera of
+ * src/shader.rgen:62-82; everything after it — the bounce loop of src/shader.rgen:84-177 with closest hit, miss, reflection, refraction and
+ * shadow rays — is the frame's, and the colours are those a frame would compute for the same rays.
+ * Rays: d_rays8 holds n = n_points * n_samples records of 32 B in rt_intersect's layout (o.xyz, w3, d.xyz, tmax), 16-B aligned, memory of
+ * ctx's GPU, sample-major: record i * n_points + p is sample i of point p (a frame's sample id i * pixels + p).  The sample index i gives
+ * the pow(0.9, i) weight of src/shader.rgen:127; n_samples = 1 is plain per-ray shading.  The first segment is traced over
+ * [0.001, tmax] (tmax = 10000 is src/shader.rgen:87); word 3 is ignored.  Every later segment and every shadow ray uses the reference's
+ * constants.  Directions are used as given, like rayDirection after the normalize of src/shader.rgen:81: the caller normalises them.
+ * A record with a non-finite component in o or d, or with d = 0, is not traced: its sample is (0, 0, 0, 0) — alpha 0 marks it — and it
+ * still counts in its point's average.  tmax <= 0.001 (or NaN) is an empty interval: a miss, the sample is the sky colour.
+ * Scene and uniforms are the context's, as for a frame: instances, BLASes, materials, instance types, skybox, light position and
+ * intensity, maxBounceCount, the object types.  The camera fields and samplesPerPixel are ignored.
+ * Outputs (at least one; float32 RGBA, 16-B aligned, memory of ctx's GPU): d_sample_rgba, optional, n float4 — each sample's tmpColor
+ * with alpha 1, the color += vec4(tmpColor, 1) term of src/shader.rgen:178; d_point_rgba, optional, n_points float4 — the average of a
+ * point's samples with the frame's ordered sum and division (src/shader.rgen:178-183).  The pinhole rays of a frame therefore give the
+ * frame bit for bit.  output_rgba8 / output_bgra8 do not apply.
+ * Ordering as rt_intersect_device: rays are read and outputs written in stream order on hip_stream (NULL = the context's stream); no host
+ * copy, no host synchronisation, no wait for a frame in flight on the context (the call has queues of its own, allocated at the first
+ * call and grown after the previous call is done).  The call sees the TLAS of the last rt_set_instances* before it and the scene as it
+ * was at the call; shading calls and device ray queries of a context run one after another.  n_points == 0 enqueues nothing.  The call
+ * is not counted in rt_get_stats.
+ * RT_ERR_INVALID_ARGUMENT: NULL ctx, NULL rays with n > 0, both outputs NULL, a misaligned pointer or one that is not device memory of
+ * ctx's GPU, n_samples == 0, n > 2^25, a maxBounceCount a frame refuses, trace_variant != 0; RT_ERR_NOT_READY: as for a frame (no uniforms, no
+ * geometry, no TLAS, a TLAS stale after rt_refit_blas_device, a frame batch held by the context). */
+int rt_shade_rays_device(rt_ctx* ctx, size_t n_points, uint32_t n_samples, const void* d_rays8, void* d_sample_rgba, void* d_point_rgba, void* hip_stream);
+
 /* Same frame as rt_trace but through the instrumented traversal kernels (visit counters). */
 int rt_trace_counting(rt_ctx* ctx, int width, int height, float* out_rgba32f_host, rt_stats* stats);
 

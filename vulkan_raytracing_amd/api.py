@@ -60,7 +60,7 @@ HIT_KIND_BACK_FACING = 0xFF
 
 EXPORTS = ["rt_create", "rt_create_frame_slot", "rt_destroy", "rt_upload_geometry", "rt_build_blas", "rt_set_instances", "rt_set_instances_device", "rt_refit_blas_device", "rt_set_materials", "rt_set_instance_types", "rt_set_uniforms", "rt_set_skybox",
            "rt_trace", "rt_trace_async", "rt_trace_wait", "rt_trace_shard", "rt_set_batch", "rt_trace_shard_batch", "rt_assemble_shards", "rt_shard_rows", "rt_synchronize", "rt_get_stats", "rt_set_timing", "rt_intersect",
-           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_set_param", "rt_debug_check_builders", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
+           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
 
 _LIBS = {}
 
@@ -102,6 +102,7 @@ def lib(variant=None):
         L.rt_intersect.argtypes = [vp, C.c_size_t, vp, C.c_int, vp, C.c_int, C.POINTER(RtStats)]
         L.rt_intersect_device.argtypes = [vp, C.c_size_t, vp, C.c_int, vp, vp, vp]
         L.rt_intersect_device_flags.argtypes = [vp, C.c_size_t, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
+        L.rt_shade_rays_device.argtypes = [vp, C.c_size_t, C.c_uint32, vp, vp, vp, vp]
         L.rt_last_error.argtypes = [vp]
         L.rt_last_error.restype = C.c_char_p
         L.rt_device_info.argtypes = [vp]
@@ -358,11 +359,55 @@ class RtContext:
         hits, attr = self._device_query(rays, attributes, stream, out, (words,), call, "rt_intersect_device_flags")
         return RayQuery(hits, attr, hit_kind=True)
 
-    def _device_query(self, rays, attributes, stream, out, inputs, call, name):
-        """the common part of intersect_device*: checks, output buffers, the null-stream detour; call(run_stream, hits, attr) -> status"""
+    def shade_rays_device(self, rays, samples=1, per_sample=True, points=True, stream=None, out=None):
+        """rt_shade_rays_device: the frame's shading of caller-generated primary rays.  `rays` is a contiguous float32 torch tensor
+        (n_points * samples, 8) on this context's GPU (o.xyz, reserved, d.xyz, tmax per row; d normalised), sample-major: row
+        i * n_points + p is sample i of point p.  Read and written in the order of `stream` (default: the current torch stream of that
+        device); the call never waits on the host.  Returns (samples_rgba, points_rgba): float32 (n, 4) per-sample colours (alpha 1; 0 for
+        a record that is not a ray) and float32 (n_points, 4) per-point averages, each None when not asked for (per_sample / points).
+        out = (samples_rgba, points_rgba) reuses such buffers (None where not asked for).  See include/rt_api.h."""
+        import torch
+        self._check_rays(rays, "shade_rays_device")
+        samples = int(samples)
+        if samples < 1:
+            raise ValueError("samples must be >= 1, got %d" % samples)
+        if not (per_sample or points):
+            raise ValueError("shade_rays_device needs per_sample or points")
+        n = rays.shape[0]
+        if n % samples:
+            raise ValueError("the ray tensor holds n_points * samples rows: %d rows are not a multiple of %d samples" % (n, samples))
+        n_points = n // samples
+        cur = torch.cuda.current_stream(rays.device)
+        if stream is None:
+            stream = cur
+        if out is None:
+            srgba = torch.empty((n, 4), dtype=torch.float32, device=rays.device) if per_sample else None
+            prgba = torch.empty((n_points, 4), dtype=torch.float32, device=rays.device) if points else None
+            if stream != cur:   # (allocated for the current stream, written on `stream`)
+                for t in (srgba, prgba):
+                    if t is not None:
+                        t.record_stream(stream)
+        else:
+            srgba, prgba = out
+            for t, want, rows, what in ((srgba, per_sample, n, "samples"), (prgba, points, n_points, "points")):
+                if want and (t is None or t.dtype != torch.float32 or tuple(t.shape) != (rows, 4) or not t.is_contiguous() or t.device != rays.device):
+                    raise ValueError("out %s must be a contiguous float32 (%d, 4) tensor on the rays' device" % (what, rows))
+            srgba = srgba if per_sample else None
+            prgba = prgba if points else None
+
+        def call(run):
+            return self.L.rt_shade_rays_device(self.h, n_points, samples, C.c_void_p(rays.data_ptr()),
+                                               C.c_void_p(srgba.data_ptr()) if srgba is not None else None,
+                                               C.c_void_p(prgba.data_ptr()) if prgba is not None else None, C.c_void_p(run.cuda_stream))
+        if n:
+            self._on_stream(stream, (rays, srgba, prgba), call, "rt_shade_rays_device")
+        return srgba, prgba
+
+    def _check_rays(self, rays, name):
+        """the checks of a (n, 8) float32 ray tensor on this context's GPU"""
         import torch
         if not isinstance(rays, torch.Tensor):
-            raise TypeError("intersect_device takes a torch tensor, got %s" % type(rays).__name__)
+            raise TypeError("%s takes a torch tensor, got %s" % (name, type(rays).__name__))
         if rays.device.type != "cuda" or rays.device.index != self.device:
             raise ValueError("ray tensor must live on cuda:%d (the context's GPU), not %s" % (self.device, rays.device))
         if rays.dtype != torch.float32:
@@ -371,6 +416,29 @@ class RtContext:
             raise ValueError("ray tensor must be contiguous")
         if rays.dim() != 2 or rays.shape[1] != 8:
             raise ValueError("ray tensor has shape (n, 8), got %s" % (tuple(rays.shape),))
+
+    def _on_stream(self, stream, tensors, call, name):
+        """call(run_stream) -> status, on `stream`; torch's default stream is the null stream, which the C ABI reads as "the context's
+        stream" (a non-blocking stream the null stream does not order): then the call goes through a side stream that waits for the
+        default stream and that the default stream waits for in turn — no host synchronisation"""
+        import torch
+        run = stream
+        if stream.cuda_stream == 0:
+            if getattr(self, "_query_stream", None) is None:
+                self._query_stream = torch.cuda.Stream(stream.device)
+            run = self._query_stream
+            run.wait_stream(stream)
+            for t in tensors:
+                if t is not None:
+                    t.record_stream(run)
+        self._chk(call(run), name)
+        if run is not stream:
+            stream.wait_stream(run)
+
+    def _device_query(self, rays, attributes, stream, out, inputs, call, name):
+        """the common part of intersect_device*: checks, output buffers, the null-stream detour; call(run_stream, hits, attr) -> status"""
+        import torch
+        self._check_rays(rays, "intersect_device")
         n = rays.shape[0]
         cur = torch.cuda.current_stream(rays.device)
         if stream is None:
@@ -390,21 +458,7 @@ class RtContext:
                 raise ValueError("out attributes must be a contiguous int32 (n, 8) tensor on the rays' device")
             attr = attr if attributes else None
         if n:
-            run = stream
-            if stream.cuda_stream == 0:
-                # torch's default stream is the null stream, which the C ABI reads as "the context's stream" (a non-blocking stream the
-                # null stream does not order): the query goes through a side stream that waits for the default stream and that the
-                # default stream waits for in turn — no host synchronisation
-                if getattr(self, "_query_stream", None) is None:
-                    self._query_stream = torch.cuda.Stream(rays.device)
-                run = self._query_stream
-                run.wait_stream(stream)
-                for t in (rays, hits, attr) + tuple(inputs):
-                    if t is not None:
-                        t.record_stream(run)
-            self._chk(call(run, hits, attr), name)
-            if run is not stream:
-                stream.wait_stream(run)
+            self._on_stream(stream, (rays, hits, attr) + tuple(inputs), lambda run: call(run, hits, attr), name)
         return hits, attr
 
 

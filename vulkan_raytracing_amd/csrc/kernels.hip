@@ -2165,6 +2165,93 @@ void launch_hit_kind(const SceneDev& sc, const float4* rays, const HitRec* hits,
   hipLaunchKernelGGL(k_hit_kind, dim3((n + 255u) / 256u), dim3(256), 0, s, sc, rays, hits, reinterpret_cast<uint32_t*>(attr), n);
 }
 
+// ---- caller-generated rays (rt_shade_rays_device): the frame's bounce pipeline between an ingest and a per-point resolve
+// k_ray_ingest takes k_raygen's place: sample sid is the caller's record sid (o.xyz, w3, d.xyz, tmax), read where the caller left it.
+// A record with a non-finite o or d component, or d = 0, is not traced: its sample is (0, 0, 0, 0).  tmax <= 0.001 (or NaN) is the
+// empty interval of the first traceRayEXT: a miss.  The others take k_raygen's two-level TLAS cull with the record's tmax, always with
+// the far-ray logic (origins are arbitrary); a ray that misses both levels gets its sky colour here (src/shader.rmiss:11 +
+// src/shader.rgen:90-94), the survivors go to bounce queue 0 with ONE allocation per workgroup, workgroup b to shard b % 8.
+__device__ __forceinline__ bool finite_bits(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
+
+__global__ __launch_bounds__(256) void k_ray_ingest(SceneDev sc, FrameDev f, const float4* __restrict__ rays, uint32_t n) {
+  const uint32_t sid = blockIdx.x * 256u + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  bool survive = false;
+  F3 o = mk3(0.f, 0.f, 0.f), d = mk3(0.f, 0.f, 1.f);
+  float tmax = 0.f;
+  if (sid < n) {
+    const float4 ro = ld_stream(&rays[2u * (size_t)sid]), rd = ld_stream(&rays[2u * (size_t)sid + 1u]);
+    o = mk3(ro.x, ro.y, ro.z); d = mk3(rd.x, rd.y, rd.z); tmax = rd.w;
+    const bool valid = finite_bits(o.x) && finite_bits(o.y) && finite_bits(o.z) && finite_bits(d.x) && finite_bits(d.y) && finite_bits(d.z) &&
+                       (d.x != 0.0f || d.y != 0.0f || d.z != 0.0f);
+    if (valid && tmax > 0.001f) {
+      F3 qs, qb; uint3 rot;
+      quant_space(o, d, sc.tlas_q_lo, sc.tlas_q_scale, qs, qb, rot);
+      const bool far = quant_far(qs, qb);
+      // (k_raygen's test with the record's interval)
+      const uint4* rp = reinterpret_cast<const uint4*>(sc.blas_nodes + sc.tlas_root);
+      const uint4 Q0 = rp[0], Q1 = rp[1];
+      float tn;
+      const bool h0 = far || slab_q(Q0.x, Q0.y, Q0.z, qs, qb, rot, 0.001f, tmax, tn);
+      const bool h1 = (far || slab_q(Q0.w, Q1.x, Q1.y, qs, qb, rot, 0.001f, tmax, tn)) && Q1.w != Q1.z;
+      const int c0 = (int)Q1.z, c1 = (int)Q1.w;
+      survive = (h0 && c0 < 0) || (h1 && c1 < 0);
+#pragma unroll
+      for (int k = 0; k < 2; k++) {
+        const int ch = k ? c1 : c0;
+        if ((k ? h1 : h0) && ch >= 0 && !survive) {
+          const uint4* np = reinterpret_cast<const uint4*>(sc.blas_nodes + ch);
+          const uint4 N0 = np[0], N1 = np[1];
+          survive = far || slab_q(N0.x, N0.y, N0.z, qs, qb, rot, 0.001f, tmax, tn) || slab_q(N0.w, N1.x, N1.y, qs, qb, rot, 0.001f, tmax, tn);
+        }
+      }
+    }
+    if (!survive) {
+      float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (valid) { const F3 s = sample_sky(sc, mk3(d.x, d.y, -d.z)); c = make_float4(s.x, s.y, s.z, 1.0f); }
+      st_stream(&f.sample_color[sid], c);
+    }
+  }
+  __shared__ uint32_t s_run[5];
+  const uint64_t smask = __ballot(survive);
+  if (lane == 0) s_run[wave] = (uint32_t)__builtin_popcountll(smask);
+  __syncthreads();
+  const uint32_t shard = blockIdx.x & (N_SHARDS - 1);
+  if (threadIdx.x == 0) {
+    uint32_t tot = 0;
+    for (uint32_t w = 0; w < 4u; w++) { const uint32_t c = s_run[w]; s_run[w] = tot; tot += c; }
+    s_run[4] = tot ? atomicAdd(f.counters + cnt_tail(0, (int)shard), tot) : 0u;
+  }
+  __syncthreads();
+  if (survive) {
+    const uint32_t v = shard * f.shard_cap + s_run[4] + s_run[wave] + prefix_rank(smask);
+    st_stream(&f.ray_o[0][v], make_float4(o.x, o.y, o.z, tmax));
+    st_stream(&f.ray_d[0][v], make_float4(d.x, d.y, d.z, __uint_as_float(sid)));
+  }
+}
+
+// k_resolve's ordered sum over the samples of a point and its division (src/shader.rgen:178-183), into the caller's buffer only
+__global__ __launch_bounds__(256) void k_resolve_points(const float4* __restrict__ sample_color, float4* __restrict__ out, uint32_t n_points,
+                                                        uint32_t n_samples) {
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= n_points) return;
+  float r = 0.f, g = 0.f, b = 0.f, al = 0.f;
+  for (uint32_t i = 0; i < n_samples; i++) {
+    const float4 c = ld_stream(&sample_color[p + (size_t)i * n_points]);
+    r += c.x; g += c.y; b += c.z; al += c.w;
+  }
+  const float nn = (float)n_samples;
+  out[p] = make_float4(r / nn, g / nn, b / nn, al / nn);
+}
+
+uint32_t ray_ingest_block_count(uint32_t n) { return (n + 255u) / 256u; }
+void launch_ray_ingest(const SceneDev& sc, const FrameDev& f, const float4* rays, uint32_t n, hipStream_t s) {
+  hipLaunchKernelGGL(k_ray_ingest, dim3(ray_ingest_block_count(n)), dim3(256), 0, s, sc, f, rays, n);
+}
+void launch_resolve_points(const float4* sample_color, float4* out, uint32_t n_points, uint32_t n_samples, hipStream_t s) {
+  hipLaunchKernelGGL(k_resolve_points, dim3((n_points + 255u) / 256u), dim3(256), 0, s, sample_color, out, n_points, n_samples);
+}
+
 int tail_blocks_per_cu() {
   // the smallest over the instantiations: any of them may be the one in flight (counting; 4-ary records in the alt build)
   int n = 1 << 30, v = 0;

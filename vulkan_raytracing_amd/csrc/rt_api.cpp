@@ -301,6 +301,11 @@ struct rt_ctx {
   hipEvent_t ev_query[2] = {nullptr, nullptr};
   bool ev_query_valid[2] = {false, false};
   int query_last = -1;             // parity of the last query (-1: none since the last host wait)
+  // rt_shade_rays_device: the bounce pipeline's queues of its own (a pending frame keeps the context's), sized by the ray count of the
+  // largest call so far; the counter block and the spill area are the query workspace's (shading calls and queries are serialised)
+  FrameDev shade{};
+  size_t shade_capacity = 0;       // entries of the ray, hit and shadow queues
+  size_t shade_colors = 0;         // float4 of shade.sample_color (0: every call so far wrote its samples into the caller's buffer)
 };
 
 namespace {
@@ -871,26 +876,38 @@ int ensure_common(rt_ctx* c) {
   return RT_OK;
 }
 
+// the buffers of a bounce pipeline (frames: c->frame; rt_shade_rays_device: c->shade), freed and allocated again: ray and hit queues
+// of `capacity` entries, shadow arrays of sh_cap, `colors` per-sample colours (0: none)
+int alloc_queues(rt_ctx* c, FrameDev& f, size_t capacity, size_t sh_cap, size_t colors) {
+  void** ptrs[] = {(void**)&f.ray_o[0], (void**)&f.ray_o[1], (void**)&f.ray_d[0], (void**)&f.ray_d[1], (void**)&f.hit_a};
+  void** sh_ptrs[] = {(void**)&f.sh_o, (void**)&f.sh_d, (void**)&f.sh_c};
+  for (void** p : ptrs) { if (*p) HIP_TRY(c, hipFree(*p)); *p = nullptr; }
+  for (void** p : sh_ptrs) { if (*p) HIP_TRY(c, hipFree(*p)); *p = nullptr; }
+  if (f.sample_color) { HIP_TRY(c, hipFree(f.sample_color)); f.sample_color = nullptr; }
+  if (f.hit_inst) { HIP_TRY(c, hipFree(f.hit_inst)); f.hit_inst = nullptr; }
+  if (f.sh_e) { HIP_TRY(c, hipFree(f.sh_e)); f.sh_e = nullptr; }
+  for (void** p : ptrs) HIP_TRY(c, hipMalloc(p, capacity * sizeof(float4)));
+  if (colors) HIP_TRY(c, hipMalloc((void**)&f.sample_color, colors * sizeof(float4)));
+  for (void** p : sh_ptrs) HIP_TRY(c, hipMalloc(p, sh_cap * sizeof(float4)));
+  HIP_TRY(c, hipMalloc((void**)&f.hit_inst, capacity * sizeof(int32_t)));
+  HIP_TRY(c, hipMalloc((void**)&f.sh_e, sh_cap * sizeof(uint32_t)));
+  return RT_OK;
+}
+void free_queues(FrameDev& f) {
+  void* ptrs[] = {f.ray_o[0], f.ray_o[1], f.ray_d[0], f.ray_d[1], f.hit_a, f.hit_inst, f.sh_o, f.sh_d, f.sh_c, f.sh_e, f.sample_color};
+  for (void* p : ptrs) if (p) hipFree(p);
+}
+
 int ensure_frame(rt_ctx* c, size_t capacity) {
   int r = ensure_common(c); if (r) return r;
   const bool want_double = c->shadow_beams != 0;
   if (capacity <= c->frame_capacity && (!want_double || c->sh_double)) return RT_OK;
   capacity = std::max(capacity, c->frame_capacity);
-  FrameDev& f = c->frame;
-  void** ptrs[] = {(void**)&f.ray_o[0], (void**)&f.ray_o[1], (void**)&f.ray_d[0], (void**)&f.ray_d[1], (void**)&f.hit_a, (void**)&f.sample_color};
+  c->frame_capacity = 0;
   // (the shadow arrays hold two regions: the shadow runs of bounce 0 in their primary rays' slots — kernels_beam.inc — and the compact
   // queue of the later bounces above them)
-  void** sh_ptrs[] = {(void**)&f.sh_o, (void**)&f.sh_d, (void**)&f.sh_c};
-  for (void** p : ptrs) { if (*p) HIP_TRY(c, hipFree(*p)); *p = nullptr; }
-  for (void** p : sh_ptrs) { if (*p) HIP_TRY(c, hipFree(*p)); *p = nullptr; }
-  if (f.hit_inst) { HIP_TRY(c, hipFree(f.hit_inst)); f.hit_inst = nullptr; }
-  if (f.sh_e) { HIP_TRY(c, hipFree(f.sh_e)); f.sh_e = nullptr; }
-  c->frame_capacity = 0;
-  for (void** p : ptrs) HIP_TRY(c, hipMalloc(p, capacity * sizeof(float4)));
   const size_t sh_cap = (want_double ? 2 : 1) * capacity;
-  for (void** p : sh_ptrs) HIP_TRY(c, hipMalloc(p, sh_cap * sizeof(float4)));
-  HIP_TRY(c, hipMalloc((void**)&f.hit_inst, capacity * sizeof(int32_t)));
-  HIP_TRY(c, hipMalloc((void**)&f.sh_e, sh_cap * sizeof(uint32_t)));
+  r = alloc_queues(c, c->frame, capacity, sh_cap, capacity); if (r) return r;
   c->sh_double = want_double;
   c->frame_capacity = capacity;
   return RT_OK;
@@ -1421,10 +1438,10 @@ void rt_destroy(rt_ctx* c) {
   hipSetDevice(c->device);
   wait_queries(c, c);   // the query workspace is freed below
   hipDeviceSynchronize();
-  FrameDev& f = c->frame;
-  void* ptrs[] = {c->d_inst[0], c->d_inst[1], c->d_out_own, c->d_counters, c->d_ovf, c->d_cover_mask, c->d_entry, c->d_light_entry, f.sh_e, c->d_fault_total, c->d_tile_blob, c->d_blob_arena, c->d_blob_list,
-                  f.ray_o[0], f.ray_o[1], f.ray_d[0], f.ray_d[1], f.hit_a, f.hit_inst, f.sh_o, f.sh_d, f.sh_c, f.sample_color};
+  void* ptrs[] = {c->d_inst[0], c->d_inst[1], c->d_out_own, c->d_counters, c->d_ovf, c->d_cover_mask, c->d_entry, c->d_light_entry, c->d_fault_total, c->d_tile_blob, c->d_blob_arena, c->d_blob_list};
   for (void* p : ptrs) if (p) hipFree(p);
+  free_queues(c->frame);
+  free_queues(c->shade);
   if (c->h_hint) hipHostFree(c->h_hint);
   if (c->h_out_pinned) hipHostFree(c->h_out_pinned);
   if (c->h_stats) hipHostFree(c->h_stats);
@@ -2161,13 +2178,10 @@ int rt_trace_wait(rt_ctx* c, const void** pixels, rt_stats* stats) {
 int rt_trace_counting(rt_ctx* c, int W, int H, float* out, rt_stats* stats) { return trace_host(c, W, H, out, stats, true); }
 
 namespace {
-// The enqueue of every ray query (rt_intersect, rt_intersect_device, rt_intersect_device_flags) on stream s, after the caller's checks.
-// flags: the flag-aware walk (MODE_QUERY_FLAGS) with the ray words `words` (or none) and the call's query word; otherwise the plain
-// walk with any_hit, instrumented when counting (its counts start from a zeroed counter block).  d_attr (optional): the hit attributes.
-// t0 / t1 (optional): events recorded around the walk.
-int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, size_t n, const void* d_rays8, bool any_hit, bool counting, bool flags,
-                  const void* words, uint32_t query_word, void* d_hits, void* d_attr, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
-  // the workspace: allocated at the first query; the spill area re-sized (after the last query is done) when the trees grew
+// The query workspace of ray queries and shading calls: allocated at the first one; the spill area re-sized (after the last one is done)
+// when the trees grew.  Then stream s is ordered on the device behind the previous query or shading call of this context (the workspace)
+// and behind the copies or the build of the TLAS.
+int query_workspace(rt_ctx* c, hipStream_t s) {
   if (!c->d_q_counters) HIP_TRY(c, hipMalloc((void**)&c->d_q_counters, CNT_WORDS * sizeof(uint32_t)));
   const size_t ovf_need = ovf_elems(c->cfg.trace_blocks, c->tail_blocks, c->ovf_stride);
   if (ovf_need > c->q_ovf_alloc) {
@@ -2179,9 +2193,26 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, size_t n, cons
   }
   for (int k = 0; k < 2; k++)
     if (!c->ev_query[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_query[k], hipEventDisableTiming));
-  // device-side ordering: behind the previous query of this context (its workspace), and behind the copies or the build of the TLAS
   if (c->query_last >= 0) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_query[c->query_last], 0));
   if (c->upload_inflight[c->parity]) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_upload[c->parity], 0));
+  return RT_OK;
+}
+// the completion event of the query or shading call just enqueued on s: it reads TLAS parity c->parity
+int query_done(rt_ctx* c, hipStream_t s) {
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipEventRecord(c->ev_query[c->parity], s));
+  c->ev_query_valid[c->parity] = true;
+  c->query_last = c->parity;
+  return RT_OK;
+}
+
+// The enqueue of every ray query (rt_intersect, rt_intersect_device, rt_intersect_device_flags) on stream s, after the caller's checks.
+// flags: the flag-aware walk (MODE_QUERY_FLAGS) with the ray words `words` (or none) and the call's query word; otherwise the plain
+// walk with any_hit, instrumented when counting (its counts start from a zeroed counter block).  d_attr (optional): the hit attributes.
+// t0 / t1 (optional): events recorded around the walk.
+int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, size_t n, const void* d_rays8, bool any_hit, bool counting, bool flags,
+                  const void* words, uint32_t query_word, void* d_hits, void* d_attr, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
+  { int r = query_workspace(c, s); if (r) return r; }
   if (counting) HIP_TRY(c, hipMemsetAsync(c->d_q_counters, 0, CNT_WORDS * sizeof(uint32_t), s));
   const SceneDev sc = scene_dev(c);
   if (t0) HIP_TRY(c, hipEventRecord(t0, s));
@@ -2190,11 +2221,7 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, size_t n, cons
   if (t1) HIP_TRY(c, hipEventRecord(t1, s));
   if (d_attr) launch_hit_attr(sc, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
   if (d_attr && flags) launch_hit_kind(sc, (const float4*)d_rays8, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipEventRecord(c->ev_query[c->parity], s));
-  c->ev_query_valid[c->parity] = true;
-  c->query_last = c->parity;
-  return RT_OK;
+  return query_done(c, s);
 }
 }  // namespace
 
@@ -2302,6 +2329,80 @@ int rt_intersect_device_flags(rt_ctx* c, size_t n, const void* d_rays8, const vo
     return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device_flags: SKIP_TRIANGLES with SKIP_AABBS or a facing cull");
   if (n && ((uintptr_t)d_ray_words & 3u)) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device_flags: ray words must be 4-byte aligned");
   return intersect_device(c, n, d_rays8, false, true, n ? d_ray_words : nullptr, (cull_mask << 24) | ray_flags, d_hits, d_attr, hip_stream);
+}
+
+// Custom ray generation: the caller's primary rays (n_points * n_samples records, sample-major) through the frame's bounce pipeline —
+// k_ray_ingest in k_raygen's place, then launch_trace_closest / launch_shade per bounce and launch_trace_shadow exactly as a frame runs
+// them — into the caller's per-sample and / or per-point colours, ordered on the caller's stream like rt_intersect_device (the query
+// workspace and bookkeeping).  What a frame of a pinhole camera has and this call cannot: no coverage mask, entry records, pixel beams or
+// jitter table (they assume one camera), no k_tail (its fault path re-renders from the host), no host readback to stop early (a bounce
+// with an empty queue costs two launches whose persistent grids leave at once).
+int rt_shade_rays_device(rt_ctx* c, size_t n_points, uint32_t n_samples, const void* d_rays8, void* d_sample_rgba, void* d_point_rgba, void* hip_stream) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  constexpr size_t MAX_RAYS = (size_t)1 << 25;
+  if (n_samples == 0) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_shade_rays_device: n_samples must be >= 1");
+  if (!d_sample_rgba && !d_point_rgba) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_shade_rays_device: d_sample_rgba and d_point_rgba are both NULL");
+  if (n_points > MAX_RAYS || (uint64_t)n_points * n_samples > MAX_RAYS)
+    return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_shade_rays_device: at most 2^25 rays (n_points * n_samples) per call");
+  const size_t n = n_points * n_samples;
+  if (n && !d_rays8) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_shade_rays_device: d_rays8 is NULL");
+  if (((uintptr_t)d_rays8 | (uintptr_t)d_sample_rgba | (uintptr_t)d_point_rgba) & 15u)
+    return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_shade_rays_device: rays and outputs must be 16-byte aligned");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_shade_rays_device needs trace_variant 0");
+  if (c->uni.max_bounce_count + 2 > (uint32_t)CNT_MAX_BOUNCES) return fail(c, RT_ERR_INVALID_ARGUMENT, "maxBounceCount too large (the frame's limit)");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (n) {
+    const void* ptrs[3] = {d_rays8, d_sample_rgba, d_point_rgba};
+    for (const void* p : ptrs) {
+      if (!p) continue;
+      hipPointerAttribute_t at{};
+      const bool ok = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == c->device;
+      (void)hipGetLastError();   // (a host pointer leaves an error behind)
+      if (!ok) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_shade_rays_device: rays and outputs must be device memory of the context's GPU (" + std::to_string(c->device) + ")");
+    }
+  }
+  if (!c->have_uni) return fail(c, RT_ERR_NOT_READY, "rt_set_uniforms has not been called");
+  int r = ready_to_trace(c); if (r) return r;
+  if (n == 0) return RT_OK;
+  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+  // k_ray_ingest's workgroup b appends to shard b % 8 and a path stays in its shard: this bounds every queue of the call
+  const size_t shard_cap = std::max<size_t>(256, ((ray_ingest_block_count((uint32_t)n) + N_SHARDS - 1) / N_SHARDS) * 256);
+  const size_t capacity = shard_cap * N_SHARDS;
+  const size_t colors = d_sample_rgba ? 0 : n;   // (the caller's per-sample buffer IS sample_color when it has one: every sample is written once)
+  if (capacity > c->shade_capacity || colors > c->shade_colors) {
+    { int q = wait_queries(c, c); if (q) return q; }   // (the previous call may still use the queues)
+    const size_t cap = std::max(capacity, c->shade_capacity), col = std::max(colors, c->shade_colors);
+    c->shade_capacity = 0; c->shade_colors = 0;
+    r = alloc_queues(c, c->shade, cap, cap, col); if (r) return r;
+    c->shade_capacity = cap; c->shade_colors = col;
+  }
+  r = query_workspace(c, s); if (r) return r;
+  FrameDev f{};
+  for (int k = 0; k < 2; k++) { f.ray_o[k] = c->shade.ray_o[k]; f.ray_d[k] = c->shade.ray_d[k]; }
+  f.hit_a = c->shade.hit_a; f.hit_inst = c->shade.hit_inst;
+  f.sh_o = c->shade.sh_o; f.sh_d = c->shade.sh_d; f.sh_c = c->shade.sh_c; f.sh_e = c->shade.sh_e;
+  f.sample_color = d_sample_rgba ? (float4*)d_sample_rgba : c->shade.sample_color;
+  f.counters = c->d_q_counters; f.ovf_stack = c->d_q_ovf;
+  f.shard_cap = (uint32_t)shard_cap;
+  // one row of n_points "pixels": k_shade's sample index sid / (rows * width) is the record's sample index
+  f.width = (int)n_points; f.height = 1; f.rows = 1; f.band_rows = 1; f.shard = 0; f.n_shards = 1;
+  f.batch_k = 1;
+  f.far_possible = 1;
+  f.settle_dead_shadow_rays = c->dead_shadow_rays;
+  LaunchCfg cfg = c->cfg;
+  cfg.packet = 0; cfg.far = 1;
+  const SceneDev sc = scene_dev(c);
+  const UniformsDev u = c->uni;
+  const BatchTab bt{};
+  HIP_TRY(c, hipMemsetAsync(c->d_q_counters, 0, CNT_WORDS * sizeof(uint32_t), s));
+  launch_ray_ingest(sc, f, (const float4*)d_rays8, (uint32_t)n, s);
+  for (uint32_t b = 0; b <= u.max_bounce_count; b++) {
+    launch_trace_closest(sc, f, (int)b, false, cfg, s);
+    launch_shade(sc, f, u, bt, (int)b, cfg, s);
+  }
+  launch_trace_shadow(sc, f, false, cfg, s);
+  if (d_point_rgba) launch_resolve_points(f.sample_color, (float4*)d_point_rgba, (uint32_t)n_points, n_samples, s);
+  return query_done(c, s);
 }
 
 }  // extern "C"

@@ -184,6 +184,13 @@ void launch_query_flags(const SceneDev& sc, const float4* rays, const uint32_t* 
                         int32_t* ovf_stack, uint32_t* counters, const LaunchCfg& cfg, hipStream_t s);
 // the hit kind (0xFE front, 0xFF back, 0 miss) of every hit of `hits` into word 7 of its rt_hit_attr (after launch_hit_attr)
 void launch_hit_kind(const SceneDev& sc, const float4* rays, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s);
+// rt_shade_rays_device: k_ray_ingest replaces k_raygen for the caller's n rays (32 bytes each, o.xyz, w3, d.xyz, tmax; sample id = record
+// index): sky colours of the rays that miss the TLAS and (0, 0, 0, 0) for invalid records into f.sample_color, the others into bounce queue 0
+// (workgroup b appends to shard b % 8: f.shard_cap >= 256 * ceil(ray_ingest_block_count(n) / 8)).  f.counters must be zero.
+uint32_t ray_ingest_block_count(uint32_t n);
+void launch_ray_ingest(const SceneDev& sc, const FrameDev& f, const float4* rays, uint32_t n, hipStream_t s);
+// k_resolve's per-pixel average for sample-major colours (sample i of point p at i * n_points + p) into out[n_points]
+void launch_resolve_points(const float4* sample_color, float4* out, uint32_t n_points, uint32_t n_samples, hipStream_t s);
 
 // de-interleave n_shards gathered compact shards (shard_stride_px pixels apart) into the width x height frame
 void launch_assemble(const void* gathered, void* out, int width, int height, int band_rows, int n_shards, size_t shard_stride_px, bool rgba8, hipStream_t s);

@@ -12,25 +12,15 @@ import numpy as np
 import pytest
 
 from tests import scenes
+from tests.exact import assert_frame_equals_oracle
 from vulkan_raytracing_amd import RtContext, api, host, workloads
 from vulkan_raytracing_amd.api import INSTANCE_DTYPE, RtError
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RES = scenes.RES
 PATHS = [os.path.join(RES, "teapot.obj"), os.path.join(RES, "cube.obj")]
-TOL = 1e-3
-FRAC = 0.999
 RT_ERR_INVALID_ARGUMENT, RT_ERR_NOT_READY = 1, 2
 W, H = 200, 112
-
-
-def check_image(gpu, ref):
-    """the bar of tests/test_gpu_parity.py: max-abs <= 1e-3 and bit-exact on >= 99.9 % of pixels"""
-    diff = np.abs(gpu - ref).max(axis=2)
-    r = {"max": float(diff.max()), "frac_within_tol": float((diff <= TOL).mean()), "frac_bit_exact": float((diff == 0).mean())}
-    assert r["frac_within_tol"] >= FRAC, r
-    assert r["frac_bit_exact"] >= FRAC, r
-    return r
 
 
 # ---- CPU ----------------------------------------------------------------------------------------------------------------------
@@ -237,7 +227,7 @@ def test_deformed_two_objects_both_instance_sources_and_oracle(ctx, geom, sky):
     sp = scenes.ScenePair(PATHS, inst, u, sky=sky)
     sp.orc.set_geometry(verts, geom.idx, geom.ranges)
     ref, _ = sp.orc.render(W, H)
-    check_image(img, ref)
+    assert_frame_equals_oracle(img, sp.orc, W, H, ref=ref)
     # device instance records: a build, a refit of the mesh, an update of the device TLAS
     dev = torch.from_numpy(np.ascontiguousarray(inst, INSTANCE_DTYPE).view(np.uint8).reshape(-1, 64).copy()).to("cuda:0")
     torch.cuda.synchronize()

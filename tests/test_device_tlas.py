@@ -10,24 +10,14 @@ import numpy as np
 import pytest
 
 from tests import scenes
+from tests.exact import assert_frame_equals_oracle
 from vulkan_raytracing_amd import RtContext, api, host, workloads
 from vulkan_raytracing_amd.api import INSTANCE_DTYPE, RtError
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RES = scenes.RES
 PATHS = [os.path.join(RES, "teapot.obj"), os.path.join(RES, "cube.obj")]
-TOL = 1e-3
-FRAC = 0.999
 RT_ERR_INVALID_ARGUMENT, RT_ERR_NOT_READY = 1, 2
-
-
-def check_image(gpu, ref):
-    """the bar of tests/test_gpu_parity.py: max-abs <= 1e-3 and bit-exact on >= 99.9 % of pixels"""
-    diff = np.abs(gpu - ref).max(axis=2)
-    r = {"max": float(diff.max()), "frac_within_tol": float((diff <= TOL).mean()), "frac_bit_exact": float((diff == 0).mean())}
-    assert r["frac_within_tol"] >= FRAC, r
-    assert r["frac_bit_exact"] >= FRAC, r
-    return r
 
 
 # ---- CPU ----------------------------------------------------------------------------------------------------------------------
@@ -132,7 +122,7 @@ def test_cfg5_ring_device_equals_host_and_oracle(ctx):
     assert np.array_equal(dev_img.view(np.uint32), host_img.view(np.uint32))
     assert (st_d.rays_primary, st_d.rays_secondary, st_d.rays_shadow) == (st_h.rays_primary, st_h.rays_secondary, st_h.rays_shadow)
     ref, rc = sp.orc.render(W, H)
-    check_image(dev_img, ref)
+    assert_frame_equals_oracle(dev_img, sp.orc, W, H, ref=ref)
     assert (st_d.rays_primary, st_d.rays_secondary, st_d.rays_shadow) == tuple(int(x) for x in rc)
 
 

@@ -525,7 +525,7 @@ def test_oracle_pixels_match_the_reference_spirv_pixels(spirv_fixture_scenes):
 def test_integer_power_matches_pow100_and_small_cases():
     L = oracle.lib()
     rng = np.random.default_rng(2)
-    xs = np.concatenate([rng.uniform(0, 1, 4000), [0.0, 1.0, 0.5, 0.999999, 1e-3]]).astype(np.float32)
+    xs = np.concatenate([rng.uniform(0, 1, 4000), [0.0, 1.0, 0.5, 1.0 - 1e-6, 1e-3]]).astype(np.float32)
     for x in xs:
         assert np.float32(L.orc_pow_int(float(x), 100)).view(np.uint32) == np.float32(L.orc_pow100(float(x))).view(np.uint32)
     x = np.float32(0.83)

@@ -364,7 +364,8 @@ int rt_intersect_device(rt_ctx* ctx, size_t n, const void* d_rays8, int any_hit,
  *  - opacity: every geometry is opaque (the reference builds them with VK_GEOMETRY_OPAQUE_BIT_KHR, src/main.cpp:330).  The ray's
  *    OPAQUE / NO_OPAQUE decides first (OPAQUE if a word sets both), then the instance's FORCE_OPAQUE / FORCE_NO_OPAQUE (FORCE_OPAQUE
  *    first).  SKIP_TRIANGLES, CULL_OPAQUE on opaque and CULL_NO_OPAQUE on non-opaque triangles skip the instance.  There is no
- *    candidate / confirm loop: a non-opaque triangle is committed as if the caller confirmed every candidate;
+ *    candidate / confirm loop: a non-opaque triangle is committed as if the caller confirmed every candidate (rt_intersect_device_hits
+ *    returns every candidate);
  *  - facing, decided in object space (an instance transform, mirroring included, does not change it): a triangle is FRONT-FACING when
  *    det = dot(e1, cross(d, e2)) < 0 (e1 = v1 - v0, e2 = v2 - v0, d the object-space direction), i.e. its vertices appear clockwise
  *    from the ray origin in a right-handed object space (the DXR / VK_NV_ray_tracing default; VK_KHR's FLIP_FACING is aliased
@@ -379,6 +380,31 @@ int rt_intersect_device(rt_ctx* ctx, size_t n, const void* d_rays8, int any_hit,
  * SKIP_TRIANGLES with SKIP_AABBS or a facing cull (Vulkan's valid-usage rules).  Per-ray words are not validated (that would need a
  * host round trip): they follow the formulas above as written. */
 int rt_intersect_device_flags(rt_ctx* ctx, size_t n, const void* d_rays8, const void* d_ray_words, uint32_t ray_flags, uint32_t cull_mask, void* d_hits, void* d_attr, void* hip_stream);
+
+/* All hits along a ray: rayQueryProceedEXT's candidate loop in data form (every candidate, in order, and how many there are), for
+ * inside/outside parity, multi-return LiDAR, depth peeling and thickness.  Rays, words, ray_flags and cull_mask as for
+ * rt_intersect_device_flags.  The candidates C(ray) are every (inst, prim) that rt_intersect_device_flags may accept for the ray under the
+ * same rules: the ray's [tmin, tmax], the flags and cull mask of the call and of the ray's word, instance masks, opacity with FORCE_*,
+ * facing culls with FLIP_FACING and FACING_CULL_DISABLE, SKIP_TRIANGLES.  Every candidate is accepted: there is no caller code in the loop.
+ *  - order: by (t, inst, prim) ascending, the closest-hit tie rule, so entry 0 is rt_intersect_device_flags' closest hit
+ *    byte for byte; an (inst, prim) appears at most once;
+ *  - d_hits: n x max_hits rt_hit, ray-major (hit j of ray i at i * max_hits + j); the entries past min(|C|, max_hits) are rt_intersect's
+ *    miss (t = tmax, u = v = 0, prim = inst = -1);
+ *  - d_attr (optional): n x max_hits rt_hit_attr in the same order, P, N, objectIndex and the hit kind in `reserved`, as
+ *    rt_intersect_device_flags fills them; a miss is zeros, object_index -1, kind 0;
+ *  - d_counts (optional): n uint32, |C(ray)| over the whole interval, not capped at max_hits.  Without it the walk may stop looking
+ *    beyond the max_hits-th entry; the lists are the same either way;
+ *  - max_hits 1..16, or 0 = count only: then d_hits and d_attr must be NULL and d_counts non-NULL.
+ * TERMINATE_ON_FIRST_HIT in ray_flags is RT_ERR_INVALID_ARGUMENT (a multi-hit query has no first-hit form); in a ray's word the bit is
+ * ignored.  SKIP_CLOSEST_HIT and SKIP_AABBS have no effect.  Parity: the canonical triangle test is not watertight, so a ray through a
+ * shared edge or vertex may be counted by both triangles or by neither; |C| % 2 is exact only for rays that pass away from edges.
+ * Alignment (rays and attributes 16 B; ray words, hits and counts 4 B), device memory of ctx's GPU, stream ordering without host
+ * synchronisation, the TLAS and scene of the call, queries of one context one after another, RT_ERR_NOT_READY and n == 0: as for
+ * rt_intersect_device_flags.  The query's workspace is rt_intersect_device's.
+ * RT_ERR_INVALID_ARGUMENT: as for rt_intersect_device_flags; max_hits > 16; max_hits == 0 with d_hits or d_attr or without d_counts;
+ * n >= 0xFFFFFF00, or n x max_hits >= 0xFFFFFF00 (the kernels index records with 32 bits). */
+int rt_intersect_device_hits(rt_ctx* ctx, size_t n, const void* d_rays8, const void* d_ray_words, uint32_t ray_flags, uint32_t cull_mask,
+                             uint32_t max_hits, void* d_hits, void* d_attr, void* d_counts, void* hip_stream);
 
 /* Custom ray generation: the frame's shading of the caller's primary rays.  The caller's rays replace the pinhole camera of
  * src/shader.rgen:62-82; everything after it — the bounce loop of src/shader.rgen:84-177 with closest hit, miss, reflection, refraction and

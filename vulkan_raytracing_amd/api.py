@@ -60,7 +60,7 @@ HIT_KIND_BACK_FACING = 0xFF
 
 EXPORTS = ["rt_create", "rt_create_frame_slot", "rt_destroy", "rt_upload_geometry", "rt_build_blas", "rt_set_instances", "rt_set_instances_device", "rt_refit_blas_device", "rt_set_materials", "rt_set_instance_types", "rt_set_uniforms", "rt_set_skybox",
            "rt_trace", "rt_trace_async", "rt_trace_wait", "rt_trace_shard", "rt_set_batch", "rt_trace_shard_batch", "rt_assemble_shards", "rt_shard_rows", "rt_synchronize", "rt_get_stats", "rt_set_timing", "rt_intersect",
-           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
+           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
 
 _LIBS = {}
 
@@ -102,6 +102,7 @@ def lib(variant=None):
         L.rt_intersect.argtypes = [vp, C.c_size_t, vp, C.c_int, vp, C.c_int, C.POINTER(RtStats)]
         L.rt_intersect_device.argtypes = [vp, C.c_size_t, vp, C.c_int, vp, vp, vp]
         L.rt_intersect_device_flags.argtypes = [vp, C.c_size_t, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
+        L.rt_intersect_device_hits.argtypes = [vp, C.c_size_t, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
         L.rt_shade_rays_device.argtypes = [vp, C.c_size_t, C.c_uint32, vp, vp, vp, vp]
         L.rt_last_error.argtypes = [vp]
         L.rt_last_error.restype = C.c_char_p
@@ -359,6 +360,55 @@ class RtContext:
         hits, attr = self._device_query(rays, attributes, stream, out, (words,), call, "rt_intersect_device_flags")
         return RayQuery(hits, attr, hit_kind=True)
 
+    def intersect_device_hits(self, rays, max_hits, ray_flags=0, cull_mask=0xFF, words=None, attributes=False, counts=True, stream=None, out=None):
+        """rt_intersect_device_hits: every candidate along each ray, the first max_hits of them in (t, inst, prim) order, and their number.
+        rays and words as for intersect_device_flags; max_hits 1..16, or 0 for counts only.  Read and written in the order of `stream`
+        (default: the current torch stream of the rays' device), with no host synchronisation.  Returns a RayHits of views over one int32
+        (n, max_hits, 5) hits buffer, with attributes=True one int32 (n, max_hits, 8) attribute buffer, with counts=True (required when
+        max_hits is 0) one int32 (n,) count buffer.  counts=False lets the walk prune beyond the max_hits-th entry.  out = (hits, attr,
+        count) reuses such buffers (None where not asked for).  See include/rt_api.h."""
+        import torch
+        self._check_rays(rays, "intersect_device_hits")
+        k = int(max_hits)
+        if not 0 <= k <= 16:
+            raise ValueError("max_hits must be 0..16, got %d" % k)
+        if k == 0 and (attributes or not counts):
+            raise ValueError("max_hits 0 counts only: counts=True and attributes=False")
+        n = rays.shape[0]
+        if words is not None:
+            if not isinstance(words, torch.Tensor):
+                raise TypeError("words must be a torch tensor, got %s" % type(words).__name__)
+            if words.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+                raise ValueError("words must be int32 or uint32, not %s" % words.dtype)
+            if words.device != rays.device or not words.is_contiguous() or tuple(words.shape) != (n,):
+                raise ValueError("words must be a contiguous (n,) tensor on the rays' device")
+        cur = torch.cuda.current_stream(rays.device)
+        if stream is None:
+            stream = cur
+        shapes = ((n, k, 5) if k else None, (n, k, 8) if attributes else None, (n,) if counts else None)
+        if out is None:
+            bufs = [torch.empty(sh, dtype=torch.int32, device=rays.device) if sh is not None else None for sh in shapes]
+            if stream != cur:   # (allocated for the current stream, written on `stream`)
+                for t in bufs:
+                    if t is not None:
+                        t.record_stream(stream)
+        else:
+            bufs = list(out)
+            for i, (t, sh, what) in enumerate(zip(bufs, shapes, ("hits", "attributes", "counts"))):
+                if sh is None:
+                    bufs[i] = None
+                elif t is None or t.dtype != torch.int32 or tuple(t.shape) != sh or not t.is_contiguous() or t.device != rays.device:
+                    raise ValueError("out %s must be a contiguous int32 %s tensor on the rays' device" % (what, sh))
+        hits, attr, count = bufs
+
+        def call(run):
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+            return self.L.rt_intersect_device_hits(self.h, n, ptr(rays), ptr(words) if n else None, int(ray_flags) & 0xFFFFFFFF, int(cull_mask) & 0xFFFFFFFF,
+                                                   k, ptr(hits), ptr(attr), ptr(count), C.c_void_p(run.cuda_stream))
+        if n:
+            self._on_stream(stream, (rays, words, hits, attr, count), call, "rt_intersect_device_hits")
+        return RayHits(hits, attr, count, n, k)
+
     def shade_rays_device(self, rays, samples=1, per_sample=True, points=True, stream=None, out=None):
         """rt_shade_rays_device: the frame's shading of caller-generated primary rays.  `rays` is a contiguous float32 torch tensor
         (n_points * samples, 8) on this context's GPU (o.xyz, reserved, d.xyz, tmax per row; d normalised), sample-major: row
@@ -485,6 +535,38 @@ class RayQuery:
         """the hit records as rt_intersect returns them (HIT_DTYPE), and the attributes as (n, 8) int32 (or None); synchronises"""
         h = self.hits.cpu().numpy().view(HIT_DTYPE).reshape(-1)
         return h, (self.attr.cpu().numpy() if self.attr is not None else None)
+
+
+class RayHits:
+    """Results of RtContext.intersect_device_hits: views over the hits buffer (int32 (n, K, 5), rt_hit rows), the optional attribute
+    buffer (int32 (n, K, 8), rt_hit_attr) and the optional counts (int32 (n,)).  t, u, v, prim, inst are (n, K); position and normal
+    (n, K, 3); object_index and hit_kind (n, K).  Entries past a ray's candidates have prim = inst = -1 and t = the ray's tmax, zero
+    position / normal, object_index -1 and kind 0.  Views that were not asked for are None."""
+
+    def __init__(self, hits, attr, count, n, k):
+        import torch
+        self.hits, self.attr, self.count = hits, attr, count
+        self.max_hits = k
+        if hits is not None:
+            f = hits[..., 0:3].view(torch.float32)
+            self.t, self.u, self.v = f[..., 0], f[..., 1], f[..., 2]
+            self.prim, self.inst = hits[..., 3], hits[..., 4]
+        else:
+            self.t = self.u = self.v = self.prim = self.inst = None
+        if attr is not None:
+            self.position = attr[..., 0:3].view(torch.float32)
+            self.object_index = attr[..., 3]
+            self.normal = attr[..., 4:7].view(torch.float32)
+            self.hit_kind = attr[..., 7]
+        else:
+            self.position = self.normal = self.object_index = self.hit_kind = None
+
+    def numpy(self):
+        """(hit records as HIT_DTYPE (n, K), attributes as (n, K, 8) int32, counts as (n,) uint32), None where not asked for; synchronises"""
+        h = self.hits.cpu().numpy().view(HIT_DTYPE).reshape(self.hits.shape[0], self.max_hits) if self.hits is not None else None
+        a = self.attr.cpu().numpy() if self.attr is not None else None
+        c = self.count.cpu().numpy().view(np.uint32) if self.count is not None else None
+        return h, a, c
 
 
 def check_builders(verts6, idx):

@@ -2165,6 +2165,8 @@ void launch_hit_kind(const SceneDev& sc, const float4* rays, const HitRec* hits,
   hipLaunchKernelGGL(k_hit_kind, dim3((n + 255u) / 256u), dim3(256), 0, s, sc, rays, hits, reinterpret_cast<uint32_t*>(attr), n);
 }
 
+#include "kernels_hits.inc"   // k_query_hits, k_query_hits_surface: the K nearest hits of every ray and their count (rt_intersect_device_hits)
+
 // ---- caller-generated rays (rt_shade_rays_device): the frame's bounce pipeline between an ingest and a per-point resolve
 // k_ray_ingest takes k_raygen's place: sample sid is the caller's record sid (o.xyz, w3, d.xyz, tmax), read where the caller left it.
 // A record with a non-finite o or d component, or d = 0, is not traced: its sample is (0, 0, 0, 0).  tmax <= 0.001 (or NaN) is the

@@ -2331,6 +2331,55 @@ int rt_intersect_device_flags(rt_ctx* c, size_t n, const void* d_rays8, const vo
   return intersect_device(c, n, d_rays8, false, true, n ? d_ray_words : nullptr, (cull_mask << 24) | ray_flags, d_hits, d_attr, hip_stream);
 }
 
+// All hits along a ray (rayQueryProceedEXT's candidate loop in data form): the flag checks of rt_intersect_device_flags, the checks and
+// ordering of a device query, then k_query_hits over the caller's rays into the caller's rows and counts, and k_query_hits_surface.
+int rt_intersect_device_hits(rt_ctx* c, size_t n, const void* d_rays8, const void* d_ray_words, uint32_t ray_flags, uint32_t cull_mask, uint32_t max_hits,
+                             void* d_hits, void* d_attr, void* d_counts, void* hip_stream) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const char* const name = "rt_intersect_device_hits";
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, "too many rays for one call");
+  if (max_hits > 16u) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": max_hits must be 0..16");
+  if ((uint64_t)n * max_hits >= 0xFFFFFF00ull)
+    return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": n * max_hits must be below 0xFFFFFF00 (32-bit record indices)");
+  if (max_hits == 0u && (d_hits || d_attr || !d_counts))
+    return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": max_hits 0 counts only: d_hits and d_attr must be NULL, d_counts non-NULL");
+  if (ray_flags & RT_RAY_FLAG_TERMINATE_ON_FIRST_HIT)
+    return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": TERMINATE_ON_FIRST_HIT in ray_flags (a multi-hit query has no first-hit form)");
+  if ((ray_flags & ~0x3FFu) != 0u || cull_mask > 0xFFu)
+    return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": ray_flags has bits outside 0x3FF or cull_mask is above 0xFF");
+  const uint32_t opacity = ray_flags & (RT_RAY_FLAG_OPAQUE | RT_RAY_FLAG_NO_OPAQUE | RT_RAY_FLAG_CULL_OPAQUE | RT_RAY_FLAG_CULL_NO_OPAQUE);
+  if ((opacity & (opacity - 1u)) != 0u)
+    return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": at most one of OPAQUE, NO_OPAQUE, CULL_OPAQUE and CULL_NO_OPAQUE");
+  const uint32_t facing = RT_RAY_FLAG_CULL_BACK_FACING | RT_RAY_FLAG_CULL_FRONT_FACING;
+  if ((ray_flags & facing) == facing) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": CULL_BACK_FACING with CULL_FRONT_FACING");
+  if ((ray_flags & RT_RAY_FLAG_SKIP_TRIANGLES) && (ray_flags & (RT_RAY_FLAG_SKIP_AABBS | facing)))
+    return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": SKIP_TRIANGLES with SKIP_AABBS or a facing cull");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + " needs trace_variant 0");
+  if (n) {
+    if (!d_rays8 || (max_hits && !d_hits)) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null ray/hit pointers");
+    if (((uintptr_t)d_rays8 & 15u) || ((uintptr_t)d_hits & 3u) || ((uintptr_t)d_attr & 15u) || ((uintptr_t)d_ray_words & 3u) || ((uintptr_t)d_counts & 3u))
+      return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": rays and attributes must be 16-byte aligned, ray words, hits and counts 4-byte aligned");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const void* ptrs[5] = {d_rays8, d_ray_words, d_hits, d_attr, d_counts};
+    for (const void* p : ptrs) {
+      if (!p) continue;
+      hipPointerAttribute_t at{};
+      const bool ok = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == c->device;
+      (void)hipGetLastError();   // (a host pointer leaves an error behind)
+      if (!ok) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": rays, ray words, hits, attributes and counts must be device memory of the context's GPU (" +
+                                                           std::to_string(c->device) + ")");
+    }
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  int r = ready_to_trace(c); if (r) return r;
+  if (n == 0) return RT_OK;
+  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+  r = query_workspace(c, s); if (r) return r;
+  launch_query_hits(scene_dev(c), (const float4*)d_rays8, (const uint32_t*)d_ray_words, (cull_mask << 24) | ray_flags, (uint32_t)n, max_hits, (HitRec*)d_hits,
+                    (float4*)d_attr, (uint32_t*)d_counts, c->d_q_ovf, c->d_q_counters, c->cfg, s);
+  return query_done(c, s);
+}
+
 // Custom ray generation: the caller's primary rays (n_points * n_samples records, sample-major) through the frame's bounce pipeline —
 // k_ray_ingest in k_raygen's place, then launch_trace_closest / launch_shade per bounce and launch_trace_shadow exactly as a frame runs
 // them — into the caller's per-sample and / or per-point colours, ordered on the caller's stream like rt_intersect_device (the query

@@ -184,6 +184,12 @@ void launch_query_flags(const SceneDev& sc, const float4* rays, const uint32_t* 
                         int32_t* ovf_stack, uint32_t* counters, const LaunchCfg& cfg, hipStream_t s);
 // the hit kind (0xFE front, 0xFF back, 0 miss) of every hit of `hits` into word 7 of its rt_hit_attr (after launch_hit_attr)
 void launch_hit_kind(const SceneDev& sc, const float4* rays, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s);
+// rt_intersect_device_hits: the k (0..16) nearest accepted candidates of every ray, sorted by (t, inst, prim), into hits (n * k records,
+// ray-major; the rest of a row in the miss form), their number into counts (optional: without it the walk prunes by the k-th entry), and
+// with attr (k >= 1) the rt_hit_attr of every record with its hit kind.  Rays, words and query_word as for launch_query_flags; the
+// walk's chunk cursor is a word of `counters`, its stack spills into ovf_stack (sized for cfg.trace_blocks workgroups).
+void launch_query_hits(const SceneDev& sc, const float4* rays, const uint32_t* words, uint32_t query_word, uint32_t n, uint32_t k, HitRec* hits,
+                       float4* attr, uint32_t* counts, int32_t* ovf_stack, uint32_t* counters, const LaunchCfg& cfg, hipStream_t s);
 // rt_shade_rays_device: k_ray_ingest replaces k_raygen for the caller's n rays (32 bytes each, o.xyz, w3, d.xyz, tmax; sample id = record
 // index): sky colours of the rays that miss the TLAS and (0, 0, 0, 0) for invalid records into f.sample_color, the others into bounce queue 0
 // (workgroup b appends to shard b % 8: f.shard_cap >= 256 * ceil(ray_ingest_block_count(n) / 8)).  f.counters must be zero.

@@ -406,6 +406,40 @@ int rt_intersect_device_flags(rt_ctx* ctx, size_t n, const void* d_rays8, const 
 int rt_intersect_device_hits(rt_ctx* ctx, size_t n, const void* d_rays8, const void* d_ray_words, uint32_t ray_flags, uint32_t cull_mask,
                              uint32_t max_hits, void* d_hits, void* d_attr, void* d_counts, void* hip_stream);
 
+/* Closest points: for every query point the nearest point of the scene's surface (Embree's point queries, Open3D's
+ * compute_closest_points), for distance fields, collision and penetration depth, snapping samples to a surface and nearest-surface
+ * attributes of point clouds.  The one query of the family that is not a ray.
+ * Points: d_points4 holds n records of 16 B (x, y, z, r_max), 16-B aligned, memory of ctx's GPU: a world-space point and a search
+ * radius, r_max >= 0 (+inf allowed).
+ * Candidates: every triangle of every instance with (mask & cull_mask) != 0.  Instance flags, opacity and facing play no part.
+ * d_hits: n rt_hit, 4-B aligned.  Record i is the candidate with the smallest key (d2, inst, prim) among those with
+ * d2 <= r_max * r_max (the product rounded to binary32), d2 the canonical squared distance below: t = sqrtf(d2) is the world-space
+ * distance to the nearest point, u and v that point's barycentrics of vertices B and C (a hit's convention), prim and inst the triangle.
+ * Nothing within r_max: the miss record t = r_max as given, u = v = 0, prim = inst = -1; the same for a non-finite coordinate, a negative
+ * r_max or a NaN r_max.  t is never NaN unless r_max was.
+ * Canonical arithmetic (DESIGN.md §5 "Closest points" has the full sequence): binary32, nothing fused except inside dot3 / xform_point /
+ * xform_vec, which are the library's.  For instance I and triangle packet (v0, e1, e2): a = xform_point(I.o2w, v0),
+ * ab = xform_vec(I.o2w, e1), ac = xform_vec(I.o2w, e2); the vertex / edge / face regions of Ericson, Real-Time Collision Detection
+ * §5.1.5, over ap = p - a, d1..d6, vc, vb, va in that order with its <= / >= comparisons and IEEE divisions;
+ * c = ap - (u * ab + v * ac), d2 = dot3(c, c).  d2 depends on the point, the instance record and the packet only, never on the tree; a
+ * triangle whose d2 is NaN (zero-area triangles only) is never a candidate.
+ * Needles (aspect 1e-4 and below) are answered with that same arithmetic, whose (u, v) is then rounding noise: the reported t can be
+ * off by the length of the needle.
+ * d_attr (optional): n rt_hit_attr, 16-B aligned: what rt_intersect_device gives for a hit with this (inst, prim, u, v) — P the nearest
+ * point, N the interpolated shading normal, objectIndex; a miss zeros and -1.  `reserved` is the side of the triangle's plane the point
+ * lies on: RT_HIT_KIND_FRONT_FACING when s = dot(cross(e1, e2), xform_point(I.w2o, p) - v0) < 0, else RT_HIT_KIND_BACK_FACING (e1, e2,
+ * v0 from the vertex buffer), inverted by FLIP_FACING, 0 on a miss: the kind rt_intersect_device_flags reports for a ray from the point
+ * that hits that triangle.  Like parity it is a per-triangle sign, not a robust inside/outside test near edges and vertices.
+ * Stream ordering without host synchronisation, the TLAS and scene of the call, the query workspace, queries and shading calls of one
+ * context one after another, RT_ERR_NOT_READY and n == 0 (nothing is enqueued): as for rt_intersect_device.
+ * RT_ERR_INVALID_ARGUMENT: a NULL or misaligned pointer, a pointer that is not memory of ctx's GPU, n >= 0xFFFFFF00, cull_mask > 0xFF,
+ * trace_variant != 0. */
+int rt_closest_point_device(rt_ctx* ctx, size_t n, const void* d_points4, uint32_t cull_mask, void* d_hits, void* d_attr, void* hip_stream);
+/* The blocking host form, as rt_intersect is to rt_intersect_device: the records are copied to the device, queried on the context's
+ * stream (same workspace and ordering) and the results copied back.  counting != 0 runs the instrumented walk and fills
+ * stats->node_visits and stats->tri_tests (boxes-pair visits and point-triangle tests of the whole call); stats may be NULL. */
+int rt_closest_point(rt_ctx* ctx, size_t n, const float* points4_host, uint32_t cull_mask, rt_hit* out_host, int counting, rt_stats* stats);
+
 /* Custom ray generation: the frame's shading of the caller's primary rays.  The caller's rays replace the pinhole camera of
  * src/shader.rgen:62-82; everything after it — the bounce loop of src/shader.rgen:84-177 with closest hit, miss, reflection, refraction and
  * shadow rays — is the frame's, and the colours are those a frame would compute for the same rays.

@@ -60,7 +60,7 @@ HIT_KIND_BACK_FACING = 0xFF
 
 EXPORTS = ["rt_create", "rt_create_frame_slot", "rt_destroy", "rt_upload_geometry", "rt_build_blas", "rt_set_instances", "rt_set_instances_device", "rt_refit_blas_device", "rt_set_materials", "rt_set_instance_types", "rt_set_uniforms", "rt_set_skybox",
            "rt_trace", "rt_trace_async", "rt_trace_wait", "rt_trace_shard", "rt_set_batch", "rt_trace_shard_batch", "rt_assemble_shards", "rt_shard_rows", "rt_synchronize", "rt_get_stats", "rt_set_timing", "rt_intersect",
-           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
+           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
 
 _LIBS = {}
 
@@ -103,6 +103,8 @@ def lib(variant=None):
         L.rt_intersect_device.argtypes = [vp, C.c_size_t, vp, C.c_int, vp, vp, vp]
         L.rt_intersect_device_flags.argtypes = [vp, C.c_size_t, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
         L.rt_intersect_device_hits.argtypes = [vp, C.c_size_t, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+        L.rt_closest_point_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, vp, vp]
+        L.rt_closest_point.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, C.c_int, C.POINTER(RtStats)]
         L.rt_shade_rays_device.argtypes = [vp, C.c_size_t, C.c_uint32, vp, vp, vp, vp]
         L.rt_last_error.argtypes = [vp]
         L.rt_last_error.restype = C.c_char_p
@@ -360,6 +362,26 @@ class RtContext:
         hits, attr = self._device_query(rays, attributes, stream, out, (words,), call, "rt_intersect_device_flags")
         return RayQuery(hits, attr, hit_kind=True)
 
+    def closest_point_device(self, points, cull_mask=0xFF, attributes=False, stream=None, out=None):
+        """rt_closest_point_device: the nearest surface point of every query point.  `points` is a contiguous float32 torch tensor (n, 4)
+        on this context's GPU (x, y, z, r_max per row: a world-space point and a search radius, inf allowed), read in the order of
+        `stream` like intersect_device's rays.  Returns a RayQuery: t the distance, u / v the nearest point's barycentrics, prim / inst the
+        triangle (a miss: t = r_max, prim = inst = -1); with attributes=True position is the nearest point, normal the shading normal
+        there and hit_kind the side of the triangle's plane the point lies on.  out = (hits, attr) reuses buffers.  See include/rt_api.h."""
+        def call(run, hits, attr):
+            return self.L.rt_closest_point_device(self.h, points.shape[0], C.c_void_p(points.data_ptr()), int(cull_mask) & 0xFFFFFFFF, C.c_void_p(hits.data_ptr()),
+                                                  C.c_void_p(attr.data_ptr()) if attr is not None else None, C.c_void_p(run.cuda_stream))
+        hits, attr = self._device_query(points, attributes, stream, out, (), call, "rt_closest_point_device", cols=4)
+        return RayQuery(hits, attr, hit_kind=True)
+
+    def closest_point(self, points4, cull_mask=0xFF, counting=False):
+        """rt_closest_point: the blocking host form -> (HIT_DTYPE records, RtStats; with counting its node_visits / tri_tests are filled)"""
+        points4 = np.ascontiguousarray(points4, np.float32).reshape(-1, 4)
+        out = np.zeros(len(points4), HIT_DTYPE)
+        st = RtStats()
+        self._chk(self.L.rt_closest_point(self.h, len(points4), _p(points4), int(cull_mask) & 0xFFFFFFFF, _p(out), int(counting), C.byref(st)), "rt_closest_point")
+        return out, st
+
     def intersect_device_hits(self, rays, max_hits, ray_flags=0, cull_mask=0xFF, words=None, attributes=False, counts=True, stream=None, out=None):
         """rt_intersect_device_hits: every candidate along each ray, the first max_hits of them in (t, inst, prim) order, and their number.
         rays and words as for intersect_device_flags; max_hits 1..16, or 0 for counts only.  Read and written in the order of `stream`
@@ -453,19 +475,19 @@ class RtContext:
             self._on_stream(stream, (rays, srgba, prgba), call, "rt_shade_rays_device")
         return srgba, prgba
 
-    def _check_rays(self, rays, name):
-        """the checks of a (n, 8) float32 ray tensor on this context's GPU"""
+    def _check_rays(self, rays, name, cols=8, noun="ray"):
+        """the checks of a (n, 8) float32 ray tensor (or, with cols=4 and noun="point", a (n, 4) point tensor) on this context's GPU"""
         import torch
         if not isinstance(rays, torch.Tensor):
             raise TypeError("%s takes a torch tensor, got %s" % (name, type(rays).__name__))
         if rays.device.type != "cuda" or rays.device.index != self.device:
-            raise ValueError("ray tensor must live on cuda:%d (the context's GPU), not %s" % (self.device, rays.device))
+            raise ValueError("%s tensor must live on cuda:%d (the context's GPU), not %s" % (noun, self.device, rays.device))
         if rays.dtype != torch.float32:
-            raise ValueError("ray tensor must be float32, not %s" % rays.dtype)
+            raise ValueError("%s tensor must be float32, not %s" % (noun, rays.dtype))
         if not rays.is_contiguous():
-            raise ValueError("ray tensor must be contiguous")
-        if rays.dim() != 2 or rays.shape[1] != 8:
-            raise ValueError("ray tensor has shape (n, 8), got %s" % (tuple(rays.shape),))
+            raise ValueError("%s tensor must be contiguous" % noun)
+        if rays.dim() != 2 or rays.shape[1] != cols:
+            raise ValueError("%s tensor has shape (n, %d), got %s" % (noun, cols, tuple(rays.shape)))
 
     def _on_stream(self, stream, tensors, call, name):
         """call(run_stream) -> status, on `stream`; torch's default stream is the null stream, which the C ABI reads as "the context's
@@ -485,10 +507,10 @@ class RtContext:
         if run is not stream:
             stream.wait_stream(run)
 
-    def _device_query(self, rays, attributes, stream, out, inputs, call, name):
+    def _device_query(self, rays, attributes, stream, out, inputs, call, name, cols=8):
         """the common part of intersect_device*: checks, output buffers, the null-stream detour; call(run_stream, hits, attr) -> status"""
         import torch
-        self._check_rays(rays, "intersect_device")
+        self._check_rays(rays, "closest_point_device" if cols == 4 else "intersect_device", cols, "point" if cols == 4 else "ray")
         n = rays.shape[0]
         cur = torch.cuda.current_stream(rays.device)
         if stream is None:

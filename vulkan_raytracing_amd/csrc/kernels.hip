@@ -2254,6 +2254,8 @@ void launch_resolve_points(const float4* sample_color, float4* out, uint32_t n_p
   hipLaunchKernelGGL(k_resolve_points, dim3((n_points + 255u) / 256u), dim3(256), 0, s, sample_color, out, n_points, n_samples);
 }
 
+#include "kernels_closest.inc"   // k_closest_point, k_closest_side: the nearest surface point of every query point (rt_closest_point_device)
+
 int tail_blocks_per_cu() {
   // the smallest over the instantiations: any of them may be the one in flight (counting; 4-ary records in the alt build)
   int n = 1 << 30, v = 0;

@@ -298,6 +298,8 @@ struct rt_ctx {
   uint32_t* d_q_counters = nullptr;
   int32_t* d_q_ovf = nullptr;
   size_t q_ovf_alloc = 0;          // int32 entries of d_q_ovf
+  float* d_q_scale = nullptr;      // rt_closest_point*: 1 + n_inst floats of launch_closest_scale, part of the query workspace
+  size_t q_scale_alloc = 0;        // floats of d_q_scale
   hipEvent_t ev_query[2] = {nullptr, nullptr};
   bool ev_query_valid[2] = {false, false};
   int query_last = -1;             // parity of the last query (-1: none since the last host wait)
@@ -1449,6 +1451,7 @@ void rt_destroy(rt_ctx* c) {
   for (int k = 0; k < 2; k++) if (c->ev_upload[k]) hipEventDestroy(c->ev_upload[k]);
   if (c->d_q_counters) hipFree(c->d_q_counters);
   if (c->d_q_ovf) hipFree(c->d_q_ovf);
+  if (c->d_q_scale) hipFree(c->d_q_scale);
   for (int k = 0; k < 2; k++) if (c->ev_query[k]) hipEventDestroy(c->ev_query[k]);
   tlas_gpu_free(c->tgpu);
   for (auto e : c->ev_pool) hipEventDestroy(e);
@@ -2191,6 +2194,14 @@ int query_workspace(rt_ctx* c, hipStream_t s) {
     HIP_TRY(c, hipMalloc((void**)&c->d_q_ovf, ovf_need * sizeof(int32_t)));
     c->q_ovf_alloc = ovf_need;
   }
+  const size_t scale_need = 1 + (size_t)std::max(scene_dev(c).n_inst, 0);   // (closest-point queries: launch_closest_scale)
+  if (scale_need > c->q_scale_alloc) {
+    { int q = wait_queries(c, c); if (q) return q; }
+    if (c->d_q_scale) HIP_TRY(c, hipFree(c->d_q_scale));
+    c->d_q_scale = nullptr; c->q_scale_alloc = 0;
+    HIP_TRY(c, hipMalloc((void**)&c->d_q_scale, scale_need * sizeof(float)));
+    c->q_scale_alloc = scale_need;
+  }
   for (int k = 0; k < 2; k++)
     if (!c->ev_query[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_query[k], hipEventDisableTiming));
   if (c->query_last >= 0) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_query[c->query_last], 0));
@@ -2206,21 +2217,29 @@ int query_done(rt_ctx* c, hipStream_t s) {
   return RT_OK;
 }
 
-// The enqueue of every ray query (rt_intersect, rt_intersect_device, rt_intersect_device_flags) on stream s, after the caller's checks.
-// flags: the flag-aware walk (MODE_QUERY_FLAGS) with the ray words `words` (or none) and the call's query word; otherwise the plain
-// walk with any_hit, instrumented when counting (its counts start from a zeroed counter block).  d_attr (optional): the hit attributes.
-// t0 / t1 (optional): events recorded around the walk.
-int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, size_t n, const void* d_rays8, bool any_hit, bool counting, bool flags,
+// The enqueue of every query (rt_intersect, rt_intersect_device, rt_intersect_device_flags, rt_closest_point*) on stream s, after the
+// caller's checks.  Walk::Flags: the flag-aware walk (MODE_QUERY_FLAGS) with the ray words `words` (or none) and the call's query word;
+// Walk::Plain: the plain walk with any_hit; Walk::Closest: the closest-point walk over n point records with the cull mask `query_word`
+// (its per-instance scales are made first, in the workspace).  counting: the instrumented Plain or Closest walk (its counts start from
+// a zeroed counter block).  d_attr (optional): the hit attributes.  t0 / t1 (optional): events recorded around the walk.
+enum class Walk { Plain, Flags, Closest };
+int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, Walk walk, size_t n, const void* d_records, bool any_hit, bool counting,
                   const void* words, uint32_t query_word, void* d_hits, void* d_attr, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
+  const bool flags = walk == Walk::Flags, closest = walk == Walk::Closest;
+  const void* const d_rays8 = d_records;
   { int r = query_workspace(c, s); if (r) return r; }
   if (counting) HIP_TRY(c, hipMemsetAsync(c->d_q_counters, 0, CNT_WORDS * sizeof(uint32_t), s));
   const SceneDev sc = scene_dev(c);
   if (t0) HIP_TRY(c, hipEventRecord(t0, s));
-  if (flags) launch_query_flags(sc, (const float4*)d_rays8, (const uint32_t*)words, query_word, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, cfg, s);
+  if (closest) {
+    launch_closest_scale(sc, c->d_q_scale, s);
+    launch_closest_point(sc, (const float4*)d_rays8, query_word, c->d_q_scale, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, counting, cfg, s);
+  } else if (flags) launch_query_flags(sc, (const float4*)d_rays8, (const uint32_t*)words, query_word, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, cfg, s);
   else launch_query(sc, (const float4*)d_rays8, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, any_hit, counting, cfg, s);
   if (t1) HIP_TRY(c, hipEventRecord(t1, s));
   if (d_attr) launch_hit_attr(sc, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
   if (d_attr && flags) launch_hit_kind(sc, (const float4*)d_rays8, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
+  if (d_attr && closest) launch_closest_side(sc, (const float4*)d_rays8, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
   return query_done(c, s);
 }
 }  // namespace
@@ -2250,7 +2269,7 @@ int rt_intersect(rt_ctx* c, size_t n, const float* rays8, int any_hit, rt_hit* o
   HIP_TRY(c, hipEventCreate(&e0)); HIP_TRY(c, hipEventCreate(&e1));
   LaunchCfg cfg = c->cfg;
   if (c->stack_need > 120) cfg.packet = 0;   // (see enqueue_frame)
-  r = enqueue_query(c, c->stream, cfg, n, d_buf, any_hit != 0, counting != 0, false, nullptr, 0u, d_h, nullptr, e0, e1); if (r) return r;
+  r = enqueue_query(c, c->stream, cfg, Walk::Plain, n, d_buf, any_hit != 0, counting != 0, nullptr, 0u, d_h, nullptr, e0, e1); if (r) return r;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipMemcpy(out, d_h, n * sizeof(HitRec), hipMemcpyDeviceToHost));
   if (stats) {
@@ -2269,6 +2288,21 @@ int rt_intersect(rt_ctx* c, size_t n, const float* rays8, int any_hit, rt_hit* o
 }
 
 namespace {
+// every non-NULL pointer is device memory of the context's GPU (`what` names them in the message)
+int check_device_pointers(rt_ctx* c, const std::string& name, const char* what, std::initializer_list<const void*> ptrs) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  for (const void* p : ptrs) {
+    if (!p) continue;
+    hipPointerAttribute_t at{};
+    const bool ok = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == c->device;
+    (void)hipGetLastError();   // (a host pointer leaves an error behind)
+    if (!ok) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": " + what + " must be device memory of the context's GPU (" + std::to_string(c->device) + ")");
+  }
+  return RT_OK;
+}
+}  // namespace
+
+namespace {
 // The body of rt_intersect_device and rt_intersect_device_flags (their own argument checks come first): the checks of a device call,
 // then the query on the caller's stream.  packet_trace does not apply to device queries.
 int intersect_device(rt_ctx* c, size_t n, const void* d_rays8, bool any_hit, bool flags, const void* words, uint32_t query_word, void* d_hits,
@@ -2279,23 +2313,14 @@ int intersect_device(rt_ctx* c, size_t n, const void* d_rays8, bool any_hit, boo
     if (!d_rays8 || !d_hits) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null ray/hit pointers");
     if (((uintptr_t)d_rays8 & 15u) || ((uintptr_t)d_hits & 3u) || ((uintptr_t)d_attr & 15u))
       return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": rays and attributes must be 16-byte aligned, hits 4-byte aligned");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const void* ptrs[4] = {d_rays8, d_hits, d_attr, words};
-    for (const void* p : ptrs) {
-      if (!p) continue;
-      hipPointerAttribute_t at{};
-      const bool ok = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == c->device;
-      (void)hipGetLastError();   // (a host pointer leaves an error behind)
-      if (!ok) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + (flags ? ": rays, ray words, hits and attributes" : ": rays, hits and attributes") +
-                                                           " must be device memory of the context's GPU (" + std::to_string(c->device) + ")");
-    }
+    { int q = check_device_pointers(c, name, flags ? "rays, ray words, hits and attributes" : "rays, hits and attributes", {d_rays8, d_hits, d_attr, words}); if (q) return q; }
   }
   HIP_TRY(c, hipSetDevice(c->device));
   int r = ready_to_trace(c); if (r) return r;
   if (n == 0) return RT_OK;
   LaunchCfg cfg = c->cfg;
   cfg.packet = 0;
-  return enqueue_query(c, hip_stream ? (hipStream_t)hip_stream : c->stream, cfg, n, d_rays8, any_hit, false, flags, words, query_word, d_hits, d_attr);
+  return enqueue_query(c, hip_stream ? (hipStream_t)hip_stream : c->stream, cfg, flags ? Walk::Flags : Walk::Plain, n, d_rays8, any_hit, false, words, query_word, d_hits, d_attr);
 }
 }  // namespace
 
@@ -2378,6 +2403,67 @@ int rt_intersect_device_hits(rt_ctx* c, size_t n, const void* d_rays8, const voi
   launch_query_hits(scene_dev(c), (const float4*)d_rays8, (const uint32_t*)d_ray_words, (cull_mask << 24) | ray_flags, (uint32_t)n, max_hits, (HitRec*)d_hits,
                     (float4*)d_attr, (uint32_t*)d_counts, c->d_q_ovf, c->d_q_counters, c->cfg, s);
   return query_done(c, s);
+}
+
+// The nearest surface point of every query point: the checks and ordering of a device query (rt_intersect_device), then k_closest_scale and
+// k_closest_point over the caller's records (enqueue_query), k_hit_attr and k_closest_side for the attributes.
+int rt_closest_point_device(rt_ctx* c, size_t n, const void* d_points4, uint32_t cull_mask, void* d_hits, void* d_attr, void* hip_stream) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const char* const name = "rt_closest_point_device";
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, "too many points for one call");
+  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": cull_mask is above 0xFF");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + " needs trace_variant 0");
+  if (n) {
+    if (!d_points4 || !d_hits) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null point/hit pointers");
+    if (((uintptr_t)d_points4 & 15u) || ((uintptr_t)d_hits & 3u) || ((uintptr_t)d_attr & 15u))
+      return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": points and attributes must be 16-byte aligned, hits 4-byte aligned");
+    { int q = check_device_pointers(c, name, "points, hits and attributes", {d_points4, d_hits, d_attr}); if (q) return q; }
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  int r = ready_to_trace(c); if (r) return r;
+  if (n == 0) return RT_OK;
+  return enqueue_query(c, hip_stream ? (hipStream_t)hip_stream : c->stream, c->cfg, Walk::Closest, n, d_points4, false, false, nullptr, cull_mask, d_hits, d_attr);
+}
+
+// The blocking host form, as rt_intersect is to rt_intersect_device: the records copied in, the same enqueue on the context's stream,
+// the hits copied out; with counting the instrumented walk, whose node visits and triangle tests come back in stats.
+int rt_closest_point(rt_ctx* c, size_t n, const float* points4, uint32_t cull_mask, rt_hit* out, int counting, rt_stats* stats) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  if ((!points4 || !out) && n) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_closest_point: null point/hit pointers");
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, "too many points for one call");
+  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_closest_point: cull_mask is above 0xFF");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_closest_point needs trace_variant 0");
+  HIP_TRY(c, hipSetDevice(c->device));
+  { int q = quiesce(c); if (q) return q; }   // (as rt_intersect)
+  int r = ready_to_trace(c); if (r) return r;
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (n == 0) return RT_OK;
+  const size_t pt_bytes = n * 4 * sizeof(float);
+  char* d_buf = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  struct Guard {   // every exit path below releases the temporaries
+    char*& buf; hipEvent_t &a, &b;
+    ~Guard() { if (buf) hipFree(buf); if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
+  } guard{d_buf, e0, e1};
+  HIP_TRY(c, hipMalloc((void**)&d_buf, pt_bytes + n * sizeof(HitRec)));
+  HitRec* const d_h = (HitRec*)(d_buf + pt_bytes);
+  HIP_TRY(c, hipMemcpy(d_buf, points4, pt_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipEventCreate(&e0)); HIP_TRY(c, hipEventCreate(&e1));
+  r = enqueue_query(c, c->stream, c->cfg, Walk::Closest, n, d_buf, false, counting != 0, nullptr, cull_mask, d_h, nullptr, e0, e1); if (r) return r;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpy(out, d_h, n * sizeof(HitRec), hipMemcpyDeviceToHost));
+  if (stats) {
+    if (counting) {
+      uint32_t cnt[CNT_TAILS];
+      HIP_TRY(c, hipMemcpy(cnt, c->d_q_counters, sizeof(cnt), hipMemcpyDeviceToHost));
+      memcpy(&stats->node_visits, &cnt[CNT_NODE_VISITS], 8);
+      memcpy(&stats->tri_tests, &cnt[CNT_TRI_TESTS], 8);
+    }
+    float ms = 0.f; hipEventElapsedTime(&ms, e0, e1);
+    stats->ms_trace_closest = ms;
+    stats->bvh_node_bytes = sizeof(BvhNodeQ); stats->bvh_tri_bytes = sizeof(TriPacket);
+  }
+  return RT_OK;
 }
 
 // Custom ray generation: the caller's primary rays (n_points * n_samples records, sample-major) through the frame's bounce pipeline —

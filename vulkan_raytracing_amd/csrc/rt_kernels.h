@@ -190,6 +190,15 @@ void launch_hit_kind(const SceneDev& sc, const float4* rays, const HitRec* hits,
 // walk's chunk cursor is a word of `counters`, its stack spills into ovf_stack (sized for cfg.trace_blocks workgroups).
 void launch_query_hits(const SceneDev& sc, const float4* rays, const uint32_t* words, uint32_t query_word, uint32_t n, uint32_t k, HitRec* hits,
                        float4* attr, uint32_t* counts, int32_t* ovf_stack, uint32_t* counters, const LaunchCfg& cfg, hipStream_t s);
+// rt_closest_point_device: the nearest surface point of every query point (16 bytes: p.xyz, r_max) among the instances the cull mask
+// admits, into hits[n] (kernels_closest.inc).  inst_scale: 1 + sc.n_inst floats that launch_closest_scale fills first, in stream
+// order ([0] the largest row-term magnitude of any instance's o2w, [1 + i] a lower bound on the smallest singular value of instance i's).  Chunk cursor, counters (counting: node visits and
+// triangle tests, the caller zeroes the block first) and spill area as for launch_query_hits.
+void launch_closest_scale(const SceneDev& sc, float* inst_scale, hipStream_t s);
+void launch_closest_point(const SceneDev& sc, const float4* points, uint32_t cull_mask, const float* inst_scale, HitRec* hits, uint32_t n, int32_t* ovf_stack,
+                          uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
+// the side of the reported triangle's plane every point lies on (0xFE front, 0xFF back, 0 miss) into word 7 of its rt_hit_attr (after launch_hit_attr)
+void launch_closest_side(const SceneDev& sc, const float4* points, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s);
 // rt_shade_rays_device: k_ray_ingest replaces k_raygen for the caller's n rays (32 bytes each, o.xyz, w3, d.xyz, tmax; sample id = record
 // index): sky colours of the rays that miss the TLAS and (0, 0, 0, 0) for invalid records into f.sample_color, the others into bounce queue 0
 // (workgroup b appends to shard b % 8: f.shard_cap >= 256 * ceil(ray_ingest_block_count(n) / 8)).  f.counters must be zero.

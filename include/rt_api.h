@@ -212,7 +212,8 @@ int rt_set_materials(rt_ctx* ctx, const rt_material* table, int n_materials, con
  * n == 0 restores `objectIndex == 0 ? centerObjectType : orbitingObjectType` (src/shader.rgen:96). */
 int rt_set_instance_types(rt_ctx* ctx, const uint32_t* types, int n);
 
-/* Uniform buffer copyData (src/main.cpp:1887-1889, 2901-2903). */
+/* Uniform buffer copyData (src/main.cpp:1887-1889, 2901-2903).  RT_ERR_NOT_READY, with nothing changed, while the context holds a frame
+ * batch (rt_set_batch with more than one frame): call rt_set_instances first. */
 int rt_set_uniforms(rt_ctx* ctx, const rt_uniforms* u);
 
 /* Cube map creation + upload (src/main.cpp:2073-2412): 6 RGBA8 faces in the order
@@ -242,8 +243,13 @@ int rt_trace_shard(rt_ctx* ctx, int width, int height, int band_rows, int shard,
  * This is the multi-GPU form of the reference's frames in flight (swapchain images, src/main.cpp:1203, 2905-2967): the frames of a batch
  * are rendered together and complete together.
  * rt_set_batch replaces rt_set_instances + rt_set_uniforms for the K frames: instances = n_frames x n records (frame k's at
- * instances + k * n, each frame a createTLAS(update) of the same topology, src/main.cpp:2848-2861), uniforms = n_frames blocks — camera
- * and light may differ from frame to frame, maxBounceCount / samplesPerPixel / object types are the batch's.  update as in rt_set_instances.
+ * instances + k * n, each frame a createTLAS(update) of the same topology, src/main.cpp:2848-2861), uniforms = n_frames blocks — the camera
+ * (position, right, up, forward), the light's position and its intensity may differ from frame to frame; maxBounceCount, samplesPerPixel and
+ * the two object types are the batch's: a block that differs from block 0 in one of them is refused (RT_ERR_INVALID_ARGUMENT, the context
+ * keeps its state); the two informational offset fields are not compared.  update as in rt_set_instances.
+ * While the context holds a batch of more than one frame its uniforms are the batch's: rt_set_uniforms returns RT_ERR_NOT_READY and changes
+ * nothing; rt_set_instances (back to single frames) comes first, then rt_set_uniforms.  The frames of a batch are walked by the one-lane
+ * kernels whatever "packet_trace" says.
  * rt_trace_shard_batch is rt_trace_shard for the batch: frame k's compact shard lands frame_stride_bytes behind frame k - 1's (0: back to
  * back, rows * width pixels apart); statistics are sums over the batch.  Results are those of the K frames rendered one by one, bit for bit (tested). */
 int rt_set_batch(rt_ctx* ctx, int n_frames, const rt_instance* instances, int n, const rt_uniforms* uniforms, int update);

@@ -50,14 +50,15 @@ int rtm_set_instance_types(rtm_ctx* ctx, int slot, const uint32_t* types, int n)
 /* rt_set_timing on the ROOT device's slots: rtm_trace_wait's stats carry that device's kernel times. */
 int rtm_set_timing(rtm_ctx* ctx, int enabled);
 
-/* Per-frame state of one slot, pushed to every device (src/main.cpp:2848-2861, 2901-2903). */
+/* Per-frame state of one slot, pushed to every device (src/main.cpp:2848-2861, 2901-2903).  rtm_set_uniforms on a slot that holds a
+ * frame batch (rtm_set_batch with more than one frame) returns RT_ERR_NOT_READY and changes nothing: rtm_set_instances comes first. */
 int rtm_set_instances(rtm_ctx* ctx, int slot, const rt_instance* instances, int n, int update);
 int rtm_set_uniforms(rtm_ctx* ctx, int slot, const rt_uniforms* u);
 
 /* vkQueueSubmit of one frame (src/main.cpp:2933-2949): every device enqueues its bands, the gather and, on the root, the
  * de-interleave and the copy to a pinned host buffer; returns at once. */
 /* Frame batches (include/rt_api.h rt_set_batch): the slot's next rtm_trace_async renders n_frames CONSECUTIVE frames — each with its own
- * instances (frame k's n records at instances + k * n), camera and light — in ONE pass on every device, with ONE gather for all of
+ * instances (frame k's n records at instances + k * n), camera, light position and light intensity — in ONE pass on every device, with ONE gather for all of
  * them; rtm_trace_wait then hands out n_frames frames back to back (width x height pixels each), rtm_frame_device likewise, and the
  * statistics are sums over the pass.  rtm_set_instances puts the slot back to single frames. */
 int rtm_set_batch(rtm_ctx* ctx, int slot, int n_frames, const rt_instance* instances, int n, const rt_uniforms* uniforms, int update);

@@ -1368,7 +1368,7 @@ def test_frame_batches_equal_the_frames_rendered_one_by_one(ctx):
         inst = anim2.instances((0, 1))
         u = sp.uniforms.copy()
         u[0]["position"][:3] = (0.4 * k - 1.0, 0.2 * k, 20.0 - 0.8 * k)
-        u[0]["light_position"][:3] = (5.0 - k, 5.0 + 0.5 * k, 5.0)
+        u[0]["light_position"][:3] = (5.0 - k, 5.0 + 0.5 * k, 5.0); u[0]["light_intensity"] = 0.5 + 0.25 * k
         return np.ascontiguousarray(inst, INSTANCE_DTYPE), u
 
     def one_by_one(frames, band, shard, n):

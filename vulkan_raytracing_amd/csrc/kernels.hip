@@ -1618,8 +1618,9 @@ __device__ __forceinline__ void shade_body(const ShadeArgs& a, const int bounce)
           } else {
             no = fma3(0.01f, N, P);
             F3 light = mk3(U.light_position[0], U.light_position[1], U.light_position[2]);
-            uint32_t fi = 0;   // frame batch: the light of the sample's frame
-            if (BATCH) { fi = frame_of(sid, a.sc.batch_samples); light = mk3(a.bt.light[fi][0], a.bt.light[fi][1], a.bt.light[fi][2]); }
+            float Iv = U.light_intensity;
+            uint32_t fi = 0;   // frame batch: the light (position and intensity) of the sample's frame
+            if (BATCH) { fi = frame_of(sid, a.sc.batch_samples); light = mk3(a.bt.light[fi][0], a.bt.light[fi][1], a.bt.light[fi][2]); Iv = a.bt.light[fi][3]; }
             const F3 toL = sub3(light, P);
             const float dist = length3(toL);
             const F3 L = mul3(toL, 1.0f / dist);
@@ -1630,7 +1631,6 @@ __device__ __forceinline__ void shade_body(const ShadeArgs& a, const int bounce)
             const uint32_t i = sid / (uint32_t)(f.rows * f.width) - fi * U.samples_per_pixel;   // sample index in its pixel
             float w = 1.0f;
             for (uint32_t k = 0; k < i; k++) w = w * 0.9f;
-            const float Iv = U.light_intensity;
             const F3 kd = M ? mk3(M->kd[0], M->kd[1], M->kd[2]) : mk3(0.2f, 1.0f, 0.2f);
             const F3 ks = M ? mk3(M->ks[0], M->ks[1], M->ks[2]) : mk3(0.8f, 0.8f, 0.8f);
             const F3 diff = mk3((Iv * kd.x) * dl, (Iv * kd.y) * dl, (Iv * kd.z) * dl);

@@ -985,6 +985,7 @@ int enqueue_frame(rt_ctx* c, int W, int H, int band_rows, int shard, int n_shard
       const UniformsDev& uk = c->batch_uni[k];
       for (int j = 0; j < 4; j++) { bt.position[k][j] = uk.position[j]; bt.right[k][j] = uk.right[j]; bt.up[k][j] = uk.up[j]; bt.forward[k][j] = uk.forward[j]; }
       for (int j = 0; j < 3; j++) bt.light[k][j] = uk.light_position[j];
+      bt.light[k][3] = uk.light_intensity;
     }
   if (K > 1) sc.batch_samples = (uint32_t)((size_t)u.samples_per_pixel * (size_t)rows * (size_t)W);
   const int n_inst1 = K > 1 ? sc.n_inst / K : sc.n_inst;   // instances of one frame
@@ -1174,6 +1175,7 @@ int enqueue_frame(rt_ctx* c, int W, int H, int band_rows, int shard, int n_shard
   // far-ray logic in this frame's kernels only if some ray can be far (a re-render decides again from the same inputs)
   LaunchCfg cfg = c->cfg;
   if (c->stack_need > 120) cfg.packet = 0;   // deeper than k_packet's 128-entry wave stack (a degenerate LBVH): the one-lane kernels spill to HBM instead
+  if (K > 1) cfg.packet = 0;   // k_packet starts every walk at frame 0's TLAS root (no tlas_stride / frame_of): the frames of a batch take the one-lane kernels
   cfg.far = far_frame ? 1 : 0;
   f.far_possible = cfg.far;
   f.settle_dead_shadow_rays = c->dead_shadow_rays;
@@ -1650,7 +1652,7 @@ int rt_set_batch(rt_ctx* c, int n_frames, const rt_instance* instances, int n, c
   for (int k = 1; k < n_frames; k++)
     if (uniforms[k].max_bounce_count != uniforms[0].max_bounce_count || uniforms[k].samples_per_pixel != uniforms[0].samples_per_pixel ||
         uniforms[k].center_object_type != uniforms[0].center_object_type || uniforms[k].orbiting_object_type != uniforms[0].orbiting_object_type)
-      return fail(c, RT_ERR_INVALID_ARGUMENT, "the frames of a batch share maxBounceCount, samplesPerPixel and the object types (camera, light and instances may differ)");
+      return fail(c, RT_ERR_INVALID_ARGUMENT, "the frames of a batch share maxBounceCount, samplesPerPixel and the object types (camera, light position and intensity, and instances may differ)");
   int r = set_instances_frames(c, instances, n, update, n_frames); if (r) return r;
   c->batch_uni.resize(n_frames);
   memcpy(c->batch_uni.data(), uniforms, (size_t)n_frames * sizeof(UniformsDev));
@@ -1822,6 +1824,9 @@ int rt_set_instance_types(rt_ctx* c, const uint32_t* types, int n) {
 int rt_set_uniforms(rt_ctx* c, const rt_uniforms* u) {
   if (!c) return RT_ERR_INVALID_ARGUMENT;
   if (!u) return fail(c, RT_ERR_INVALID_ARGUMENT, "uniforms pointer is NULL");
+  // a batch's uniforms are the K blocks rt_set_batch checked and stored: one block here would change the shared fields behind that check
+  // and leave the cameras and lights of the batch in place
+  if (c->batch_k > 1) return fail(c, RT_ERR_NOT_READY, "the context holds a frame batch: its uniforms are set by rt_set_batch; call rt_set_instances first for a single frame");
   memcpy(&c->uni, u, sizeof(UniformsDev));
   c->have_uni = true;
   return RT_OK;

@@ -762,6 +762,29 @@ __device__ __forceinline__ uint32_t frame_row(const FrameDev& f, uint32_t ly) {
 // table entry of (tile, sample, lane): tile-major, so that a wavefront of k_raygen reads 512 consecutive bytes
 __device__ __forceinline__ size_t jitter_index(uint32_t tile, uint32_t i, uint32_t spp, uint32_t lane) { return ((size_t)tile * spp + i) * 64u + lane; }
 
+// A SKY tile: no mesh can touch 8x8 tile (tx, by) of frame fi (by: the tile row within this shard's rows of that frame; rec: the tile's
+// entry record, counted over all frames of a batch) — the coverage mask leaves it unmarked (a mask whose word 0 is set marks every
+// tile), or its entry record says that its beam touches nothing.  Uniform over a tile.  k_raygen finishes the pixels of such a tile
+// itself and k_resolve leaves them alone: both ask here, so they cannot disagree.  Frames without a mask and without records have no sky tiles.
+// (The local tile row maps to a tile row of the full frame because bands are whole tiles when the mask is on: rt_api enables it only
+// for band heights that are multiples of 8.)
+__device__ __forceinline__ bool tile_is_sky(const FrameDev& f, uint32_t fi, uint32_t tx, uint32_t by, uint32_t rec) {
+  if (f.cover != nullptr) {
+    const uint32_t* const cover = f.cover + (size_t)fi * f.cover_view_words;
+    if (cover[0] == 0u) {
+      uint32_t fty = by;
+      if (f.n_shards != 1) {
+        const uint32_t tiles_per_band = (uint32_t)f.band_rows >> 3;
+        const uint32_t band = by / tiles_per_band, sub = by - band * tiles_per_band;
+        fty = (band * (uint32_t)f.n_shards + (uint32_t)f.shard) * tiles_per_band + sub;
+      }
+      const uint32_t t = fty * (uint32_t)f.cover_tiles_x + tx;
+      if (((cover[1u + (t >> 5)] >> (t & 31u)) & 1u) == 0u) return true;
+    }
+  }
+  return f.entry != nullptr && (uint32_t)f.entry[rec].w[0] == ENTRY_EMPTY;
+}
+
 // same grid as k_raygen
 __global__ __launch_bounds__(256) void k_jitter_table(FrameDev f, uint32_t spp, float2* table) {
   const uint32_t lane = threadIdx.x;
@@ -785,24 +808,49 @@ __global__ __launch_bounds__(256) void k_raygen(SceneDev sc, FrameDev f, Uniform
   const uint32_t npx1 = (uint32_t)(f.rows * f.width);
   const uint32_t ly = by * 8u + (lane >> 3);
   const bool live = i < spp && x < (uint32_t)f.width && ly < (uint32_t)f.rows;
-  // coverage mask (uniform per workgroup): can any mesh touch this tile?  The local tile row maps to a tile row of the full
-  // frame because bands are whole tiles when the mask is on (rt_api enables it only for band heights that are multiples of 8).
-  bool covered = true;
-  const uint32_t* const cover = f.cover != nullptr ? f.cover + (size_t)fi * f.cover_view_words : nullptr;
-  if (cover != nullptr && cover[0] == 0u) {
-    uint32_t fty = by;
-    if (f.n_shards != 1) {
-      const uint32_t tiles_per_band = (uint32_t)f.band_rows >> 3;
-      const uint32_t band = by / tiles_per_band, sub = by - band * tiles_per_band;
-      fty = (band * (uint32_t)f.n_shards + (uint32_t)f.shard) * tiles_per_band + sub;
-    }
-    const uint32_t t = fty * (uint32_t)f.cover_tiles_x + blockIdx.x;
-    covered = ((cover[1u + (t >> 5)] >> (t & 31u)) & 1u) != 0u;
-  }
-  // entry lists (k_entry): the record of this tile says whether its beam touches anything at all
+  // coverage mask and entry lists (k_cover, k_entry; uniform per workgroup): can any mesh touch this tile?
   const uint32_t tile = blockIdx.y * gridDim.x + blockIdx.x;   // (over all frames of a batch: the records of frame k follow those of frame k - 1)
   const uint32_t tile1 = by * gridDim.x + blockIdx.x;          // within its frame
-  if (f.entry != nullptr && covered && (uint32_t)f.entry[tile].w[0] == ENTRY_EMPTY) covered = false;
+  const bool covered = !tile_is_sky(f, fi, blockIdx.x, by, tile);
+  __shared__ float4 s_col[4][64];
+  if (!covered) {
+    // A sky tile (4/5 of the headline's): every sample of every pixel is a miss, so the pixels are final here (src/shader.rgen:64,
+    // 180-185: the same ordered sum and division as k_resolve) and NOTHING is written but the pixel: k_resolve asks tile_is_sky too and
+    // keeps away from these pixels, so they need no marker, and there is no queue run to allocate and no vote to take.
+    F3 right = mk3(u.right[0], u.right[1], u.right[2]), up = mk3(u.up[0], u.up[1], u.up[2]), fwd = mk3(u.forward[0], u.forward[1], u.forward[2]);
+    if (f.batch_k > 1) { right = mk3(bt.right[fi][0], bt.right[fi][1], bt.right[fi][2]); up = mk3(bt.up[fi][0], bt.up[fi][1], bt.up[fi][2]); fwd = mk3(bt.forward[fi][0], bt.forward[fi][1], bt.forward[fi][2]); }
+    const uint32_t fy = frame_row(f, ly);
+    const float nn = (float)spp;
+    float r = 0.f, g = 0.f, b = 0.f, al = 0.f;
+    if (gridDim.z == 1u) {
+      // the workgroup holds all samples of its pixels (spp <= 4): a wave per sample — the sky fetches of a pixel's samples are in flight
+      // together — then the colours are exchanged through LDS and sample 0's wave sums them in order.  (One wave looping over a
+      // pixel's samples, no LDS and no barrier, measured SLOWER: 167 against 134 us per frame, profiles/r05_experiments.txt — the
+      // chain jitter -> direction -> four taps of a sample does not overlap the next sample's.)
+      float4 col = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (live) {
+        const float2 uv = f.jitter != nullptr ? f.jitter[jitter_index(tile1, i, spp, lane)] : sample_uv(x, fy, i, spp, f.width, f.height);
+        const F3 d = normalize3(fma3(2.5f, fwd, fma3(uv.y, up, mul3(right, uv.x))));
+        const F3 c = sample_sky(sc, mk3(d.x, d.y, -d.z));
+        col = make_float4(c.x, c.y, c.z, 1.0f);
+      }
+      s_col[threadIdx.y][lane] = col;
+      __syncthreads();
+      if (threadIdx.y != 0u || !live) return;
+      for (uint32_t w = 0; w < blockDim.y; w++) { const float4 c = s_col[w][lane]; r += c.x; g += c.y; b += c.z; al += c.w; }
+    } else {
+      // more samples than a workgroup holds: the first wave of the tile's first workgroup walks all of them, a lane per pixel
+      if (threadIdx.y != 0u || blockIdx.z != 0u || x >= (uint32_t)f.width || ly >= (uint32_t)f.rows) return;
+      for (uint32_t k = 0; k < spp; k++) {
+        const float2 uv = f.jitter != nullptr ? f.jitter[jitter_index(tile1, k, spp, lane)] : sample_uv(x, fy, k, spp, f.width, f.height);
+        const F3 d = normalize3(fma3(2.5f, fwd, fma3(uv.y, up, mul3(right, uv.x))));
+        const F3 c = sample_sky(sc, mk3(d.x, d.y, -d.z));
+        r += c.x; g += c.y; b += c.z; al += 1.0f;
+      }
+    }
+    store_pixel(f, fi * f.out_frame_stride + ly * (uint32_t)f.width + x, make_float4(r / nn, g / nn, b / nn, al / nn));
+    return;
+  }
 #ifdef RT_ALT_KERNELS
   // tile blobs (k_blob, alt library only): the rays of a tile that has one are walked in LDS by k_tile
   if (f.tile_blob != nullptr && covered && f.tile_blob[tile] != BLOB_NONE) return;   // (uniform over the workgroup) k_tile generates and walks this tile's rays
@@ -819,7 +867,7 @@ __global__ __launch_bounds__(256) void k_raygen(SceneDev sc, FrameDev f, Uniform
     if (f.batch_k > 1) { right = mk3(bt.right[fi][0], bt.right[fi][1], bt.right[fi][2]); up = mk3(bt.up[fi][0], bt.up[fi][1], bt.up[fi][2]); fwd = mk3(bt.forward[fi][0], bt.forward[fi][1], bt.forward[fi][2]); }
     d = normalize3(fma3(2.5f, fwd, fma3(uy, up, mul3(right, ux))));
     sid = (fi * spp + i) * npx1 + ly * (uint32_t)f.width + x;
-    if (covered) {
+    {
       const F3 o = f.batch_k > 1 ? mk3(bt.position[fi][0], bt.position[fi][1], bt.position[fi][2]) : mk3(u.position[0], u.position[1], u.position[2]);
       F3 qs, qb; uint3 rot;
       quant_space(o, d, sc.tlas_q_lo, sc.tlas_q_scale, qs, qb, rot);
@@ -847,28 +895,13 @@ __global__ __launch_bounds__(256) void k_raygen(SceneDev sc, FrameDev f, Uniform
       miss_col = make_float4(c.x, c.y, c.z, 1.0f);
     }
   }
-  // A pixel ALL of whose samples are misses is resolved right here (src/shader.rgen:180-185: the same ordered sum and division as
-  // k_resolve) when the workgroup holds all of them (spp <= 4): 4/5 of the headline's pixels are sky, and for them the per-sample
-  // colours never travel to HBM and back — one pixel and one marker are stored instead of four colours, k_resolve reads the marker only.
+  // A tile some mesh may touch.  A pixel ALL of whose samples are misses is still resolved right here (the same ordered sum and division)
+  // when the workgroup holds all of them (spp <= 4): its per-sample colours never travel to HBM and back — one pixel and one marker
+  // (PIXEL_DONE in sample 0's colour slot) are stored instead of four colours, and k_resolve reads the marker only.  These pixels are
+  // few: the rims of the covered tiles.
   const bool missed = live && !survive;
   const bool fuse = gridDim.z == 1u;
-  __shared__ float4 s_col[4][64];
   __shared__ unsigned long long s_miss[4];
-  if (fuse && !covered) {
-    // a tile no mesh can touch (uniform over the workgroup; 4/5 of the headline's tiles): every sample is a miss, so there is no queue
-    // run to allocate and no vote to take — exchange the colours, sum, store, done
-    s_col[threadIdx.y][lane] = miss_col;
-    __syncthreads();
-    if (threadIdx.y == 0 && live) {
-      float r = 0.f, g = 0.f, b = 0.f, al = 0.f;
-      for (uint32_t w = 0; w < blockDim.y; w++) { const float4 c = s_col[w][lane]; r += c.x; g += c.y; b += c.z; al += c.w; }
-      const float nn = (float)spp;
-      const uint32_t p = ly * (uint32_t)f.width + x;
-      store_pixel(f, fi * f.out_frame_stride + p, make_float4(r / nn, g / nn, b / nn, al / nn));
-      st_stream(&f.sample_color[fi * spp * npx1 + p], make_float4(0.f, 0.f, 0.f, PIXEL_DONE));
-    }
-    return;
-  }
   if (fuse) {
     s_col[threadIdx.y][lane] = miss_col;
     const uint64_t mm = __ballot(missed);
@@ -892,6 +925,12 @@ __global__ __launch_bounds__(256) void k_raygen(SceneDev sc, FrameDev f, Uniform
       tot = run;
     }
     s_run[4] = tot ? atomicAdd(f.counters + cnt_tail(0, (int)shard), tot) : 0u;
+    if (f.pixel_runs && tot) {
+      // the rays of a run all leave the camera of their frame, from one tile: ONE origin per run, in the slot of its first entry
+      // (k_beam reads it for the whole wave; k_shade takes the camera from its own arguments)
+      const F3 o = f.batch_k > 1 ? mk3(bt.position[fi][0], bt.position[fi][1], bt.position[fi][2]) : mk3(u.position[0], u.position[1], u.position[2]);
+      f.ray_o[0][shard * f.shard_cap + s_run[4]] = make_float4(o.x, o.y, o.z, f.entry != nullptr ? __uint_as_float(tile) : 10000.0f);
+    }
     s_run[0] = f.pixel_runs ? tot : s_run[0];   // (pixel runs: row 0's offset is not needed; the word says whether the tile has a run)
   }
   __syncthreads();
@@ -913,9 +952,12 @@ __global__ __launch_bounds__(256) void k_raygen(SceneDev sc, FrameDev f, Uniform
   }
   if (survive || run_tile) {
     const uint32_t v = shard * f.shard_cap + slot;
-    // (with entry lists the ray carries its tile instead of tmax, which is the constant 10000 of src/shader.rgen:87)
-    const F3 o = f.batch_k > 1 ? mk3(bt.position[fi][0], bt.position[fi][1], bt.position[fi][2]) : mk3(u.position[0], u.position[1], u.position[2]);
-    st_stream(&f.ray_o[0][v], make_float4(o.x, o.y, o.z, f.entry != nullptr ? __uint_as_float(tile) : 10000.0f));
+    if (!f.pixel_runs) {
+      // one walk per ray (k_trace): the ray carries its origin and, with entry lists, its tile instead of tmax, which is the constant
+      // 10000 of src/shader.rgen:87.  (Pixel runs: both are the run's, stored once above.)
+      const F3 o = f.batch_k > 1 ? mk3(bt.position[fi][0], bt.position[fi][1], bt.position[fi][2]) : mk3(u.position[0], u.position[1], u.position[2]);
+      st_stream(&f.ray_o[0][v], make_float4(o.x, o.y, o.z, f.entry != nullptr ? __uint_as_float(tile) : 10000.0f));
+    }
     st_stream(&f.ray_d[0][v], survive ? make_float4(d.x, d.y, d.z, __uint_as_float(sid)) : make_float4(0.f, 0.f, 0.f, __uint_as_float(SID_DEAD)));   // (a zero direction: no ray in this slot)
   }
 }
@@ -1688,8 +1730,14 @@ __device__ __forceinline__ void shade_body(const ShadeArgs& a, const int bounce)
           push_next = true;
         } else {
           // unknown type: the reference loop re-traces the unchanged ray until the bounce budget ends
-          const float4 ro = ld_stream(&f.ray_o[cur][q]);
-          no = mk3(ro.x, ro.y, ro.z); nd = d; push_next = true;
+          if (bounce == 0 && f.pixel_runs) {   // (pixel runs: queue 0 has one origin per run, not per ray — the camera of the ray's frame)
+            no = mk3(U.position[0], U.position[1], U.position[2]);
+            if (BATCH) { const uint32_t fk = frame_of(sid, a.sc.batch_samples); no = mk3(a.bt.position[fk][0], a.bt.position[fk][1], a.bt.position[fk][2]); }
+          } else {
+            const float4 ro = ld_stream(&f.ray_o[cur][q]);
+            no = mk3(ro.x, ro.y, ro.z);
+          }
+          nd = d; push_next = true;
         }
         if (push_next && last) {
           // loop of src/shader.rgen:84 ends: tmpColor keeps Iamb*ka
@@ -1802,28 +1850,41 @@ __global__ __launch_bounds__(256) void k_tail(TailArgs t) {
 
 // ------------------------------------------------------------------------------------------------
 // k_resolve: src/shader.rgen:64,180-185 — ordered sum over samples, divide, store.
+// Grid (tiles_x, tile rows [of all frames of a batch] / 4), block 256: ONE WAVE PER 8x8 TILE of k_raygen's grid, a lane per pixel.  The
+// pixels of a sky tile are final since k_raygen (tile_is_sky, the predicate both kernels share): such a tile costs its wave one mask
+// word and one record word, read as scalars.  In the other tiles a pixel ALL of whose samples missed carries PIXEL_DONE in sample 0's
+// colour slot (k_raygen stored the pixel; spp <= 4 only); every other pixel is summed here.
 __global__ __launch_bounds__(256) void k_resolve(FrameDev f, UniformsDev u) {
-  const uint32_t npx1 = (uint32_t)(f.rows * f.width), npx = npx1 * (uint32_t)f.batch_k;   // (a frame batch: the frames back to back)
-  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t fi = f.batch_k > 1 ? p / npx1 : 0u, p1 = p - fi * npx1;
-  const size_t s0 = (size_t)fi * u.samples_per_pixel * npx1 + p1;   // sample 0 of this pixel
-  if (p < npx && f.sample_color[s0].w != PIXEL_DONE) {   // (PIXEL_DONE: every sample of the pixel was a miss and k_raygen stored the pixel)
-    float r = 0.f, g = 0.f, b = 0.f, al = 0.f;
-    for (uint32_t i = 0; i < u.samples_per_pixel; i++) {
-      const float4 c = ld_stream(&f.sample_color[s0 + (size_t)i * npx1]);
-      r += c.x; g += c.y; b += c.z; al += c.w;
+  const uint32_t npx1 = (uint32_t)(f.rows * f.width);
+  const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const uint32_t tile_rows1 = ((uint32_t)f.rows + 7u) >> 3;
+  const uint32_t trow = blockIdx.y * 4u + wave;   // tile row over the frames of a batch (the frames' tile rows are stacked, as in k_raygen)
+  if (trow < tile_rows1 * (uint32_t)f.batch_k) {
+    const uint32_t fi = f.batch_k > 1 ? trow / tile_rows1 : 0u, by = trow - fi * tile_rows1;
+    const uint32_t x = blockIdx.x * 8u + (lane & 7u), ly = by * 8u + (lane >> 3);
+    if (!tile_is_sky(f, fi, blockIdx.x, by, trow * gridDim.x + blockIdx.x) && x < (uint32_t)f.width && ly < (uint32_t)f.rows) {
+      const uint32_t p1 = ly * (uint32_t)f.width + x;
+      const size_t s0 = (size_t)fi * u.samples_per_pixel * npx1 + p1;   // sample 0 of this pixel
+      if (f.sample_color[s0].w != PIXEL_DONE) {
+        float r = 0.f, g = 0.f, b = 0.f, al = 0.f;
+        for (uint32_t i = 0; i < u.samples_per_pixel; i++) {
+          const float4 c = ld_stream(&f.sample_color[s0 + (size_t)i * npx1]);
+          r += c.x; g += c.y; b += c.z; al += c.w;
+        }
+        const float nn = (float)u.samples_per_pixel;
+        store_pixel(f, fi * f.out_frame_stride + p1, make_float4(r / nn, g / nn, b / nn, al / nn));
+      }
     }
-    const float nn = (float)u.samples_per_pixel;
-    store_pixel(f, fi * f.out_frame_stride + p1, make_float4(r / nn, g / nn, b / nn, al / nn));
   }
+  const uint32_t p = (blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x, n_threads = gridDim.x * gridDim.y * blockDim.x;
   // The next frame of this context finds its counters zeroed (no memset dispatch per frame): it uses the other block.
   if (f.counters_next)
-    for (uint32_t i = p; i < (uint32_t)CNT_WORDS; i += gridDim.x * blockDim.x) f.counters_next[i] = 0u;
+    for (uint32_t i = p; i < (uint32_t)CNT_WORDS; i += n_threads) f.counters_next[i] = 0u;
   if (f.cover_next)   // and its coverage mask cleared
-    for (uint32_t i = p; i < f.cover_words; i += gridDim.x * blockDim.x) f.cover_next[i] = 0u;
+    for (uint32_t i = p; i < f.cover_words; i += n_threads) f.cover_next[i] = 0u;
   // This is the last kernel of the frame, so every counter is final: workgroup 0 condenses them into the host-mapped
   // statistics block (rt_device.h StatSlot).
-  if (blockIdx.x == 0 && f.stats_out) {
+  if (blockIdx.x == 0 && blockIdx.y == 0 && f.stats_out) {
     __shared__ unsigned long long s_q[N_QUEUES];
     const uint32_t t = threadIdx.x;
     if (t < (uint32_t)N_QUEUES) {
@@ -2330,8 +2391,8 @@ void launch_assemble(const void* gathered, void* out, int width, int height, int
 }
 
 void launch_resolve(const FrameDev& f, const UniformsDev& u, hipStream_t s) {
-  const uint32_t npx = (uint32_t)(f.rows * f.width) * (uint32_t)f.batch_k;
-  hipLaunchKernelGGL(k_resolve, dim3((npx + 255u) / 256u), dim3(256), 0, s, f, u);
+  const uint32_t tile_rows = (((uint32_t)f.rows + 7u) >> 3) * (uint32_t)f.batch_k;   // k_raygen's tiles, four tile rows per workgroup
+  hipLaunchKernelGGL(k_resolve, dim3(((uint32_t)f.width + 7u) >> 3, (tile_rows + 3u) / 4u), dim3(256), 0, s, f, u);
 }
 
 }  // namespace rt

@@ -16,6 +16,8 @@
 // k_raygen, <= 4), one per covered tile and sample group, NOT compacted: slot run + 64 j + l is sample j of the tile's pixel l; a
 // sample that is not traced (it missed the TLAS, or lies outside the frame) leaves a slot with a zero direction, and gets HIT_DEAD as
 // its hit record (k_shade skips it: k_raygen has given it its colour).  A wavefront takes a run; lane l walks pixel l.
+// A slot holds a direction and a sample id only: the origin of every primary ray is the camera of its frame and its tile is the run's, so
+// k_raygen stores (camera, tile) ONCE per run, in the origin slot of the run's first entry; the wave reads that one address.
 // No far-ray logic: the host launches this kernel only in frames without far rays (rt_api far_possible).  With camera records (k_entry)
 // a pixel's walk starts at its tile's record, without them at the root of the TLAS.
 struct BeamSpace { F3 s0, b0, s1, b1; uint3 rot; };   // (qs, qb) of slab_q for the smallest (0) and the largest (1) reciprocal direction per axis
@@ -90,7 +92,7 @@ __device__ __forceinline__ void beam_body(const TraceArgs& a, const uint32_t run
     if (!got) break;
     const uint32_t v0 = base + lane;
 
-    // ---- the lane's pixel: origin (the camera) and tile from sample 0's slot, the directions of its live samples
+    // ---- the lane's pixel: the directions of its live samples (origin and tile are the run's)
     uint32_t alive = 0, sid = 0;   // (sid: of one of the live samples — its frame, in a frame batch)
     F3 co = mk3(0, 0, 0), cd0 = mk3(0, 0, 1), cd1 = cd0, cd2 = cd0, cd3 = cd0;
     float bt0 = -1.0f, bt1 = -1.0f, bt2 = -1.0f, bt3 = -1.0f;   // closest-hit distance so far; a slot without a ray never accepts a hit
@@ -113,7 +115,7 @@ __device__ __forceinline__ void beam_body(const TraceArgs& a, const uint32_t run
     // (object-space origin and direction, t preserved), and the (qs, qb) pair of the beam.  The world directions are not kept in
     // registers: they are read from the queue again (a pixel changes its space once or twice in its life).  Returns the instance's root.
     auto set_space = [&](int ii, int& root, uint32_t& imask) {
-      const float4 ro = a.ray_o[v0];
+      const float4 ro = a.ray_o[base];   // the run's one origin word (k_raygen): the camera of its frame — one address for the whole wave
       const F3 wo = mk3(ro.x, ro.y, ro.z);
       F3 w0 = mk3(0, 0, 1), w1 = w0, w2 = w0, w3 = w0;
 #define RT_BEAM_LD(j) if (alive & (1u << j)) { const float4 r = a.ray_d[v0 + 64u * j]; w##j = mk3(r.x, r.y, r.z); }
@@ -174,8 +176,8 @@ __device__ __forceinline__ void beam_body(const TraceArgs& a, const uint32_t run
       int root; uint32_t imask;
       set_space(-1, root, imask);
     } else if (alive != 0u) {
-      // the walk starts at the record of the pixel's tile (k_entry), as in k_trace<closest, ENTRY>; the slot of sample 0 carries the tile
-      const uint32_t tile = __float_as_uint(ld_stream(&a.ray_o[v0]).w);
+      // the walk starts at the record of the pixel's tile (k_entry), as in k_trace<closest, ENTRY>; the run's first origin slot carries the tile
+      const uint32_t tile = __float_as_uint(ld_stream(&a.ray_o[base]).w);
       const int4* rp = reinterpret_cast<const int4*>(a.entry + tile);
       const int4 r0 = rp[0], r1 = rp[1];
       const uint32_t hdr = (uint32_t)r0.x;

@@ -32,7 +32,7 @@ struct SceneDev {
 };
 
 struct FrameDev {
-  float4* ray_o[2];            // ping-pong ray queues: (o.xyz, tmax)
+  float4* ray_o[2];            // ping-pong ray queues: (o.xyz, tmax) — queue 0 with pixel runs: ONE origin per run (camera, tile), in the slot of the run's first entry
   float4* ray_d[2];            //                        (d.xyz, sample id bits)
   float4* hit_a;               // closest-hit records: (t, u, v, prim bits)
   int32_t* hit_inst;           //                       instance index, -1 = miss

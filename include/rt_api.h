@@ -446,6 +446,41 @@ int rt_closest_point_device(rt_ctx* ctx, size_t n, const void* d_points4, uint32
  * stats->node_visits and stats->tri_tests (boxes-pair visits and point-triangle tests of the whole call); stats may be NULL. */
 int rt_closest_point(rt_ctx* ctx, size_t n, const float* points4_host, uint32_t cull_mask, rt_hit* out_host, int counting, rt_stats* stats);
 
+/* Box overlaps: for every query box the triangles of the scene that touch it (PhysX's overlap query, an occupancy test per voxel), for
+ * voxelisation and occupancy grids, broad-phase collision against the live scene, region selection and "is this cell empty" tests.
+ * Boxes: d_boxes8 holds n records of 32 B (lo.x, lo.y, lo.z, w3, hi.x, hi.y, hi.z, w7), 16-B aligned, memory of ctx's GPU: a closed
+ * world-space axis-aligned box; words 3 and 7 are ignored.  lo == hi on any axis is allowed (a plane, a line, a point).  A record with a
+ * non-finite bound or with lo > hi on an axis is invalid: its count is 0 and it lists nothing.
+ * Candidates C(box): the triangles of every instance with (mask & cull_mask) != 0 that the canonical predicate below does not separate
+ * from the box.  Both sets are closed: touching counts.  Instance flags, opacity and facing play no part.
+ * d_counts (optional): n uint32, 4-B aligned: |C(box)|, not capped at max_ids.
+ * d_ids: n x max_ids records of 8 B (int32 inst, int32 prim), 4-B aligned, box-major: a row lists the max_ids smallest candidates by
+ * (inst, prim) ascending, entries past min(|C|, max_ids) are (-1, -1).  max_ids is 0..16; with 0 the call counts only (d_ids NULL,
+ * d_counts non-NULL).  Without d_counts the walk stops looking for ids larger than a full row's last entry; the rows are the same.
+ * RT_OVERLAP_ANY in flags answers occupancy: max_ids must be 0, d_counts receives 0 or 1 (|C| > 0) and the walk of a box ends at its
+ * first candidate.
+ * Canonical predicate (DESIGN.md §5 "Box overlaps" has every operation in order): binary32, nothing fused except inside dot3 / cross3 /
+ * xform_point / xform_vec.  A = xform_point(I.o2w, v0), ab = xform_vec(I.o2w, e1), ac = xform_vec(I.o2w, e2), B = A + ab,
+ * C = A + ac (a non-finite A, B or C: never a candidate); the box axes on lo / hi themselves; then with c = 0.5 lo + 0.5 hi,
+ * h = 0.5 hi - 0.5 lo and the centred vertices the nine axes e_i x f_j and the triangle's plane of Akenine-Moller's "Fast 3D
+ * Triangle-Box Overlap Testing".  Every comparison is strict: a tie is not a separation.  The predicate depends on the box, the instance
+ * record and the packet only, never on the tree.
+ * Stream ordering without host synchronisation, the TLAS and scene of the call, the query workspace, queries and shading calls of one
+ * context one after another, RT_ERR_NOT_READY and n == 0 (nothing is enqueued): as for rt_closest_point_device.
+ * RT_ERR_INVALID_ARGUMENT: a NULL or misaligned pointer, a pointer that is not memory of ctx's GPU, n >= 0xFFFFFF00 or
+ * n x max_ids >= 0xFFFFFF00, cull_mask > 0xFF, unknown flag bits, max_ids > 16, max_ids == 0 with d_ids or without d_counts,
+ * RT_OVERLAP_ANY with max_ids != 0, neither output given, trace_variant != 0. */
+#define RT_OVERLAP_ANY 0x1u
+int rt_overlap_boxes_device(rt_ctx* ctx, size_t n, const void* d_boxes8, uint32_t cull_mask, uint32_t flags,
+                            uint32_t max_ids, void* d_ids, void* d_counts, void* hip_stream);
+/* The blocking host form, as rt_closest_point is to rt_closest_point_device: the boxes are copied to the device, queried on the
+ * context's stream (same workspace and ordering) and ids_host (n x max_ids pairs; NULL with max_ids 0) and counts_host (n; optional
+ * unless max_ids is 0) copied back.  counting != 0 runs the instrumented walk and fills stats->node_visits and stats->tri_tests (node
+ * visits and triangle-box tests of the whole call); stats may be NULL.  As rt_closest_point does, the call also reports the walk's device
+ * time in stats->ms_trace_closest and the node and packet sizes in stats->bvh_node_bytes / bvh_tri_bytes; every other field is 0. */
+int rt_overlap_boxes(rt_ctx* ctx, size_t n, const float* boxes8_host, uint32_t cull_mask, uint32_t flags,
+                     uint32_t max_ids, int32_t* ids_host, uint32_t* counts_host, int counting, rt_stats* stats);
+
 /* Custom ray generation: the frame's shading of the caller's primary rays.  The caller's rays replace the pinhole camera of
  * src/shader.rgen:62-82; everything after it — the bounce loop of src/shader.rgen:84-177 with closest hit, miss, reflection, refraction and
  * shadow rays — is the frame's, and the colours are those a frame would compute for the same rays.

@@ -57,10 +57,11 @@ INSTANCE_FLAG_FORCE_OPAQUE = 0x4
 INSTANCE_FLAG_FORCE_NO_OPAQUE = 0x8
 HIT_KIND_FRONT_FACING = 0xFE
 HIT_KIND_BACK_FACING = 0xFF
+OVERLAP_ANY = 0x1   # rt_overlap_boxes_device: occupancy (counts of 0 or 1)
 
 EXPORTS = ["rt_create", "rt_create_frame_slot", "rt_destroy", "rt_upload_geometry", "rt_build_blas", "rt_set_instances", "rt_set_instances_device", "rt_refit_blas_device", "rt_set_materials", "rt_set_instance_types", "rt_set_uniforms", "rt_set_skybox",
            "rt_trace", "rt_trace_async", "rt_trace_wait", "rt_trace_shard", "rt_set_batch", "rt_trace_shard_batch", "rt_assemble_shards", "rt_shard_rows", "rt_synchronize", "rt_get_stats", "rt_set_timing", "rt_intersect",
-           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
+           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
 
 _LIBS = {}
 
@@ -105,6 +106,8 @@ def lib(variant=None):
         L.rt_intersect_device_hits.argtypes = [vp, C.c_size_t, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
         L.rt_closest_point_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, vp, vp]
         L.rt_closest_point.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, C.c_int, C.POINTER(RtStats)]
+        L.rt_overlap_boxes_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]
+        L.rt_overlap_boxes.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_int, C.POINTER(RtStats)]
         L.rt_shade_rays_device.argtypes = [vp, C.c_size_t, C.c_uint32, vp, vp, vp, vp]
         L.rt_last_error.argtypes = [vp]
         L.rt_last_error.restype = C.c_char_p
@@ -382,6 +385,64 @@ class RtContext:
         self._chk(self.L.rt_closest_point(self.h, len(points4), _p(points4), int(cull_mask) & 0xFFFFFFFF, _p(out), int(counting), C.byref(st)), "rt_closest_point")
         return out, st
 
+    def overlap_boxes_device(self, boxes, max_ids=0, cull_mask=0xFF, any=False, counts=True, stream=None, out=None):
+        """rt_overlap_boxes_device: the triangles that touch every query box.  `boxes` is a contiguous float32 torch tensor (n, 8) on this
+        context's GPU (lo.xyz, ignored, hi.xyz, ignored per row: a closed world-space box), read in the order of `stream` like
+        intersect_device's rays.  Returns a BoxOverlaps: count, int32 (n,), the number of triangles the canonical predicate does not
+        separate from the box (with counts=True; required when max_ids is 0), and ids, int32 (n, max_ids, 2), the max_ids smallest
+        (inst, prim) of them in ascending order, (-1, -1) past the last.  counts=False lets the walk stop once a row is full.  any=True
+        answers occupancy (max_ids 0): count is 0 or 1.  out = (ids, count) reuses such buffers (None where not asked for).  See
+        include/rt_api.h."""
+        import torch
+        self._check_rays(boxes, "overlap_boxes_device", 8, "box")
+        k = int(max_ids)
+        if not 0 <= k <= 16:
+            raise ValueError("max_ids must be 0..16, got %d" % k)
+        if k == 0 and not counts:
+            raise ValueError("max_ids 0 counts only: counts=True")
+        if any and k:
+            raise ValueError("any=True answers occupancy: max_ids must be 0")
+        n = boxes.shape[0]
+        cur = torch.cuda.current_stream(boxes.device)
+        if stream is None:
+            stream = cur
+        shapes = ((n, k, 2) if k else None, (n,) if counts else None)
+        if out is None:
+            bufs = [torch.empty(sh, dtype=torch.int32, device=boxes.device) if sh is not None else None for sh in shapes]
+            if stream != cur:   # (allocated for the current stream, written on `stream`)
+                for t in bufs:
+                    if t is not None:
+                        t.record_stream(stream)
+        else:
+            bufs = list(out)
+            for i, (t, sh, what) in enumerate(zip(bufs, shapes, ("ids", "counts"))):
+                if sh is None:
+                    bufs[i] = None
+                elif t is None or t.dtype != torch.int32 or tuple(t.shape) != sh or not t.is_contiguous() or t.device != boxes.device:
+                    raise ValueError("out %s must be a contiguous int32 %s tensor on the boxes' device" % (what, sh))
+        ids, count = bufs
+
+        def call(run):
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+            return self.L.rt_overlap_boxes_device(self.h, n, ptr(boxes), int(cull_mask) & 0xFFFFFFFF, OVERLAP_ANY if any else 0, k, ptr(ids), ptr(count),
+                                                  C.c_void_p(run.cuda_stream))
+        if n:
+            self._on_stream(stream, (boxes, ids, count), call, "rt_overlap_boxes_device")
+        return BoxOverlaps(ids, count)
+
+    def overlap_boxes(self, boxes8, max_ids=0, cull_mask=0xFF, any=False, counts=True, counting=False):
+        """rt_overlap_boxes: the blocking host form -> (counts uint32 (n,) or None, ids int32 (n, max_ids, 2) or None, RtStats; with
+        counting its node_visits / tri_tests are filled)"""
+        boxes8 = np.ascontiguousarray(boxes8, np.float32).reshape(-1, 8)
+        n, k = len(boxes8), int(max_ids)
+        cnt = np.zeros(n, np.uint32) if counts else None
+        ids = np.zeros((n, k, 2), np.int32) if k else None
+        st = RtStats()
+        self._chk(self.L.rt_overlap_boxes(self.h, n, _p(boxes8), int(cull_mask) & 0xFFFFFFFF, OVERLAP_ANY if any else 0, k & 0xFFFFFFFF,
+                                          _p(ids) if ids is not None else None, _p(cnt) if cnt is not None else None, int(counting), C.byref(st)),
+                  "rt_overlap_boxes")
+        return cnt, ids, st
+
     def intersect_device_hits(self, rays, max_hits, ray_flags=0, cull_mask=0xFF, words=None, attributes=False, counts=True, stream=None, out=None):
         """rt_intersect_device_hits: every candidate along each ray, the first max_hits of them in (t, inst, prim) order, and their number.
         rays and words as for intersect_device_flags; max_hits 1..16, or 0 for counts only.  Read and written in the order of `stream`
@@ -589,6 +650,22 @@ class RayHits:
         a = self.attr.cpu().numpy() if self.attr is not None else None
         c = self.count.cpu().numpy().view(np.uint32) if self.count is not None else None
         return h, a, c
+
+
+class BoxOverlaps:
+    """Results of RtContext.overlap_boxes_device: ids, int32 (n, max_ids, 2) rows of (inst, prim) in ascending order with (-1, -1) past a
+    box's candidates, and count, int32 (n,), the number of candidates (not capped at max_ids).  inst and prim are (n, max_ids) views.
+    What was not asked for is None."""
+
+    def __init__(self, ids, count):
+        self.ids, self.count = ids, count
+        self.inst = ids[..., 0] if ids is not None else None
+        self.prim = ids[..., 1] if ids is not None else None
+
+    def numpy(self):
+        """(counts as (n,) uint32, ids as (n, max_ids, 2) int32), None where not asked for; synchronises"""
+        return (self.count.cpu().numpy().view(np.uint32) if self.count is not None else None,
+                self.ids.cpu().numpy() if self.ids is not None else None)
 
 
 def check_builders(verts6, idx):

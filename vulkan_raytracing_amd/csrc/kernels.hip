@@ -2317,6 +2317,8 @@ void launch_resolve_points(const float4* sample_color, float4* out, uint32_t n_p
 
 #include "kernels_closest.inc"   // k_closest_point, k_closest_side: the nearest surface point of every query point (rt_closest_point_device)
 
+#include "kernels_overlap.inc"   // k_overlap_boxes: the triangles that touch every query box (rt_overlap_boxes_device)
+
 int tail_blocks_per_cu() {
   // the smallest over the instantiations: any of them may be the one in flight (counting; 4-ary records in the alt build)
   int n = 1 << 30, v = 0;

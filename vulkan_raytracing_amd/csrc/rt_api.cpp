@@ -2222,21 +2222,28 @@ int query_done(rt_ctx* c, hipStream_t s) {
   return RT_OK;
 }
 
-// The enqueue of every query (rt_intersect, rt_intersect_device, rt_intersect_device_flags, rt_closest_point*) on stream s, after the
+// The enqueue of every query (rt_intersect, rt_intersect_device, rt_intersect_device_flags, rt_closest_point*, rt_overlap_boxes*) on stream s, after the
 // caller's checks.  Walk::Flags: the flag-aware walk (MODE_QUERY_FLAGS) with the ray words `words` (or none) and the call's query word;
 // Walk::Plain: the plain walk with any_hit; Walk::Closest: the closest-point walk over n point records with the cull mask `query_word`
-// (its per-instance scales are made first, in the workspace).  counting: the instrumented Plain or Closest walk (its counts start from
-// a zeroed counter block).  d_attr (optional): the hit attributes.  t0 / t1 (optional): events recorded around the walk.
-enum class Walk { Plain, Flags, Closest };
+// (its per-instance scales are made first, in the workspace); Walk::Overlap: the box-overlap walk over n box records with the cull mask
+// `query_word`, any_hit standing for RT_OVERLAP_ANY, d_hits for the id rows of max_ids entries and d_counts for the counts (the same
+// scales first).  counting: the instrumented Plain, Closest or Overlap walk (its counts start from a zeroed counter block).  d_attr
+// (optional): the hit attributes.  t0 / t1 (optional): events recorded around the walk.
+enum class Walk { Plain, Flags, Closest, Overlap };
 int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, Walk walk, size_t n, const void* d_records, bool any_hit, bool counting,
-                  const void* words, uint32_t query_word, void* d_hits, void* d_attr, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
-  const bool flags = walk == Walk::Flags, closest = walk == Walk::Closest;
+                  const void* words, uint32_t query_word, void* d_hits, void* d_attr, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr,
+                  uint32_t max_ids = 0u, void* d_counts = nullptr) {
+  const bool flags = walk == Walk::Flags, closest = walk == Walk::Closest, overlap = walk == Walk::Overlap;
   const void* const d_rays8 = d_records;
   { int r = query_workspace(c, s); if (r) return r; }
   if (counting) HIP_TRY(c, hipMemsetAsync(c->d_q_counters, 0, CNT_WORDS * sizeof(uint32_t), s));
   const SceneDev sc = scene_dev(c);
   if (t0) HIP_TRY(c, hipEventRecord(t0, s));
-  if (closest) {
+  if (overlap) {
+    launch_closest_scale(sc, c->d_q_scale, s);
+    launch_overlap_boxes(sc, (const float4*)d_records, query_word, c->d_q_scale, any_hit, max_ids, d_hits, (uint32_t*)d_counts, (uint32_t)n, c->d_q_ovf,
+                         c->d_q_counters, counting, cfg, s);
+  } else if (closest) {
     launch_closest_scale(sc, c->d_q_scale, s);
     launch_closest_point(sc, (const float4*)d_rays8, query_word, c->d_q_scale, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, counting, cfg, s);
   } else if (flags) launch_query_flags(sc, (const float4*)d_rays8, (const uint32_t*)words, query_word, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, cfg, s);
@@ -2457,6 +2464,91 @@ int rt_closest_point(rt_ctx* c, size_t n, const float* points4, uint32_t cull_ma
   r = enqueue_query(c, c->stream, c->cfg, Walk::Closest, n, d_buf, false, counting != 0, nullptr, cull_mask, d_h, nullptr, e0, e1); if (r) return r;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipMemcpy(out, d_h, n * sizeof(HitRec), hipMemcpyDeviceToHost));
+  if (stats) {
+    if (counting) {
+      uint32_t cnt[CNT_TAILS];
+      HIP_TRY(c, hipMemcpy(cnt, c->d_q_counters, sizeof(cnt), hipMemcpyDeviceToHost));
+      memcpy(&stats->node_visits, &cnt[CNT_NODE_VISITS], 8);
+      memcpy(&stats->tri_tests, &cnt[CNT_TRI_TESTS], 8);
+    }
+    float ms = 0.f; hipEventElapsedTime(&ms, e0, e1);
+    stats->ms_trace_closest = ms;
+    stats->bvh_node_bytes = sizeof(BvhNodeQ); stats->bvh_tri_bytes = sizeof(TriPacket);
+  }
+  return RT_OK;
+}
+
+namespace {
+// the argument rules rt_overlap_boxes_device and rt_overlap_boxes share (pointers aside)
+int overlap_arguments(rt_ctx* c, const char* name, size_t n, uint32_t cull_mask, uint32_t flags, uint32_t max_ids, const void* ids, const void* counts) {
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": too many boxes for one call");
+  if (max_ids > 16u) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": max_ids must be 0..16");
+  if ((uint64_t)n * max_ids >= 0xFFFFFF00ull)
+    return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": n * max_ids must be below 0xFFFFFF00 (32-bit record indices)");
+  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": cull_mask is above 0xFF");
+  if ((flags & ~RT_OVERLAP_ANY) != 0u) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": unknown flag bits");
+  if ((flags & RT_OVERLAP_ANY) && max_ids != 0u) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": RT_OVERLAP_ANY needs max_ids 0");
+  if (!ids && !counts) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": neither ids nor counts given");
+  if (max_ids == 0u && (ids || !counts))
+    return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": max_ids 0 counts only: the ids must be NULL, the counts non-NULL");
+  if (max_ids != 0u && !ids) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null id pointer with max_ids above 0");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + " needs trace_variant 0");
+  return RT_OK;
+}
+}  // namespace
+
+// The triangles that touch every query box: the checks and ordering of a device query (rt_closest_point_device), then k_closest_scale and
+// k_overlap_boxes over the caller's records into the caller's rows and counts (enqueue_query).
+int rt_overlap_boxes_device(rt_ctx* c, size_t n, const void* d_boxes8, uint32_t cull_mask, uint32_t flags, uint32_t max_ids, void* d_ids, void* d_counts,
+                            void* hip_stream) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const char* const name = "rt_overlap_boxes_device";
+  { int q = overlap_arguments(c, name, n, cull_mask, flags, max_ids, d_ids, d_counts); if (q) return q; }
+  if (n) {
+    if (!d_boxes8) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null box pointer");
+    if (((uintptr_t)d_boxes8 & 15u) || ((uintptr_t)d_ids & 3u) || ((uintptr_t)d_counts & 3u))
+      return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": boxes must be 16-byte aligned, ids and counts 4-byte aligned");
+    { int q = check_device_pointers(c, name, "boxes, ids and counts", {d_boxes8, d_ids, d_counts}); if (q) return q; }
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  int r = ready_to_trace(c); if (r) return r;
+  if (n == 0) return RT_OK;
+  return enqueue_query(c, hip_stream ? (hipStream_t)hip_stream : c->stream, c->cfg, Walk::Overlap, n, d_boxes8, (flags & RT_OVERLAP_ANY) != 0u, false, nullptr,
+                       cull_mask, d_ids, nullptr, nullptr, nullptr, max_ids, d_counts);
+}
+
+// The blocking host form, as rt_closest_point is to rt_closest_point_device: the records copied in, the same enqueue on the context's
+// stream, the rows and counts copied out; with counting the instrumented walk, whose node visits and triangle tests come back in stats.
+int rt_overlap_boxes(rt_ctx* c, size_t n, const float* boxes8, uint32_t cull_mask, uint32_t flags, uint32_t max_ids, int32_t* ids, uint32_t* counts,
+                     int counting, rt_stats* stats) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const char* const name = "rt_overlap_boxes";
+  { int q = overlap_arguments(c, name, n, cull_mask, flags, max_ids, ids, counts); if (q) return q; }
+  if (!boxes8 && n) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null box pointer");
+  HIP_TRY(c, hipSetDevice(c->device));
+  { int q = quiesce(c); if (q) return q; }   // (as rt_intersect)
+  int r = ready_to_trace(c); if (r) return r;
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (n == 0) return RT_OK;
+  // one allocation: the boxes (32 B each), then the counts, then the rows
+  const size_t box_bytes = n * 8 * sizeof(float), count_bytes = n * sizeof(uint32_t), id_bytes = n * max_ids * 2 * sizeof(int32_t);
+  char* d_buf = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  struct Guard {   // every exit path below releases the temporaries
+    char*& buf; hipEvent_t &a, &b;
+    ~Guard() { if (buf) hipFree(buf); if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
+  } guard{d_buf, e0, e1};
+  HIP_TRY(c, hipMalloc((void**)&d_buf, box_bytes + count_bytes + id_bytes));
+  uint32_t* const d_c = counts ? (uint32_t*)(d_buf + box_bytes) : nullptr;
+  void* const d_i = max_ids ? (void*)(d_buf + box_bytes + count_bytes) : nullptr;
+  HIP_TRY(c, hipMemcpy(d_buf, boxes8, box_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipEventCreate(&e0)); HIP_TRY(c, hipEventCreate(&e1));
+  r = enqueue_query(c, c->stream, c->cfg, Walk::Overlap, n, d_buf, (flags & RT_OVERLAP_ANY) != 0u, counting != 0, nullptr, cull_mask, d_i, nullptr, e0, e1,
+                    max_ids, d_c);
+  if (r) return r;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (d_c) HIP_TRY(c, hipMemcpy(counts, d_c, count_bytes, hipMemcpyDeviceToHost));
+  if (d_i) HIP_TRY(c, hipMemcpy(ids, d_i, id_bytes, hipMemcpyDeviceToHost));
   if (stats) {
     if (counting) {
       uint32_t cnt[CNT_TAILS];

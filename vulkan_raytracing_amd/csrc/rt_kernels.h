@@ -199,6 +199,12 @@ void launch_closest_point(const SceneDev& sc, const float4* points, uint32_t cul
                           uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
 // the side of the reported triangle's plane every point lies on (0xFE front, 0xFF back, 0 miss) into word 7 of its rt_hit_attr (after launch_hit_attr)
 void launch_closest_side(const SceneDev& sc, const float4* points, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s);
+// rt_overlap_boxes_device: the triangles that touch every query box (32 bytes: lo.xyz, w3, hi.xyz, w7) among the instances the cull mask
+// admits (kernels_overlap.inc): the k smallest (inst, prim) of each box into ids[n * k] (8 bytes each; k == 0: none), their number into
+// counts[n] (or null: the walk prunes); any: counts of 0 or 1, a box ends at its first candidate.  inst_scale as for launch_closest_point
+// (launch_closest_scale fills it first); chunk cursor, counters (counting) and spill area as for launch_query_hits.
+void launch_overlap_boxes(const SceneDev& sc, const float4* boxes, uint32_t cull_mask, const float* inst_scale, bool any, uint32_t k, void* ids, uint32_t* counts,
+                          uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
 // rt_shade_rays_device: k_ray_ingest replaces k_raygen for the caller's n rays (32 bytes each, o.xyz, w3, d.xyz, tmax; sample id = record
 // index): sky colours of the rays that miss the TLAS and (0, 0, 0, 0) for invalid records into f.sample_color, the others into bounce queue 0
 // (workgroup b appends to shard b % 8: f.shard_cap >= 256 * ceil(ray_ingest_block_count(n) / 8)).  f.counters must be zero.

@@ -309,6 +309,9 @@ int rt_set_timing(rt_ctx* ctx, int enabled);
  * "jitter_table" 1 (default) = k_raygen reads the sample positions of a frame size from a table made once, 0 = evaluates the hash per sample and frame;
  * "tile_blobs" 1 = the nodes and triangle packets of a screen tile staged through LDS (k_blob / k_tile; default 0: measured slower;
  * librt_mi355x_alt.so only, like "shadow_beams").  In the product library the tile-blob fields of rt_stats are always 0.
+ * round 6: "fused_shade" 1 (default) = bounce 0 of a single frame with pixel beams is ONE launch: the kernel that walks a pixel's primary rays shades
+ * their hits (k_beam_shade; not in counting frames, frame batches or with "camera_records" 0), 0 = the walk and the shading are two launches with the
+ * hit records between them.  With timing on, rt_stats::ms_trace_closest of a fused frame covers walk + shading of bounce 0 and ms_shade the later bounces only.
  * Results do not depend on any of them. */
 int rt_set_param(rt_ctx* ctx, const char* name, int value);
 

@@ -1,7 +1,8 @@
 #!/bin/bash
 # Runs on the GPU box (through gpurun): kernel-trace stats and PMC traffic passes for bench.py.
 # Usage: tools/profile_gpu.sh <tag> [bench args]      -> gpurun_out/prof_<tag>/...  (summary.txt, latest_profile.json, bench_under_profiler.json)
-# The program follows `--` directly; counters are collected in their own passes with --kernel-trace only.
+# The program follows `--` directly; counters are collected in passes of their own with no tracing beside them.
+# RT_PROFILE_SKIP_L2=1 leaves out the (informational) L2 hit / miss pass.
 set -o pipefail
 TAG=${1:-r02}
 shift
@@ -9,12 +10,13 @@ OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 ARGS="--no-cpu-baseline --no-extras $@"
+PMC_STEPS=${RT_PROFILE_PMC_STEPS:-8}   # timed steps of the counter passes (the profiler serialises the kernels)
 # 1) per-kernel time: the bench line printed under the profiler is kept next to the trace it belongs to
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py $ARGS > $OUT/bench_under_profiler.json 2> $OUT/trace.log || { echo "kernel-trace failed"; tail -5 $OUT/trace.log; exit 1; }
-# 2) PMC passes (own runs, no tracing domains besides kernel-trace): FETCH_SIZE and WRITE_SIZE separately
-timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 bench.py $ARGS --steps 8 > $OUT/pmc_fetch.log 2>&1 || { echo "pmc fetch failed"; tail -5 $OUT/pmc_fetch.log; exit 1; }
-timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 bench.py $ARGS --steps 8 > $OUT/pmc_write.log 2>&1 || { echo "pmc write failed"; tail -5 $OUT/pmc_write.log; exit 1; }
-timeout -k 10 300 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d $OUT/pmc_l2 -- python3 bench.py $ARGS --steps 8 > $OUT/pmc_l2.log 2>&1 || echo "pmc l2 failed (non-fatal)"
+# 2) PMC passes (own runs, no tracing): FETCH_SIZE and WRITE_SIZE separately
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 bench.py $ARGS --steps $PMC_STEPS > $OUT/pmc_fetch.log 2>&1 || { echo "pmc fetch failed"; tail -5 $OUT/pmc_fetch.log; exit 1; }
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 bench.py $ARGS --steps $PMC_STEPS > $OUT/pmc_write.log 2>&1 || { echo "pmc write failed"; tail -5 $OUT/pmc_write.log; exit 1; }
+[ -n "$RT_PROFILE_SKIP_L2" ] || timeout -k 10 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d $OUT/pmc_l2 -- python3 bench.py $ARGS --steps $PMC_STEPS > $OUT/pmc_l2.log 2>&1 || echo "pmc l2 failed (non-fatal)"
 export RT_PROFILE_TAG=$(python3 -c "
 import json,sys,bench
 a=' $ARGS '.split()

@@ -79,7 +79,9 @@ def main():
     pm = res.get("pmc", {})
 
     def is_closest(k):
-        return "k_trace<0, false, false" in k or "k_trace4<0, false, false" in k or "k_packet<0, false, false" in k or "k_beam(" in k or k.endswith("k_beam")
+        # (k_beam_shade: the walk of the primary rays with the shading of their hits in the same launch)
+        return ("k_trace<0, false, false" in k or "k_trace4<0, false, false" in k or "k_packet<0, false, false" in k or "k_beam(" in k or k.endswith("k_beam")
+                or "k_beam_shade(" in k or k.endswith("k_beam_shade"))
 
     def is_shadow(k):
         return "k_trace<1, true, false" in k or "k_trace4<1, true, false" in k or "k_packet<1, true, false" in k or "k_beam_shadow" in k

@@ -1548,8 +1548,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_WAVES_PE
 template <int MODE, bool ANY, bool WIDE, bool ENTRY = false, bool FAR = true, bool CONT = false>
 __global__ __launch_bounds__(256) void k_trace_count(TraceArgs a) { trace_body<MODE, ANY, true, WIDE, ENTRY, FAR, CONT>(a); }
 
-#include "kernels_beam.inc"   // k_beam: the primary rays of a pixel walked together (and, in the alt library, k_beam_shadow: their shadow rays)
-
 #ifdef RT_ALT_KERNELS
 // alternatives measured slower, only in librt_mi355x_alt.so
 #include "kernels_alt.inc"    // k_packet, k_trace4
@@ -1585,6 +1583,192 @@ __device__ __forceinline__ Surface hit_surface(const SceneDev& sc, const Instanc
   return s;
 }
 
+// shade_slot, the per-slot part of shading (TILE, BATCH, RUNS: see shade_body): queue entry q of `shard` (in_range: it lies below the queue's tail) is shaded, its continuation ray goes to the
+// next bounce queue and its shadow ray to the shadow queue of the same shard.  WAVE-CONVERGENT: all 64 lanes of a wave call it together
+// (__ballot, wave_alloc), a lane without an entry with in_range false or, with REG, with HIT_DEAD.
+// REG: the hit of the entry comes from the caller's registers — inst_r, h_r = (t, u, v, primitive bits) — and not from f.hit_inst / f.hit_a
+// (k_beam_shade, kernels_beam.inc: the walk that found the hit shades it).  A: ShadeArgs, or any block with the members this reads (sc, f, u).
+// (REG: the colour Iamb * ka is made where it is stored.  Inside k_beam_shade the compiler otherwise builds the four-register constant once at
+// kernel entry and carries it across the walk, which has no register for it: 16 bytes of scratch per lane)
+template <bool PIN> __device__ __forceinline__ float4 ambient_default() {
+  float r = 0.08f;
+  if constexpr (PIN) asm volatile("" : "+v"(r));
+  return make_float4(r, 0.24f, r, 1.0f);
+}
+template <bool TILE, bool BATCH, bool RUNS, bool REG, typename A>
+__device__ __forceinline__ void shade_slot(const A& a, const int bounce, const uint32_t shard, const uint32_t q, const bool in_range, const int inst_r, const float4 h_r) {
+  const auto& f = a.f;
+  const auto& U = a.u;
+  const int cur = bounce & 1, nxt = cur ^ 1;
+  const uint32_t lane = threadIdx.x & 63u;
+  bool push_next = false, push_shadow = false, settled = false;   // settled: a shadow ray whose outcome cannot change the sample
+  F3 no = mk3(0, 0, 0), nd = mk3(0, 0, 1);
+  float sh_tmax = 0.f; F3 sh_c = mk3(0, 0, 0); float sh_w = 0.f;
+  uint32_t sh_ent = ENTRY_FROM_ROOT;
+  uint32_t sid = SID_DEAD;
+  int inst = HIT_DEAD;
+  if (in_range) { if constexpr (REG) inst = inst_r; else inst = ld_stream(&f.hit_inst[q]); }
+  if (inst != HIT_DEAD) {   // (a slot of the tile region without a ray: nothing to shade)
+    const float4 rd = ld_stream(&f.ray_d[cur][q]);
+    sid = __float_as_uint(rd.w);
+    const F3 d = mk3(rd.x, rd.y, rd.z);
+    if (inst < 0) {
+      // src/shader.rmiss:11 + src/shader.rgen:90-94
+      const F3 c = sample_sky(a.sc, mk3(d.x, d.y, -d.z));
+      st_stream(&f.sample_color[sid], make_float4(c.x, c.y, c.z, 1.0f));
+    } else {
+      // src/shader.rchit:50-96
+      float4 h = h_r;
+      if constexpr (!REG) h = ld_stream(&f.hit_a[q]);
+      const InstanceDev* I = a.sc.inst + inst;
+      const uint32_t prim = __float_as_uint(h.w);
+      const Surface S = hit_surface(a.sc, I, prim, h.y, h.z);
+      const F3 P = S.P;
+      F3 N = S.N;
+      const int objectIndex = I->custom_index;
+      // src/shader.rgen:96, generalised (row n4): a per-instance type replaces the two-way switch when the host set one,
+      // and an MTL material may fix its own type (illum)
+      uint32_t type = I->type != TYPE_BY_OBJECT_INDEX ? I->type : (objectIndex == 0 ? U.center_object_type : U.orbiting_object_type);
+      const MaterialDev* M = nullptr;
+      uint32_t mat = MATERIAL_NONE;
+      if (a.sc.n_materials != 0) {
+        mat = a.sc.prim_material[I->first_index / 3u + prim];
+        M = a.sc.materials + mat;
+        if (M->type != TYPE_BY_INSTANCE) type = M->type;
+      }
+      const bool last = (uint32_t)bounce >= U.max_bounce_count;
+      if (type == 0u) {
+        // src/shader.rgen:97-131
+        if (dot3(d, N) >= 0.0f) {
+          st_stream(&f.sample_color[sid], ambient_default<REG>());
+        } else {
+          no = fma3(0.01f, N, P);
+          F3 light = mk3(U.light_position[0], U.light_position[1], U.light_position[2]);
+          float Iv = U.light_intensity;
+          uint32_t fi = 0;   // frame batch: the light (position and intensity) of the sample's frame
+          if constexpr (BATCH) { fi = frame_of(sid, a.sc.batch_samples); light = mk3(a.bt.light[fi][0], a.bt.light[fi][1], a.bt.light[fi][2]); Iv = a.bt.light[fi][3]; }
+          const F3 toL = sub3(light, P);
+          const float dist = length3(toL);
+          const F3 L = mul3(toL, 1.0f / dist);
+          const F3 Hh = normalize3(add3(L, neg3(d)));
+          const float NdotL = dot3(N, L), NdotH = dot3(N, Hh);
+          const float dl = fmaxf(0.0f, NdotL);
+          const float sp = M ? pow_int(fmaxf(0.0f, NdotH), (uint32_t)M->ns) : pow100(fmaxf(0.0f, NdotH));
+          const uint32_t i = sid / (uint32_t)(f.rows * f.width) - fi * U.samples_per_pixel;   // sample index in its pixel
+          float w = 1.0f;
+          for (uint32_t k = 0; k < i; k++) w = w * 0.9f;
+          const F3 kd = M ? mk3(M->kd[0], M->kd[1], M->kd[2]) : mk3(0.2f, 1.0f, 0.2f);
+          const F3 ks = M ? mk3(M->ks[0], M->ks[1], M->ks[2]) : mk3(0.8f, 0.8f, 0.8f);
+          const F3 diff = mk3((Iv * kd.x) * dl, (Iv * kd.y) * dl, (Iv * kd.z) * dl);
+          const F3 spec = mk3((Iv * ks.x) * sp, (Iv * ks.y) * sp, (Iv * ks.z) * sp);
+          // tmpColor += pow(0.9, i) * (diffuse + specular) on top of Iamb*ka; the shadow kernel writes it if the light is visible
+          const F3 amb = ambient_of(a.sc, mat);
+          sh_c = fma3(w, add3(diff, spec), amb); sh_w = __uint_as_float(mat);
+          nd = L; sh_tmax = dist;
+          push_shadow = true;
+          // A surface that faces away from the light (and whose half vector does too) gets NOTHING from it: diffuse and specular are
+          // exactly 0 and tmpColor stays Iamb*ka whether the shadow ray finds the light or not (src/shader.rgen:113-128) — the sample's
+          // colour is the same bits either way, so the ray need not be walked.  It still counts as a shadow ray (the reference issues
+          // the traceRayEXT); rt_stats::rays_shadow_untraced says how many were settled here.
+          if (f.settle_dead_shadow_rays && __float_as_uint(sh_c.x) == __float_as_uint(amb.x) && __float_as_uint(sh_c.y) == __float_as_uint(amb.y) &&
+              __float_as_uint(sh_c.z) == __float_as_uint(amb.z)) {
+            st_stream(&f.sample_color[sid], make_float4(amb.x, amb.y, amb.z, 1.0f));
+            push_shadow = false; settled = true;
+          }
+          if (f.light_entry != nullptr) {
+            // which tile of the cube around the light does this ray belong to?  Seen from the light the ray's ORIGIN lies in
+            // direction v; the ray then runs to within 0.01 of the light (k_entry's beams are widened by that much).
+            const F3 v = sub3(no, light);
+            const float ax = __builtin_fabsf(v.x), ay = __builtin_fabsf(v.y), az = __builtin_fabsf(v.z);
+            const int axis = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
+            const float vc = axis == 0 ? v.x : (axis == 1 ? v.y : v.z), va = axis == 0 ? v.y : (axis == 1 ? v.z : v.x), vb = axis == 0 ? v.z : (axis == 1 ? v.x : v.y);
+            const float c = __builtin_fabsf(vc);
+            if (c > 0.0f) {
+              const float T8 = (float)(8 * f.light_tiles);
+              const float px = (va / c + 1.0f) * 0.5f * T8, py = (1.0f - vb / c) * 0.5f * T8;
+              const int tx = min(max((int)(px * 0.125f), 0), f.light_tiles - 1), ty = min(max((int)(py * 0.125f), 0), f.light_tiles - 1);
+              const int face = 2 * axis + (vc < 0.0f ? 1 : 0);
+              // a surface that faces away from the light is almost always shadowed by its own neighbourhood: start there
+              sh_ent = (uint32_t)((face * f.light_tiles + ty) * f.light_tiles + tx) | (NdotL < 0.0f ? ENTRY_REVERSE : 0u);
+            }
+          }
+        }
+      } else if (type == 1u) {
+        // src/shader.rgen:132-138
+        no = fma3(0.01f, N, P);
+        nd = reflect3(d, N);
+        push_next = true;
+      } else if (type == 2u) {
+        // src/shader.rgen:139-165
+        float ndoti = dot3(d, N);
+        const bool outwards = ndoti > 0.0f;
+        if (outwards) { N = neg3(N); ndoti = -ndoti; }
+        const float ratio = M ? (outwards ? M->ni : 1.0f / M->ni) : (outwards ? 1.52f : (1.0f / 1.52f));
+        const float k = 1.0f - (ratio * ratio) * (1.0f - ndoti * ndoti);
+        if (k < 0.0f) { nd = reflect3(d, N); no = fma3(0.01f, N, P); }
+        else {
+          const float c = __builtin_fmaf(ratio, ndoti, __builtin_sqrtf(k));
+          nd = normalize3(fma3(-c, N, mul3(d, ratio)));
+          no = fma3(-0.01f, N, P);
+        }
+        push_next = true;
+      } else {
+        // unknown type: the reference loop re-traces the unchanged ray until the bounce budget ends
+        if (bounce == 0 && f.pixel_runs) {   // (pixel runs: queue 0 has one origin per run, not per ray — the camera of the ray's frame)
+          no = mk3(U.position[0], U.position[1], U.position[2]);
+          if constexpr (BATCH) { const uint32_t fk = frame_of(sid, a.sc.batch_samples); no = mk3(a.bt.position[fk][0], a.bt.position[fk][1], a.bt.position[fk][2]); }
+        } else {
+          const float4 ro = ld_stream(&f.ray_o[cur][q]);
+          no = mk3(ro.x, ro.y, ro.z);
+        }
+        nd = d; push_next = true;
+      }
+      if (push_next && last) {
+        // loop of src/shader.rgen:84 ends: tmpColor keeps Iamb*ka
+        push_next = false;
+        st_stream(&f.sample_color[sid], ambient_default<REG>());
+      }
+    }
+  }
+  {
+    const uint64_t m_st = __ballot(settled);   // (statistics: non-returning atomics)
+    if (lane == 0 && m_st != 0ull) {
+      __hip_atomic_fetch_add(f.counters + cnt_tail(Q_SHADOW0, (int)shard), (uint32_t)__builtin_popcountll(m_st), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_add(f.counters + cnt_work(Q_DEAD, (int)shard), (uint32_t)__builtin_popcountll(m_st), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  // wavefront ballot compaction into the next-bounce queue / the shadow queue of the same shard
+  const uint32_t slot_n = wave_alloc(push_next, f.counters + cnt_tail(bounce + 1, (int)shard));
+  if (push_next) {
+    const uint32_t v = shard * f.shard_cap + slot_n;
+    st_stream(&f.ray_o[nxt][v], make_float4(no.x, no.y, no.z, 10000.0f));
+    st_stream(&f.ray_d[nxt][v], make_float4(nd.x, nd.y, nd.z, __uint_as_float(sid)));
+  }
+  if constexpr (RUNS) {
+    // shadow runs: no allocation — the ray's place is its primary ray's; every slot of the run says whether it holds one
+    if (in_range) {
+      if (push_shadow) {
+        st_stream(&f.sh_o[q], make_float4(no.x, no.y, no.z, sh_tmax));
+        st_stream(&f.sh_c[q], make_float4(sh_c.x, sh_c.y, sh_c.z, sh_w));
+        if (f.sh_e != nullptr) f.sh_e[q] = sh_ent;
+      }
+      st_stream(&f.sh_d[q], push_shadow ? make_float4(nd.x, nd.y, nd.z, __uint_as_float(sid)) : make_float4(0.f, 0.f, 0.f, __uint_as_float(SID_DEAD)));
+    }
+    const uint64_t m_sh = __ballot(push_shadow);   // (statistics: a non-returning atomic)
+    if (lane == 0 && m_sh != 0ull) __hip_atomic_fetch_add(f.counters + cnt_tail(Q_SHADOW0, (int)shard), (uint32_t)__builtin_popcountll(m_sh), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else {
+    const uint32_t slot_s = wave_alloc(push_shadow, f.counters + cnt_tail(Q_SHADOW, (int)shard));
+    if (push_shadow) {
+      const uint32_t v = f.sh_base + shard * f.shard_cap + slot_s;   // (sh_base: above the shadow runs of bounce 0, when the frame has them)
+      st_stream(&f.sh_o[v], make_float4(no.x, no.y, no.z, sh_tmax));
+      st_stream(&f.sh_d[v], make_float4(nd.x, nd.y, nd.z, __uint_as_float(sid)));
+      st_stream(&f.sh_c[v], make_float4(sh_c.x, sh_c.y, sh_c.z, sh_w));
+      if (f.sh_e != nullptr) f.sh_e[v] = sh_ent;
+    }
+  }
+}
+
+// The queue of one bounce, 64 entries per wave and trip, each through shade_slot.
 // TILE: bounce 0 of a frame with tile blobs — the hit records lie in two regions per shard (kernels_tile.inc; alt library only)
 // BATCH: the frame is one of a frame batch — the light is the one of the sample's frame (the single-frame instantiations are untouched)
 // RUNS: bounce 0 of a frame with shadow runs (k_beam_shadow, kernels_beam.inc; alt library only) — the shadow ray of a primary hit goes
@@ -1593,7 +1777,6 @@ template <bool TILE = false, bool BATCH = false, bool RUNS = false>
 __device__ __forceinline__ void shade_body(const ShadeArgs& a, const int bounce) {
   const FrameDev& f = a.f;
   const UniformsDev& U = a.u;
-  const int cur = bounce & 1, nxt = cur ^ 1;
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   // bounce 0 of a frame with tile blobs has its rays in two regions per shard: queue 0 at the bottom, the tile rays (walked by
   // k_trace_tile) at the top — a second pass with the other count and offset
@@ -1618,176 +1801,16 @@ __device__ __forceinline__ void shade_body(const ShadeArgs& a, const int bounce)
     for (int t = 0; t < N_SHARDS; t++) n = (shard == (uint32_t)t) ? cnt[t] : n;
     if (base >= n) continue;
     const uint32_t q = shard * f.shard_cap + ((TILE && pass) ? f.shard_cap - n : 0u) + base + lane;
-    bool push_next = false, push_shadow = false, settled = false;   // settled: a shadow ray whose outcome cannot change the sample
-    F3 no = mk3(0, 0, 0), nd = mk3(0, 0, 1);
-    float sh_tmax = 0.f; F3 sh_c = mk3(0, 0, 0); float sh_w = 0.f;
-    uint32_t sh_ent = ENTRY_FROM_ROOT;
-    uint32_t sid = SID_DEAD;
-    int inst = HIT_DEAD;
-    if (base + lane < n) inst = ld_stream(&f.hit_inst[q]);
-    if (inst != HIT_DEAD) {   // (a slot of the tile region without a ray: nothing to shade)
-      const float4 rd = ld_stream(&f.ray_d[cur][q]);
-      sid = __float_as_uint(rd.w);
-      const F3 d = mk3(rd.x, rd.y, rd.z);
-      if (inst < 0) {
-        // src/shader.rmiss:11 + src/shader.rgen:90-94
-        const F3 c = sample_sky(a.sc, mk3(d.x, d.y, -d.z));
-        st_stream(&f.sample_color[sid], make_float4(c.x, c.y, c.z, 1.0f));
-      } else {
-        // src/shader.rchit:50-96
-        const float4 h = ld_stream(&f.hit_a[q]);
-        const InstanceDev* I = a.sc.inst + inst;
-        const uint32_t prim = __float_as_uint(h.w);
-        const Surface S = hit_surface(a.sc, I, prim, h.y, h.z);
-        const F3 P = S.P;
-        F3 N = S.N;
-        const int objectIndex = I->custom_index;
-        // src/shader.rgen:96, generalised (row n4): a per-instance type replaces the two-way switch when the host set one,
-        // and an MTL material may fix its own type (illum)
-        uint32_t type = I->type != TYPE_BY_OBJECT_INDEX ? I->type : (objectIndex == 0 ? U.center_object_type : U.orbiting_object_type);
-        const MaterialDev* M = nullptr;
-        uint32_t mat = MATERIAL_NONE;
-        if (a.sc.n_materials != 0) {
-          mat = a.sc.prim_material[I->first_index / 3u + prim];
-          M = a.sc.materials + mat;
-          if (M->type != TYPE_BY_INSTANCE) type = M->type;
-        }
-        const bool last = (uint32_t)bounce >= U.max_bounce_count;
-        if (type == 0u) {
-          // src/shader.rgen:97-131
-          if (dot3(d, N) >= 0.0f) {
-            st_stream(&f.sample_color[sid], make_float4(0.08f, 0.24f, 0.08f, 1.0f));
-          } else {
-            no = fma3(0.01f, N, P);
-            F3 light = mk3(U.light_position[0], U.light_position[1], U.light_position[2]);
-            float Iv = U.light_intensity;
-            uint32_t fi = 0;   // frame batch: the light (position and intensity) of the sample's frame
-            if (BATCH) { fi = frame_of(sid, a.sc.batch_samples); light = mk3(a.bt.light[fi][0], a.bt.light[fi][1], a.bt.light[fi][2]); Iv = a.bt.light[fi][3]; }
-            const F3 toL = sub3(light, P);
-            const float dist = length3(toL);
-            const F3 L = mul3(toL, 1.0f / dist);
-            const F3 Hh = normalize3(add3(L, neg3(d)));
-            const float NdotL = dot3(N, L), NdotH = dot3(N, Hh);
-            const float dl = fmaxf(0.0f, NdotL);
-            const float sp = M ? pow_int(fmaxf(0.0f, NdotH), (uint32_t)M->ns) : pow100(fmaxf(0.0f, NdotH));
-            const uint32_t i = sid / (uint32_t)(f.rows * f.width) - fi * U.samples_per_pixel;   // sample index in its pixel
-            float w = 1.0f;
-            for (uint32_t k = 0; k < i; k++) w = w * 0.9f;
-            const F3 kd = M ? mk3(M->kd[0], M->kd[1], M->kd[2]) : mk3(0.2f, 1.0f, 0.2f);
-            const F3 ks = M ? mk3(M->ks[0], M->ks[1], M->ks[2]) : mk3(0.8f, 0.8f, 0.8f);
-            const F3 diff = mk3((Iv * kd.x) * dl, (Iv * kd.y) * dl, (Iv * kd.z) * dl);
-            const F3 spec = mk3((Iv * ks.x) * sp, (Iv * ks.y) * sp, (Iv * ks.z) * sp);
-            // tmpColor += pow(0.9, i) * (diffuse + specular) on top of Iamb*ka; the shadow kernel writes it if the light is visible
-            const F3 amb = ambient_of(a.sc, mat);
-            sh_c = fma3(w, add3(diff, spec), amb); sh_w = __uint_as_float(mat);
-            nd = L; sh_tmax = dist;
-            push_shadow = true;
-            // A surface that faces away from the light (and whose half vector does too) gets NOTHING from it: diffuse and specular are
-            // exactly 0 and tmpColor stays Iamb*ka whether the shadow ray finds the light or not (src/shader.rgen:113-128) — the sample's
-            // colour is the same bits either way, so the ray need not be walked.  It still counts as a shadow ray (the reference issues
-            // the traceRayEXT); rt_stats::rays_shadow_untraced says how many were settled here.
-            if (f.settle_dead_shadow_rays && __float_as_uint(sh_c.x) == __float_as_uint(amb.x) && __float_as_uint(sh_c.y) == __float_as_uint(amb.y) &&
-                __float_as_uint(sh_c.z) == __float_as_uint(amb.z)) {
-              st_stream(&f.sample_color[sid], make_float4(amb.x, amb.y, amb.z, 1.0f));
-              push_shadow = false; settled = true;
-            }
-            if (f.light_entry != nullptr) {
-              // which tile of the cube around the light does this ray belong to?  Seen from the light the ray's ORIGIN lies in
-              // direction v; the ray then runs to within 0.01 of the light (k_entry's beams are widened by that much).
-              const F3 v = sub3(no, light);
-              const float ax = __builtin_fabsf(v.x), ay = __builtin_fabsf(v.y), az = __builtin_fabsf(v.z);
-              const int axis = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
-              const float vc = axis == 0 ? v.x : (axis == 1 ? v.y : v.z), va = axis == 0 ? v.y : (axis == 1 ? v.z : v.x), vb = axis == 0 ? v.z : (axis == 1 ? v.x : v.y);
-              const float c = __builtin_fabsf(vc);
-              if (c > 0.0f) {
-                const float T8 = (float)(8 * f.light_tiles);
-                const float px = (va / c + 1.0f) * 0.5f * T8, py = (1.0f - vb / c) * 0.5f * T8;
-                const int tx = min(max((int)(px * 0.125f), 0), f.light_tiles - 1), ty = min(max((int)(py * 0.125f), 0), f.light_tiles - 1);
-                const int face = 2 * axis + (vc < 0.0f ? 1 : 0);
-                // a surface that faces away from the light is almost always shadowed by its own neighbourhood: start there
-                sh_ent = (uint32_t)((face * f.light_tiles + ty) * f.light_tiles + tx) | (NdotL < 0.0f ? ENTRY_REVERSE : 0u);
-              }
-            }
-          }
-        } else if (type == 1u) {
-          // src/shader.rgen:132-138
-          no = fma3(0.01f, N, P);
-          nd = reflect3(d, N);
-          push_next = true;
-        } else if (type == 2u) {
-          // src/shader.rgen:139-165
-          float ndoti = dot3(d, N);
-          const bool outwards = ndoti > 0.0f;
-          if (outwards) { N = neg3(N); ndoti = -ndoti; }
-          const float ratio = M ? (outwards ? M->ni : 1.0f / M->ni) : (outwards ? 1.52f : (1.0f / 1.52f));
-          const float k = 1.0f - (ratio * ratio) * (1.0f - ndoti * ndoti);
-          if (k < 0.0f) { nd = reflect3(d, N); no = fma3(0.01f, N, P); }
-          else {
-            const float c = __builtin_fmaf(ratio, ndoti, __builtin_sqrtf(k));
-            nd = normalize3(fma3(-c, N, mul3(d, ratio)));
-            no = fma3(-0.01f, N, P);
-          }
-          push_next = true;
-        } else {
-          // unknown type: the reference loop re-traces the unchanged ray until the bounce budget ends
-          if (bounce == 0 && f.pixel_runs) {   // (pixel runs: queue 0 has one origin per run, not per ray — the camera of the ray's frame)
-            no = mk3(U.position[0], U.position[1], U.position[2]);
-            if (BATCH) { const uint32_t fk = frame_of(sid, a.sc.batch_samples); no = mk3(a.bt.position[fk][0], a.bt.position[fk][1], a.bt.position[fk][2]); }
-          } else {
-            const float4 ro = ld_stream(&f.ray_o[cur][q]);
-            no = mk3(ro.x, ro.y, ro.z);
-          }
-          nd = d; push_next = true;
-        }
-        if (push_next && last) {
-          // loop of src/shader.rgen:84 ends: tmpColor keeps Iamb*ka
-          push_next = false;
-          st_stream(&f.sample_color[sid], make_float4(0.08f, 0.24f, 0.08f, 1.0f));
-        }
-      }
-    }
-    {
-      const uint64_t m_st = __ballot(settled);   // (statistics: non-returning atomics)
-      if (lane == 0 && m_st != 0ull) {
-        __hip_atomic_fetch_add(f.counters + cnt_tail(Q_SHADOW0, (int)shard), (uint32_t)__builtin_popcountll(m_st), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(f.counters + cnt_work(Q_DEAD, (int)shard), (uint32_t)__builtin_popcountll(m_st), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-    // wavefront ballot compaction into the next-bounce queue / the shadow queue of the same shard
-    const uint32_t slot_n = wave_alloc(push_next, f.counters + cnt_tail(bounce + 1, (int)shard));
-    if (push_next) {
-      const uint32_t v = shard * f.shard_cap + slot_n;
-      st_stream(&f.ray_o[nxt][v], make_float4(no.x, no.y, no.z, 10000.0f));
-      st_stream(&f.ray_d[nxt][v], make_float4(nd.x, nd.y, nd.z, __uint_as_float(sid)));
-    }
-    if (RUNS) {
-      // shadow runs: no allocation — the ray's place is its primary ray's; every slot of the run says whether it holds one
-      if (base + lane < n) {
-        if (push_shadow) {
-          st_stream(&f.sh_o[q], make_float4(no.x, no.y, no.z, sh_tmax));
-          st_stream(&f.sh_c[q], make_float4(sh_c.x, sh_c.y, sh_c.z, sh_w));
-          if (f.sh_e != nullptr) f.sh_e[q] = sh_ent;
-        }
-        st_stream(&f.sh_d[q], push_shadow ? make_float4(nd.x, nd.y, nd.z, __uint_as_float(sid)) : make_float4(0.f, 0.f, 0.f, __uint_as_float(SID_DEAD)));
-      }
-      const uint64_t m_sh = __ballot(push_shadow);   // (statistics: a non-returning atomic)
-      if (lane == 0 && m_sh != 0ull) __hip_atomic_fetch_add(f.counters + cnt_tail(Q_SHADOW0, (int)shard), (uint32_t)__builtin_popcountll(m_sh), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      const uint32_t slot_s = wave_alloc(push_shadow, f.counters + cnt_tail(Q_SHADOW, (int)shard));
-      if (push_shadow) {
-        const uint32_t v = f.sh_base + shard * f.shard_cap + slot_s;   // (sh_base: above the shadow runs of bounce 0, when the frame has them)
-        st_stream(&f.sh_o[v], make_float4(no.x, no.y, no.z, sh_tmax));
-        st_stream(&f.sh_d[v], make_float4(nd.x, nd.y, nd.z, __uint_as_float(sid)));
-        st_stream(&f.sh_c[v], make_float4(sh_c.x, sh_c.y, sh_c.z, sh_w));
-        if (f.sh_e != nullptr) f.sh_e[v] = sh_ent;
-      }
-    }
+    shade_slot<TILE, BATCH, RUNS, false>(a, bounce, shard, q, base + lane < n, HIT_DEAD, make_float4(0.f, 0.f, 0.f, 0.f));
   }
   }
 }
 
 template <bool TILE, bool BATCH, bool RUNS = false>
 __global__ __launch_bounds__(256) void k_shade(ShadeArgs a) { shade_body<TILE, BATCH, RUNS>(a, a.bounce); }
+
+// (behind shade_slot: k_beam_shade shades the hits of a run from its registers)
+#include "kernels_beam.inc"   // k_beam: the primary rays of a pixel walked together (and, in the alt library, k_beam_shadow: their shadow rays)
 
 // ------------------------------------------------------------------------------------------------
 // k_tail: bounces first..maxBounceCount of one frame in ONE launch.  After the first bounce a frame usually
@@ -2049,6 +2072,28 @@ void launch_trace_closest(const SceneDev& sc, const FrameDev& f, int bounce, boo
     return;
   }
   launch_trace<MODE_CLOSEST, false>(a, counting, cfg, s);
+}
+
+// bounce 0 of a frame with pixel runs in ONE launch: k_beam's walk, and the shading of its hits from the walk's registers (k_beam_shade).
+// The caller (rt_api enqueue_frame) has checked that the frame is a single one without counting, tile blobs or shadow runs.
+void launch_beam_shade(const SceneDev& sc, const FrameDev& f, const UniformsDev& u, const LaunchCfg& cfg, hipStream_t s) {
+  BeamShadeArgs a{};
+  a.sc = sc;
+  a.ray_o = f.ray_o[0]; a.ray_d = f.ray_d[0];
+  a.tails = f.counters + cnt_tail(0, 0); a.work = f.counters + cnt_work(0, 0);
+  a.shard_cap = f.shard_cap; a.ovf_stack = f.ovf_stack; a.counters = f.counters;
+  a.tmin = 0.001f;  // src/shader.rgen:87
+  a.entry = f.entry;   // (NULL: the walks start at the TLAS root)
+  a.next_o = f.ray_o[1]; a.next_d = f.ray_d[1];
+  a.sh_o = f.sh_o; a.sh_d = f.sh_d; a.sh_c = f.sh_c; a.sh_e = f.sh_e;
+  a.sample_color = f.sample_color;
+  a.light_entry = f.light_entry;
+  a.width = f.width; a.rows = f.rows; a.light_tiles = f.light_tiles; a.settle_dead_shadow_rays = f.settle_dead_shadow_rays;
+  for (int k = 0; k < 3; k++) { a.u.position[k] = u.position[k]; a.u.light_position[k] = u.light_position[k]; }
+  a.u.light_intensity = u.light_intensity;
+  a.u.max_bounce_count = u.max_bounce_count; a.u.samples_per_pixel = u.samples_per_pixel;
+  a.u.center_object_type = u.center_object_type; a.u.orbiting_object_type = u.orbiting_object_type;
+  hipLaunchKernelGGL(k_beam_shade, dim3(cfg.trace_blocks), dim3(256), 0, s, a, (uint32_t)f.pixel_runs);
 }
 
 void launch_entry(const SceneDev& sc, const EntryViews& a, hipStream_t s) {

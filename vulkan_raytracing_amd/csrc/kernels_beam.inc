@@ -1,4 +1,4 @@
-// kernels_beam.inc — closest-hit traversal of the PRIMARY rays, one walk per PIXEL (round 4; included by kernels.hip behind trace_body).
+// kernels_beam.inc — closest-hit traversal of the PRIMARY rays, one walk per PIXEL (round 4; included by kernels.hip behind trace_body and shade_slot).
 //
 // The (up to four) samples of a pixel leave the same point — the camera — in directions a fraction of a pixel apart
 // (src/shader.rgen:62-79), and walk almost the same nodes one after the other in the one-lane-per-ray kernel.  Here one lane walks the
@@ -55,8 +55,54 @@ __device__ __forceinline__ void beam_axis(float lo, float hi, float da, float t_
 #define RT_BEAM_UNROLL RT_INTERIOR_UNROLL     /* visits per trip of that loop */
 #endif
 
-template <bool COUNT>
-__device__ __forceinline__ void beam_body(const TraceArgs& a, const uint32_t run) {
+// k_beam_shade (round 6): the walk that found a pixel's hits shades them.  k_beam ends a run with the hit of every sample in registers and LDS
+// (bt0..bt3, s_best), stores them as hit_a / hit_inst for every slot of queue 0, and a second launch (k_shade) reads them back.  Here the
+// epilogue of a run hands them to shade_slot (kernels.hip: the one copy of the shading arithmetic) instead: no hit record is written or
+// read, and bounce 0 has no k_shade launch.  The host launches it in single frames without counting, tile blobs or shadow runs.
+// The argument block carries what the walk and bounce-0 shading read, and nothing else (no BatchTab, one SceneDev): what a kernel does not
+// name it does not load, and every word it holds across the interior loop is a scalar register the walk cannot use.
+struct BeamShadeUniforms {            // of UniformsDev, under the same names
+  float position[3], light_position[3], light_intensity;
+  uint32_t max_bounce_count, samples_per_pixel, center_object_type, orbiting_object_type;
+};
+struct BeamShadeArgs {
+  SceneDev sc;
+  const float4* ray_o;                // bounce queue 0 (TraceArgs' names: beam_body reads either block)
+  const float4* ray_d;
+  const uint32_t* tails;
+  uint32_t* work;
+  uint32_t shard_cap;
+  int32_t* ovf_stack;
+  uint32_t* counters;
+  float tmin;
+  const EntryRec* entry;
+  float4* next_o;                     // bounce queue 1
+  float4* next_d;
+  float4* sh_o;                       // the shadow queue, FrameDev's names
+  float4* sh_d;
+  float4* sh_c;
+  uint32_t* sh_e;
+  float4* sample_color;
+  const EntryRec* light_entry;
+  int width, rows, light_tiles, settle_dead_shadow_rays;
+  BeamShadeUniforms u;
+};
+// what shade_slot reads of FrameDev at bounce 0 of such a frame, under the same names; made from the argument block inside the kernel
+struct BeamShadeFrame {
+  float4* ray_o[2]; float4* ray_d[2];
+  float4* sh_o; float4* sh_d; float4* sh_c; uint32_t* sh_e;
+  float4* sample_color;
+  uint32_t* counters;
+  const EntryRec* light_entry;
+  uint32_t shard_cap;
+  int width, rows, light_tiles, settle_dead_shadow_rays;
+  static constexpr int pixel_runs = 64;       // such a frame has pixel runs (one origin per run: the camera) and no shadow runs
+  static constexpr uint32_t sh_base = 0u;
+};
+struct BeamShadeView { const SceneDev& sc; const BeamShadeFrame& f; const BeamShadeUniforms& u; };
+
+template <bool COUNT, bool SHADE = false, typename Args = TraceArgs>
+__device__ __forceinline__ void beam_body(const Args& a, const uint32_t run) {
   __shared__ int s_stack[4][STACK2_LDS + 1][64];
   __shared__ float s_best[4][16][64];    // ray j of lane l: rows 4 j .. 4 j + 3 = u, v, primitive, instance of its closest hit so far (t stays in a register)
   __shared__ float4 s_inst[LDS_INSTANCES ? LDS_INSTANCES : 1][5];
@@ -298,6 +344,26 @@ __device__ __forceinline__ void beam_body(const TraceArgs& a, const uint32_t run
         atomicAdd(reinterpret_cast<unsigned long long*>(a.counters + CNT_TILE_DIAG + 4), 1ull);
       }
     }
+    if constexpr (SHADE) {
+      // ---- the pixel's samples shaded where they lie: sample j of the run's 64 pixels is one convergent call of all 64 lanes
+      // (a slot without a ray: HIT_DEAD, as k_beam would have stored it)
+      const uint32_t run_shard = (uint32_t)__builtin_amdgcn_readfirstlane((int)shard);
+      // What shading reads of the argument block is read HERE, per run, through the kernarg pointer: named as `a.x` the compiler loads every
+      // word at kernel entry and carries it across the walk in scalar registers the walk needs (68 of them spilled to lanes of two more
+      // VGPRs); the empty asm keeps the loads below it.  A run's scalar loads hit the constant cache.
+      const BeamShadeArgs* ka = (const BeamShadeArgs*)__builtin_amdgcn_kernarg_segment_ptr();   // (the block is the kernel's first argument: offset 0)
+      asm volatile("" : "+s"(ka));
+      const BeamShadeFrame sf{{const_cast<float4*>(ka->ray_o), ka->next_o}, {const_cast<float4*>(ka->ray_d), ka->next_d}, ka->sh_o, ka->sh_d, ka->sh_c, ka->sh_e, ka->sample_color,
+                              ka->counters, ka->light_entry, ka->shard_cap, ka->width, ka->rows, ka->light_tiles, ka->settle_dead_shadow_rays};
+      const BeamShadeView sv{ka->sc, sf, ka->u};
+#pragma nounroll
+      for (uint32_t j = 0; j < S; j++) {
+        const float tj = j == 0u ? bt0 : (j == 1u ? bt1 : (j == 2u ? bt2 : bt3));
+        const float* const b = bst + 256u * j;   // rows 4 j .. 4 j + 3
+        const int ij = (alive >> j) & 1u ? __float_as_int(b[192]) : HIT_DEAD;
+        shade_slot<false, false, false, true>(sv, 0, run_shard, v0 + 64u * j, true, ij, make_float4(tj, b[0], b[64], b[128]));
+      }
+    } else {
     // ---- the hit records of the pixel's samples (a slot without a ray: HIT_DEAD)
 #define RT_BEAM_OUT(j) if (j < S) { \
       const uint32_t v = v0 + 64u * j; \
@@ -307,6 +373,7 @@ __device__ __forceinline__ void beam_body(const TraceArgs& a, const uint32_t run
       } else st_stream(&a.hit_inst[v], HIT_DEAD); }
     RT_BEAM_EACH(RT_BEAM_OUT)
 #undef RT_BEAM_OUT
+    }
   }
   if (COUNT) {
     for (int off = 32; off > 0; off >>= 1) {
@@ -328,6 +395,7 @@ __device__ __forceinline__ void beam_body(const TraceArgs& a, const uint32_t run
 #endif
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_BEAM_WAVES, RT_BEAM_WAVES))) void k_beam(TraceArgs a, uint32_t run) { beam_body<false>(a, run); }
 __global__ __launch_bounds__(256) void k_beam_count(TraceArgs a, uint32_t run) { beam_body<true>(a, run); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_BEAM_WAVES, RT_BEAM_WAVES))) void k_beam_shade(BeamShadeArgs a, uint32_t run) { beam_body<false, true>(a, run); }
 
 #ifdef RT_ALT_KERNELS   // k_beam_shadow measured slower: only in librt_mi355x_alt.so
 // ------------------------------------------------------------------------------------------------

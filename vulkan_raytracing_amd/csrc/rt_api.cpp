@@ -241,6 +241,7 @@ struct rt_ctx {
                         // at very different times — the first hit ends a ray — so most lanes of a wave wait: profiles/r04_experiments.txt); rt_set_param("shadow_beams", 1),
                         // alt library only (alt_kernels_built())
   bool sh_double = false;   // the shadow arrays of this context's frame have room for the shadow runs beside the compact queue (shadow_beams only)
+  int fused_shade = 1;  // bounce 0 of a frame with pixel beams in one launch: k_beam_shade shades the hits of its walk from registers; result-identical; rt_set_param("fused_shade", 0) restores k_beam + k_shade
   int pixel_beams = 1;  // the primary rays of a pixel walked together (kernels_beam.inc): result-identical; rt_set_param("pixel_beams", 0) restores one walk per ray
   // tile blobs (rt_device.h; kernels_tile.inc): 1 = k_blob writes, for every tile whose record names an instance, the nodes and triangle packets the tile's beam
   // can touch as one blob, and k_tile walks the tile's primary rays through it in LDS (result-identical; needs entry_points; alt library only: alt_kernels_built())
@@ -1221,6 +1222,9 @@ int enqueue_frame(rt_ctx* c, int W, int H, int band_rows, int shard, int n_shard
     else if (tail_ok && c->tail_mode == 1)
       for (uint32_t b = 1; b <= u.max_bounce_count && b < (uint32_t)CNT_MAX_BOUNCES; b++)
         if (((volatile uint32_t*)c->h_hint)[b] <= TAIL_MAX_RAYS) { tail_start = b; break; }
+    // bounce 0 of a plain single frame with pixel beams: walk and shading in one launch (k_beam_shade), no hit records in between
+    // ("camera_records" 0, like the other switched-off paths, keeps the two launches; a scene too large for records does not)
+    const bool fused0 = c->fused_shade && beam_on && c->camera_records && K == 1 && !c->counting && !f.tile_blob && !f.shadow_runs && tail_start != 0u;
     for (uint32_t b = 0; b <= u.max_bounce_count; b++) {
       if (b == tail_start) {
         // every later bounce in one launch (src/shader.rgen:84 loop), leaving as soon as a queue is empty
@@ -1245,8 +1249,9 @@ int enqueue_frame(rt_ctx* c, int W, int H, int band_rows, int shard, int n_shard
       { LaunchCfg cc = cfg; if (b == 0 && cap_closest > 0) cc.trace_blocks = std::min(cfg.trace_blocks, c->n_cu * cap_closest);
         Span sp(c, CAT_TRACE, s);
         if (b == 0 && f.tile_blob) launch_tile(sc, f, u, c->counting, s);   // the tiles with a blob: their rays generated and walked in LDS (it hands a few on to queue 0)
-        launch_trace_closest(sc, f, (int)b, c->counting, cc, s); }
-      { Span sp(c, CAT_SHADE, s); launch_shade(sc, f, u, bt, (int)b, cfg, s); }
+        if (b == 0 && fused0) launch_beam_shade(sc, f, u, cc, s);
+        else launch_trace_closest(sc, f, (int)b, c->counting, cc, s); }
+      if (!(b == 0 && fused0)) { Span sp(c, CAT_SHADE, s); launch_shade(sc, f, u, bt, (int)b, cfg, s); }
       if (b >= 7 && (b & 3) == 3 && b < u.max_bounce_count) {
         // deep bounce budgets (the reference default is 63): stop launching once every path has ended
         uint32_t tails[N_SHARDS * CNT_STRIDE];
@@ -1925,6 +1930,7 @@ int rt_set_param(rt_ctx* c, const char* name, int value) {
     c->tile_blobs = value != 0; return RT_OK;
   }
   if (k == "pixel_beams") { c->pixel_beams = value != 0; return RT_OK; }
+  if (k == "fused_shade") { c->fused_shade = value != 0; return RT_OK; }
   if (k == "camera_records") { c->camera_records = value != 0; return RT_OK; }
   if (k == "dead_shadow_rays") { c->dead_shadow_rays = value != 0; return RT_OK; }
   if (k == "shadow_beams") {

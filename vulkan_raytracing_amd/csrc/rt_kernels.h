@@ -154,6 +154,9 @@ size_t jitter_table_elems(int width, int rows, uint32_t spp);
 void launch_jitter_table(const FrameDev& f, uint32_t spp, float2* table, hipStream_t s);
 // bounce 0 of a frame with entry lists (f.entry) starts every ray at its tile's record
 void launch_trace_closest(const SceneDev& sc, const FrameDev& f, int bounce, bool counting, const LaunchCfg& cfg, hipStream_t s);
+// bounce 0 of a single frame with pixel runs (f.pixel_runs) and neither counting, tile blobs nor shadow runs: the walk of the primary rays
+// and the shading of their hits in one launch (k_beam_shade) — launch_trace_closest + launch_shade of bounce 0, without the hit records
+void launch_beam_shade(const SceneDev& sc, const FrameDev& f, const UniformsDev& u, const LaunchCfg& cfg, hipStream_t s);
 // one lane per tile of the shard: the record of every tile the coverage mask marks
 void launch_entry(const SceneDev& sc, const EntryViews& a, hipStream_t s);
 // tile blobs and shadow beams (alt library only; empty in the product library, whose frames never have tile_blob / shadow_runs):

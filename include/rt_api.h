@@ -484,6 +484,45 @@ int rt_overlap_boxes_device(rt_ctx* ctx, size_t n, const void* d_boxes8, uint32_
 int rt_overlap_boxes(rt_ctx* ctx, size_t n, const float* boxes8_host, uint32_t cull_mask, uint32_t flags,
                      uint32_t max_ids, int32_t* ids_host, uint32_t* counts_host, int counting, rt_stats* stats);
 
+/* Sphere sweeps: for every record the first contact of a sphere that moves along a direction (PhysX's sweep query), for continuous
+ * collision detection, character controllers, camera booms, clearance along a path and thick-beam sensors.
+ * Sweeps: d_sweeps8 holds n records of 32 B (o.x, o.y, o.z, r, d.x, d.y, d.z, tmax), 16-B aligned, memory of ctx's GPU: a ray's layout
+ * with the radius where tmin sits.  The sphere of radius r >= 0 has its centre at p(t) = o + t d for t in [0, tmax]; d need not be
+ * normalised, t is in units of d, tmax = +inf is allowed.
+ * Candidates: every triangle of every instance with (mask & cull_mask) != 0.  Instance flags, opacity and facing play no part.
+ * d_hits: n rt_hit, 4-B aligned.  Record i is the candidate with the smallest key (t, inst, prim) among those whose canonical contact
+ * time below exists and is <= tmax: t the first time the sphere touches the triangle, u and v the contact point's barycentrics of
+ * vertices B and C (a hit's convention), prim and inst the triangle.  A sphere that touches a triangle at t = 0 already reports t = 0
+ * with the closest-point barycentrics of o on that triangle.  No contact: the miss record t = tmax as given, u = v = 0,
+ * prim = inst = -1; the same for a non-finite component of o, d or r, r < 0, d = 0, tmax < 0 or a NaN tmax.  t is never NaN unless tmax
+ * was.
+ * Canonical contact time (DESIGN.md §5 "Sphere sweeps" has every operation in order): binary32, world space, nothing fused except
+ * inside dot3 / cross3 / xform_point / xform_vec.  A = xform_point(I.o2w, v0), ab = xform_vec(I.o2w, e1),
+ * ac = xform_vec(I.o2w, e2) (non-finite: never a candidate); rt_closest_point_device's sequence for p = o decides the initial overlap
+ * (d2 <= r * r: t = 0); otherwise the path is re-centred at its point nearest to A (t_c clamped to [0, tmax]) and the features of
+ * Ericson, Real-Time Collision Detection §5.5.6 are tested from there: the face (plane contact, accepted when its barycentrics lie in
+ * the triangle and the point they stand for is the contact point within 2^-10 of the longer edge, dot3(c, c) <= 2^-20 max(d00, d11):
+ * a needle or zero-area triangle whose 2 x 2 system is rounding noise is answered by its edges and vertices), else the entering roots of the edge cylinders AB, AC, BC and the vertex spheres A, B, C, the smallest root in
+ * [0, tmax], the earlier feature on a tie.  It depends on the record, the instance record and the packet only, never on the tree.
+ * r = 0 is valid and answered by this arithmetic; bitwise equality with rt_intersect_device is not promised.  The edge and vertex
+ * quadratics lose about 2^-24 (E + r)^2 / r of the radius for a triangle with longest edge E.
+ * d_attr (optional): n rt_hit_attr, 16-B aligned: what rt_closest_point_device gives for (inst, prim, u, v) — P the contact point, N the
+ * interpolated shading normal, objectIndex; a miss zeros and -1.  `reserved` is the side of the triangle's plane the centre
+ * p(t) = o + t d lies on, by rt_closest_point_device's rule (FLIP_FACING included), 0 on a miss.  The contact normal is (p(t) - P) / r;
+ * the caller forms it.
+ * Stream ordering without host synchronisation, the TLAS and scene of the call, the query workspace, queries and shading calls of one
+ * context one after another, RT_ERR_NOT_READY and n == 0 (nothing is enqueued): as for rt_closest_point_device.
+ * RT_ERR_INVALID_ARGUMENT: a NULL or misaligned pointer, a pointer that is not memory of ctx's GPU, n >= 0xFFFFFF00, cull_mask > 0xFF,
+ * trace_variant != 0. */
+int rt_sweep_spheres_device(rt_ctx* ctx, size_t n, const void* d_sweeps8, uint32_t cull_mask,
+                            void* d_hits, void* d_attr, void* hip_stream);
+/* The blocking host form, as rt_closest_point is to rt_closest_point_device: the records are copied to the device, swept on the
+ * context's stream (same workspace and ordering) and the hits copied back.  counting != 0 runs the instrumented walk and fills
+ * stats->node_visits and stats->tri_tests; stats may be NULL.  As rt_overlap_boxes does, the call also reports the walk's device time in
+ * stats->ms_trace_closest and the node and packet sizes in stats->bvh_node_bytes / bvh_tri_bytes; every other field is 0. */
+int rt_sweep_spheres(rt_ctx* ctx, size_t n, const float* sweeps8_host, uint32_t cull_mask,
+                     rt_hit* out_host, int counting, rt_stats* stats);
+
 /* Custom ray generation: the frame's shading of the caller's primary rays.  The caller's rays replace the pinhole camera of
  * src/shader.rgen:62-82; everything after it — the bounce loop of src/shader.rgen:84-177 with closest hit, miss, reflection, refraction and
  * shadow rays — is the frame's, and the colours are those a frame would compute for the same rays.

@@ -61,7 +61,7 @@ OVERLAP_ANY = 0x1   # rt_overlap_boxes_device: occupancy (counts of 0 or 1)
 
 EXPORTS = ["rt_create", "rt_create_frame_slot", "rt_destroy", "rt_upload_geometry", "rt_build_blas", "rt_set_instances", "rt_set_instances_device", "rt_refit_blas_device", "rt_set_materials", "rt_set_instance_types", "rt_set_uniforms", "rt_set_skybox",
            "rt_trace", "rt_trace_async", "rt_trace_wait", "rt_trace_shard", "rt_set_batch", "rt_trace_shard_batch", "rt_assemble_shards", "rt_shard_rows", "rt_synchronize", "rt_get_stats", "rt_set_timing", "rt_intersect",
-           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
+           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_sweep_spheres_device", "rt_sweep_spheres", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
 
 _LIBS = {}
 
@@ -106,6 +106,8 @@ def lib(variant=None):
         L.rt_intersect_device_hits.argtypes = [vp, C.c_size_t, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
         L.rt_closest_point_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, vp, vp]
         L.rt_closest_point.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, C.c_int, C.POINTER(RtStats)]
+        L.rt_sweep_spheres_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, vp, vp]
+        L.rt_sweep_spheres.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, C.c_int, C.POINTER(RtStats)]
         L.rt_overlap_boxes_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]
         L.rt_overlap_boxes.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_int, C.POINTER(RtStats)]
         L.rt_shade_rays_device.argtypes = [vp, C.c_size_t, C.c_uint32, vp, vp, vp, vp]
@@ -383,6 +385,28 @@ class RtContext:
         out = np.zeros(len(points4), HIT_DTYPE)
         st = RtStats()
         self._chk(self.L.rt_closest_point(self.h, len(points4), _p(points4), int(cull_mask) & 0xFFFFFFFF, _p(out), int(counting), C.byref(st)), "rt_closest_point")
+        return out, st
+
+    def sweep_spheres_device(self, sweeps, cull_mask=0xFF, attributes=False, stream=None, out=None):
+        """rt_sweep_spheres_device: the first contact of every moving sphere.  `sweeps` is a contiguous float32 torch tensor (n, 8) on this
+        context's GPU (o.xyz, r, d.xyz, tmax per row: the sphere of radius r with its centre at o + t d, t in [0, tmax], inf allowed),
+        read in the order of `stream` like intersect_device's rays.  Returns a RayQuery: t the contact time in units of d, u / v the
+        contact point's barycentrics, prim / inst the triangle (a miss: t = tmax, prim = inst = -1); with attributes=True position is
+        the contact point, normal the shading normal there and hit_kind the side of the triangle's plane the centre lies on at the
+        contact.  out = (hits, attr) reuses buffers.  See include/rt_api.h."""
+        def call(run, hits, attr):
+            return self.L.rt_sweep_spheres_device(self.h, sweeps.shape[0], C.c_void_p(sweeps.data_ptr()), int(cull_mask) & 0xFFFFFFFF, C.c_void_p(hits.data_ptr()),
+                                                  C.c_void_p(attr.data_ptr()) if attr is not None else None, C.c_void_p(run.cuda_stream))
+        self._check_rays(sweeps, "sweep_spheres_device", 8, "sweep")
+        hits, attr = self._device_query(sweeps, attributes, stream, out, (), call, "rt_sweep_spheres_device")
+        return RayQuery(hits, attr, hit_kind=True)
+
+    def sweep_spheres(self, sweeps8, cull_mask=0xFF, counting=False):
+        """rt_sweep_spheres: the blocking host form -> (HIT_DTYPE records, RtStats; with counting its node_visits / tri_tests are filled)"""
+        sweeps8 = np.ascontiguousarray(sweeps8, np.float32).reshape(-1, 8)
+        out = np.zeros(len(sweeps8), HIT_DTYPE)
+        st = RtStats()
+        self._chk(self.L.rt_sweep_spheres(self.h, len(sweeps8), _p(sweeps8), int(cull_mask) & 0xFFFFFFFF, _p(out), int(counting), C.byref(st)), "rt_sweep_spheres")
         return out, st
 
     def overlap_boxes_device(self, boxes, max_ids=0, cull_mask=0xFF, any=False, counts=True, stream=None, out=None):

@@ -2364,6 +2364,8 @@ void launch_resolve_points(const float4* sample_color, float4* out, uint32_t n_p
 
 #include "kernels_overlap.inc"   // k_overlap_boxes: the triangles that touch every query box (rt_overlap_boxes_device)
 
+#include "kernels_sweep.inc"   // k_sweep_spheres, k_sweep_side: the first contact of every moving sphere (rt_sweep_spheres_device)
+
 int tail_blocks_per_cu() {
   // the smallest over the instantiations: any of them may be the one in flight (counting; 4-ary records in the alt build)
   int n = 1 << 30, v = 0;

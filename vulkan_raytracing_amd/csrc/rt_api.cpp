@@ -2228,18 +2228,19 @@ int query_done(rt_ctx* c, hipStream_t s) {
   return RT_OK;
 }
 
-// The enqueue of every query (rt_intersect, rt_intersect_device, rt_intersect_device_flags, rt_closest_point*, rt_overlap_boxes*) on stream s, after the
+// The enqueue of every query (rt_intersect, rt_intersect_device, rt_intersect_device_flags, rt_closest_point*, rt_overlap_boxes*, rt_sweep_spheres*) on stream s, after the
 // caller's checks.  Walk::Flags: the flag-aware walk (MODE_QUERY_FLAGS) with the ray words `words` (or none) and the call's query word;
 // Walk::Plain: the plain walk with any_hit; Walk::Closest: the closest-point walk over n point records with the cull mask `query_word`
 // (its per-instance scales are made first, in the workspace); Walk::Overlap: the box-overlap walk over n box records with the cull mask
 // `query_word`, any_hit standing for RT_OVERLAP_ANY, d_hits for the id rows of max_ids entries and d_counts for the counts (the same
-// scales first).  counting: the instrumented Plain, Closest or Overlap walk (its counts start from a zeroed counter block).  d_attr
+// scales first); Walk::Sweep: the sphere-sweep walk over n sweep records with the cull mask `query_word` (the same scales first).
+// counting: the instrumented Plain, Closest, Overlap or Sweep walk (its counts start from a zeroed counter block).  d_attr
 // (optional): the hit attributes.  t0 / t1 (optional): events recorded around the walk.
-enum class Walk { Plain, Flags, Closest, Overlap };
+enum class Walk { Plain, Flags, Closest, Overlap, Sweep };
 int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, Walk walk, size_t n, const void* d_records, bool any_hit, bool counting,
                   const void* words, uint32_t query_word, void* d_hits, void* d_attr, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr,
                   uint32_t max_ids = 0u, void* d_counts = nullptr) {
-  const bool flags = walk == Walk::Flags, closest = walk == Walk::Closest, overlap = walk == Walk::Overlap;
+  const bool flags = walk == Walk::Flags, closest = walk == Walk::Closest, overlap = walk == Walk::Overlap, sweep = walk == Walk::Sweep;
   const void* const d_rays8 = d_records;
   { int r = query_workspace(c, s); if (r) return r; }
   if (counting) HIP_TRY(c, hipMemsetAsync(c->d_q_counters, 0, CNT_WORDS * sizeof(uint32_t), s));
@@ -2249,6 +2250,9 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, Walk walk, siz
     launch_closest_scale(sc, c->d_q_scale, s);
     launch_overlap_boxes(sc, (const float4*)d_records, query_word, c->d_q_scale, any_hit, max_ids, d_hits, (uint32_t*)d_counts, (uint32_t)n, c->d_q_ovf,
                          c->d_q_counters, counting, cfg, s);
+  } else if (sweep) {
+    launch_closest_scale(sc, c->d_q_scale, s);
+    launch_sweep_spheres(sc, (const float4*)d_records, query_word, c->d_q_scale, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, counting, cfg, s);
   } else if (closest) {
     launch_closest_scale(sc, c->d_q_scale, s);
     launch_closest_point(sc, (const float4*)d_rays8, query_word, c->d_q_scale, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, counting, cfg, s);
@@ -2258,6 +2262,7 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, Walk walk, siz
   if (d_attr) launch_hit_attr(sc, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
   if (d_attr && flags) launch_hit_kind(sc, (const float4*)d_rays8, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
   if (d_attr && closest) launch_closest_side(sc, (const float4*)d_rays8, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
+  if (d_attr && sweep) launch_sweep_side(sc, (const float4*)d_records, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
   return query_done(c, s);
 }
 }  // namespace
@@ -2555,6 +2560,69 @@ int rt_overlap_boxes(rt_ctx* c, size_t n, const float* boxes8, uint32_t cull_mas
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (d_c) HIP_TRY(c, hipMemcpy(counts, d_c, count_bytes, hipMemcpyDeviceToHost));
   if (d_i) HIP_TRY(c, hipMemcpy(ids, d_i, id_bytes, hipMemcpyDeviceToHost));
+  if (stats) {
+    if (counting) {
+      uint32_t cnt[CNT_TAILS];
+      HIP_TRY(c, hipMemcpy(cnt, c->d_q_counters, sizeof(cnt), hipMemcpyDeviceToHost));
+      memcpy(&stats->node_visits, &cnt[CNT_NODE_VISITS], 8);
+      memcpy(&stats->tri_tests, &cnt[CNT_TRI_TESTS], 8);
+    }
+    float ms = 0.f; hipEventElapsedTime(&ms, e0, e1);
+    stats->ms_trace_closest = ms;
+    stats->bvh_node_bytes = sizeof(BvhNodeQ); stats->bvh_tri_bytes = sizeof(TriPacket);
+  }
+  return RT_OK;
+}
+
+// The first contact of every moving sphere: the checks and ordering of a device query (rt_closest_point_device), then k_closest_scale and
+// k_sweep_spheres over the caller's records (enqueue_query), k_hit_attr and k_sweep_side for the attributes.
+int rt_sweep_spheres_device(rt_ctx* c, size_t n, const void* d_sweeps8, uint32_t cull_mask, void* d_hits, void* d_attr, void* hip_stream) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const char* const name = "rt_sweep_spheres_device";
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": too many sweeps for one call");
+  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": cull_mask is above 0xFF");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + " needs trace_variant 0");
+  if (n) {
+    if (!d_sweeps8 || !d_hits) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null sweep/hit pointers");
+    if (((uintptr_t)d_sweeps8 & 15u) || ((uintptr_t)d_hits & 3u) || ((uintptr_t)d_attr & 15u))
+      return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": sweeps and attributes must be 16-byte aligned, hits 4-byte aligned");
+    { int q = check_device_pointers(c, name, "sweeps, hits and attributes", {d_sweeps8, d_hits, d_attr}); if (q) return q; }
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  int r = ready_to_trace(c); if (r) return r;
+  if (n == 0) return RT_OK;
+  return enqueue_query(c, hip_stream ? (hipStream_t)hip_stream : c->stream, c->cfg, Walk::Sweep, n, d_sweeps8, false, false, nullptr, cull_mask, d_hits, d_attr);
+}
+
+// The blocking host form, as rt_closest_point is to rt_closest_point_device: the records copied in, the same enqueue on the context's
+// stream, the hits copied out; with counting the instrumented walk, whose node visits and triangle tests come back in stats.
+int rt_sweep_spheres(rt_ctx* c, size_t n, const float* sweeps8, uint32_t cull_mask, rt_hit* out, int counting, rt_stats* stats) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const char* const name = "rt_sweep_spheres";
+  if ((!sweeps8 || !out) && n) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null sweep/hit pointers");
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": too many sweeps for one call");
+  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": cull_mask is above 0xFF");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + " needs trace_variant 0");
+  HIP_TRY(c, hipSetDevice(c->device));
+  { int q = quiesce(c); if (q) return q; }   // (as rt_intersect)
+  int r = ready_to_trace(c); if (r) return r;
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (n == 0) return RT_OK;
+  // one allocation: the sweeps (32 B each), then the hits
+  const size_t sweep_bytes = n * 8 * sizeof(float);
+  char* d_buf = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  struct Guard {   // every exit path below releases the temporaries
+    char*& buf; hipEvent_t &a, &b;
+    ~Guard() { if (buf) hipFree(buf); if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
+  } guard{d_buf, e0, e1};
+  HIP_TRY(c, hipMalloc((void**)&d_buf, sweep_bytes + n * sizeof(HitRec)));
+  HitRec* const d_h = (HitRec*)(d_buf + sweep_bytes);
+  HIP_TRY(c, hipMemcpy(d_buf, sweeps8, sweep_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipEventCreate(&e0)); HIP_TRY(c, hipEventCreate(&e1));
+  r = enqueue_query(c, c->stream, c->cfg, Walk::Sweep, n, d_buf, false, counting != 0, nullptr, cull_mask, d_h, nullptr, e0, e1); if (r) return r;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpy(out, d_h, n * sizeof(HitRec), hipMemcpyDeviceToHost));
   if (stats) {
     if (counting) {
       uint32_t cnt[CNT_TAILS];

@@ -208,6 +208,13 @@ void launch_closest_side(const SceneDev& sc, const float4* points, const HitRec*
 // (launch_closest_scale fills it first); chunk cursor, counters (counting) and spill area as for launch_query_hits.
 void launch_overlap_boxes(const SceneDev& sc, const float4* boxes, uint32_t cull_mask, const float* inst_scale, bool any, uint32_t k, void* ids, uint32_t* counts,
                           uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
+// rt_sweep_spheres_device: the first contact of every moving sphere (32 bytes: o.xyz, r, d.xyz, tmax) with the instances the cull mask
+// admits, into hits[n] (kernels_sweep.inc).  inst_scale as for launch_closest_point (launch_closest_scale fills it first); chunk cursor,
+// counters (counting) and spill area as for launch_query_hits.
+void launch_sweep_spheres(const SceneDev& sc, const float4* sweeps, uint32_t cull_mask, const float* inst_scale, HitRec* hits, uint32_t n, int32_t* ovf_stack,
+                          uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
+// the side of the reported triangle's plane every sphere's centre lies on at its contact (launch_closest_side's rule and word)
+void launch_sweep_side(const SceneDev& sc, const float4* sweeps, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s);
 // rt_shade_rays_device: k_ray_ingest replaces k_raygen for the caller's n rays (32 bytes each, o.xyz, w3, d.xyz, tmax; sample id = record
 // index): sky colours of the rays that miss the TLAS and (0, 0, 0, 0) for invalid records into f.sample_color, the others into bounce queue 0
 // (workgroup b appends to shard b % 8: f.shard_cap >= 256 * ceil(ray_ingest_block_count(n) / 8)).  f.counters must be zero.

@@ -523,6 +523,49 @@ int rt_sweep_spheres_device(rt_ctx* ctx, size_t n, const void* d_sweeps8, uint32
 int rt_sweep_spheres(rt_ctx* ctx, size_t n, const float* sweeps8_host, uint32_t cull_mask,
                      rt_hit* out_host, int counting, rt_stats* stats);
 
+/* Inside / outside: for every point, is it enclosed by the scene's surfaces (Open3D's compute_occupancy and compute_signed_distance),
+ * for signed distance fields, penetration tests, occupancy and voxel filling.  The answer is a vote over the crossing parities of a few
+ * rays from the point along a fixed table of generic directions; one ray is not enough, because the canonical triangle test is not
+ * watertight (a ray through a shared edge or vertex may be counted by both triangles or by neither), and three are (DESIGN.md §5
+ * "Inside / outside").
+ * Points: d_points4 holds n records of 16 B (x, y, z, w), 16-B aligned, memory of ctx's GPU: rt_closest_point_device's record.
+ * rt_point_inside* ignores w, so one buffer feeds both queries.
+ * Directions: n_dirs is 1, 3 or 5, the first n_dirs rows of RT_INSIDE_DIRS below, as these decimal literals round to binary32; they
+ * are used as given, not normalised.
+ * Crossing count: count_k(p) is the value rt_intersect_device_hits writes to d_counts for the ray (p, tmin 0, D_k, tmax +inf) with
+ * max_hits 0, ray_flags 0 and the call's cull_mask: its candidates, its instance mask rule, its object-space transform of the ray and
+ * the canonical triangle test.  Instance flags, opacity and facing play no part.  It depends on the point, the instance records and the
+ * packets only, never on the tree.
+ * Vote: the directions are taken in order k = 0, 1, ...; the walk stops as soon as odd or even holds more than n_dirs / 2 votes.
+ * d_inside: n uint32, 4-B aligned.  Word i: bit 0 is 1 when odd won (the point is inside); bits 8-15 the number of odd votes among the
+ * directions taken; bits 16-23 the number of directions taken.  The word is a function of the counts alone.
+ * d_counts (optional): n x n_dirs uint32, point-major, 4-B aligned: count_k of every direction.  Then every direction is taken: bits
+ * 16-23 read n_dirs, bits 8-15 count the odd votes among all of them, and bit 0 is the same either way.
+ * A point with a non-finite coordinate gets word 0 and counts 0.
+ * Stream ordering without host synchronisation, the TLAS and scene of the call, the query workspace, queries and shading calls of one
+ * context one after another, RT_ERR_NOT_READY and n == 0 (nothing is enqueued): as for rt_closest_point_device.
+ * RT_ERR_INVALID_ARGUMENT: a NULL (d_counts aside) or misaligned pointer, a pointer that is not memory of ctx's GPU, n >= 0xFFFFFF00,
+ * n x n_dirs >= 0xFFFFFF00 when d_counts is given, cull_mask > 0xFF, n_dirs not 1, 3 or 5, trace_variant != 0. */
+#define RT_INSIDE_MAX_DIRS 5
+#define RT_INSIDE_DIRS { {0.36f, 0.48f, 0.8f}, {-0.8f, 0.36f, -0.48f}, {0.48f, -0.8f, -0.36f}, {-0.6f, -0.64f, 0.48f}, {0.64f, -0.48f, 0.6f} }
+int rt_point_inside_device(rt_ctx* ctx, size_t n, const void* d_points4, uint32_t cull_mask, uint32_t n_dirs,
+                           void* d_inside, void* d_counts, void* hip_stream);
+/* The blocking host form, as rt_closest_point is to rt_closest_point_device: the points are copied to the device, voted on the
+ * context's stream (same workspace and ordering) and the words (and counts, when counts_host is not NULL) copied back.  counting != 0
+ * runs the instrumented walk and fills stats->node_visits and stats->tri_tests; stats may be NULL.  As rt_sweep_spheres does, the call
+ * also reports the walk's device time in stats->ms_trace_closest and the node and packet sizes in stats->bvh_node_bytes /
+ * bvh_tri_bytes; every other field is 0. */
+int rt_point_inside(rt_ctx* ctx, size_t n, const float* points4_host, uint32_t cull_mask, uint32_t n_dirs,
+                    uint32_t* inside_host, uint32_t* counts_host, int counting, rt_stats* stats);
+/* Signed distance: rt_closest_point_device and the vote above in one call, under one ordering.  d_hits and d_attr receive
+ * rt_closest_point_device's records for (x, y, z, r_max) byte for byte, except the sign bit of t, which is set when bit 0 of the point's
+ * word is set: a point inside has t <= -0.0, the miss record of a point inside is -r_max, and t = 0 becomes -0.0.  A record that is not
+ * a valid closest-point query (a non-finite coordinate, a negative or NaN r_max) keeps its miss form unchanged.
+ * d_inside (optional): n uint32, the early-stop words of rt_point_inside_device.
+ * Everything else, RT_ERR_INVALID_ARGUMENT included: as for rt_closest_point_device and rt_point_inside_device. */
+int rt_signed_distance_device(rt_ctx* ctx, size_t n, const void* d_points4, uint32_t cull_mask, uint32_t n_dirs,
+                              void* d_hits, void* d_attr, void* d_inside, void* hip_stream);
+
 /* Custom ray generation: the frame's shading of the caller's primary rays.  The caller's rays replace the pinhole camera of
  * src/shader.rgen:62-82; everything after it — the bounce loop of src/shader.rgen:84-177 with closest hit, miss, reflection, refraction and
  * shadow rays — is the frame's, and the colours are those a frame would compute for the same rays.

@@ -58,10 +58,12 @@ INSTANCE_FLAG_FORCE_NO_OPAQUE = 0x8
 HIT_KIND_FRONT_FACING = 0xFE
 HIT_KIND_BACK_FACING = 0xFF
 OVERLAP_ANY = 0x1   # rt_overlap_boxes_device: occupancy (counts of 0 or 1)
+# rt_point_inside_device: the direction table (RT_INSIDE_DIRS of include/rt_api.h; rounded to binary32, not normalised)
+INSIDE_DIRS = ((0.36, 0.48, 0.8), (-0.8, 0.36, -0.48), (0.48, -0.8, -0.36), (-0.6, -0.64, 0.48), (0.64, -0.48, 0.6))
 
 EXPORTS = ["rt_create", "rt_create_frame_slot", "rt_destroy", "rt_upload_geometry", "rt_build_blas", "rt_set_instances", "rt_set_instances_device", "rt_refit_blas_device", "rt_set_materials", "rt_set_instance_types", "rt_set_uniforms", "rt_set_skybox",
            "rt_trace", "rt_trace_async", "rt_trace_wait", "rt_trace_shard", "rt_set_batch", "rt_trace_shard_batch", "rt_assemble_shards", "rt_shard_rows", "rt_synchronize", "rt_get_stats", "rt_set_timing", "rt_intersect",
-           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_sweep_spheres_device", "rt_sweep_spheres", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
+           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_sweep_spheres_device", "rt_sweep_spheres", "rt_point_inside_device", "rt_point_inside", "rt_signed_distance_device", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
 
 _LIBS = {}
 
@@ -108,6 +110,9 @@ def lib(variant=None):
         L.rt_closest_point.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, C.c_int, C.POINTER(RtStats)]
         L.rt_sweep_spheres_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, vp, vp]
         L.rt_sweep_spheres.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, C.c_int, C.POINTER(RtStats)]
+        L.rt_point_inside_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
+        L.rt_point_inside.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_int, C.POINTER(RtStats)]
+        L.rt_signed_distance_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
         L.rt_overlap_boxes_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]
         L.rt_overlap_boxes.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_int, C.POINTER(RtStats)]
         L.rt_shade_rays_device.argtypes = [vp, C.c_size_t, C.c_uint32, vp, vp, vp, vp]
@@ -409,6 +414,82 @@ class RtContext:
         self._chk(self.L.rt_sweep_spheres(self.h, len(sweeps8), _p(sweeps8), int(cull_mask) & 0xFFFFFFFF, _p(out), int(counting), C.byref(st)), "rt_sweep_spheres")
         return out, st
 
+    def point_inside_device(self, points, n_dirs=3, cull_mask=0xFF, counts=False, stream=None, out=None):
+        """rt_point_inside_device: is every point enclosed by the scene's surfaces?  `points` is closest_point_device's tensor, a contiguous
+        float32 (n, 4) on this context's GPU (x, y, z, ignored per row), read in the order of `stream` like intersect_device's rays.  The
+        answer is the majority of the crossing parities of the rays from the point along the first n_dirs (1, 3 or 5) rows of INSIDE_DIRS.
+        Returns a PointsInside: word, int32 (n,) (bit 0: inside; bits 8-15: odd votes; bits 16-23: directions taken), inside, its bit 0 as
+        a bool tensor, and with counts=True count, int32 (n, n_dirs), the crossings of every direction (then every direction is taken).
+        out = (word, count) reuses such buffers (None where not asked for).  See include/rt_api.h."""
+        import torch
+        self._check_rays(points, "point_inside_device", 4, "point")
+        k = int(n_dirs)
+        if k not in (1, 3, 5):
+            raise ValueError("n_dirs must be 1, 3 or 5, got %d" % k)
+        n = points.shape[0]
+        cur = torch.cuda.current_stream(points.device)
+        if stream is None:
+            stream = cur
+        shapes = ((n,), (n, k) if counts else None)
+        if out is None:
+            bufs = [torch.empty(sh, dtype=torch.int32, device=points.device) if sh is not None else None for sh in shapes]
+            if stream != cur:   # (allocated for the current stream, written on `stream`)
+                for t in bufs:
+                    if t is not None:
+                        t.record_stream(stream)
+        else:
+            bufs = list(out)
+            for i, (t, sh, what) in enumerate(zip(bufs, shapes, ("words", "counts"))):
+                if sh is None:
+                    bufs[i] = None
+                elif t is None or t.dtype != torch.int32 or tuple(t.shape) != sh or not t.is_contiguous() or t.device != points.device:
+                    raise ValueError("out %s must be a contiguous int32 %s tensor on the points' device" % (what, sh))
+        word, count = bufs
+
+        def call(run):
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+            return self.L.rt_point_inside_device(self.h, n, ptr(points), int(cull_mask) & 0xFFFFFFFF, k, ptr(word), ptr(count), C.c_void_p(run.cuda_stream))
+        if n:
+            self._on_stream(stream, (points, word, count), call, "rt_point_inside_device")
+        return PointsInside(word, count)
+
+    def point_inside(self, points4, n_dirs=3, cull_mask=0xFF, counts=False, counting=False):
+        """rt_point_inside: the blocking host form -> (words uint32 (n,), counts uint32 (n, n_dirs) or None, RtStats; with counting its
+        node_visits / tri_tests are filled)"""
+        points4 = np.ascontiguousarray(points4, np.float32).reshape(-1, 4)
+        n, k = len(points4), int(n_dirs)
+        word = np.zeros(n, np.uint32)
+        cnt = np.zeros((n, max(k, 0)), np.uint32) if counts else None
+        st = RtStats()
+        self._chk(self.L.rt_point_inside(self.h, n, _p(points4), int(cull_mask) & 0xFFFFFFFF, k & 0xFFFFFFFF, _p(word),
+                                         _p(cnt) if cnt is not None else None, int(counting), C.byref(st)), "rt_point_inside")
+        return word, cnt, st
+
+    def signed_distance_device(self, points, n_dirs=3, cull_mask=0xFF, attributes=False, stream=None, out=None, words=False):
+        """rt_signed_distance_device: closest_point_device and point_inside_device in one call.  Returns closest_point_device's RayQuery
+        with the sign bit of t set for the points inside (a miss inside: -r_max; t = 0 inside: -0.0); everything else is byte for byte
+        closest_point_device's.  out = (hits, attr) reuses buffers.  With words=True the result's `word` is point_inside_device's int32
+        (n,) vote word of every point (early stop).  See include/rt_api.h."""
+        import torch
+        k = int(n_dirs)
+        if k not in (1, 3, 5):
+            raise ValueError("n_dirs must be 1, 3 or 5, got %d" % k)
+        word = None
+
+        def call(run, hits, attr):
+            if word is not None:
+                word.record_stream(run)
+            return self.L.rt_signed_distance_device(self.h, points.shape[0], C.c_void_p(points.data_ptr()), int(cull_mask) & 0xFFFFFFFF, k, C.c_void_p(hits.data_ptr()),
+                                                    C.c_void_p(attr.data_ptr()) if attr is not None else None,
+                                                    C.c_void_p(word.data_ptr()) if word is not None else None, C.c_void_p(run.cuda_stream))
+        self._check_rays(points, "signed_distance_device", 4, "point")
+        if words:
+            word = torch.empty((points.shape[0],), dtype=torch.int32, device=points.device)
+        hits, attr = self._device_query(points, attributes, stream, out, (), call, "rt_signed_distance_device", cols=4)
+        res = RayQuery(hits, attr, hit_kind=True)
+        res.word = word
+        return res
+
     def overlap_boxes_device(self, boxes, max_ids=0, cull_mask=0xFF, any=False, counts=True, stream=None, out=None):
         """rt_overlap_boxes_device: the triangles that touch every query box.  `boxes` is a contiguous float32 torch tensor (n, 8) on this
         context's GPU (lo.xyz, ignored, hi.xyz, ignored per row: a closed world-space box), read in the order of `stream` like
@@ -674,6 +755,23 @@ class RayHits:
         a = self.attr.cpu().numpy() if self.attr is not None else None
         c = self.count.cpu().numpy().view(np.uint32) if self.count is not None else None
         return h, a, c
+
+
+class PointsInside:
+    """Results of RtContext.point_inside_device: word, int32 (n,), the vote word of every point (bit 0: inside; bits 8-15: the odd votes
+    among the directions taken; bits 16-23: the directions taken), and count, int32 (n, n_dirs), the crossings of every direction, or
+    None when not asked for.  inside is bit 0 of word as a bool tensor (computed on the current torch stream when read)."""
+
+    def __init__(self, word, count):
+        self.word, self.count = word, count
+
+    @property
+    def inside(self):
+        return (self.word & 1) != 0
+
+    def numpy(self):
+        """(words as (n,) uint32, counts as (n, n_dirs) uint32 or None); synchronises"""
+        return (self.word.cpu().numpy().view(np.uint32), self.count.cpu().numpy().view(np.uint32) if self.count is not None else None)
 
 
 class BoxOverlaps:

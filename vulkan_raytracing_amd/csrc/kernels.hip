@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rt_kernels.h"
+#include "../../include/rt_api.h"   // RT_INSIDE_DIRS (kernels_inside.inc)
 
 namespace rt {
 
@@ -2365,6 +2366,8 @@ void launch_resolve_points(const float4* sample_color, float4* out, uint32_t n_p
 #include "kernels_overlap.inc"   // k_overlap_boxes: the triangles that touch every query box (rt_overlap_boxes_device)
 
 #include "kernels_sweep.inc"   // k_sweep_spheres, k_sweep_side: the first contact of every moving sphere (rt_sweep_spheres_device)
+
+#include "kernels_inside.inc"   // k_point_inside, k_sign_distance: inside / outside by a vote of crossing parities (rt_point_inside_device, rt_signed_distance_device)
 
 int tail_blocks_per_cu() {
   // the smallest over the instantiations: any of them may be the one in flight (counting; 4-ary records in the alt build)

@@ -301,6 +301,8 @@ struct rt_ctx {
   size_t q_ovf_alloc = 0;          // int32 entries of d_q_ovf
   float* d_q_scale = nullptr;      // rt_closest_point*: 1 + n_inst floats of launch_closest_scale, part of the query workspace
   size_t q_scale_alloc = 0;        // floats of d_q_scale
+  uint32_t* d_q_words = nullptr;   // rt_signed_distance_device without d_inside: the vote words, part of the query workspace
+  size_t q_words_alloc = 0;        // words of d_q_words
   hipEvent_t ev_query[2] = {nullptr, nullptr};
   bool ev_query_valid[2] = {false, false};
   int query_last = -1;             // parity of the last query (-1: none since the last host wait)
@@ -1459,6 +1461,7 @@ void rt_destroy(rt_ctx* c) {
   if (c->d_q_counters) hipFree(c->d_q_counters);
   if (c->d_q_ovf) hipFree(c->d_q_ovf);
   if (c->d_q_scale) hipFree(c->d_q_scale);
+  if (c->d_q_words) hipFree(c->d_q_words);
   for (int k = 0; k < 2; k++) if (c->ev_query[k]) hipEventDestroy(c->ev_query[k]);
   tlas_gpu_free(c->tgpu);
   for (auto e : c->ev_pool) hipEventDestroy(e);
@@ -2228,21 +2231,36 @@ int query_done(rt_ctx* c, hipStream_t s) {
   return RT_OK;
 }
 
-// The enqueue of every query (rt_intersect, rt_intersect_device, rt_intersect_device_flags, rt_closest_point*, rt_overlap_boxes*, rt_sweep_spheres*) on stream s, after the
+// The enqueue of every query (rt_intersect, rt_intersect_device, rt_intersect_device_flags, rt_closest_point*, rt_overlap_boxes*, rt_sweep_spheres*,
+// rt_point_inside*, rt_signed_distance_device) on stream s, after the
 // caller's checks.  Walk::Flags: the flag-aware walk (MODE_QUERY_FLAGS) with the ray words `words` (or none) and the call's query word;
 // Walk::Plain: the plain walk with any_hit; Walk::Closest: the closest-point walk over n point records with the cull mask `query_word`
 // (its per-instance scales are made first, in the workspace); Walk::Overlap: the box-overlap walk over n box records with the cull mask
 // `query_word`, any_hit standing for RT_OVERLAP_ANY, d_hits for the id rows of max_ids entries and d_counts for the counts (the same
 // scales first); Walk::Sweep: the sphere-sweep walk over n sweep records with the cull mask `query_word` (the same scales first).
-// counting: the instrumented Plain, Closest, Overlap or Sweep walk (its counts start from a zeroed counter block).  d_attr
+// Walk::Inside: the inside / outside vote over n point records with the cull mask `query_word`, max_ids standing for n_dirs, into
+// d_words and, optionally, d_counts; with d_hits the signed distance: the closest-point walk into d_hits (and d_attr) first, the vote
+// with the counter block's cursor initialised again, then the sign pass over d_hits (d_words null: the workspace's words).
+// counting: the instrumented Plain, Closest, Overlap, Sweep or Inside walk (its counts start from a zeroed counter block).  d_attr
 // (optional): the hit attributes.  t0 / t1 (optional): events recorded around the walk.
-enum class Walk { Plain, Flags, Closest, Overlap, Sweep };
+enum class Walk { Plain, Flags, Closest, Overlap, Sweep, Inside };
 int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, Walk walk, size_t n, const void* d_records, bool any_hit, bool counting,
                   const void* words, uint32_t query_word, void* d_hits, void* d_attr, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr,
-                  uint32_t max_ids = 0u, void* d_counts = nullptr) {
-  const bool flags = walk == Walk::Flags, closest = walk == Walk::Closest, overlap = walk == Walk::Overlap, sweep = walk == Walk::Sweep;
+                  uint32_t max_ids = 0u, void* d_counts = nullptr, void* d_words = nullptr) {
+  const bool flags = walk == Walk::Flags, overlap = walk == Walk::Overlap, sweep = walk == Walk::Sweep, inside = walk == Walk::Inside;
+  const bool closest = walk == Walk::Closest || (inside && d_hits);
   const void* const d_rays8 = d_records;
   { int r = query_workspace(c, s); if (r) return r; }
+  if (inside && !d_words) {   // (signed distance without d_inside)
+    if (n > c->q_words_alloc) {
+      { int q = wait_queries(c, c); if (q) return q; }
+      if (c->d_q_words) HIP_TRY(c, hipFree(c->d_q_words));
+      c->d_q_words = nullptr; c->q_words_alloc = 0;
+      HIP_TRY(c, hipMalloc((void**)&c->d_q_words, n * sizeof(uint32_t)));
+      c->q_words_alloc = n;
+    }
+    d_words = c->d_q_words;
+  }
   if (counting) HIP_TRY(c, hipMemsetAsync(c->d_q_counters, 0, CNT_WORDS * sizeof(uint32_t), s));
   const SceneDev sc = scene_dev(c);
   if (t0) HIP_TRY(c, hipEventRecord(t0, s));
@@ -2255,7 +2273,10 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, Walk walk, siz
     launch_sweep_spheres(sc, (const float4*)d_records, query_word, c->d_q_scale, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, counting, cfg, s);
   } else if (closest) {
     launch_closest_scale(sc, c->d_q_scale, s);
-    launch_closest_point(sc, (const float4*)d_rays8, query_word, c->d_q_scale, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, counting, cfg, s);
+    launch_closest_point(sc, (const float4*)d_rays8, query_word, c->d_q_scale, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, counting && !inside, cfg, s);
+    if (inside) launch_point_inside(sc, (const float4*)d_records, query_word, max_ids, (uint32_t*)d_words, (uint32_t*)d_counts, (uint32_t)n, c->d_q_ovf, c->d_q_counters, counting, cfg, s);
+  } else if (inside) {
+    launch_point_inside(sc, (const float4*)d_records, query_word, max_ids, (uint32_t*)d_words, (uint32_t*)d_counts, (uint32_t)n, c->d_q_ovf, c->d_q_counters, counting, cfg, s);
   } else if (flags) launch_query_flags(sc, (const float4*)d_rays8, (const uint32_t*)words, query_word, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, cfg, s);
   else launch_query(sc, (const float4*)d_rays8, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, any_hit, counting, cfg, s);
   if (t1) HIP_TRY(c, hipEventRecord(t1, s));
@@ -2263,6 +2284,7 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, Walk walk, siz
   if (d_attr && flags) launch_hit_kind(sc, (const float4*)d_rays8, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
   if (d_attr && closest) launch_closest_side(sc, (const float4*)d_rays8, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
   if (d_attr && sweep) launch_sweep_side(sc, (const float4*)d_records, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
+  if (inside && d_hits) launch_sign_distance((const float4*)d_records, (const uint32_t*)d_words, (HitRec*)d_hits, (uint32_t)n, s);   // (after the attributes: they read the records)
   return query_done(c, s);
 }
 }  // namespace
@@ -2635,6 +2657,102 @@ int rt_sweep_spheres(rt_ctx* c, size_t n, const float* sweeps8, uint32_t cull_ma
     stats->bvh_node_bytes = sizeof(BvhNodeQ); stats->bvh_tri_bytes = sizeof(TriPacket);
   }
   return RT_OK;
+}
+
+namespace {
+// the argument rules rt_point_inside_device, rt_point_inside and rt_signed_distance_device share (pointers aside)
+int inside_arguments(rt_ctx* c, const char* name, size_t n, uint32_t cull_mask, uint32_t n_dirs, bool with_counts) {
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": too many points for one call");
+  if (n_dirs != 1u && n_dirs != 3u && n_dirs != 5u) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": n_dirs must be 1, 3 or 5");
+  if (with_counts && (uint64_t)n * n_dirs >= 0xFFFFFF00ull)
+    return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": n * n_dirs must be below 0xFFFFFF00 (32-bit record indices)");
+  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": cull_mask is above 0xFF");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + " needs trace_variant 0");
+  return RT_OK;
+}
+}  // namespace
+
+// Inside / outside of every point: the checks and ordering of a device query (rt_closest_point_device), then k_point_inside over the
+// caller's records (enqueue_query, Walk::Inside).
+int rt_point_inside_device(rt_ctx* c, size_t n, const void* d_points4, uint32_t cull_mask, uint32_t n_dirs, void* d_inside, void* d_counts, void* hip_stream) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const char* const name = "rt_point_inside_device";
+  { int q = inside_arguments(c, name, n, cull_mask, n_dirs, d_counts != nullptr); if (q) return q; }
+  if (n) {
+    if (!d_points4 || !d_inside) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null point/word pointers");
+    if (((uintptr_t)d_points4 & 15u) || ((uintptr_t)d_inside & 3u) || ((uintptr_t)d_counts & 3u))
+      return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": points must be 16-byte aligned, words and counts 4-byte aligned");
+    { int q = check_device_pointers(c, name, "points, words and counts", {d_points4, d_inside, d_counts}); if (q) return q; }
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  int r = ready_to_trace(c); if (r) return r;
+  if (n == 0) return RT_OK;
+  return enqueue_query(c, hip_stream ? (hipStream_t)hip_stream : c->stream, c->cfg, Walk::Inside, n, d_points4, false, false, nullptr, cull_mask, nullptr, nullptr,
+                       nullptr, nullptr, n_dirs, d_counts, d_inside);
+}
+
+// The blocking host form, as rt_closest_point is to rt_closest_point_device: the points copied in, the same enqueue on the context's
+// stream, the words and counts copied out; with counting the instrumented walk, whose node visits and triangle tests come back in stats.
+int rt_point_inside(rt_ctx* c, size_t n, const float* points4, uint32_t cull_mask, uint32_t n_dirs, uint32_t* inside, uint32_t* counts, int counting,
+                    rt_stats* stats) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const char* const name = "rt_point_inside";
+  if ((!points4 || !inside) && n) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null point/word pointers");
+  { int q = inside_arguments(c, name, n, cull_mask, n_dirs, counts != nullptr); if (q) return q; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  { int q = quiesce(c); if (q) return q; }   // (as rt_intersect)
+  int r = ready_to_trace(c); if (r) return r;
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (n == 0) return RT_OK;
+  // one allocation: the points (16 B each), then the words, then the counts
+  const size_t pt_bytes = n * 4 * sizeof(float), word_bytes = n * sizeof(uint32_t), count_bytes = counts ? n * n_dirs * sizeof(uint32_t) : 0;
+  char* d_buf = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  struct Guard {   // every exit path below releases the temporaries
+    char*& buf; hipEvent_t &a, &b;
+    ~Guard() { if (buf) hipFree(buf); if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
+  } guard{d_buf, e0, e1};
+  HIP_TRY(c, hipMalloc((void**)&d_buf, pt_bytes + word_bytes + count_bytes));
+  uint32_t* const d_w = (uint32_t*)(d_buf + pt_bytes);
+  uint32_t* const d_c = counts ? (uint32_t*)(d_buf + pt_bytes + word_bytes) : nullptr;
+  HIP_TRY(c, hipMemcpy(d_buf, points4, pt_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipEventCreate(&e0)); HIP_TRY(c, hipEventCreate(&e1));
+  r = enqueue_query(c, c->stream, c->cfg, Walk::Inside, n, d_buf, false, counting != 0, nullptr, cull_mask, nullptr, nullptr, e0, e1, n_dirs, d_c, d_w); if (r) return r;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpy(inside, d_w, word_bytes, hipMemcpyDeviceToHost));
+  if (counts) HIP_TRY(c, hipMemcpy(counts, d_c, count_bytes, hipMemcpyDeviceToHost));
+  if (stats) {
+    if (counting) {
+      uint32_t cnt[CNT_TAILS];
+      HIP_TRY(c, hipMemcpy(cnt, c->d_q_counters, sizeof(cnt), hipMemcpyDeviceToHost));
+      memcpy(&stats->node_visits, &cnt[CNT_NODE_VISITS], 8);
+      memcpy(&stats->tri_tests, &cnt[CNT_TRI_TESTS], 8);
+    }
+    float ms = 0.f; hipEventElapsedTime(&ms, e0, e1);
+    stats->ms_trace_closest = ms;
+    stats->bvh_node_bytes = sizeof(BvhNodeQ); stats->bvh_tri_bytes = sizeof(TriPacket);
+  }
+  return RT_OK;
+}
+
+// Signed distance: rt_closest_point_device's checks, then one enqueue_query under one ordering: k_closest_scale and k_closest_point into
+// the caller's records, k_point_inside with the cursor initialised again, the attributes, and k_sign_distance over the records.
+int rt_signed_distance_device(rt_ctx* c, size_t n, const void* d_points4, uint32_t cull_mask, uint32_t n_dirs, void* d_hits, void* d_attr, void* d_inside,
+                              void* hip_stream) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const char* const name = "rt_signed_distance_device";
+  { int q = inside_arguments(c, name, n, cull_mask, n_dirs, false); if (q) return q; }
+  if (n) {
+    if (!d_points4 || !d_hits) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null point/hit pointers");
+    if (((uintptr_t)d_points4 & 15u) || ((uintptr_t)d_hits & 3u) || ((uintptr_t)d_attr & 15u) || ((uintptr_t)d_inside & 3u))
+      return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": points and attributes must be 16-byte aligned, hits and words 4-byte aligned");
+    { int q = check_device_pointers(c, name, "points, hits, attributes and words", {d_points4, d_hits, d_attr, d_inside}); if (q) return q; }
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  int r = ready_to_trace(c); if (r) return r;
+  if (n == 0) return RT_OK;
+  return enqueue_query(c, hip_stream ? (hipStream_t)hip_stream : c->stream, c->cfg, Walk::Inside, n, d_points4, false, false, nullptr, cull_mask, d_hits, d_attr,
+                       nullptr, nullptr, n_dirs, nullptr, d_inside);
 }
 
 // Custom ray generation: the caller's primary rays (n_points * n_samples records, sample-major) through the frame's bounce pipeline —

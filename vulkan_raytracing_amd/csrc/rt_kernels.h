@@ -215,6 +215,14 @@ void launch_sweep_spheres(const SceneDev& sc, const float4* sweeps, uint32_t cul
                           uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
 // the side of the reported triangle's plane every sphere's centre lies on at its contact (launch_closest_side's rule and word)
 void launch_sweep_side(const SceneDev& sc, const float4* sweeps, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s);
+// rt_point_inside_device: the vote word of every point (16 bytes: p.xyz, ignored) over the crossing parities of the rays along the first
+// n_dirs (1, 3 or 5) directions of RT_INSIDE_DIRS, counted as launch_query_hits counts them for the word 0 | cull_mask << 24
+// (kernels_inside.inc), into words[n]; counts (optional): the n * n_dirs crossing counts, point-major, and then no early stop.  Chunk
+// cursor, counters (counting) and spill area as for launch_query_hits.
+void launch_point_inside(const SceneDev& sc, const float4* points, uint32_t cull_mask, uint32_t n_dirs, uint32_t* words, uint32_t* counts, uint32_t n,
+                         int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
+// rt_signed_distance_device: sets the sign bit of hits[i].t where bit 0 of words[i] is set and points[i] was a valid closest-point record
+void launch_sign_distance(const float4* points, const uint32_t* words, HitRec* hits, uint32_t n, hipStream_t s);
 // rt_shade_rays_device: k_ray_ingest replaces k_raygen for the caller's n rays (32 bytes each, o.xyz, w3, d.xyz, tmax; sample id = record
 // index): sky colours of the rays that miss the TLAS and (0, 0, 0, 0) for invalid records into f.sample_color, the others into bounce queue 0
 // (workgroup b appends to shard b % 8: f.shard_cap >= 256 * ceil(ray_ingest_block_count(n) / 8)).  f.counters must be zero.

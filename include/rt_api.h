@@ -600,6 +600,21 @@ int rt_trace_counting(rt_ctx* ctx, int width, int height, float* out_rgba32f_hos
  * children inside parents, quantized boxes containing float boxes, depth and stack bounds).  out[8] = nodes, leaves,
  * depth, max leaf size, BVH4 nodes, BVH4 stack need, violations, triangles reached.  0 = all invariants hold. */
 int rt_debug_check_builders(const float* verts6, size_t n_floats, const uint32_t* idx, size_t n_idx, uint64_t* out8);
+/* Host-only sibling of rt_debug_snapshot (needs no GPU): the quantized BVH2 and the triangle packets that rt_build_blas(blas_builder 0)
+ * produces for an indexed mesh, in the device record layouts (32-byte nodes with links local to the mesh, 48-byte packets).  out8 = nodes,
+ * packets, q_lo[3], q_scale[3] (binary32 bit patterns).  n triangles give at most max(1, n - 1) nodes and n packets;
+ * RT_ERR_INVALID_ARGUMENT on a NULL pointer, an index outside verts6 or a buffer that is too small. */
+int rt_debug_host_blas(const float* verts6, size_t n_floats, const uint32_t* idx, size_t n_idx, void* nodes, size_t nodes_capacity_bytes,
+                       void* packets, size_t packets_capacity_bytes, uint64_t* out8);
+/* TEST HOOK, not a product path: copies to the host, as raw bytes in the device record layouts, what the kernels of ctx read.  Waits for
+ * the pending frames, queries and uploads of the scene (as rt_build_blas does), launches no kernel.  what = 0: 20 x uint64 — linked BLAS
+ * nodes, tlas_base (global node index of ctx's TLAS region of its current parity), nodes of one TLAS, tlas_stride (0 without a batch),
+ * batch_k, triangle packets, instance records (all frames of a batch), instances per frame, meshes, vertex floats, indices, frontier
+ * boxes, tlas_q_lo[3], tlas_q_scale[3] (binary32 bit patterns), TLAS nodes item 2 copies (batch_k * tlas_stride for a batch), 0;
+ * 1: the linked BLAS nodes; 2: the TLAS region; 3: the triangle packets; 4: the instance records of the current parity; 5: the device
+ * mesh table; 6: the device vertex buffer; 7: the device index buffer; 8: the frontier boxes (6 floats each).  *bytes (may be NULL)
+ * receives the item's size.  RT_ERR_NOT_READY without a valid TLAS; RT_ERR_INVALID_ARGUMENT: NULL ctx or out, unknown item, capacity_bytes too small. */
+int rt_debug_snapshot(rt_ctx* ctx, int what, void* out, size_t capacity_bytes, size_t* bytes);
 /* Host-only view of the launch/allocation sizing rules (needs no GPU): out2[0] = workgroups of the k_tail grid on a device
  * of n_cu compute units holding resident_per_cu of them each (0 = k_tail is not used), out2[1] = int32 elements of the
  * spill-stack allocation for that grid, a traversal grid of trace_blocks workgroups and ovf_stride entries per thread. */

@@ -1,0 +1,356 @@
+"""Node-by-node validator of the acceleration structures the kernels walk, in plain numpy and independent of the library's C++.
+
+Input is a snapshot as RtContext.debug_snapshot returns it (or one assembled by hand, see link_meshes): the linked BLAS nodes, one
+context's TLAS region, the triangle packets, the instance records, the device mesh table, the vertex and index buffers and the frontier
+boxes.  `validate` visits every node, packet and instance once, level by level, and returns the number of violations per kind
+("The contract of every tree producer").
+
+Decisions are exact.  A plane is q_lo + q * q_scale in real arithmetic.  The difference between a coordinate and a plane is first
+evaluated in binary64 together with a bound on its rounding error; whatever lies inside that bound (ties, axes with q_scale = 1e-30)
+is decided with fractions.Fraction.  There is no tolerance anywhere."""
+from fractions import Fraction
+
+import numpy as np
+
+BLAS_MAX_DEPTH = 40
+TLAS_MAX_DEPTH = 20
+
+KINDS = (
+    # BLAS
+    "blas_node_twice",       # a node slot reached twice (within a mesh or across meshes)
+    "blas_link_range",       # an interior link outside [0, n_blas_nodes)
+    "blas_inverted_link",    # a child with inverted planes whose link does not repeat its sibling's
+    "blas_leaf_range",       # a leaf whose packets do not lie inside the packet array
+    "packet_twice",          # a packet reached more than once
+    "packet_unreached",      # a mesh reaches fewer packets than it has triangles
+    "prim_permutation",      # the prim values of a mesh's packets are not a permutation of 0..prim_count-1
+    "packet_bits",           # v0 / e1 / e2 differ from verts[idx[3p]], fl32(v1 - v0), fl32(v2 - v0)
+    "blas_lo",               # a lower plane on the path lies above a vertex of the triangle
+    "blas_hi",               # an upper plane on the path lies below a vertex of the triangle
+    "frontier",              # a vertex of the mesh lies in none of its frontier boxes
+    "blas_depth",            # interior levels differ from the mesh table's, or exceed BLAS_MAX_DEPTH
+    # TLAS
+    "tlas_node_twice",
+    "tlas_link_range",       # an interior link outside the frame's node range
+    "tlas_inverted_link",
+    "tlas_leaf_range",       # a leaf naming a record outside the frame's record range
+    "instance_twice",
+    "instance_unreached",    # an instance with triangles and a mask that is not 0 in no leaf
+    "tlas_containment",      # a corner of the instance's transformed bounds outside the boxes on its path
+    "record_fields",         # an InstanceDev field differs from the mesh table's current entry
+    "tlas_depth",
+)
+
+_EPS = np.finfo(np.float64).eps
+
+
+def cmp_plane(a, b, q_lo, q, s):
+    """sign of (a + b) - (q_lo + q * s) in real arithmetic, elementwise (int8 array of -1, 0, 1).  a, b, q_lo and s are binary64 arrays
+    (holding binary32 values, or binary64 ones), q integers in 0..65535."""
+    a, b, q_lo, q, s = np.broadcast_arrays(np.asarray(a, np.float64), np.asarray(b, np.float64), np.asarray(q_lo, np.float64),
+                                           np.asarray(q, np.float64), np.asarray(s, np.float64))
+    shape = a.shape
+    a, b, q_lo, q, s = (x.reshape(-1) for x in (a, b, q_lo, q, s))
+    qs = q * s                                      # (its rounding, if any, is inside the bound below)
+    d = (a + b) - (q_lo + qs)
+    bound = 16.0 * _EPS * (np.abs(a) + np.abs(b) + np.abs(q_lo) + np.abs(qs))
+    out = np.sign(d).astype(np.int8)
+    tie = ~(np.abs(d) > bound)
+    if tie.any():
+        rows = np.stack([a[tie], b[tie], q_lo[tie], q[tie], s[tie]], axis=1)
+        uniq, inv = np.unique(rows, axis=0, return_inverse=True)
+        res = np.empty(len(uniq), np.int8)
+        for i, (ua, ub, ul, uq, us) in enumerate(uniq.tolist()):
+            e = Fraction(ua) + Fraction(ub) - Fraction(ul) - int(uq) * Fraction(us)
+            res[i] = (e > 0) - (e < 0)
+        out[tie] = res[np.asarray(inv).reshape(-1)]
+    return out.reshape(shape)
+
+
+def _walk(nodes, first_global, root, lo_ok, hi_ok, visited, out, prefix, max_iter):
+    """Level-by-level walk of one tree.  nodes[i] is global node first_global + i; links must stay inside [lo_ok, hi_ok); visited is the
+    shared per-slot flag array of `nodes`.  Every entered child carries the intersection (in quanta) of the child boxes on its path.
+    Returns (leaf refs, leaf lo (n, 3), leaf hi (n, 3), interior levels, nodes visited, shape_ok)."""
+    bad0 = out[prefix + "_node_twice"] + out[prefix + "_link_range"] + out[prefix + "_inverted_link"]
+    cur = np.array([root], np.int64)
+    blo = np.zeros((1, 3), np.int64)
+    bhi = np.full((1, 3), 65535, np.int64)
+    leaves, llo, lhi = [], [], []
+    levels = n_visited = 0
+    for _ in range(max_iter):
+        ok = (cur >= lo_ok) & (cur < hi_ok)
+        out[prefix + "_link_range"] += int((~ok).sum())
+        cur, blo, bhi = cur[ok], blo[ok], bhi[ok]
+        loc = cur - first_global
+        _, first_at = np.unique(loc, return_index=True)
+        fresh = np.zeros(len(loc), bool)
+        fresh[first_at] = True
+        fresh &= ~visited[loc]
+        out[prefix + "_node_twice"] += int((~fresh).sum())
+        cur, blo, bhi, loc = cur[fresh], blo[fresh], bhi[fresh], loc[fresh]
+        if not len(cur):
+            break
+        visited[loc] = True
+        levels += 1
+        n_visited += len(cur)
+        w = nodes["w"][loc].astype(np.int64).reshape(-1, 2, 3)
+        ch = nodes["child"][loc].astype(np.int64)
+        qlo, qhi = w & 0xFFFF, w >> 16
+        inverted = (qlo > qhi).any(axis=2)                                  # (n, 2)
+        out[prefix + "_inverted_link"] += int((inverted & (ch != ch[:, ::-1])).sum())
+        nlo = np.maximum(blo[:, None, :], qlo)
+        nhi = np.minimum(bhi[:, None, :], qhi)
+        enter = ~inverted
+        ref, nlo, nhi = ch[enter], nlo[enter], nhi[enter]
+        leaf = ref < 0
+        leaves.append(~ref[leaf]); llo.append(nlo[leaf]); lhi.append(nhi[leaf])
+        cur, blo, bhi = ref[~leaf], nlo[~leaf], nhi[~leaf]
+    else:
+        out[prefix + "_node_twice"] += 1                                    # (cannot happen: every slot is entered once)
+    shape_ok = out[prefix + "_node_twice"] + out[prefix + "_link_range"] + out[prefix + "_inverted_link"] == bad0
+    cat = lambda xs, shape: np.concatenate(xs) if xs else np.zeros(shape, np.int64)
+    return cat(leaves, (0,)), cat(llo, (0, 3)), cat(lhi, (0, 3)), levels, n_visited, shape_ok
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def validate(snap, inst_mesh):
+    """snap: a snapshot (RtContext.debug_snapshot / link_meshes); inst_mesh: the mesh index of every instance record (all frames of a
+    batch).  Returns (violations, reached): violations maps every kind of KINDS to a count; reached holds what the walk visited —
+    packets[m], nodes[m], leaves[m], levels[m] per mesh with triangles, instances[k] and tlas_levels[k] per frame."""
+    out = {k: 0 for k in KINDS}
+    reached = {"packets": {}, "nodes": {}, "leaves": {}, "levels": {}, "instances": [], "tlas_levels": []}
+    meshes, inst, packets = snap["meshes"], snap["instances"], snap["packets"]
+    inst_mesh = np.asarray(inst_mesh, np.int64)
+    assert len(inst_mesh) == len(inst)
+    verts, idx = snap["verts"], snap["idx"]
+    bn = snap["blas_nodes"]
+    n_blas, n_pk = len(bn), len(packets)
+
+    # ---- record fields: every InstanceDev carries the mesh table's current entry, bit for bit ----
+    mt = meshes[inst_mesh]
+    for f in ("blas_root", "first_float", "first_index", "cover_first", "cover_count"):
+        out["record_fields"] += int((inst[f] != mt[f]).sum())
+    for f in ("q_lo", "q_scale"):
+        out["record_fields"] += int((_bits(inst[f]) != _bits(mt[f])).sum())
+
+    # ---- BLAS ----
+    visited = np.zeros(n_blas, bool)
+    pk_count = np.zeros(n_pk, np.int64)
+    mesh_bounds = {}
+    for m in range(len(meshes)):
+        M = meshes[m]
+        pc = int(M["prim_count"])
+        if pc == 0:
+            continue
+        users = np.nonzero(inst_mesh == m)[0]
+        src = inst[users[0]] if len(users) else M                            # the dequantisation the kernels use
+        q_lo, q_s = src["q_lo"].astype(np.float64), src["q_scale"].astype(np.float64)
+        ff, fi = int(M["first_float"]), int(M["first_index"])
+        tri = idx[fi:fi + 3 * pc].astype(np.int64).reshape(-1, 3)
+        pos = verts[ff:].reshape(-1)                                         # position of vertex v: pos[6v : 6v + 3]
+        P = np.stack([pos[6 * tri + a] for a in range(3)], axis=2)           # (pc, 3 corners, 3 axes) float32
+        used = np.unique(tri)
+        vp = np.stack([pos[6 * used + a] for a in range(3)], axis=1)         # referenced positions
+        mesh_bounds[m] = (vp.min(axis=0), vp.max(axis=0))
+
+        refs, llo, lhi, levels, n_nodes, shape_ok = _walk(bn, 0, int(M["blas_root"]), 0, n_blas, visited, out, "blas", n_blas + 2)
+        first, cnt = refs >> 3, (refs & 7) + 1
+        in_range = first + cnt <= n_pk
+        out["blas_leaf_range"] += int((~in_range).sum())
+        first, cnt, llo, lhi = first[in_range], cnt[in_range], llo[in_range], lhi[in_range]
+        leaf_of = np.repeat(np.arange(len(first)), cnt)
+        pk = np.repeat(first, cnt) + (np.arange(len(leaf_of)) - np.repeat(np.cumsum(cnt) - cnt, cnt))
+        upk, ucnt = np.unique(pk, return_counts=True)
+        out["packet_twice"] += int(((ucnt > 1) | (pk_count[upk] > 0)).sum())      # within this mesh, or already reached from another
+        pk_count[upk] += ucnt
+        reached["packets"][m], reached["nodes"][m], reached["leaves"][m], reached["levels"][m] = len(upk), n_nodes, len(refs), levels
+        if shape_ok:
+            out["packet_unreached"] += max(0, pc - len(upk))
+            if levels != int(M["levels"]) or levels > BLAS_MAX_DEPTH:
+                out["blas_depth"] += 1
+        prim = packets["prim"][upk].astype(np.int64)
+        good = prim < pc
+        out["prim_permutation"] += int((~good).sum()) + int(len(prim[good]) - len(np.unique(prim[good])))
+
+        # packets against the vertex and index buffers, bit for bit
+        prim_all = packets["prim"][pk].astype(np.int64)
+        okp = prim_all < pc
+        pk, leaf_of, prim_all = pk[okp], leaf_of[okp], prim_all[okp]
+        T = P[prim_all]                                                      # (n, 3, 3)
+        rec = packets[pk]
+        bad = (_bits(rec["v0"]) != _bits(T[:, 0])).any(axis=1) | (_bits(rec["e1"]) != _bits(T[:, 1] - T[:, 0])).any(axis=1) | \
+              (_bits(rec["e2"]) != _bits(T[:, 2] - T[:, 0])).any(axis=1)
+        out["packet_bits"] += int(bad.sum())
+
+        # containment along the path: the three buffer positions, and the exact v0, v0 + e1, v0 + e2 of the packet
+        v0 = rec["v0"].astype(np.float64)
+        a = np.concatenate([T.astype(np.float64), np.stack([v0, v0, v0], axis=1)], axis=1)                        # (n, 6, 3)
+        b = np.concatenate([np.zeros_like(T, dtype=np.float64),
+                            np.stack([np.zeros_like(v0), rec["e1"].astype(np.float64), rec["e2"].astype(np.float64)], axis=1)], axis=1)
+        lo_q, hi_q = llo[leaf_of][:, None, :], lhi[leaf_of][:, None, :]
+        out["blas_lo"] += int((cmp_plane(a, b, q_lo, lo_q, q_s) < 0).sum())
+        out["blas_hi"] += int((cmp_plane(a, b, q_lo, hi_q, q_s) > 0).sum())
+
+        # frontier boxes: every referenced position in at least one
+        cf, cc = int(M["cover_first"]), int(M["cover_count"])
+        boxes = snap["cover_boxes"][cf:cf + cc]
+        covered = np.zeros(len(vp), bool)
+        for s0 in range(0, len(vp), 2048):
+            v = vp[s0:s0 + 2048][:, None, :]
+            covered[s0:s0 + 2048] = ((v >= boxes[None, :, :3]) & (v <= boxes[None, :, 3:])).all(axis=2).any(axis=1)
+        out["frontier"] += int((~covered).sum())
+
+    # ---- TLAS ----
+    tn = snap["tlas_nodes"]
+    K, n = int(snap["batch_k"]), int(snap["inst_per_frame"])
+    base, count = int(snap["tlas_base"]), int(snap["tlas_node_count"])
+    stride = int(snap["tlas_stride"]) if K > 1 else 0
+    t_lo, t_s = np.asarray(snap["tlas_q_lo"], np.float32).astype(np.float64), np.asarray(snap["tlas_q_scale"], np.float32).astype(np.float64)
+    tvisited = np.zeros(len(tn), bool)
+    has_tris = meshes["prim_count"][inst_mesh] > 0
+    for k in range(K):
+        root = base + k * stride
+        refs, llo, lhi, levels, _, shape_ok = _walk(tn, base, root, root, root + count, tvisited, out, "tlas", len(tn) + 2)
+        in_frame = (refs >= k * n) & (refs < (k + 1) * n)
+        out["tlas_leaf_range"] += int((~in_frame).sum())
+        refs, llo, lhi = refs[in_frame], llo[in_frame], lhi[in_frame]
+        times = np.bincount(refs - k * n, minlength=n)
+        out["instance_twice"] += int((times > 1).sum())
+        need = has_tris[k * n:(k + 1) * n] & (inst["mask"][k * n:(k + 1) * n] != 0)
+        if shape_ok:
+            out["instance_unreached"] += int((need & (times == 0)).sum())
+            if levels > TLAS_MAX_DEPTH:
+                out["tlas_depth"] += 1
+        reached["instances"].append(int((has_tris[k * n:(k + 1) * n] & (times > 0)).sum()))
+        reached["tlas_levels"].append(levels)
+        sel = has_tris[refs]
+        refs, llo, lhi = refs[sel], llo[sel], lhi[sel]
+        if not len(refs):
+            continue
+        lo = np.stack([mesh_bounds[int(m)][0] for m in inst_mesh[refs]]).astype(np.float64)
+        hi = np.stack([mesh_bounds[int(m)][1] for m in inst_mesh[refs]]).astype(np.float64)
+        corner = np.array([[(c >> a) & 1 for a in range(3)] for c in range(8)], bool)                 # (8, 3)
+        p = np.where(corner[None], hi[:, None, :], lo[:, None, :])                                    # (r, 8, 3)
+        o2w = inst["o2w"][refs].astype(np.float64).reshape(-1, 3, 4)
+        img = (o2w[:, None, :, 0] * p[:, :, None, 0] + o2w[:, None, :, 1] * p[:, :, None, 1] + o2w[:, None, :, 2] * p[:, :, None, 2]) + o2w[:, None, :, 3]
+        out["tlas_containment"] += int((cmp_plane(img, 0.0, t_lo, llo[:, None, :], t_s) < 0).sum())
+        out["tlas_containment"] += int((cmp_plane(img, 0.0, t_lo, lhi[:, None, :], t_s) > 0).sum())
+    return out, reached
+
+
+# ---- snapshots assembled by hand (the self-test of the validator, host-built trees without a GPU) --------------------------------------
+
+def quantise_box(lo, hi, q_lo, q_scale, margin):
+    """the documented rule: lower planes rounded down and upper planes rounded up, `margin` whole quanta further out, clamped to 16 bits.
+    lo, hi (3,) floats; returns the three words lo | hi << 16."""
+    base, scale = np.asarray(q_lo, np.float32).astype(np.float64), np.asarray(q_scale, np.float32).astype(np.float64)
+    ql = np.clip(np.floor((np.asarray(lo, np.float64) - base) / scale) - margin, 0, 65535).astype(np.int64)
+    qh = np.clip(np.ceil((np.asarray(hi, np.float64) - base) / scale) + margin, 0, 65535).astype(np.int64)
+    return (ql | (qh << 16)).astype(np.uint32)
+
+
+def quant_params(lo, hi, quanta=65530.0, below=2.0):
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    ext = hi - lo
+    scale = np.where(ext > 0, ext * (1.0 + 1e-6) / quanta, 1e-30)
+    return (lo - below * scale).astype(np.float32), scale.astype(np.float32)
+
+
+INVERTED = np.uint32(0x0000FFFF)
+
+
+def world_box(o2w, lo, hi):
+    corner = np.array([[(c >> a) & 1 for a in range(3)] for c in range(8)], bool)
+    p = np.where(corner, np.asarray(hi, np.float64), np.asarray(lo, np.float64))
+    M = np.asarray(o2w, np.float64).reshape(3, 4)
+    img = p @ M[:, :3].T + M[:, 3]
+    return img.min(axis=0), img.max(axis=0)
+
+
+def build_tree(topo, leaf_box, leaf_ref, q_lo, q_scale, margin=1, first=0):
+    """BvhNodeQ records of the tree `topo`: an interior node is a tuple of one or two children, anything else is a leaf.  leaf_box(leaf)
+    gives (lo, hi) or None for a leaf without a box (its planes are inverted and its link repeats the sibling's, as quantize_bvh2_in
+    leaves it); leaf_ref(leaf) the value a leaf link names.  Interior links are first + index.  A root that is a leaf gets the synthetic
+    single-child root."""
+    from vulkan_raytracing_amd.api import NODEQ_DTYPE
+    if not isinstance(topo, tuple):
+        topo = (topo,)
+    recs = []
+
+    def box_of(t):
+        if not isinstance(t, tuple):
+            return leaf_box(t)
+        bs = [b for b in (box_of(c) for c in t) if b is not None]
+        return (np.min([b[0] for b in bs], axis=0), np.max([b[1] for b in bs], axis=0)) if bs else None
+
+    def emit(t):
+        i = len(recs)
+        recs.append(None)
+        w, link = np.full(6, INVERTED, np.uint32), [None, None]
+        for k, c in enumerate(t):
+            b = box_of(c)
+            if b is not None:
+                w[3 * k:3 * k + 3] = quantise_box(b[0], b[1], q_lo, q_scale, margin)
+                link[k] = first + emit(c) if isinstance(c, tuple) else ~int(leaf_ref(c))
+        if link[0] is None:
+            link[0] = link[1]
+        if link[1] is None:
+            link[1] = link[0]
+        recs[i] = (w, link)
+        return i
+
+    emit(topo)
+    out = np.zeros(len(recs), NODEQ_DTYPE)
+    for i, (w, link) in enumerate(recs):
+        out[i]["w"] = w
+        out[i]["child"] = link
+    return out
+
+
+def balanced(items):
+    items = list(items)
+    if len(items) == 1:
+        return items[0]
+    h = len(items) // 2
+    return (balanced(items[:h]), balanced(items[h:]))
+
+
+def link_meshes(parts, transforms=None):
+    """A snapshot of host-built meshes without a GPU.  parts: one (verts6, idx, nodes, packets, q_lo, q_scale, levels) per mesh, nodes
+    and packets as rt_debug_host_blas returns them (links local to the mesh).  One instance per mesh (identity unless given), a TLAS
+    quantised by the documented rule, one frontier box per mesh (its bounds).  Returns (snapshot, mesh index of every instance)."""
+    from vulkan_raytracing_amd.api import INSTANCE_DEV_DTYPE, NODEQ_DTYPE, TLAS_MESH_DTYPE, TRI_PACKET_DTYPE
+    n = len(parts)
+    meshes, inst = np.zeros(n, TLAS_MESH_DTYPE), np.zeros(n, INSTANCE_DEV_DTYPE)
+    nodes, packets, verts, idx, cover = [], [], [], [], []
+    nn = nt = nf = ni = 0
+    for m, (v, ix, nd, pk, q_lo, q_scale, levels) in enumerate(parts):
+        v, ix = np.ascontiguousarray(v, np.float32).reshape(-1), np.ascontiguousarray(ix, np.uint32).reshape(-1)
+        nd = nd.copy()
+        ch = nd["child"].astype(np.int64)
+        ref = ~ch
+        nd["child"] = np.where(ch >= 0, ch + nn, ~((((ref >> 3) + nt) << 3) | (ref & 7))).astype(np.int32)
+        pos = v.reshape(-1, 6)[np.unique(ix), :3]
+        lo, hi = pos.min(axis=0), pos.max(axis=0)
+        meshes[m] = (nn, 0, nf, ni, m, 1, len(ix) // 3, 1, levels, q_lo, q_scale, lo, hi)
+        M = np.eye(4, dtype=np.float32)[:3].reshape(12) if transforms is None else np.asarray(transforms[m], np.float32).reshape(12)
+        inst[m]["o2w"] = M
+        inst[m]["w2o"] = np.linalg.inv(np.vstack([M.reshape(3, 4).astype(np.float64), [0, 0, 0, 1]]))[:3].reshape(12).astype(np.float32)
+        for f in ("blas_root", "first_float", "first_index", "cover_first", "cover_count", "q_lo", "q_scale"):
+            inst[m][f] = meshes[m][f]
+        inst[m]["mask"] = 0xFF
+        cover.append(np.concatenate([lo, hi]))
+        nodes.append(nd); packets.append(pk); verts.append(v); idx.append(ix)
+        nn += len(nd); nt += len(pk); nf += len(v); ni += len(ix)
+    boxes = [world_box(inst[m]["o2w"], meshes[m]["lo"], meshes[m]["hi"]) for m in range(n)]
+    t_lo, t_s = quant_params(np.min([b[0] for b in boxes], axis=0), np.max([b[1] for b in boxes], axis=0))
+    base = nn + 8
+    tlas = build_tree(balanced(range(n)), lambda i: boxes[i], lambda i: i, t_lo, t_s, margin=1, first=base)
+    snap = {"n_blas_nodes": nn, "tlas_base": base, "tlas_node_count": len(tlas), "tlas_stride": 0, "batch_k": 1, "inst_per_frame": n,
+            "tlas_q_lo": t_lo, "tlas_q_scale": t_s, "blas_nodes": np.concatenate(nodes).astype(NODEQ_DTYPE), "tlas_nodes": tlas,
+            "packets": np.concatenate(packets).astype(TRI_PACKET_DTYPE), "instances": inst, "meshes": meshes,
+            "verts": np.concatenate(verts), "idx": np.concatenate(idx), "cover_boxes": np.array(cover, np.float32).reshape(-1, 6)}
+    return snap, np.arange(n)

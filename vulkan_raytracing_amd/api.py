@@ -16,6 +16,17 @@ UNIFORMS_DTYPE = np.dtype([("position", np.float32, 4), ("right", np.float32, 4)
 MATERIAL_DTYPE = np.dtype([("ka", np.float32, 3), ("ns", np.float32), ("kd", np.float32, 3), ("ni", np.float32), ("ks", np.float32, 3), ("type", np.uint32)])
 MATERIAL_TYPE_OF_INSTANCE = 0xFFFFFFFF
 assert MATERIAL_DTYPE.itemsize == 48
+# device records (csrc/rt_device.h, csrc/tlas_gpu.h) as rt_debug_snapshot / rt_debug_host_blas return them
+NODEQ_DTYPE = np.dtype([("w", np.uint32, 6), ("child", np.int32, 2)])
+TRI_PACKET_DTYPE = np.dtype([("v0", np.float32, 3), ("e1", np.float32, 3), ("e2", np.float32, 3), ("prim", np.uint32), ("pad", np.uint32, 2)])
+INSTANCE_DEV_DTYPE = np.dtype([("w2o", np.float32, 12), ("o2w", np.float32, 12), ("blas_root", np.int32), ("mask", np.uint32), ("custom_index", np.int32),
+                               ("first_float", np.uint32), ("first_index", np.uint32), ("blas_root4", np.int32), ("q_lo", np.float32, 3), ("q_scale", np.float32, 3),
+                               ("type", np.uint32), ("cover_first", np.uint32), ("cover_count", np.uint32), ("pad", np.uint32)])
+TLAS_MESH_DTYPE = np.dtype([("blas_root", np.int32), ("blas_root4", np.int32), ("first_float", np.uint32), ("first_index", np.uint32),
+                            ("cover_first", np.uint32), ("cover_count", np.uint32), ("prim_count", np.uint32), ("built", np.uint32), ("levels", np.int32),
+                            ("q_lo", np.float32, 3), ("q_scale", np.float32, 3), ("lo", np.float32, 3), ("hi", np.float32, 3)])
+assert NODEQ_DTYPE.itemsize == 32 and TRI_PACKET_DTYPE.itemsize == 48 and INSTANCE_DEV_DTYPE.itemsize == 160 and TLAS_MESH_DTYPE.itemsize == 84
+SNAPSHOT_INFO_WORDS = 20
 assert INSTANCE_DTYPE.itemsize == 64 and UNIFORMS_DTYPE.itemsize == 104 and MESH_RANGE_DTYPE.itemsize == 24
 
 
@@ -63,7 +74,7 @@ INSIDE_DIRS = ((0.36, 0.48, 0.8), (-0.8, 0.36, -0.48), (0.48, -0.8, -0.36), (-0.
 
 EXPORTS = ["rt_create", "rt_create_frame_slot", "rt_destroy", "rt_upload_geometry", "rt_build_blas", "rt_set_instances", "rt_set_instances_device", "rt_refit_blas_device", "rt_set_materials", "rt_set_instance_types", "rt_set_uniforms", "rt_set_skybox",
            "rt_trace", "rt_trace_async", "rt_trace_wait", "rt_trace_shard", "rt_set_batch", "rt_trace_shard_batch", "rt_assemble_shards", "rt_shard_rows", "rt_synchronize", "rt_get_stats", "rt_set_timing", "rt_intersect",
-           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_sweep_spheres_device", "rt_sweep_spheres", "rt_point_inside_device", "rt_point_inside", "rt_signed_distance_device", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
+           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_sweep_spheres_device", "rt_sweep_spheres", "rt_point_inside_device", "rt_point_inside", "rt_signed_distance_device", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_host_blas", "rt_debug_snapshot", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
 
 _LIBS = {}
 
@@ -102,6 +113,8 @@ def lib(variant=None):
         L.rt_set_param.argtypes = [vp, C.c_char_p, C.c_int]
         L.rt_debug_check_builders.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp]
         L.rt_debug_sizing.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, vp]
+        L.rt_debug_host_blas.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp]
+        L.rt_debug_snapshot.argtypes = [vp, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.rt_intersect.argtypes = [vp, C.c_size_t, vp, C.c_int, vp, C.c_int, C.POINTER(RtStats)]
         L.rt_intersect_device.argtypes = [vp, C.c_size_t, vp, C.c_int, vp, vp, vp]
         L.rt_intersect_device_flags.argtypes = [vp, C.c_size_t, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
@@ -322,6 +335,29 @@ class RtContext:
         st = RtStats()
         self._chk(self.L.rt_get_stats(self.h, C.byref(st)), "rt_get_stats")
         return st
+
+    def debug_snapshot(self):
+        """rt_debug_snapshot (a test hook, not a product path): what this context's kernels read, copied to the host as numpy structured
+        arrays in the device record layouts.  Returns a dict: the counts of the info call (n_blas_nodes, tlas_base, tlas_node_count,
+        tlas_stride, batch_k, inst_per_frame), tlas_q_lo / tlas_q_scale (float32 (3,)), and the arrays blas_nodes, tlas_nodes (this
+        context's region of its current parity, all frames of a batch), packets, instances, meshes, verts, idx, cover_boxes ((n, 6))."""
+        info = np.zeros(SNAPSHOT_INFO_WORDS, np.uint64)
+        self._chk(self.L.rt_debug_snapshot(self.h, 0, _p(info), info.nbytes, None), "rt_debug_snapshot")
+        i = [int(x) for x in info]
+
+        def item(what, n, dtype):
+            a = np.zeros(n, dtype)
+            got = C.c_size_t(0)
+            self._chk(self.L.rt_debug_snapshot(self.h, what, _p(a) if n else _p(np.zeros(1, np.uint8)), a.nbytes, C.byref(got)), "rt_debug_snapshot")
+            assert got.value == a.nbytes, (what, got.value, a.nbytes)
+            return a
+
+        bits = info[12:18].astype(np.uint32).view(np.float32)
+        return {"n_blas_nodes": i[0], "tlas_base": i[1], "tlas_node_count": i[2], "tlas_stride": i[3], "batch_k": i[4], "inst_per_frame": i[7],
+                "tlas_q_lo": bits[:3].copy(), "tlas_q_scale": bits[3:].copy(),
+                "blas_nodes": item(1, i[0], NODEQ_DTYPE), "tlas_nodes": item(2, i[18], NODEQ_DTYPE), "packets": item(3, i[5], TRI_PACKET_DTYPE),
+                "instances": item(4, i[6], INSTANCE_DEV_DTYPE), "meshes": item(5, i[8], TLAS_MESH_DTYPE), "verts": item(6, i[9], np.float32),
+                "idx": item(7, i[10], np.uint32), "cover_boxes": item(8, 6 * i[11], np.float32).reshape(-1, 6)}
 
     def set_timing(self, on):
         self._chk(self.L.rt_set_timing(self.h, int(on)), "rt_set_timing")
@@ -798,3 +834,15 @@ def check_builders(verts6, idx):
     rc = lib().rt_debug_check_builders(_p(verts6), verts6.size, _p(idx), idx.size, _p(out))
     keys = ("nodes", "leaves", "depth", "max_leaf", "bvh4_nodes", "bvh4_stack_need", "violations", "reached")
     return rc, dict(zip(keys, (int(x) for x in out)))
+
+
+def host_blas(verts6, idx):
+    """rt_debug_host_blas: the quantized BVH2 (links local to the mesh) and the triangle packets of the host builder, without a GPU;
+    returns (status, dict of nodes, packets, q_lo, q_scale)."""
+    verts6 = np.ascontiguousarray(verts6, np.float32)
+    idx = np.ascontiguousarray(idx, np.uint32)
+    n = idx.size // 3
+    nodes, packets, out = np.zeros(max(1, n), NODEQ_DTYPE), np.zeros(max(1, n), TRI_PACKET_DTYPE), np.zeros(8, np.uint64)
+    rc = lib().rt_debug_host_blas(_p(verts6), verts6.size, _p(idx), idx.size, _p(nodes), nodes.nbytes, _p(packets), packets.nbytes, _p(out))
+    bits = out[2:8].astype(np.uint32).view(np.float32)
+    return rc, {"nodes": nodes[:int(out[0])].copy(), "packets": packets[:int(out[1])].copy(), "q_lo": bits[:3].copy(), "q_scale": bits[3:].copy()}

@@ -2039,6 +2039,75 @@ int rt_debug_check_builders(const float* verts6, size_t n_floats, const uint32_t
   return violations ? RT_ERR_INVALID_ARGUMENT : RT_OK;
 }
 
+// Host-only: the quantized tree and the packets rt_build_blas(blas_builder 0) + quantize_bvh2 produce for an indexed mesh, in the record
+// layouts of rt_device.h with links local to the mesh (no cache-line layout).  out8 = nodes, packets, q_lo[3] and q_scale[3] as binary32
+// bit patterns.  The buffers must hold them (a mesh of n triangles has at most max(1, n - 1) nodes and exactly n packets).
+int rt_debug_host_blas(const float* verts6, size_t n_floats, const uint32_t* idx, size_t n_idx, void* nodes, size_t nodes_capacity_bytes,
+                       void* packets, size_t packets_capacity_bytes, uint64_t* out) {
+  if (!verts6 || !idx || !nodes || !packets || !out || n_idx == 0 || n_idx % 3 != 0) return RT_ERR_INVALID_ARGUMENT;
+  const uint32_t n = (uint32_t)(n_idx / 3);
+  for (size_t k = 0; k < n_idx; k++) if ((size_t)idx[k] * 6 + 5 >= n_floats) return RT_ERR_INVALID_ARGUMENT;
+  BuiltBvh bvh; std::vector<TriPacket> tris; std::vector<BvhNodeQ> q; float q_lo[3], q_scale[3];
+  build_blas(verts6, idx, n, bvh, tris);
+  quantize_bvh2(bvh, q, q_lo, q_scale);
+  if (q.size() * sizeof(BvhNodeQ) > nodes_capacity_bytes || tris.size() * sizeof(TriPacket) > packets_capacity_bytes) return RT_ERR_INVALID_ARGUMENT;
+  memcpy(nodes, q.data(), q.size() * sizeof(BvhNodeQ));
+  memcpy(packets, tris.data(), tris.size() * sizeof(TriPacket));
+  out[0] = q.size(); out[1] = tris.size();
+  for (int k = 0; k < 3; k++) { uint32_t a, b; memcpy(&a, &q_lo[k], 4); memcpy(&b, &q_scale[k], 4); out[2 + k] = a; out[5 + k] = b; }
+  return RT_OK;
+}
+
+// Test hook, not a product path: a read-only copy of what the kernels of this context read, as raw bytes in the layouts of rt_device.h
+// and tlas_gpu.h.  Waits for the scene's pending work as rt_build_blas does and launches no kernel.
+//   what 0: RT_SNAPSHOT_INFO_WORDS x uint64 — [0] linked BLAS nodes, [1] tlas_base (global index of this context's TLAS region of its
+//           current parity), [2] nodes of one TLAS, [3] tlas_stride (0 without a batch), [4] batch_k, [5] triangle packets, [6] instance
+//           records (all frames of a batch), [7] instances per frame, [8] meshes, [9] vertex floats, [10] indices, [11] frontier boxes,
+//           [12..14] tlas_q_lo and [15..17] tlas_q_scale as binary32 bit patterns, [18] TLAS nodes copied by what 2
+//   what 1: BvhNodeQ [0, n_blas_nodes)      2: BvhNodeQ of the TLAS region (batch_k * tlas_stride for a batch)      3: TriPacket
+//   what 4: InstanceDev of the current parity      5: TlasMeshDev per mesh      6: vertex floats      7: indices      8: frontier boxes (6 floats)
+// *bytes (optional) receives the size of the item; RT_ERR_INVALID_ARGUMENT when out is NULL or capacity_bytes is smaller.
+int rt_debug_snapshot(rt_ctx* c, int what, void* out, size_t capacity_bytes, size_t* bytes) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  if (!out) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_debug_snapshot: out is NULL");
+  if (what < 0 || what > 8) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_debug_snapshot: what must be 0..8");
+  Scene* S = c->scene;
+  if (!c->tlas_valid || !S->blas_linked || !S->arrays_ready) return fail(c, RT_ERR_NOT_READY, "rt_debug_snapshot: the context has no valid TLAS (rt_set_instances)");
+  { int q = quiesce_scene(c); if (q) return q; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (c->tgpu.stream) HIP_TRY(c, hipStreamSynchronize(c->tgpu.stream));
+  const int par = c->parity;
+  const size_t tlas_nodes = c->batch_k > 1 ? (size_t)c->batch_k * (size_t)c->tlas_stride[par] : (size_t)c->tlas_node_count[par];
+  size_t n_cover = 0;
+  for (const Mesh& m : S->meshes) n_cover = std::max(n_cover, (size_t)m.cover_first + m.cover_count);
+  uint64_t info[20] = {0};
+  info[0] = S->n_blas_nodes; info[1] = tlas_base(c); info[2] = (uint64_t)c->tlas_node_count[par]; info[3] = c->batch_k > 1 ? (uint64_t)c->tlas_stride[par] : 0;
+  info[4] = (uint64_t)c->batch_k; info[5] = S->n_tris; info[6] = (uint64_t)c->n_inst; info[7] = (uint64_t)c->inst_per_frame; info[8] = S->meshes.size();
+  info[9] = S->h_verts.size(); info[10] = S->h_idx.size(); info[11] = n_cover;
+  for (int k = 0; k < 3; k++) { uint32_t a, b; memcpy(&a, &c->tlas_q_lo[k], 4); memcpy(&b, &c->tlas_q_scale[k], 4); info[12 + k] = a; info[15 + k] = b; }
+  info[18] = tlas_nodes;
+  const void* src = nullptr; size_t need = 0; bool host = false;
+  switch (what) {
+    case 0: src = info; need = sizeof(info); host = true; break;
+    case 1: src = S->d_blas_nodes; need = S->n_blas_nodes * sizeof(BvhNodeQ); break;
+    case 2: src = S->d_blas_nodes + tlas_base(c); need = tlas_nodes * sizeof(BvhNodeQ); break;
+    case 3: src = S->d_tris; need = S->n_tris * sizeof(TriPacket); break;
+    case 4: src = c->d_inst[par]; need = (size_t)c->n_inst * sizeof(InstanceDev); break;
+    case 5: src = S->d_mesh_table; need = S->meshes.size() * sizeof(TlasMeshDev); break;
+    case 6: src = S->d_verts; need = S->h_verts.size() * sizeof(float); break;
+    case 7: src = S->d_idx; need = S->h_idx.size() * sizeof(uint32_t); break;
+    default: src = S->d_cover_boxes; need = n_cover * 6 * sizeof(float); break;
+  }
+  if (bytes) *bytes = need;
+  if (need > capacity_bytes) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_debug_snapshot: the buffer holds " + std::to_string(capacity_bytes) + " bytes, item " + std::to_string(what) + " needs " + std::to_string(need));
+  if (!need) return RT_OK;
+  if (host) { memcpy(out, src, need); return RT_OK; }
+  if (!src) return fail(c, RT_ERR_NOT_READY, "rt_debug_snapshot: item " + std::to_string(what) + " is not on the device");
+  HIP_TRY(c, hipMemcpy(out, src, need, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
 // Host-only view of the sizing rules (no device needed): out[0] = grid of k_tail for a device with n_cu compute units that
 // can hold resident_per_cu of its workgroups each (0 = k_tail unusable), out[1] = int32 elements of the spill-stack
 // allocation for that grid, a traversal grid of trace_blocks and ovf_stride entries per thread.

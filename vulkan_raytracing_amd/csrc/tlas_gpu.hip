@@ -143,6 +143,31 @@ __global__ __launch_bounds__(256) void k_tlas_refit(const Box* inst_boxes, const
   }
 }
 
+// The radix tree is as deep as the keys make it: a level per bit in which neighbours differ, and further levels among equal keys.  The
+// kernels' contract is a TLAS of at most TLAS_MAX_DEPTH interior levels (rt_device.h; the host builder enforces it), so a deeper radix
+// tree is replaced by the BALANCED tree over the same Morton order: every range of leaves is split at its middle, ceil(log2 n) levels,
+// 20 at the 2^20 instances the call accepts.  Numbering as in k_radix_tree (the left child of a split at m is node m, the right child
+// node m + 1, the root node 0), so everything downstream is unchanged.  One thread per internal node finds its range from the root.
+constexpr int TLAS_MAX_DEPTH = 20;
+__global__ __launch_bounds__(256) void k_balanced_tree(int n, int2* children, int2* ranges, int* parent_internal, int* parent_leaf) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n - 1) return;
+  int l = 0, r = n - 1, self = 0;
+  for (int step = 0; step < 32 && self != i; step++) {   // (node i lies below [l, r]: among l + 1 .. m on the left, m + 1 .. r - 1 on the right)
+    const int m = l + ((r - l) >> 1);
+    if (i <= m) { r = m; self = m; } else { l = m + 1; self = m + 1; }
+  }
+  if (self != i || r <= l) return;   // (cannot happen)
+  const int m = l + ((r - l) >> 1);
+  const int left = m > l ? m : ~l;
+  const int right = m + 1 < r ? m + 1 : ~r;
+  children[i] = make_int2(left, right);
+  ranges[i] = make_int2(l, r);
+  if (left >= 0) parent_internal[left] = i; else parent_leaf[~left] = i;
+  if (right >= 0) parent_internal[right] = i; else parent_leaf[~right] = i;
+  if (i == 0) parent_internal[0] = -1;
+}
+
 // quant_params (bvh_build.cpp) over the instance bounds, in binary64 like the host
 __global__ void k_tlas_quant(TlasSummary* s, const int* height, int n) {
   const int k = threadIdx.x;
@@ -283,16 +308,26 @@ int tlas_gpu_build(TlasGpu& g, const TlasBuildArgs& a, std::string& err) {
       TG_TRY(hipcub::DeviceRadixSort::SortPairs(g.d_sort_tmp, bytes, g.d_keys, g.d_keys2, g.d_vals, g.d_vals2, n, 0, 30, s));
       hipLaunchKernelGGL(k_radix_tree, dim3(nb), dim3(256), 0, s, g.d_keys2, n, g.d_children, g.d_ranges, g.d_parent_int, g.d_parent_leaf);
     }
-    TG_TRY(hipMemsetAsync(g.d_flags, 0, (size_t)(n - 1) * sizeof(uint32_t), s));
-    hipLaunchKernelGGL(k_tlas_refit, dim3(nb), dim3(256), 0, s, boxes, g.d_vals2, n, g.d_children, g.d_parent_int, g.d_parent_leaf, node_boxes, g.d_height, g.d_flags);
   }
-  hipLaunchKernelGGL(k_tlas_quant, dim3(1), dim3(64), 0, s, g.d_sum, g.d_height, n);
+  // boxes bottom-up over the topology, the dequantisation and the depth, the nodes, the far flag, one readback; once more over the
+  // balanced tree when the radix tree turns out deeper than the contract allows
   const int n_nodes = n >= 2 ? n - 1 : 1;
-  hipLaunchKernelGGL(k_tlas_emit, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, s, boxes, g.d_vals2, n, g.d_children, node_boxes, g.d_sum, a.d_nodes, a.node_base);
-  hipLaunchKernelGGL(k_tlas_far, dim3(nb), dim3(256), 0, s, rec, n, a.meshes, a.n_meshes, a.d_inst, g.d_sum);
-  TG_TRY(hipGetLastError());
-  TG_TRY(hipMemcpyAsync(g.h_sum, g.d_sum, sizeof(TlasSummary), hipMemcpyDeviceToHost, s));
-  TG_TRY(hipStreamSynchronize(s));
+  for (int pass = 0; pass < 2; pass++) {
+    if (pass == 1) {
+      if (a.refit || n < 2 || g.h_sum->depth <= TLAS_MAX_DEPTH) break;
+      hipLaunchKernelGGL(k_balanced_tree, dim3(nb), dim3(256), 0, s, n, g.d_children, g.d_ranges, g.d_parent_int, g.d_parent_leaf);   // (the radix tree is too deep)
+    }
+    if (n >= 2) {
+      TG_TRY(hipMemsetAsync(g.d_flags, 0, (size_t)(n - 1) * sizeof(uint32_t), s));
+      hipLaunchKernelGGL(k_tlas_refit, dim3(nb), dim3(256), 0, s, boxes, g.d_vals2, n, g.d_children, g.d_parent_int, g.d_parent_leaf, node_boxes, g.d_height, g.d_flags);
+    }
+    hipLaunchKernelGGL(k_tlas_quant, dim3(1), dim3(64), 0, s, g.d_sum, g.d_height, n);
+    hipLaunchKernelGGL(k_tlas_emit, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, s, boxes, g.d_vals2, n, g.d_children, node_boxes, g.d_sum, a.d_nodes, a.node_base);
+    hipLaunchKernelGGL(k_tlas_far, dim3(nb), dim3(256), 0, s, rec, n, a.meshes, a.n_meshes, a.d_inst, g.d_sum);
+    TG_TRY(hipGetLastError());
+    TG_TRY(hipMemcpyAsync(g.h_sum, g.d_sum, sizeof(TlasSummary), hipMemcpyDeviceToHost, s));
+    TG_TRY(hipStreamSynchronize(s));
+  }
   if (!a.refit) g.topo_n = n;
   return 0;
 #undef TG_TRY

@@ -138,6 +138,40 @@ def grazing_rays(n, seed):
     return rays
 
 
+# ---- corridors: geometry whose every ray along the axis holds one stack entry per tree level (tests/stack_reference.py) --------
+CORRIDOR_SIDE = 16.0
+CORRIDOR_SPACING = {256: 0.05, 512: 0.03, 1024: 0.02, 2048: 0.015, 4096: 0.01, 8192: 0.006, 16384: 0.004, 32768: 0.002, 65536: 0.001}
+
+
+def corridor(n, spacing=None, normal=(0.0, 0.0, 1.0)):
+    """n parallel squares (2 triangles each) of side CORRIDOR_SIDE about the z axis, facing +z, square k in the plane z = -k * spacing.
+    Every box of a tree over them has the same footprint, and the host's SAH builder halves the row at each level: a ray that runs
+    along the row inside the footprint, in either direction, enters both children of every node and keeps one of them on its stack
+    per level.  Returns (verts6 (4n, 6) float32 with the given vertex normal, idx (6n,) uint32): triangles 2k and 2k + 1 are square k."""
+    spacing = CORRIDOR_SPACING[n] if spacing is None else spacing
+    h = CORRIDOR_SIDE / 2
+    v = np.zeros((n, 4, 6), np.float32)
+    v[:, :, 0] = (-h, h, h, -h)
+    v[:, :, 1] = (-h, -h, h, h)
+    v[:, :, 2] = (-spacing * np.arange(n, dtype=np.float64))[:, None]
+    v[:, :, 3:] = normal
+    idx = (4 * np.arange(n, dtype=np.uint32)[:, None] + np.array([0, 1, 2, 0, 2, 3], np.uint32)).reshape(-1)
+    return v.reshape(-1, 6), idx
+
+
+def corridor_length(n, spacing=None):
+    return (n - 1) * (CORRIDOR_SPACING[n] if spacing is None else spacing)
+
+
+def write_obj(path, verts6, idx):
+    """the mesh as an OBJ file with one normal per vertex, triangles in order"""
+    v = np.asarray(verts6, np.float32).reshape(-1, 6)
+    t = np.asarray(idx, np.int64).reshape(-1, 3) + 1
+    with open(path, "w") as f:
+        f.write("".join("v %.9g %.9g %.9g\nvn %.9g %.9g %.9g\n" % tuple(r) for r in v.tolist()))
+        f.write("".join("f %d//%d %d//%d %d//%d\n" % (a, a, b, b, c, c) for a, b, c in t.tolist()))
+
+
 # ---- fixtures produced by interpreting the reference's own SPIR-V shaders (tests/golden/make_spirv_fixtures.py) ---------------
 class SpirvFixtureScene:
     def __init__(self, meta, bounces, pixels):

@@ -11,7 +11,7 @@ import os
 import numpy as np
 import pytest
 
-from tests import scenes
+from tests import scenes, stack_reference
 from tests.exact import assert_frame_equals_oracle, assert_hits_equal_oracle
 from tests.shade_reference import pinhole_rays
 from vulkan_raytracing_amd import RtContext, api, host, tiling
@@ -224,18 +224,7 @@ def axis_rays(n, seed):
     return rays
 
 
-def chain_mesh(path, n=120, s=0.5):
-    """n copies of one large triangle (x 80 .. 140, y -20 .. 40) stacked below the plane z = 0 at z = -4 s^k: every box of the
-    host builder's tree covers the same footprint, and a ray down through it enters every one.  Nearer the camera (above) lies the
-    subtree of the smaller offsets, so such a walk goes down the whole chain and keeps the farther sibling of each level on its
-    stack: as many entries as the tree has levels, more than the LDS part of the stack holds"""
-    with open(path, "w") as f:
-        for k in range(n):
-            z = -4.0 * s ** k
-            for v in ((80.0, -20.0, z), (140.0, -20.0, z), (80.0, 40.0, z)):
-                f.write("v %.9g %.9g %.9g\nvn 0 0 1\n" % v)
-        for k in range(n):
-            f.write("f %d//%d %d//%d %d//%d\n" % (3 * k + 1, 3 * k + 1, 3 * k + 2, 3 * k + 2, 3 * k + 3, 3 * k + 3))
+CORRIDOR = 8192                 # squares of the frame's corridor: 12 levels, 14 stack entries with the sentinel and the marker (the oracle visits half the tree per ray)
 
 
 DEEP_W, DEEP_H = 1024, 640      # more pixels than the threads of the resident part of the largest grid
@@ -243,17 +232,21 @@ DEEP_W, DEEP_H = 1024, 640      # more pixels than the threads of the resident p
 
 def test_spill_areas_grow_with_the_grid(tmp_path):
     """Two host-built trees: a 40-level one (deep_mesh: its spill area per thread is wider than the smallest) that the queries walk
-    along its axis, and a chain (chain_mesh) that fills the frame, so that every primary ray of the frame spills (its walk starts at
-    the TLAS root: camera_records 0).  A frame and a query on the smallest grid (trace_blocks_per_cu 1), then on the largest, with
+    along its axis, and a corridor (scenes.corridor: a row of squares whose tree a ray along the row walks with one stack entry per
+    level) that fills the frame, so that every primary ray of the frame spills (its walk starts at the TLAS root: camera_records 0);
+    the model of tests/stack_reference.py says so for a sample of them, on this context's own trees.  A frame and a query on the
+    smallest grid (trace_blocks_per_cu 1), then on the largest, with
     trace_rays_per_lane 1 and trace_min_blocks above the grid so that k_trace trims none of it.  The work is handed out in chunks (64
     rays, or a run of pixels) to every wave that starts, and there are more rays than the resident part of the grid has threads (524288 query rays,
     655360 pixels), so workgroups beyond the first grid's walk deep rays too: both spill areas, the frame's and the query
     workspace's, must have grown with the grid."""
     import torch
-    deep, chain = str(tmp_path / "deep.obj"), str(tmp_path / "chain.obj")
+    deep, chain = str(tmp_path / "deep.obj"), str(tmp_path / "corridor.obj")
     deep_mesh(deep)
-    chain_mesh(chain)
-    for path, depth in ((deep, 40), (chain, 24)):
+    cv, ci = scenes.corridor(CORRIDOR, spacing=0.0005)  # 4.1 long: the rays of the frame's corners stay inside its footprint to the end
+    cv[:, 0] += 110.0; cv[:, 1] += 10.0                 # x 102 .. 118, y 2 .. 18: out of the deep mesh's way
+    scenes.write_obj(chain, cv, ci)
+    for path, depth in ((deep, 40), (chain, 12)):
         g = host.SceneGeometry([path])
         rc, info = api.check_builders(g.verts, g.idx)
         assert rc == 0 and info["depth"] >= depth, (path, info)
@@ -268,8 +261,8 @@ def test_spill_areas_grow_with_the_grid(tmp_path):
         u = host.default_uniforms(max_bounce_count=1, samples_per_pixel=1, center_object_type=0, orbiting_object_type=0,
                                   orbiting_object_primitive_offset=geom.orbiting_primitive_offset,
                                   orbiting_object_vertex_offset=geom.orbiting_vertex_offset)
-        u[0]["position"][:3] = (100.0, 0.0, 6.0)           # looking down on the chain; the deep mesh lies out of view
-        u[0]["light_position"][:3] = (100.0, 3.0, 10.0)
+        u[0]["position"][:3] = (110.0, 10.0, 2.5)          # looking down the corridor, which fills the view; the deep mesh lies out of it
+        u[0]["light_position"][:3] = (110.0, 13.0, 10.0)
         sp = scenes.ScenePair([deep, chain], np.asarray(inst, INSTANCE_DTYPE), u, sky=scenes.synthetic_skybox(32), ctx=c)
         rays = axis_rays(1 << 19, seed=5)
         bf = sp.orc.intersect(rays, use_bvh=False)
@@ -281,7 +274,10 @@ def test_spill_areas_grow_with_the_grid(tmp_path):
         for i, (x, y) in enumerate(xy):
             od = sp.orc.primary_ray(x, y, DEEP_W, DEEP_H, 0)
             prim[i] = (od[0], od[1], od[2], 0.001, od[3], od[4], od[5], 10000.0)
-        assert (sp.orc.intersect(prim, use_bvh=False)["inst"] == 1).all()    # the chain fills the frame
+        assert (sp.orc.intersect(prim, use_bvh=False)["inst"] == 1).all()    # the corridor fills the frame
+        model = stack_reference.StackModel(c.debug_snapshot())
+        peaks = [model.first(q) for q in stack_reference.rays_of(prim)]
+        assert stack_reference.stack2_lds() == 12 and min(peaks) >= 12 + 2, peaks       # every one of them spills
         for params in ({}, {"trace_blocks_per_cu": 8, "trace_rays_per_lane": 1, "trace_min_blocks": 4096}):
             for k, v in params.items():
                 c.set_param(k, v)

@@ -1032,6 +1032,11 @@ constexpr int MODE_QUERY_FLAGS = 4;   // MODE_QUERY with ray flags and a cull ma
 #define RT_STACK2_LDS 12   /* 12 entries in LDS (3 KB per wave) let 6 blocks share a CU; deeper paths spill to HBM */
 #endif
 constexpr int STACK2_LDS = RT_STACK2_LDS;
+// An entry record is seeded straight into the LDS rows, without push(): the sentinel in row 0 and up to ENTRY_WORDS words in rows
+// 1 .. ENTRY_WORDS (trace_body, beam_body, beam_shadow_body: stk[(1u + k) * 64u]).  Row STACK2_LDS is the scratch row and entries from
+// there on are read back from the spill area, so the seed must end below it.  The unrolled fast visits add nothing to the bound: their
+// `deep` guard (sp + UNROLL > STACK2_LDS) sends a stack that close to the end through push() / pop(), whatever the value.
+static_assert(STACK2_LDS >= 1 + ENTRY_WORDS, "RT_STACK2_LDS: the LDS part of the stack must hold the sentinel and the words of an entry record");
 constexpr uint32_t REFILL_MIN = RT_REFILL_MIN;
 
 // experiment builds (-DRT_EXP_PHASE_SEL=k): diag = (times region k ran, wave cycles spent in it, wave cycles); regions:

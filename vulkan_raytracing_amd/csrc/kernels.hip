@@ -2277,6 +2277,7 @@ void launch_hit_kind(const SceneDev& sc, const float4* rays, const HitRec* hits,
   hipLaunchKernelGGL(k_hit_kind, dim3((n + 255u) / 256u), dim3(256), 0, s, sc, rays, hits, reinterpret_cast<uint32_t*>(attr), n);
 }
 
+#include "walk_common.inc"   // the stack, the chunk feed, the trip exit and the counters of the record-level walks below
 #include "kernels_hits.inc"   // k_query_hits, k_query_hits_surface: the K nearest hits of every ray and their count (rt_intersect_device_hits)
 
 // ---- caller-generated rays (rt_shade_rays_device): the frame's bounce pipeline between an ingest and a per-point resolve

@@ -1,10 +1,8 @@
 // kernels_closest.inc — included by kernels.hip (product and alt translation units alike).
 // rt_closest_point_device: for every query point the nearest point of the scene's surface within the record's radius.  A record-level
-// walk of its own, like kernels_hits.inc: no frame kernel and no k_trace instantiation changes.
+// walk of its own (walk_common.inc: the stack, the chunk feed, the trip exit, the counters), one lane per point: no frame kernel and no
+// k_trace instantiation changes.
 //
-//  * one lane per point; a wave takes 64-point chunks from one cursor of the query's counter block and a lane that finishes takes the
-//    next point of the wave's chunk (ballot + prefix rank), exactly as k_query_hits;
-//  * per-lane stack: STACK2_LDS entries in LDS, deeper ones in the query's spill area (ovf_stride ints per thread of the grid);
 //  * the box test is the point-to-box distance on the dequantised planes: in world space for TLAS nodes, in the instance's object space
 //    for BLAS nodes, there times s_i <= sigma_min(linear part of o2w) (k_closest_scale), which makes it a lower bound on the world
 //    distance under any affine instance;
@@ -108,25 +106,20 @@ __device__ __forceinline__ float closest_tri(F3 p, F3 a, F3 ab, F3 ac, float& u,
 // the deflated squared distance from q to the quantised box (wx, wy, wz) of a tree with dequantisation (q_lo, q_scale): every axis
 // distance shortened by `slack`, the sum times `scale2`
 __device__ __forceinline__ float box_bound(uint32_t wx, uint32_t wy, uint32_t wz, F3 q, F3 q_lo, F3 q_scale, float slack, float scale2) {
-  const float lx = __builtin_fmaf((float)(wx & 0xFFFFu), q_scale.x, q_lo.x), hx = __builtin_fmaf((float)(wx >> 16), q_scale.x, q_lo.x);
-  const float ly = __builtin_fmaf((float)(wy & 0xFFFFu), q_scale.y, q_lo.y), hy = __builtin_fmaf((float)(wy >> 16), q_scale.y, q_lo.y);
-  const float lz = __builtin_fmaf((float)(wz & 0xFFFFu), q_scale.z, q_lo.z), hz = __builtin_fmaf((float)(wz >> 16), q_scale.z, q_lo.z);
-  const float dx = fmaxf(fmaxf(lx - q.x, q.x - hx) - slack, 0.0f);
-  const float dy = fmaxf(fmaxf(ly - q.y, q.y - hy) - slack, 0.0f);
-  const float dz = fmaxf(fmaxf(lz - q.z, q.z - hz) - slack, 0.0f);
+  F3 lo, hi;
+  box_planes(wx, wy, wz, q_lo, q_scale, lo, hi);
+  const float dx = fmaxf(fmaxf(lo.x - q.x, q.x - hi.x) - slack, 0.0f);
+  const float dy = fmaxf(fmaxf(lo.y - q.y, q.y - hi.y) - slack, 0.0f);
+  const float dz = fmaxf(fmaxf(lo.z - q.z, q.z - hi.z) - slack, 0.0f);
   return (dx * dx + dy * dy + dz * dz) * scale2;
 }
 
 template <bool COUNT>
 __device__ __forceinline__ void closest_body(const ClosestArgs& a) {
   __shared__ int s_stack[4][STACK2_LDS][64];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  int* const stk = &s_stack[wave][0][lane];   // entry e at stk[e * 64]
-  int32_t* const ovf = a.ovf_stack + (size_t)(blockIdx.x * 256u + threadIdx.x) * a.sc.ovf_stride;
+  WalkStack st(s_stack, a.ovf_stack, a.sc.ovf_stride);
+  WalkFeed feed;
   constexpr int NONE = 0x7FFFFFFF;            // best_inst / best_prim before the first candidate: every (inst, prim) precedes it
-
-  uint32_t chunk_next = 0, chunk_end = 0;
-  bool drained = false;
 
   bool need = true;
   uint32_t pt = 0;
@@ -135,86 +128,55 @@ __device__ __forceinline__ void closest_body(const ClosestArgs& a) {
   F3 q_lo = wp, q_scale = wp;                 // dequantisation of that tree
   float best = 0.f, best_u = 0.f, best_v = 0.f;
   int best_prim = NONE, best_inst = NONE;
-  int cur = REF_DONE, cur_inst = -1, sp = 0;
+  int cur = REF_DONE, cur_inst = -1;
   unsigned long long cnt_nodes = 0, cnt_tris = 0;
 
-  auto push = [&](int v) {
-    if (sp < STACK2_LDS) stk[sp * 64] = v;
-    else *reinterpret_cast<volatile int32_t*>(ovf + (sp - STACK2_LDS)) = v;
-    sp++;
-  };
-  auto pop = [&]() {
-    sp--;
-    if (sp < STACK2_LDS) cur = stk[sp * 64];
-    else cur = *reinterpret_cast<volatile int32_t*>(ovf + (sp - STACK2_LDS));
-  };
-  auto world_space = [&]() { q = wp; slack = w_slack; scale2 = CP_REL; q_lo = mk3(a.sc.tlas_q_lo[0], a.sc.tlas_q_lo[1], a.sc.tlas_q_lo[2]); q_scale = mk3(a.sc.tlas_q_scale[0], a.sc.tlas_q_scale[1], a.sc.tlas_q_scale[2]);
-  };
+  auto world_space = [&]() { q = wp; slack = w_slack; scale2 = CP_REL; tlas_dequant(a.sc, q_lo, q_scale); };
 
   for (;;) {
-    // ---- refill: idle lanes take the next points of the wave's chunk, a new chunk when it is used up
-    const uint64_t need_mask = __ballot(need);
-    if (need_mask != 0 && !drained) {
-      if (chunk_next == chunk_end) {
-        uint32_t c = 0;
-        if (lane == 0) c = atomicAdd(a.cursor, 1u);
-        c = (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
-        const uint64_t b = (uint64_t)c * 64u;
-        if (b >= a.n) drained = true;
-        else { chunk_next = (uint32_t)b; chunk_end = (uint32_t)min((uint64_t)a.n, b + 64u); }
-      }
-      if (!drained) {
-        const uint32_t rank = prefix_rank(need_mask), avail = chunk_end - chunk_next;
-        if (need && rank < avail) {
-          pt = chunk_next + rank;
-          const float4 r = ld_stream(&a.points[pt]);
-          wp = mk3(r.x, r.y, r.z);
-          const bool valid = finite_bits(r.x) && finite_bits(r.y) && finite_bits(r.z) && r.w >= 0.0f;
-          best = r.w * r.w; best_u = 0.f; best_v = 0.f; best_prim = NONE; best_inst = NONE;
-          const float pmag = fmaxf(fmaxf(__builtin_fabsf(r.x), __builtin_fabsf(r.y)), __builtin_fabsf(r.z));
-          float tmag = 0.f;
-          for (int k = 0; k < 3; k++)
-            tmag = fmaxf(tmag, fmaxf(__builtin_fabsf(a.sc.tlas_q_lo[k]), __builtin_fabsf(__builtin_fmaf(65535.0f, a.sc.tlas_q_scale[k], a.sc.tlas_q_lo[k]))));
-          w_slack = CP_ABS * fmaxf(fmaxf(pmag, tmag), a.inst_scale[0]);
-          world_space();
-          cur_inst = -1;
-          stk[0] = REF_DONE; sp = 1; cur = valid ? a.sc.tlas_root : REF_DONE;
-          need = false;
-        }
-        const uint32_t n_need = (uint32_t)__builtin_popcountll(need_mask);
-        chunk_next += n_need < avail ? n_need : avail;
-      }
+    // ---- refill: idle lanes take the next points of the wave's chunk
+    const uint32_t rec = feed.take(__ballot(need), a.cursor, a.n);
+    if (need && rec != WALK_NONE) {
+      pt = rec;
+      const float4 r = ld_stream(&a.points[pt]);
+      wp = mk3(r.x, r.y, r.z);
+      const bool valid = finite_bits(r.x) && finite_bits(r.y) && finite_bits(r.z) && r.w >= 0.0f;
+      best = r.w * r.w; best_u = 0.f; best_v = 0.f; best_prim = NONE; best_inst = NONE;
+      const float pmag = fmaxf(fmaxf(__builtin_fabsf(r.x), __builtin_fabsf(r.y)), __builtin_fabsf(r.z));
+      w_slack = CP_ABS * fmaxf(fmaxf(pmag, tlas_magnitude(a.sc, 0.f)), a.inst_scale[0]);
+      world_space();
+      cur_inst = -1;
+      st.reset(); cur = valid ? a.sc.tlas_root : REF_DONE;
+      need = false;
     }
     if (__ballot(!need) == 0) break;   // every lane idle and the points used up
 
     // ---- interior nodes: every lane at one takes a visit; the trip repeats while most live lanes are interior
     for (;;) {
       if (cur >= 0) {
-        const uint4* np = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(a.sc.blas_nodes) + ((uint32_t)cur << 5));
-        const uint4 Q0 = np[0], Q1 = np[1];
+        uint4 Q0, Q1;
+        walk_node(a.sc, cur, Q0, Q1);
         if (COUNT) cnt_nodes++;
         const float b0 = box_bound(Q0.x, Q0.y, Q0.z, q, q_lo, q_scale, slack, scale2);
         const float b1 = box_bound(Q0.w, Q1.x, Q1.y, q, q_lo, q_scale, slack, scale2);
-        // (a missing child is an inverted box, as in k_query_hits' far case; !(b > best): inclusive, and an unbounded best opens all)
-        const bool h0 = (Q0.x & 0xFFFFu) <= (Q0.x >> 16) && !(b0 > best);
-        const bool h1 = (Q0.w & 0xFFFFu) <= (Q0.w >> 16) && !(b1 > best);
+        // (!(b > best): inclusive, and an unbounded best opens all)
+        const bool h0 = box_present(Q0.x) && !(b0 > best);
+        const bool h1 = box_present(Q0.w) && !(b1 > best);
         if (h0 && h1) {
           const bool swap = b1 < b0;
-          push(swap ? (int)Q1.z : (int)Q1.w);
+          st.push(swap ? (int)Q1.z : (int)Q1.w);
           cur = swap ? (int)Q1.w : (int)Q1.z;
         } else if (h0) cur = (int)Q1.z;
         else if (h1) cur = (int)Q1.w;
-        else pop();
+        else cur = st.pop();
       }
-      const uint32_t live = 64u - (uint32_t)__builtin_popcountll(__ballot(need));
-      const uint32_t n_int = (uint32_t)__builtin_popcountll(__ballot(cur >= 0));
-      if (n_int == 0 || n_int * 8u < live * 5u) break;
+      if (walk_trip_done(need, cur)) break;
     }
 
     if (!need && cur < 0 && cur > REF_MARK && cur_inst >= 0) {
       // ---- BLAS leaf: the canonical test of every packet, in world space; the smallest key (d2, inst, prim) stays
-      const uint32_t ref = (uint32_t)(~cur);
-      const uint32_t first = ref >> 3, nt = (ref & 7u) + 1u;
+      uint32_t first, nt;
+      walk_leaf(cur, first, nt);
       const float* m = a.sc.inst[cur_inst].o2w;
       for (uint32_t j = 0; j < nt; j++) {
         const float4* tp = a.sc.tris + (size_t)(first + j) * 3;
@@ -227,13 +189,13 @@ __device__ __forceinline__ void closest_body(const ClosestArgs& a) {
           best = d2; best_u = uu; best_v = vv; best_prim = prim; best_inst = cur_inst;
         }
       }
-      pop();
+      cur = st.pop();
     }
     if (!need && cur == REF_MARK) {
       // ---- leave the instance
       cur_inst = -1;
       world_space();
-      pop();
+      cur = st.pop();
     }
     if (!need && cur < 0 && cur > REF_MARK && cur_inst < 0) {
       // ---- TLAS leaf: enter the instance if the call's mask lets it (point -> object space, the slack of both spaces in object units)
@@ -256,9 +218,9 @@ __device__ __forceinline__ void closest_body(const ClosestArgs& a) {
         }
         slack = CP_ABS * om + wm / s;   // (s == 0: an infinite slack, every bound 0)
         scale2 = CP_REL * (s * s);
-        push(REF_MARK);
+        st.push(REF_MARK);
         cur_inst = ii; cur = I->blas_root;
-      } else pop();
+      } else cur = st.pop();
     }
     if (!need && cur == REF_DONE) {
       // ---- finished: the record, or the miss form with the radius as given
@@ -269,16 +231,7 @@ __device__ __forceinline__ void closest_body(const ClosestArgs& a) {
       need = true;
     }
   }
-  if (COUNT) {
-    for (int off = 32; off > 0; off >>= 1) {
-      cnt_nodes += __shfl_down((unsigned long long)cnt_nodes, off);
-      cnt_tris += __shfl_down((unsigned long long)cnt_tris, off);
-    }
-    if (lane == 0) {
-      atomicAdd(reinterpret_cast<unsigned long long*>(a.counters + CNT_NODE_VISITS), (unsigned long long)cnt_nodes);
-      atomicAdd(reinterpret_cast<unsigned long long*>(a.counters + CNT_TRI_TESTS), (unsigned long long)cnt_tris);
-    }
-  }
+  if (COUNT) walk_flush_counters(a.counters, cnt_nodes, cnt_tris);
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_CLOSEST_WAVES_PER_EU))) void k_closest_point(ClosestArgs a) { closest_body<false>(a); }
@@ -315,14 +268,9 @@ void launch_closest_scale(const SceneDev& sc, float* inst_scale, hipStream_t s) 
 
 void launch_closest_point(const SceneDev& sc, const float4* points, uint32_t cull_mask, const float* inst_scale, HitRec* hits, uint32_t n, int32_t* ovf_stack,
                           uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s) {
-  hipLaunchKernelGGL(k_query_init, dim3(1), dim3(64), 0, s, counters, n);   // (zeroes the chunk cursor, cnt_work(0, 0))
   ClosestArgs a{};
-  a.sc = sc; a.points = points; a.inst_scale = inst_scale; a.cull_mask = cull_mask; a.n = n; a.hits = hits;
-  a.cursor = counters + cnt_work(0, 0); a.counters = counters; a.ovf_stack = ovf_stack;
-  // the persistent grid the spill area is sized for, no larger than the points need
-  const uint32_t blocks = min((uint32_t)cfg.trace_blocks, (n + 255u) / 256u);
-  if (counting) hipLaunchKernelGGL(k_closest_point_count, dim3(blocks), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(k_closest_point, dim3(blocks), dim3(256), 0, s, a);
+  a.sc = sc; a.points = points; a.inst_scale = inst_scale; a.cull_mask = cull_mask; a.n = n; a.hits = hits; a.counters = counters; a.ovf_stack = ovf_stack;
+  launch_walk(k_closest_point, k_closest_point_count, a, counters, counting, cfg, s);
 }
 
 void launch_closest_side(const SceneDev& sc, const float4* points, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s) {

@@ -1,13 +1,11 @@
 // kernels_hits.inc — included by kernels.hip (product and alt translation units alike).
 // rt_intersect_device_hits: the K nearest accepted candidates of every ray and the number of them (VK_KHR_ray_query's
-// rayQueryProceedEXT loop in data form).  A record-level walk of its own, not a mode of trace_body: the frame kernels and the
-// k_trace query instantiations stay exactly what they were.
+// rayQueryProceedEXT loop in data form).  A record-level walk of its own (walk_common.inc: the stack, the chunk feed, the trip exit),
+// not a mode of trace_body: the frame kernels and the k_trace query instantiations stay exactly what they were.
 //
-//  * one lane per ray; a wave takes 64-ray chunks from one cursor of the query's counter block and a lane that finishes takes the
-//    next ray of the wave's chunk (ballot + prefix rank), so lanes stay busy without the phased loop of k_trace;
+//  * one lane per ray, without the phased loop of k_trace;
 //  * the quantised BVH2 with the far-ray logic always on (origins are arbitrary): slab_q / slab_q_far, a far ray in world space opens
 //    every TLAS child, exactly as trace_body's generic visit (interior_step);
-//  * per-lane stack: STACK2_LDS entries in LDS, deeper ones in the query's spill area (ovf_stride ints per thread of the grid);
 //  * the instance rules of MODE_QUERY_FLAGS (query_enters) and its facing cull (tri_test_facing) over the ray's own [tmin, tmax];
 //    TERMINATE_ON_FIRST_HIT is ignored, every accepted candidate counts;
 //  * the list: in the lane's own row of the caller's hit array, kept sorted by (t, inst, prim) by insertion; only the count and
@@ -38,15 +36,10 @@ __device__ __forceinline__ bool hit_before(float t, int inst, int prim, const Hi
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_HITS_WAVES_PER_EU))) void k_query_hits(HitsArgs a) {
   __shared__ int s_stack[4][STACK2_LDS][64];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  int* const stk = &s_stack[wave][0][lane];   // entry e at stk[e * 64]
-  int32_t* const ovf = a.ovf_stack + (size_t)(blockIdx.x * 256u + threadIdx.x) * a.sc.ovf_stride;
+  WalkStack st(s_stack, a.ovf_stack, a.sc.ovf_stride);
+  WalkFeed feed;
   const uint32_t K = a.k;
   const bool prune = a.counts == nullptr;
-
-  // wave-uniform work distribution: the current 64-ray chunk
-  uint32_t chunk_next = 0, chunk_end = 0;
-  bool drained = false;
 
   // per-lane ray state
   bool need = true;
@@ -55,84 +48,57 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_HITS_WAV
   F3 wo = mk3(0, 0, 0), wd = mk3(0, 0, 1), co = wo, cd = wd, qs = mk3(1, 1, 1), qb = mk3(0, 0, 0);
   uint3 rot = make_uint3(0u, 0u, 0u);
   bool far = false;
-  int cur = REF_DONE, cur_inst = -1, sp = 0;
+  int cur = REF_DONE, cur_inst = -1;
   HitRec* row = nullptr;
 
-  auto push = [&](int v) {
-    if (sp < STACK2_LDS) stk[sp * 64] = v;
-    else *reinterpret_cast<volatile int32_t*>(ovf + (sp - STACK2_LDS)) = v;
-    sp++;
-  };
-  auto pop = [&]() {
-    sp--;
-    if (sp < STACK2_LDS) cur = stk[sp * 64];
-    else cur = *reinterpret_cast<volatile int32_t*>(ovf + (sp - STACK2_LDS));
-  };
   auto world_space = [&]() {
     quant_space(wo, wd, a.sc.tlas_q_lo, a.sc.tlas_q_scale, qs, qb, rot); far = quant_far_o(wo, a.sc.tlas_q_lo, a.sc.tlas_q_scale);
   };
 
   for (;;) {
-    // ---- refill: idle lanes take the next rays of the wave's chunk, a new chunk when it is used up
-    const uint64_t need_mask = __ballot(need);
-    if (need_mask != 0 && !drained) {
-      if (chunk_next == chunk_end) {
-        uint32_t c = 0;
-        if (lane == 0) c = atomicAdd(a.cursor, 1u);
-        c = (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
-        const uint64_t b = (uint64_t)c * 64u;
-        if (b >= a.n) drained = true;
-        else { chunk_next = (uint32_t)b; chunk_end = (uint32_t)min((uint64_t)a.n, b + 64u); }
-      }
-      if (!drained) {
-        const uint32_t rank = prefix_rank(need_mask), avail = chunk_end - chunk_next;
-        if (need && rank < avail) {
-          ray = chunk_next + rank;
-          const float4 ro = ld_stream(&a.rays[2u * (size_t)ray]), rd = ld_stream(&a.rays[2u * (size_t)ray + 1u]);
-          const uint32_t w = a.ray_words ? (uint32_t)ld_stream(reinterpret_cast<const int*>(a.ray_words) + ray) : 0xFF000000u;
-          qword = ((a.query_word | w) & QF_FLAGS) | (a.query_word & w & 0xFF000000u);
-          tmin = ro.w; tmax = rd.w; lim = tmax;
-          wo = mk3(ro.x, ro.y, ro.z); wd = mk3(rd.x, rd.y, rd.z);
-          co = wo; cd = wd;
-          world_space();
-          cur_inst = -1; count = 0;
-          stk[0] = REF_DONE; sp = 1; cur = a.sc.tlas_root;
-          row = a.hits + (size_t)ray * K;
-          need = false;
-        }
-        const uint32_t n_need = (uint32_t)__builtin_popcountll(need_mask);
-        chunk_next += n_need < avail ? n_need : avail;
-      }
+    // ---- refill: idle lanes take the next rays of the wave's chunk
+    const uint32_t rec = feed.take(__ballot(need), a.cursor, a.n);
+    if (need && rec != WALK_NONE) {
+      ray = rec;
+      const float4 ro = ld_stream(&a.rays[2u * (size_t)ray]), rd = ld_stream(&a.rays[2u * (size_t)ray + 1u]);
+      const uint32_t w = a.ray_words ? (uint32_t)ld_stream(reinterpret_cast<const int*>(a.ray_words) + ray) : 0xFF000000u;
+      qword = ((a.query_word | w) & QF_FLAGS) | (a.query_word & w & 0xFF000000u);
+      tmin = ro.w; tmax = rd.w; lim = tmax;
+      wo = mk3(ro.x, ro.y, ro.z); wd = mk3(rd.x, rd.y, rd.z);
+      co = wo; cd = wd;
+      world_space();
+      cur_inst = -1; count = 0;
+      st.reset(); cur = a.sc.tlas_root;
+      row = a.hits + (size_t)ray * K;
+      need = false;
     }
     if (__ballot(!need) == 0) break;   // every lane idle and the rays used up
 
     // ---- interior nodes: every lane at one takes a visit; the trip repeats while most live lanes are interior
     for (;;) {
       if (cur >= 0) {
-        const uint4* np = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(a.sc.blas_nodes) + ((uint32_t)cur << 5));
-        const uint4 Q0 = np[0], Q1 = np[1];
+        uint4 Q0, Q1;
+        walk_node(a.sc, cur, Q0, Q1);
         float t0, t1;
         const bool open_all = far && cur_inst < 0;   // (a far ray in world space: the TLAS does not cull, trace_body's interior_step)
-        const bool h0 = open_all ? (Q0.x & 0xFFFFu) <= (Q0.x >> 16) : (far ? slab_q_far(Q0.x, Q0.y, Q0.z, qs, qb, rot, tmin, lim, t0) : slab_q(Q0.x, Q0.y, Q0.z, qs, qb, rot, tmin, lim, t0));
-        const bool h1 = open_all ? (Q0.w & 0xFFFFu) <= (Q0.w >> 16) : (far ? slab_q_far(Q0.w, Q1.x, Q1.y, qs, qb, rot, tmin, lim, t1) : slab_q(Q0.w, Q1.x, Q1.y, qs, qb, rot, tmin, lim, t1));
+        const bool h0 = open_all ? box_present(Q0.x) : (far ? slab_q_far(Q0.x, Q0.y, Q0.z, qs, qb, rot, tmin, lim, t0) : slab_q(Q0.x, Q0.y, Q0.z, qs, qb, rot, tmin, lim, t0));
+        const bool h1 = open_all ? box_present(Q0.w) : (far ? slab_q_far(Q0.w, Q1.x, Q1.y, qs, qb, rot, tmin, lim, t1) : slab_q(Q0.w, Q1.x, Q1.y, qs, qb, rot, tmin, lim, t1));
         if (open_all) { t0 = 0.0f; t1 = 0.0f; }
         if (h0 && h1) {
           const bool swap = t1 < t0;
-          push(swap ? (int)Q1.z : (int)Q1.w);
+          st.push(swap ? (int)Q1.z : (int)Q1.w);
           cur = swap ? (int)Q1.w : (int)Q1.z;
         } else if (h0) cur = (int)Q1.z;
         else if (h1) cur = (int)Q1.w;
-        else pop();
+        else cur = st.pop();
       }
-      const uint32_t live = 64u - (uint32_t)__builtin_popcountll(__ballot(need));
-      const uint32_t n_int = (uint32_t)__builtin_popcountll(__ballot(cur >= 0));
-      if (n_int == 0 || n_int * 8u < live * 5u) break;
+      if (walk_trip_done(need, cur)) break;
     }
 
     if (!need && cur < 0 && cur > REF_MARK && cur_inst >= 0) {
       // ---- BLAS leaf: every accepted candidate is counted and, if it belongs in the row, inserted in (t, inst, prim) order
-      const uint32_t ref = (uint32_t)(~cur);
-      const uint32_t first = ref >> 3, nt = (ref & 7u) + 1u;
+      uint32_t first, nt;
+      walk_leaf(cur, first, nt);
       for (uint32_t j = 0; j < nt; j++) {
         const float4* tp = a.sc.tris + (size_t)(first + j) * 3;
         const float4 T0 = tp[0], T1 = tp[1], T2 = tp[2];
@@ -157,12 +123,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_HITS_WAV
         row[p] = h;
         if (prune && count >= K) lim = row[K - 1u].t;
       }
-      pop();
+      cur = st.pop();
     }
     if (!need && cur == REF_MARK) {
       // ---- leave the instance: back to world space if a TLAS node follows
       cur_inst = -1;
-      pop();
+      cur = st.pop();
       if (cur >= 0) world_space();
     }
     if (!need && cur < 0 && cur > REF_MARK && cur_inst < 0) {
@@ -174,10 +140,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_HITS_WAV
         qword = (qword & ~(QF_CULL_NEG | QF_CULL_POS)) | cull;
         co = xform_point(I->w2o, wo); cd = xform_vec(I->w2o, wd);
         quant_space(co, cd, I->q_lo, I->q_scale, qs, qb, rot); far = quant_far_o(co, I->q_lo, I->q_scale);
-        push(REF_MARK);
+        st.push(REF_MARK);
         cur_inst = ii; cur = I->blas_root;
       } else {
-        pop();
+        cur = st.pop();
         if (cur >= 0) world_space();
       }
     }
@@ -218,13 +184,9 @@ __global__ __launch_bounds__(256) void k_query_hits_surface(SceneDev sc, const f
 
 void launch_query_hits(const SceneDev& sc, const float4* rays, const uint32_t* words, uint32_t query_word, uint32_t n, uint32_t k, HitRec* hits,
                        float4* attr, uint32_t* counts, int32_t* ovf_stack, uint32_t* counters, const LaunchCfg& cfg, hipStream_t s) {
-  hipLaunchKernelGGL(k_query_init, dim3(1), dim3(64), 0, s, counters, n);   // (zeroes the chunk cursor, cnt_work(0, 0))
   HitsArgs a{};
-  a.sc = sc; a.rays = rays; a.ray_words = words; a.query_word = query_word; a.n = n; a.k = k; a.hits = hits; a.counts = counts;
-  a.cursor = counters + cnt_work(0, 0); a.ovf_stack = ovf_stack;
-  // the persistent grid the spill area is sized for, no larger than the rays need
-  const uint32_t blocks = min((uint32_t)cfg.trace_blocks, (n + 255u) / 256u);
-  hipLaunchKernelGGL(k_query_hits, dim3(blocks), dim3(256), 0, s, a);
+  a.sc = sc; a.rays = rays; a.ray_words = words; a.query_word = query_word; a.n = n; a.k = k; a.hits = hits; a.counts = counts; a.ovf_stack = ovf_stack;
+  launch_walk(k_query_hits, k_query_hits, a, counters, false, cfg, s);   // (no counting form)
   if (attr) {
     const uint32_t total = n * k;
     hipLaunchKernelGGL(k_query_hits_surface, dim3((total + 255u) / 256u), dim3(256), 0, s, sc, rays, (const HitRec*)hits, attr, total, k);

@@ -2,13 +2,12 @@
 // rt_point_inside_device / rt_signed_distance_device: is a point inside the scene's surfaces?  For each point the crossings of the
 // rays (p, tmin 0, D_k, tmax +inf) along a fixed table of directions are counted with the arithmetic of rt_intersect_device_hits'
 // count-only query (query word 0 | cull_mask << 24), and the majority of the parities decides (DESIGN.md §5 "Inside / outside").
-// A record-level walk of its own on k_query_hits' skeleton; no existing kernel changes.
+// A record-level walk of its own (walk_common.inc: the stack, the chunk feed, the trip exit, the counters); no existing kernel changes.
 //
 //  * one lane per point: the lane walks direction 0, and while the vote is undecided it restarts at the TLAS root with the next
 //    direction of the table.  The early stop costs nothing, no lane waits for another lane's vote, and the ray exists in registers
 //    only: nothing ray-sized touches memory;
-//  * 64-point chunks from the query's cursor, ballot + prefix-rank refill, the LDS stack with the spill area behind it, the far-ray
-//    logic always on, REF_MARK leaving an instance: k_query_hits';
+//  * the far-ray logic always on, REF_MARK leaving an instance: k_query_hits';
 //  * no rows, no per-ray words, no flags: an instance is entered when (mask & cull_mask) != 0 (what query_enters decides for the
 //    word 0 | cull_mask << 24) and a leaf runs tri_test_facing without a facing cull over (0, +inf), so the counts are
 //    k_query_hits' bit for bit.
@@ -37,16 +36,11 @@ __device__ __forceinline__ F3 inside_dir(uint32_t k) {
 template <bool COUNT>
 __device__ __forceinline__ void inside_body(const InsideArgs& a) {
   __shared__ int s_stack[4][STACK2_LDS][64];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  int* const stk = &s_stack[wave][0][lane];   // entry e at stk[e * 64]
-  int32_t* const ovf = a.ovf_stack + (size_t)(blockIdx.x * 256u + threadIdx.x) * a.sc.ovf_stride;
+  WalkStack st(s_stack, a.ovf_stack, a.sc.ovf_stride);
+  WalkFeed feed;
   const uint32_t n_dirs = a.n_dirs, half = a.n_dirs >> 1;
   const bool all_dirs = a.counts != nullptr;
   const float tmin = 0.0f, tmax = __builtin_inff();
-
-  // wave-uniform work distribution: the current 64-point chunk
-  uint32_t chunk_next = 0, chunk_end = 0;
-  bool drained = false;
 
   // per-lane state: the point, the direction being walked and the votes so far
   bool need = true;
@@ -54,19 +48,9 @@ __device__ __forceinline__ void inside_body(const InsideArgs& a) {
   F3 wo = mk3(0, 0, 0), wd = mk3(0, 0, 1), co = wo, cd = wd, qs = mk3(1, 1, 1), qb = mk3(0, 0, 0);
   uint3 rot = make_uint3(0u, 0u, 0u);
   bool far = false;
-  int cur = REF_DONE, cur_inst = -1, sp = 0;
+  int cur = REF_DONE, cur_inst = -1;
   unsigned long long cnt_nodes = 0, cnt_tris = 0;
 
-  auto push = [&](int v) {
-    if (sp < STACK2_LDS) stk[sp * 64] = v;
-    else *reinterpret_cast<volatile int32_t*>(ovf + (sp - STACK2_LDS)) = v;
-    sp++;
-  };
-  auto pop = [&]() {
-    sp--;
-    if (sp < STACK2_LDS) cur = stk[sp * 64];
-    else cur = *reinterpret_cast<volatile int32_t*>(ovf + (sp - STACK2_LDS));
-  };
   auto world_space = [&]() {
     quant_space(wo, wd, a.sc.tlas_q_lo, a.sc.tlas_q_scale, qs, qb, rot); far = quant_far_o(wo, a.sc.tlas_q_lo, a.sc.tlas_q_scale);
   };
@@ -76,72 +60,55 @@ __device__ __forceinline__ void inside_body(const InsideArgs& a) {
     co = wo; cd = wd;
     world_space();
     cur_inst = -1; count = 0;
-    stk[0] = REF_DONE; sp = 1; cur = a.sc.tlas_root;
+    st.reset(); cur = a.sc.tlas_root;
   };
 
   for (;;) {
-    // ---- refill: idle lanes take the next points of the wave's chunk, a new chunk when it is used up
-    const uint64_t need_mask = __ballot(need);
-    if (need_mask != 0 && !drained) {
-      if (chunk_next == chunk_end) {
-        uint32_t c = 0;
-        if (lane == 0) c = atomicAdd(a.cursor, 1u);
-        c = (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
-        const uint64_t b = (uint64_t)c * 64u;
-        if (b >= a.n) drained = true;
-        else { chunk_next = (uint32_t)b; chunk_end = (uint32_t)min((uint64_t)a.n, b + 64u); }
-      }
-      if (!drained) {
-        const uint32_t rank = prefix_rank(need_mask), avail = chunk_end - chunk_next;
-        if (need && rank < avail) {
-          pt = chunk_next + rank;
-          const float4 r = ld_stream(&a.points[pt]);
-          wo = mk3(r.x, r.y, r.z);
-          dir = 0u; odd = 0u;
-          if (finite_bits(r.x) && finite_bits(r.y) && finite_bits(r.z)) {
-            start_dir();
-            need = false;
-          } else {
-            // a point with a non-finite coordinate: word 0, counts 0; the lane stays idle and takes another point next trip
-            a.words[pt] = 0u;
-            if (all_dirs) for (uint32_t k = 0; k < n_dirs; k++) a.counts[(size_t)pt * n_dirs + k] = 0u;
-          }
-        }
-        const uint32_t n_need = (uint32_t)__builtin_popcountll(need_mask);
-        chunk_next += n_need < avail ? n_need : avail;
+    // ---- refill: idle lanes take the next points of the wave's chunk
+    const uint32_t rec = feed.take(__ballot(need), a.cursor, a.n);
+    if (need && rec != WALK_NONE) {
+      pt = rec;
+      const float4 r = ld_stream(&a.points[pt]);
+      wo = mk3(r.x, r.y, r.z);
+      dir = 0u; odd = 0u;
+      if (finite_bits(r.x) && finite_bits(r.y) && finite_bits(r.z)) {
+        start_dir();
+        need = false;
+      } else {
+        // a point with a non-finite coordinate: word 0, counts 0; the lane stays idle and takes another point next trip
+        a.words[pt] = 0u;
+        if (all_dirs) for (uint32_t k = 0; k < n_dirs; k++) a.counts[(size_t)pt * n_dirs + k] = 0u;
       }
     }
     if (__ballot(!need) == 0) {
-      if (drained) break;   // every lane idle and the points used up
-      continue;             // (a chunk of invalid points only: take the next one)
+      if (feed.drained) break;   // every lane idle and the points used up
+      continue;                  // (a chunk of invalid points only: take the next one)
     }
 
     // ---- interior nodes: every lane at one takes a visit; the trip repeats while most live lanes are interior
     for (;;) {
       if (cur >= 0) {
-        const uint4* np = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(a.sc.blas_nodes) + ((uint32_t)cur << 5));
-        const uint4 Q0 = np[0], Q1 = np[1];
+        uint4 Q0, Q1;
+        walk_node(a.sc, cur, Q0, Q1);
         if (COUNT) cnt_nodes++;
         float t0, t1;
         const bool open_all = far && cur_inst < 0;   // (a far ray in world space: the TLAS does not cull, as in k_query_hits)
-        const bool h0 = open_all ? (Q0.x & 0xFFFFu) <= (Q0.x >> 16) : (far ? slab_q_far(Q0.x, Q0.y, Q0.z, qs, qb, rot, tmin, tmax, t0) : slab_q(Q0.x, Q0.y, Q0.z, qs, qb, rot, tmin, tmax, t0));
-        const bool h1 = open_all ? (Q0.w & 0xFFFFu) <= (Q0.w >> 16) : (far ? slab_q_far(Q0.w, Q1.x, Q1.y, qs, qb, rot, tmin, tmax, t1) : slab_q(Q0.w, Q1.x, Q1.y, qs, qb, rot, tmin, tmax, t1));
+        const bool h0 = open_all ? box_present(Q0.x) : (far ? slab_q_far(Q0.x, Q0.y, Q0.z, qs, qb, rot, tmin, tmax, t0) : slab_q(Q0.x, Q0.y, Q0.z, qs, qb, rot, tmin, tmax, t0));
+        const bool h1 = open_all ? box_present(Q0.w) : (far ? slab_q_far(Q0.w, Q1.x, Q1.y, qs, qb, rot, tmin, tmax, t1) : slab_q(Q0.w, Q1.x, Q1.y, qs, qb, rot, tmin, tmax, t1));
         if (h0 && h1) {
-          push((int)Q1.w);   // (every candidate counts: no order among the children)
+          st.push((int)Q1.w);   // (every candidate counts: no order among the children)
           cur = (int)Q1.z;
         } else if (h0) cur = (int)Q1.z;
         else if (h1) cur = (int)Q1.w;
-        else pop();
+        else cur = st.pop();
       }
-      const uint32_t live = 64u - (uint32_t)__builtin_popcountll(__ballot(need));
-      const uint32_t n_int = (uint32_t)__builtin_popcountll(__ballot(cur >= 0));
-      if (n_int == 0 || n_int * 8u < live * 5u) break;
+      if (walk_trip_done(need, cur)) break;
     }
 
     if (!need && cur < 0 && cur > REF_MARK && cur_inst >= 0) {
       // ---- BLAS leaf: every accepted candidate is a crossing
-      const uint32_t ref = (uint32_t)(~cur);
-      const uint32_t first = ref >> 3, nt = (ref & 7u) + 1u;
+      uint32_t first, nt;
+      walk_leaf(cur, first, nt);
       for (uint32_t j = 0; j < nt; j++) {
         const float4* tp = a.sc.tris + (size_t)(first + j) * 3;
         const float4 T0 = tp[0], T1 = tp[1], T2 = tp[2];
@@ -149,12 +116,12 @@ __device__ __forceinline__ void inside_body(const InsideArgs& a) {
         float tt, uu, vv;
         if (tri_test_facing(T0, T1, T2, co, cd, tmin, tmax, 0u, tt, uu, vv)) count++;
       }
-      pop();
+      cur = st.pop();
     }
     if (!need && cur == REF_MARK) {
       // ---- leave the instance: back to world space if a TLAS node follows
       cur_inst = -1;
-      pop();
+      cur = st.pop();
       if (cur >= 0) world_space();
     }
     if (!need && cur < 0 && cur > REF_MARK && cur_inst < 0) {
@@ -164,10 +131,10 @@ __device__ __forceinline__ void inside_body(const InsideArgs& a) {
       if ((I->mask & a.cull_mask & 0xFFu) != 0u) {
         co = xform_point(I->w2o, wo); cd = xform_vec(I->w2o, wd);
         quant_space(co, cd, I->q_lo, I->q_scale, qs, qb, rot); far = quant_far_o(co, I->q_lo, I->q_scale);
-        push(REF_MARK);
+        st.push(REF_MARK);
         cur_inst = ii; cur = I->blas_root;
       } else {
-        pop();
+        cur = st.pop();
         if (cur >= 0) world_space();
       }
     }
@@ -183,16 +150,7 @@ __device__ __forceinline__ void inside_body(const InsideArgs& a) {
       } else start_dir();
     }
   }
-  if (COUNT) {
-    for (int off = 32; off > 0; off >>= 1) {
-      cnt_nodes += __shfl_down((unsigned long long)cnt_nodes, off);
-      cnt_tris += __shfl_down((unsigned long long)cnt_tris, off);
-    }
-    if (lane == 0) {
-      atomicAdd(reinterpret_cast<unsigned long long*>(a.counters + CNT_NODE_VISITS), (unsigned long long)cnt_nodes);
-      atomicAdd(reinterpret_cast<unsigned long long*>(a.counters + CNT_TRI_TESTS), (unsigned long long)cnt_tris);
-    }
-  }
+  if (COUNT) walk_flush_counters(a.counters, cnt_nodes, cnt_tris);
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_HITS_WAVES_PER_EU))) void k_point_inside(InsideArgs a) { inside_body<false>(a); }
@@ -212,14 +170,9 @@ __global__ __launch_bounds__(256) void k_sign_distance(const float4* __restrict_
 
 void launch_point_inside(const SceneDev& sc, const float4* points, uint32_t cull_mask, uint32_t n_dirs, uint32_t* words, uint32_t* counts, uint32_t n,
                          int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s) {
-  hipLaunchKernelGGL(k_query_init, dim3(1), dim3(64), 0, s, counters, n);   // (zeroes the chunk cursor, cnt_work(0, 0))
   InsideArgs a{};
-  a.sc = sc; a.points = points; a.cull_mask = cull_mask; a.n_dirs = n_dirs; a.n = n; a.words = words; a.counts = counts;
-  a.cursor = counters + cnt_work(0, 0); a.counters = counters; a.ovf_stack = ovf_stack;
-  // the persistent grid the spill area is sized for, no larger than the points need
-  const uint32_t blocks = min((uint32_t)cfg.trace_blocks, (n + 255u) / 256u);
-  if (counting) hipLaunchKernelGGL(k_point_inside_count, dim3(blocks), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(k_point_inside, dim3(blocks), dim3(256), 0, s, a);
+  a.sc = sc; a.points = points; a.cull_mask = cull_mask; a.n_dirs = n_dirs; a.n = n; a.words = words; a.counts = counts; a.counters = counters; a.ovf_stack = ovf_stack;
+  launch_walk(k_point_inside, k_point_inside_count, a, counters, counting, cfg, s);
 }
 
 void launch_sign_distance(const float4* points, const uint32_t* words, HitRec* hits, uint32_t n, hipStream_t s) {

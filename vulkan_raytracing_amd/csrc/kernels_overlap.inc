@@ -1,11 +1,8 @@
 // kernels_overlap.inc — included by kernels.hip after kernels_closest.inc (product and alt translation units alike).
 // rt_overlap_boxes_device: for every query box the triangles of the scene that touch it — their number and the smallest of them by
-// (inst, prim).  A record-level walk of its own, like kernels_hits.inc and kernels_closest.inc: no frame kernel and no existing query
-// kernel changes.
+// (inst, prim).  A record-level walk of its own (walk_common.inc: the stack, the chunk feed, the trip exit, the counters), one lane per
+// box: no frame kernel and no existing query kernel changes.
 //
-//  * one lane per box; a wave takes 64-box chunks from one cursor of the query's counter block and a lane that finishes takes the next
-//    box of the wave's chunk (ballot + prefix rank), exactly as k_closest_point;
-//  * per-lane stack: STACK2_LDS entries in LDS, deeper ones in the query's spill area (ovf_stride ints per thread of the grid);
 //  * the node test is box against box on the dequantised planes, the query box inflated (DESIGN.md §5 "Box overlaps"): in world space by
 //    2^-13 of the magnitudes that enter a candidate's world vertices (the box, the TLAS bounds, the row terms of every o2w: word 0 of
 //    k_closest_scale's array); inside an instance the query is the bound of that inflated box's eight corners under w2o, inflated again
@@ -80,24 +77,19 @@ __device__ __forceinline__ bool id_before(int inst, int prim, int bi, int bp) { 
 
 // the quantised box (wx, wy, wz) of a tree with dequantisation (q_lo, q_scale) against the query box [lo, hi]: closed, and a NaN opens
 __device__ __forceinline__ bool box_touches(uint32_t wx, uint32_t wy, uint32_t wz, F3 lo, F3 hi, F3 q_lo, F3 q_scale) {
-  const float lx = __builtin_fmaf((float)(wx & 0xFFFFu), q_scale.x, q_lo.x), hx = __builtin_fmaf((float)(wx >> 16), q_scale.x, q_lo.x);
-  const float ly = __builtin_fmaf((float)(wy & 0xFFFFu), q_scale.y, q_lo.y), hy = __builtin_fmaf((float)(wy >> 16), q_scale.y, q_lo.y);
-  const float lz = __builtin_fmaf((float)(wz & 0xFFFFu), q_scale.z, q_lo.z), hz = __builtin_fmaf((float)(wz >> 16), q_scale.z, q_lo.z);
-  return !(lx > hi.x) && !(hx < lo.x) && !(ly > hi.y) && !(hy < lo.y) && !(lz > hi.z) && !(hz < lo.z);
+  F3 bl, bh;
+  box_planes(wx, wy, wz, q_lo, q_scale, bl, bh);
+  return !(bl.x > hi.x) && !(bh.x < lo.x) && !(bl.y > hi.y) && !(bh.y < lo.y) && !(bl.z > hi.z) && !(bh.z < lo.z);
 }
 
 template <bool COUNT>
 __device__ __forceinline__ void overlap_body(const OverlapArgs& a) {
   __shared__ int s_stack[4][STACK2_LDS][64];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  int* const stk = &s_stack[wave][0][lane];   // entry e at stk[e * 64]
-  int32_t* const ovf = a.ovf_stack + (size_t)(blockIdx.x * 256u + threadIdx.x) * a.sc.ovf_stride;
+  WalkStack st(s_stack, a.ovf_stack, a.sc.ovf_stride);
+  WalkFeed feed;
   const uint32_t K = a.k;
   const bool prune = a.counts == nullptr;
   const float INF = __builtin_inff();
-
-  uint32_t chunk_next = 0, chunk_end = 0;
-  bool drained = false;
 
   bool need = true;
   uint32_t bx = 0, count = 0;
@@ -106,86 +98,56 @@ __device__ __forceinline__ void overlap_body(const OverlapArgs& a) {
   float w_slack = 0.f;
   F3 q_lo = wlo, q_scale = wlo;               // dequantisation of that tree
   int last_inst = 0, last_prim = 0;           // the row's last entry once it is full
-  int cur = REF_DONE, cur_inst = -1, sp = 0;
+  int cur = REF_DONE, cur_inst = -1;
   IdRec* row = nullptr;
   unsigned long long cnt_nodes = 0, cnt_tris = 0;
 
-  auto push = [&](int v) {
-    if (sp < STACK2_LDS) stk[sp * 64] = v;
-    else *reinterpret_cast<volatile int32_t*>(ovf + (sp - STACK2_LDS)) = v;
-    sp++;
-  };
-  auto pop = [&]() {
-    sp--;
-    if (sp < STACK2_LDS) cur = stk[sp * 64];
-    else cur = *reinterpret_cast<volatile int32_t*>(ovf + (sp - STACK2_LDS));
-  };
   auto world_space = [&]() {
     qlo = mk3(wlo.x - w_slack, wlo.y - w_slack, wlo.z - w_slack); qhi = mk3(whi.x + w_slack, whi.y + w_slack, whi.z + w_slack);
-    q_lo = mk3(a.sc.tlas_q_lo[0], a.sc.tlas_q_lo[1], a.sc.tlas_q_lo[2]); q_scale = mk3(a.sc.tlas_q_scale[0], a.sc.tlas_q_scale[1], a.sc.tlas_q_scale[2]);
+    tlas_dequant(a.sc, q_lo, q_scale);
   };
 
   for (;;) {
-    // ---- refill: idle lanes take the next boxes of the wave's chunk, a new chunk when it is used up
-    const uint64_t need_mask = __ballot(need);
-    if (need_mask != 0 && !drained) {
-      if (chunk_next == chunk_end) {
-        uint32_t c = 0;
-        if (lane == 0) c = atomicAdd(a.cursor, 1u);
-        c = (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
-        const uint64_t b = (uint64_t)c * 64u;
-        if (b >= a.n) drained = true;
-        else { chunk_next = (uint32_t)b; chunk_end = (uint32_t)min((uint64_t)a.n, b + 64u); }
-      }
-      if (!drained) {
-        const uint32_t rank = prefix_rank(need_mask), avail = chunk_end - chunk_next;
-        if (need && rank < avail) {
-          bx = chunk_next + rank;
-          const float4 r0 = ld_stream(&a.boxes[2u * (size_t)bx]), r1 = ld_stream(&a.boxes[2u * (size_t)bx + 1u]);
-          wlo = mk3(r0.x, r0.y, r0.z); whi = mk3(r1.x, r1.y, r1.z);
-          const bool valid = finite_bits(r0.x) && finite_bits(r0.y) && finite_bits(r0.z) && finite_bits(r1.x) && finite_bits(r1.y) && finite_bits(r1.z) &&
-                             r0.x <= r1.x && r0.y <= r1.y && r0.z <= r1.z;
-          float mag = fmaxf(fmaxf(fmaxf(__builtin_fabsf(r0.x), __builtin_fabsf(r0.y)), __builtin_fabsf(r0.z)),
-                            fmaxf(fmaxf(__builtin_fabsf(r1.x), __builtin_fabsf(r1.y)), __builtin_fabsf(r1.z)));
-          for (int k = 0; k < 3; k++)
-            mag = fmaxf(mag, fmaxf(__builtin_fabsf(a.sc.tlas_q_lo[k]), __builtin_fabsf(__builtin_fmaf(65535.0f, a.sc.tlas_q_scale[k], a.sc.tlas_q_lo[k]))));
-          w_slack = OB_ABS * fmaxf(mag, a.inst_scale[0]);
-          world_space();
-          cur_inst = -1; count = 0;
-          stk[0] = REF_DONE; sp = 1; cur = valid ? a.sc.tlas_root : REF_DONE;
-          row = a.ids + (size_t)bx * K;
-          need = false;
-        }
-        const uint32_t n_need = (uint32_t)__builtin_popcountll(need_mask);
-        chunk_next += n_need < avail ? n_need : avail;
-      }
+    // ---- refill: idle lanes take the next boxes of the wave's chunk
+    const uint32_t rec = feed.take(__ballot(need), a.cursor, a.n);
+    if (need && rec != WALK_NONE) {
+      bx = rec;
+      const float4 r0 = ld_stream(&a.boxes[2u * (size_t)bx]), r1 = ld_stream(&a.boxes[2u * (size_t)bx + 1u]);
+      wlo = mk3(r0.x, r0.y, r0.z); whi = mk3(r1.x, r1.y, r1.z);
+      const bool valid = finite_bits(r0.x) && finite_bits(r0.y) && finite_bits(r0.z) && finite_bits(r1.x) && finite_bits(r1.y) && finite_bits(r1.z) &&
+                         r0.x <= r1.x && r0.y <= r1.y && r0.z <= r1.z;
+      const float mag = fmaxf(fmaxf(fmaxf(__builtin_fabsf(r0.x), __builtin_fabsf(r0.y)), __builtin_fabsf(r0.z)),
+                              fmaxf(fmaxf(__builtin_fabsf(r1.x), __builtin_fabsf(r1.y)), __builtin_fabsf(r1.z)));
+      w_slack = OB_ABS * fmaxf(tlas_magnitude(a.sc, mag), a.inst_scale[0]);
+      world_space();
+      cur_inst = -1; count = 0;
+      st.reset(); cur = valid ? a.sc.tlas_root : REF_DONE;
+      row = a.ids + (size_t)bx * K;
+      need = false;
     }
     if (__ballot(!need) == 0) break;   // every lane idle and the boxes used up
 
     // ---- interior nodes: every lane at one takes a visit; the trip repeats while most live lanes are interior
     for (;;) {
       if (cur >= 0) {
-        const uint4* np = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(a.sc.blas_nodes) + ((uint32_t)cur << 5));
-        const uint4 Q0 = np[0], Q1 = np[1];
+        uint4 Q0, Q1;
+        walk_node(a.sc, cur, Q0, Q1);
         if (COUNT) cnt_nodes++;
-        // (a missing child is an inverted box, as in k_query_hits' far case)
-        const bool h0 = (Q0.x & 0xFFFFu) <= (Q0.x >> 16) && box_touches(Q0.x, Q0.y, Q0.z, qlo, qhi, q_lo, q_scale);
-        const bool h1 = (Q0.w & 0xFFFFu) <= (Q0.w >> 16) && box_touches(Q0.w, Q1.x, Q1.y, qlo, qhi, q_lo, q_scale);
-        if (h0 && h1) { push((int)Q1.w); cur = (int)Q1.z; }
+        const bool h0 = box_present(Q0.x) && box_touches(Q0.x, Q0.y, Q0.z, qlo, qhi, q_lo, q_scale);
+        const bool h1 = box_present(Q0.w) && box_touches(Q0.w, Q1.x, Q1.y, qlo, qhi, q_lo, q_scale);
+        if (h0 && h1) { st.push((int)Q1.w); cur = (int)Q1.z; }
         else if (h0) cur = (int)Q1.z;
         else if (h1) cur = (int)Q1.w;
-        else pop();
+        else cur = st.pop();
       }
-      const uint32_t live = 64u - (uint32_t)__builtin_popcountll(__ballot(need));
-      const uint32_t n_int = (uint32_t)__builtin_popcountll(__ballot(cur >= 0));
-      if (n_int == 0 || n_int * 8u < live * 5u) break;
+      if (walk_trip_done(need, cur)) break;
     }
 
     if (!need && cur < 0 && cur > REF_MARK && cur_inst >= 0) {
       // ---- BLAS leaf: the canonical test of every packet, in world space; a candidate is counted and, if it belongs in the row,
       // inserted in (inst, prim) order
-      const uint32_t ref = (uint32_t)(~cur);
-      const uint32_t first = ref >> 3, nt = (ref & 7u) + 1u;
+      uint32_t first, nt;
+      walk_leaf(cur, first, nt);
       const float* m = a.sc.inst[cur_inst].o2w;
       bool done = false;
       for (uint32_t j = 0; j < nt; j++) {
@@ -216,13 +178,13 @@ __device__ __forceinline__ void overlap_body(const OverlapArgs& a) {
         if (count >= K) { const IdRec l = row[K - 1u]; last_inst = l.inst; last_prim = l.prim; }
       }
       if (done) cur = REF_DONE;
-      else pop();
+      else cur = st.pop();
     }
     if (!need && cur == REF_MARK) {
       // ---- leave the instance
       cur_inst = -1;
       world_space();
-      pop();
+      cur = st.pop();
     }
     if (!need && cur < 0 && cur > REF_MARK && cur_inst < 0) {
       // ---- TLAS leaf: enter the instance if the call's mask lets it and, when pruning, the row could still take one of its triangles
@@ -254,9 +216,9 @@ __device__ __forceinline__ void overlap_body(const OverlapArgs& a) {
         } else {   // a singular or non-finite transform, an unbounded slack: the instance's boxes do not prune
           qlo = mk3(-INF, -INF, -INF); qhi = mk3(INF, INF, INF);
         }
-        push(REF_MARK);
+        st.push(REF_MARK);
         cur_inst = ii; cur = I->blas_root;
-      } else pop();
+      } else cur = st.pop();
     }
     if (!need && cur == REF_DONE) {
       // ---- finished: the rest of the row empty, the count
@@ -266,16 +228,7 @@ __device__ __forceinline__ void overlap_body(const OverlapArgs& a) {
       need = true;
     }
   }
-  if (COUNT) {
-    for (int off = 32; off > 0; off >>= 1) {
-      cnt_nodes += __shfl_down((unsigned long long)cnt_nodes, off);
-      cnt_tris += __shfl_down((unsigned long long)cnt_tris, off);
-    }
-    if (lane == 0) {
-      atomicAdd(reinterpret_cast<unsigned long long*>(a.counters + CNT_NODE_VISITS), (unsigned long long)cnt_nodes);
-      atomicAdd(reinterpret_cast<unsigned long long*>(a.counters + CNT_TRI_TESTS), (unsigned long long)cnt_tris);
-    }
-  }
+  if (COUNT) walk_flush_counters(a.counters, cnt_nodes, cnt_tris);
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_OVERLAP_WAVES_PER_EU))) void k_overlap_boxes(OverlapArgs a) { overlap_body<false>(a); }
@@ -283,12 +236,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_OVERLAP_
 
 void launch_overlap_boxes(const SceneDev& sc, const float4* boxes, uint32_t cull_mask, const float* inst_scale, bool any, uint32_t k, void* ids, uint32_t* counts,
                           uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s) {
-  hipLaunchKernelGGL(k_query_init, dim3(1), dim3(64), 0, s, counters, n);   // (zeroes the chunk cursor, cnt_work(0, 0))
   OverlapArgs a{};
   a.sc = sc; a.boxes = boxes; a.inst_scale = inst_scale; a.cull_mask = cull_mask; a.n = n; a.k = k; a.any = any ? 1u : 0u; a.ids = (IdRec*)ids; a.counts = counts;
-  a.cursor = counters + cnt_work(0, 0); a.counters = counters; a.ovf_stack = ovf_stack;
-  // the persistent grid the spill area is sized for, no larger than the boxes need
-  const uint32_t blocks = min((uint32_t)cfg.trace_blocks, (n + 255u) / 256u);
-  if (counting) hipLaunchKernelGGL(k_overlap_boxes_count, dim3(blocks), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(k_overlap_boxes, dim3(blocks), dim3(256), 0, s, a);
+  a.counters = counters; a.ovf_stack = ovf_stack;
+  launch_walk(k_overlap_boxes, k_overlap_boxes_count, a, counters, counting, cfg, s);
 }

@@ -1,11 +1,8 @@
 // kernels_sweep.inc — included by kernels.hip after kernels_overlap.inc (product and alt translation units alike).
 // rt_sweep_spheres_device: for every sweep record (o, r, d, tmax) the first triangle of the scene that the sphere of radius r touches while
-// its centre moves along p(t) = o + t d, t in [0, tmax].  A record-level walk of its own, like kernels_closest.inc and
-// kernels_overlap.inc: no frame kernel and no existing query kernel changes.
+// its centre moves along p(t) = o + t d, t in [0, tmax].  A record-level walk of its own (walk_common.inc: the stack, the chunk feed,
+// the trip exit, the counters), one lane per sweep: no frame kernel and no existing query kernel changes.
 //
-//  * one lane per sweep; a wave takes 64-record chunks from one cursor of the query's counter block and a lane that finishes takes the
-//    next record of the wave's chunk (ballot + prefix rank), exactly as k_closest_point;
-//  * per-lane stack: STACK2_LDS entries in LDS, deeper ones in the query's spill area (ovf_stride ints per thread of the grid);
 //  * the node test is the slab test of the centre's path against the dequantised child boxes inflated by the radius (DESIGN.md §5
 //    "Sphere sweeps"): by R(E) = sqrt(r^2 + 2^-16 L^2) (1 + 2^-13) + 2^-10 L with L = r + 2 E, E the box's own diagonal in world units (no
 //    triangle under the box has a longer edge; L bounds the feature offsets whose squares the canonical quadratics cancel), plus 2^-16
@@ -137,9 +134,9 @@ __device__ __forceinline__ bool sweep_box(uint32_t wx, uint32_t wy, uint32_t wz,
               ez = (float)((int)(wz >> 16) - (int)(wz & 0xFFFFu)) * q_scale.z;
   const float diag = __builtin_sqrtf(ex * ex + ey * ey + ez * ez) * SW_T_HI;
   const float infl = add + sweep_reach(wr, rr, esc * diag) * inv_s;
-  const float lx = __builtin_fmaf((float)(wx & 0xFFFFu), q_scale.x, q_lo.x) - infl, hx = __builtin_fmaf((float)(wx >> 16), q_scale.x, q_lo.x) + infl;
-  const float ly = __builtin_fmaf((float)(wy & 0xFFFFu), q_scale.y, q_lo.y) - infl, hy = __builtin_fmaf((float)(wy >> 16), q_scale.y, q_lo.y) + infl;
-  const float lz = __builtin_fmaf((float)(wz & 0xFFFFu), q_scale.z, q_lo.z) - infl, hz = __builtin_fmaf((float)(wz >> 16), q_scale.z, q_lo.z) + infl;
+  F3 lo, hi;
+  box_planes(wx, wy, wz, q_lo, q_scale, lo, hi);
+  const float lx = lo.x - infl, hx = hi.x + infl, ly = lo.y - infl, hy = hi.y + infl, lz = lo.z - infl, hz = hi.z + infl;
   const float ax = (lx - q.x) * qi.x, bx = (hx - q.x) * qi.x;
   const float ay = (ly - q.y) * qi.y, by = (hy - q.y) * qi.y;
   const float az = (lz - q.z) * qi.z, bz = (hz - q.z) * qi.z;
@@ -153,13 +150,9 @@ __device__ __forceinline__ bool sweep_box(uint32_t wx, uint32_t wy, uint32_t wz,
 template <bool COUNT>
 __device__ __forceinline__ void sweep_body(const SweepArgs& a) {
   __shared__ int s_stack[4][STACK2_LDS][64];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  int* const stk = &s_stack[wave][0][lane];   // entry e at stk[e * 64]
-  int32_t* const ovf = a.ovf_stack + (size_t)(blockIdx.x * 256u + threadIdx.x) * a.sc.ovf_stride;
+  WalkStack st(s_stack, a.ovf_stack, a.sc.ovf_stride);
+  WalkFeed feed;
   constexpr int NONE = 0x7FFFFFFF;            // best_inst / best_prim before the first candidate: every (inst, prim) precedes it
-
-  uint32_t chunk_next = 0, chunk_end = 0;
-  bool drained = false;
 
   bool need = true;
   uint32_t pt = 0;
@@ -170,87 +163,57 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a) {
   F3 q_lo = wo, q_scale = wo;                 // dequantisation of that tree
   float best = 0.f, best_u = 0.f, best_v = 0.f;
   int best_prim = NONE, best_inst = NONE;
-  int cur = REF_DONE, cur_inst = -1, sp = 0;
+  int cur = REF_DONE, cur_inst = -1;
   unsigned long long cnt_nodes = 0, cnt_tris = 0;
 
-  auto push = [&](int v) {
-    if (sp < STACK2_LDS) stk[sp * 64] = v;
-    else *reinterpret_cast<volatile int32_t*>(ovf + (sp - STACK2_LDS)) = v;
-    sp++;
-  };
-  auto pop = [&]() {
-    sp--;
-    if (sp < STACK2_LDS) cur = stk[sp * 64];
-    else cur = *reinterpret_cast<volatile int32_t*>(ovf + (sp - STACK2_LDS));
-  };
   auto world_space = [&]() {
     q = wo; qi = mk3(1.0f / wd.x, 1.0f / wd.y, 1.0f / wd.z); add = w_slack; inv_s = 1.0f; esc = 1.0f;
-    q_lo = mk3(a.sc.tlas_q_lo[0], a.sc.tlas_q_lo[1], a.sc.tlas_q_lo[2]); q_scale = mk3(a.sc.tlas_q_scale[0], a.sc.tlas_q_scale[1], a.sc.tlas_q_scale[2]);
+    tlas_dequant(a.sc, q_lo, q_scale);
   };
 
   for (;;) {
-    // ---- refill: idle lanes take the next records of the wave's chunk, a new chunk when it is used up
-    const uint64_t need_mask = __ballot(need);
-    if (need_mask != 0 && !drained) {
-      if (chunk_next == chunk_end) {
-        uint32_t c = 0;
-        if (lane == 0) c = atomicAdd(a.cursor, 1u);
-        c = (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
-        const uint64_t b = (uint64_t)c * 64u;
-        if (b >= a.n) drained = true;
-        else { chunk_next = (uint32_t)b; chunk_end = (uint32_t)min((uint64_t)a.n, b + 64u); }
-      }
-      if (!drained) {
-        const uint32_t rank = prefix_rank(need_mask), avail = chunk_end - chunk_next;
-        if (need && rank < avail) {
-          pt = chunk_next + rank;
-          const float4 r0 = ld_stream(&a.sweeps[2u * (size_t)pt]), r1 = ld_stream(&a.sweeps[2u * (size_t)pt + 1u]);
-          wo = mk3(r0.x, r0.y, r0.z); wr = r0.w; wd = mk3(r1.x, r1.y, r1.z); tmax = r1.w;
-          const bool valid = finite_bits(r0.x) && finite_bits(r0.y) && finite_bits(r0.z) && finite_bits(r0.w) && r0.w >= 0.0f && finite_bits(r1.x) &&
-                             finite_bits(r1.y) && finite_bits(r1.z) && (r1.x != 0.0f || r1.y != 0.0f || r1.z != 0.0f) && r1.w >= 0.0f;
-          best = tmax; best_u = 0.f; best_v = 0.f; best_prim = NONE; best_inst = NONE;
-          float mag = fmaxf(fmaxf(__builtin_fabsf(r0.x), __builtin_fabsf(r0.y)), __builtin_fabsf(r0.z));
-          for (int k = 0; k < 3; k++)
-            mag = fmaxf(mag, fmaxf(__builtin_fabsf(a.sc.tlas_q_lo[k]), __builtin_fabsf(__builtin_fmaf(65535.0f, a.sc.tlas_q_scale[k], a.sc.tlas_q_lo[k]))));
-          w_slack = CP_ABS * fmaxf(mag, a.inst_scale[0]);
-          world_space();
-          cur_inst = -1;
-          stk[0] = REF_DONE; sp = 1; cur = valid ? a.sc.tlas_root : REF_DONE;
-          need = false;
-        }
-        const uint32_t n_need = (uint32_t)__builtin_popcountll(need_mask);
-        chunk_next += n_need < avail ? n_need : avail;
-      }
+    // ---- refill: idle lanes take the next records of the wave's chunk
+    const uint32_t rec = feed.take(__ballot(need), a.cursor, a.n);
+    if (need && rec != WALK_NONE) {
+      pt = rec;
+      const float4 r0 = ld_stream(&a.sweeps[2u * (size_t)pt]), r1 = ld_stream(&a.sweeps[2u * (size_t)pt + 1u]);
+      wo = mk3(r0.x, r0.y, r0.z); wr = r0.w; wd = mk3(r1.x, r1.y, r1.z); tmax = r1.w;
+      const bool valid = finite_bits(r0.x) && finite_bits(r0.y) && finite_bits(r0.z) && finite_bits(r0.w) && r0.w >= 0.0f && finite_bits(r1.x) &&
+                         finite_bits(r1.y) && finite_bits(r1.z) && (r1.x != 0.0f || r1.y != 0.0f || r1.z != 0.0f) && r1.w >= 0.0f;
+      best = tmax; best_u = 0.f; best_v = 0.f; best_prim = NONE; best_inst = NONE;
+      const float mag = fmaxf(fmaxf(__builtin_fabsf(r0.x), __builtin_fabsf(r0.y)), __builtin_fabsf(r0.z));
+      w_slack = CP_ABS * fmaxf(tlas_magnitude(a.sc, mag), a.inst_scale[0]);
+      world_space();
+      cur_inst = -1;
+      st.reset(); cur = valid ? a.sc.tlas_root : REF_DONE;
+      need = false;
     }
     if (__ballot(!need) == 0) break;   // every lane idle and the records used up
 
     // ---- interior nodes: every lane at one takes a visit; the trip repeats while most live lanes are interior
     for (;;) {
       if (cur >= 0) {
-        const uint4* np = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(a.sc.blas_nodes) + ((uint32_t)cur << 5));
-        const uint4 Q0 = np[0], Q1 = np[1];
+        uint4 Q0, Q1;
+        walk_node(a.sc, cur, Q0, Q1);
         if (COUNT) cnt_nodes++;
         float n0, n1;
-        // (a missing child is an inverted box, as in k_query_hits' far case)
-        const bool h0 = sweep_box(Q0.x, Q0.y, Q0.z, q, qi, q_lo, q_scale, wr, wr * wr, add, inv_s, esc, best, n0) && (Q0.x & 0xFFFFu) <= (Q0.x >> 16);
-        const bool h1 = sweep_box(Q0.w, Q1.x, Q1.y, q, qi, q_lo, q_scale, wr, wr * wr, add, inv_s, esc, best, n1) && (Q0.w & 0xFFFFu) <= (Q0.w >> 16);
+        const bool h0 = sweep_box(Q0.x, Q0.y, Q0.z, q, qi, q_lo, q_scale, wr, wr * wr, add, inv_s, esc, best, n0) && box_present(Q0.x);
+        const bool h1 = sweep_box(Q0.w, Q1.x, Q1.y, q, qi, q_lo, q_scale, wr, wr * wr, add, inv_s, esc, best, n1) && box_present(Q0.w);
         if (h0 && h1) {
           const bool swap = n1 < n0;
-          push(swap ? (int)Q1.z : (int)Q1.w);
+          st.push(swap ? (int)Q1.z : (int)Q1.w);
           cur = swap ? (int)Q1.w : (int)Q1.z;
         } else if (h0) cur = (int)Q1.z;
         else if (h1) cur = (int)Q1.w;
-        else pop();
+        else cur = st.pop();
       }
-      const uint32_t live = 64u - (uint32_t)__builtin_popcountll(__ballot(need));
-      const uint32_t n_int = (uint32_t)__builtin_popcountll(__ballot(cur >= 0));
-      if (n_int == 0 || n_int * 8u < live * 5u) break;
+      if (walk_trip_done(need, cur)) break;
     }
 
     if (!need && cur < 0 && cur > REF_MARK && cur_inst >= 0) {
       // ---- BLAS leaf: the canonical test of every packet, in world space; the smallest key (t, inst, prim) stays
-      const uint32_t ref = (uint32_t)(~cur);
-      const uint32_t first = ref >> 3, nt = (ref & 7u) + 1u;
+      uint32_t first, nt;
+      walk_leaf(cur, first, nt);
       const float* m = a.sc.inst[cur_inst].o2w;
       for (uint32_t j = 0; j < nt; j++) {
         const float4* tp = a.sc.tris + (size_t)(first + j) * 3;
@@ -264,13 +227,13 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a) {
           best = tt; best_u = uu; best_v = vv; best_prim = prim; best_inst = cur_inst;
         }
       }
-      pop();
+      cur = st.pop();
     }
     if (!need && cur == REF_MARK) {
       // ---- leave the instance
       cur_inst = -1;
       world_space();
-      pop();
+      cur = st.pop();
     }
     if (!need && cur < 0 && cur > REF_MARK && cur_inst < 0) {
       // ---- TLAS leaf: enter the instance if the call's mask lets it (the path -> object space, the inflation in object units)
@@ -301,9 +264,9 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a) {
         inv_s = 1.0f / s;
         add = CP_ABS * om + wm * inv_s;
         if (!(add <= 3.0e38f)) add = __builtin_inff();
-        push(REF_MARK);
+        st.push(REF_MARK);
         cur_inst = ii; cur = I->blas_root;
-      } else pop();
+      } else cur = st.pop();
     }
     if (!need && cur == REF_DONE) {
       // ---- finished: the record, or the miss form with tmax as given
@@ -314,16 +277,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a) {
       need = true;
     }
   }
-  if (COUNT) {
-    for (int off = 32; off > 0; off >>= 1) {
-      cnt_nodes += __shfl_down((unsigned long long)cnt_nodes, off);
-      cnt_tris += __shfl_down((unsigned long long)cnt_tris, off);
-    }
-    if (lane == 0) {
-      atomicAdd(reinterpret_cast<unsigned long long*>(a.counters + CNT_NODE_VISITS), (unsigned long long)cnt_nodes);
-      atomicAdd(reinterpret_cast<unsigned long long*>(a.counters + CNT_TRI_TESTS), (unsigned long long)cnt_tris);
-    }
-  }
+  if (COUNT) walk_flush_counters(a.counters, cnt_nodes, cnt_tris);
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SWEEP_WAVES_PER_EU))) void k_sweep_spheres(SweepArgs a) { sweep_body<false>(a); }
@@ -354,14 +308,9 @@ __global__ __launch_bounds__(256) void k_sweep_side(SceneDev sc, const float4* _
 
 void launch_sweep_spheres(const SceneDev& sc, const float4* sweeps, uint32_t cull_mask, const float* inst_scale, HitRec* hits, uint32_t n, int32_t* ovf_stack,
                           uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s) {
-  hipLaunchKernelGGL(k_query_init, dim3(1), dim3(64), 0, s, counters, n);   // (zeroes the chunk cursor, cnt_work(0, 0))
   SweepArgs a{};
-  a.sc = sc; a.sweeps = sweeps; a.inst_scale = inst_scale; a.cull_mask = cull_mask; a.n = n; a.hits = hits;
-  a.cursor = counters + cnt_work(0, 0); a.counters = counters; a.ovf_stack = ovf_stack;
-  // the persistent grid the spill area is sized for, no larger than the records need
-  const uint32_t blocks = min((uint32_t)cfg.trace_blocks, (n + 255u) / 256u);
-  if (counting) hipLaunchKernelGGL(k_sweep_spheres_count, dim3(blocks), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(k_sweep_spheres, dim3(blocks), dim3(256), 0, s, a);
+  a.sc = sc; a.sweeps = sweeps; a.inst_scale = inst_scale; a.cull_mask = cull_mask; a.n = n; a.hits = hits; a.counters = counters; a.ovf_stack = ovf_stack;
+  launch_walk(k_sweep_spheres, k_sweep_spheres_count, a, counters, counting, cfg, s);
 }
 
 void launch_sweep_side(const SceneDev& sc, const float4* sweeps, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s) {

@@ -2300,108 +2300,141 @@ int query_done(rt_ctx* c, hipStream_t s) {
   return RT_OK;
 }
 
-// The enqueue of every query (rt_intersect, rt_intersect_device, rt_intersect_device_flags, rt_closest_point*, rt_overlap_boxes*, rt_sweep_spheres*,
-// rt_point_inside*, rt_signed_distance_device) on stream s, after the
-// caller's checks.  Walk::Flags: the flag-aware walk (MODE_QUERY_FLAGS) with the ray words `words` (or none) and the call's query word;
-// Walk::Plain: the plain walk with any_hit; Walk::Closest: the closest-point walk over n point records with the cull mask `query_word`
-// (its per-instance scales are made first, in the workspace); Walk::Overlap: the box-overlap walk over n box records with the cull mask
-// `query_word`, any_hit standing for RT_OVERLAP_ANY, d_hits for the id rows of max_ids entries and d_counts for the counts (the same
-// scales first); Walk::Sweep: the sphere-sweep walk over n sweep records with the cull mask `query_word` (the same scales first).
-// Walk::Inside: the inside / outside vote over n point records with the cull mask `query_word`, max_ids standing for n_dirs, into
-// d_words and, optionally, d_counts; with d_hits the signed distance: the closest-point walk into d_hits (and d_attr) first, the vote
-// with the counter block's cursor initialised again, then the sign pass over d_hits (d_words null: the workspace's words).
-// counting: the instrumented Plain, Closest, Overlap, Sweep or Inside walk (its counts start from a zeroed counter block).  d_attr
-// (optional): the hit attributes.  t0 / t1 (optional): events recorded around the walk.
-enum class Walk { Plain, Flags, Closest, Overlap, Sweep, Inside };
-int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, Walk walk, size_t n, const void* d_records, bool any_hit, bool counting,
-                  const void* words, uint32_t query_word, void* d_hits, void* d_attr, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr,
-                  uint32_t max_ids = 0u, void* d_counts = nullptr, void* d_words = nullptr) {
-  const bool flags = walk == Walk::Flags, overlap = walk == Walk::Overlap, sweep = walk == Walk::Sweep, inside = walk == Walk::Inside;
-  const bool closest = walk == Walk::Closest || (inside && d_hits);
-  const void* const d_rays8 = d_records;
+// One query as enqueue_query runs it, after the caller's checks.  Every pointer is device memory; a field a walk does not use stays as
+// it is here.
+enum class Walk {
+  Plain,     // rt_intersect, rt_intersect_device: the plain walk, closest hit or any_hit
+  Flags,     // rt_intersect_device_flags: the flag-aware walk (MODE_QUERY_FLAGS) and k_hit_kind behind the attributes
+  Hits,      // rt_intersect_device_hits: the max_hits nearest hits of every ray and their number
+  Closest,   // rt_closest_point*: the nearest surface point (the per-instance scales are made first, in the workspace)
+  Overlap,   // rt_overlap_boxes*: the triangles that touch every box (the same scales first)
+  Sweep,     // rt_sweep_spheres*: the first contact of every moving sphere (the same scales first)
+  Inside     // rt_point_inside*: the inside / outside vote; with hits, rt_signed_distance_device: the closest-point walk into hits (and
+             // attr) first, the vote with the counter block's cursor initialised again, then the sign pass over hits
+};
+struct Query {
+  Walk walk = Walk::Plain;
+  size_t n = 0;
+  const void* records = nullptr;     // n ray, point, box or sweep records
+  const void* ray_words = nullptr;   // Flags, Hits: n per-ray words, or none
+  uint32_t query_word = 0;           // Flags, Hits: the call's ray flags | cull mask << 24
+  uint32_t cull_mask = 0;            // Closest, Overlap, Sweep, Inside
+  bool any_hit = false;              // Plain
+  bool overlap_any = false;          // Overlap: RT_OVERLAP_ANY
+  uint32_t max_hits = 0;             // Hits: records per row of hits
+  uint32_t max_ids = 0;              // Overlap: entries per row of ids
+  uint32_t n_dirs = 0;               // Inside
+  void* hits = nullptr;              // hit records (Hits: n rows; Overlap: none; Inside: the signed distances, or none)
+  void* ids = nullptr;               // Overlap: n rows of (inst, prim)
+  void* counts = nullptr;            // Hits, Overlap: n counts; Inside: n * n_dirs crossing counts (optional)
+  void* words = nullptr;             // Inside: n vote words (null with hits: the workspace's)
+  void* attr = nullptr;              // the hit attributes (optional)
+  bool counting = false;             // the instrumented walk (Hits and Flags have none): its counts start from a zeroed counter block
+  hipEvent_t t0 = nullptr, t1 = nullptr;   // recorded around the walk (optional)
+};
+int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q) {
+  const bool flags = q.walk == Walk::Flags, sweep = q.walk == Walk::Sweep, inside = q.walk == Walk::Inside;
+  const bool closest = q.walk == Walk::Closest || (inside && q.hits);
+  const uint32_t n = (uint32_t)q.n;
+  const float4* const records = (const float4*)q.records;
   { int r = query_workspace(c, s); if (r) return r; }
-  if (inside && !d_words) {   // (signed distance without d_inside)
-    if (n > c->q_words_alloc) {
-      { int q = wait_queries(c, c); if (q) return q; }
+  uint32_t* words = (uint32_t*)q.words;
+  if (inside && !words) {   // (signed distance without d_inside)
+    if (q.n > c->q_words_alloc) {
+      { int w = wait_queries(c, c); if (w) return w; }
       if (c->d_q_words) HIP_TRY(c, hipFree(c->d_q_words));
       c->d_q_words = nullptr; c->q_words_alloc = 0;
-      HIP_TRY(c, hipMalloc((void**)&c->d_q_words, n * sizeof(uint32_t)));
-      c->q_words_alloc = n;
+      HIP_TRY(c, hipMalloc((void**)&c->d_q_words, q.n * sizeof(uint32_t)));
+      c->q_words_alloc = q.n;
     }
-    d_words = c->d_q_words;
+    words = c->d_q_words;
   }
-  if (counting) HIP_TRY(c, hipMemsetAsync(c->d_q_counters, 0, CNT_WORDS * sizeof(uint32_t), s));
+  if (q.counting) HIP_TRY(c, hipMemsetAsync(c->d_q_counters, 0, CNT_WORDS * sizeof(uint32_t), s));
   const SceneDev sc = scene_dev(c);
-  if (t0) HIP_TRY(c, hipEventRecord(t0, s));
-  if (overlap) {
-    launch_closest_scale(sc, c->d_q_scale, s);
-    launch_overlap_boxes(sc, (const float4*)d_records, query_word, c->d_q_scale, any_hit, max_ids, d_hits, (uint32_t*)d_counts, (uint32_t)n, c->d_q_ovf,
-                         c->d_q_counters, counting, cfg, s);
-  } else if (sweep) {
-    launch_closest_scale(sc, c->d_q_scale, s);
-    launch_sweep_spheres(sc, (const float4*)d_records, query_word, c->d_q_scale, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, counting, cfg, s);
-  } else if (closest) {
-    launch_closest_scale(sc, c->d_q_scale, s);
-    launch_closest_point(sc, (const float4*)d_rays8, query_word, c->d_q_scale, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, counting && !inside, cfg, s);
-    if (inside) launch_point_inside(sc, (const float4*)d_records, query_word, max_ids, (uint32_t*)d_words, (uint32_t*)d_counts, (uint32_t)n, c->d_q_ovf, c->d_q_counters, counting, cfg, s);
-  } else if (inside) {
-    launch_point_inside(sc, (const float4*)d_records, query_word, max_ids, (uint32_t*)d_words, (uint32_t*)d_counts, (uint32_t)n, c->d_q_ovf, c->d_q_counters, counting, cfg, s);
-  } else if (flags) launch_query_flags(sc, (const float4*)d_rays8, (const uint32_t*)words, query_word, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, cfg, s);
-  else launch_query(sc, (const float4*)d_rays8, (HitRec*)d_hits, (uint32_t)n, c->d_q_ovf, c->d_q_counters, any_hit, counting, cfg, s);
-  if (t1) HIP_TRY(c, hipEventRecord(t1, s));
-  if (d_attr) launch_hit_attr(sc, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
-  if (d_attr && flags) launch_hit_kind(sc, (const float4*)d_rays8, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
-  if (d_attr && closest) launch_closest_side(sc, (const float4*)d_rays8, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
-  if (d_attr && sweep) launch_sweep_side(sc, (const float4*)d_records, (const HitRec*)d_hits, (float4*)d_attr, (uint32_t)n, s);
-  if (inside && d_hits) launch_sign_distance((const float4*)d_records, (const uint32_t*)d_words, (HitRec*)d_hits, (uint32_t)n, s);   // (after the attributes: they read the records)
+  if (q.t0) HIP_TRY(c, hipEventRecord(q.t0, s));
+  if (closest || sweep || q.walk == Walk::Overlap) launch_closest_scale(sc, c->d_q_scale, s);
+  switch (q.walk) {
+    case Walk::Plain: launch_query(sc, records, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, q.any_hit, q.counting, cfg, s); break;
+    case Walk::Flags: launch_query_flags(sc, records, (const uint32_t*)q.ray_words, q.query_word, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, cfg, s); break;
+    case Walk::Hits:   // (with k_query_hits_surface for the attributes)
+      launch_query_hits(sc, records, (const uint32_t*)q.ray_words, q.query_word, n, q.max_hits, (HitRec*)q.hits, (float4*)q.attr, (uint32_t*)q.counts, c->d_q_ovf,
+                        c->d_q_counters, cfg, s);
+      break;
+    case Walk::Closest: launch_closest_point(sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s); break;
+    case Walk::Overlap:
+      launch_overlap_boxes(sc, records, q.cull_mask, c->d_q_scale, q.overlap_any, q.max_ids, q.ids, (uint32_t*)q.counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
+      break;
+    case Walk::Sweep: launch_sweep_spheres(sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s); break;
+    case Walk::Inside:
+      if (closest) launch_closest_point(sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, false, cfg, s);
+      launch_point_inside(sc, records, q.cull_mask, q.n_dirs, words, (uint32_t*)q.counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
+      break;
+  }
+  if (q.t1) HIP_TRY(c, hipEventRecord(q.t1, s));
+  if (q.attr && q.walk != Walk::Hits) {
+    launch_hit_attr(sc, (const HitRec*)q.hits, (float4*)q.attr, n, s);
+    if (flags) launch_hit_kind(sc, records, (const HitRec*)q.hits, (float4*)q.attr, n, s);
+    if (closest) launch_closest_side(sc, records, (const HitRec*)q.hits, (float4*)q.attr, n, s);
+    if (sweep) launch_sweep_side(sc, records, (const HitRec*)q.hits, (float4*)q.attr, n, s);
+  }
+  if (inside && q.hits) launch_sign_distance(records, words, (HitRec*)q.hits, n, s);   // (after the attributes: they read the records)
   return query_done(c, s);
 }
-}  // namespace
 
-// A blocking ray query from host memory: the rays are copied to the device as they are, walked on the context's stream like a device
-// query (its workspace and ordering) and the hits copied back.
-int rt_intersect(rt_ctx* c, size_t n, const float* rays8, int any_hit, rt_hit* out, int counting, rt_stats* stats) {
-  if (!c) return RT_ERR_INVALID_ARGUMENT;
-  if ((!rays8 || !out) && n) return fail(c, RT_ERR_INVALID_ARGUMENT, "null ray/hit pointers");
-  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, "too many rays for one call");
+// What every device query does after its own checks: the query on the caller's stream (NULL: the context's).  packet_trace does not
+// apply to device queries.
+int device_query(rt_ctx* c, const Query& q, void* hip_stream) {
   HIP_TRY(c, hipSetDevice(c->device));
-  { int q = quiesce(c); if (q) return q; }   // not beside a frame of rt_trace_async; a finished pending frame is collected
+  int r = ready_to_trace(c); if (r) return r;
+  if (q.n == 0) return RT_OK;
+  LaunchCfg cfg = c->cfg;
+  cfg.packet = 0;
+  return enqueue_query(c, hip_stream ? (hipStream_t)hip_stream : c->stream, cfg, q);
+}
+
+// One output of a blocking query: its place in the staging buffer, the Query field that points there, and the host memory it is copied
+// to afterwards (NULL: the caller does not want it; the field stays null and nothing is copied).
+struct HostOutput { void* Query::*field; size_t offset; void* host; size_t bytes; };
+
+// What every blocking host form does after its own checks: a query from host memory, walked on the context's stream like a device
+// query (its workspace and ordering).  One staging allocation of total_bytes: the records (record_bytes, copied in as they are) at its
+// start, the outputs behind them; two events time the walk.  With q.counting the instrumented walk's node visits and triangle tests
+// come back in stats.
+int blocking_query(rt_ctx* c, Query q, const void* records, size_t record_bytes, size_t total_bytes, std::initializer_list<HostOutput> outs, rt_stats* stats) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  { int w = quiesce(c); if (w) return w; }   // not beside a frame of rt_trace_async; a finished pending frame is collected
   int r = ready_to_trace(c); if (r) return r;
   if (stats) memset(stats, 0, sizeof(*stats));
-  if (n == 0) return RT_OK;
-  // one allocation: the rays (32 B each), then the hits
-  const size_t ray_bytes = n * 8 * sizeof(float);
-  char* d_buf = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  struct Guard {   // every exit path below releases the temporaries
-    char*& buf; hipEvent_t &a, &b;
-    ~Guard() { if (buf) hipFree(buf); if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
-  } guard{d_buf, e0, e1};
-  HIP_TRY(c, hipMalloc((void**)&d_buf, ray_bytes + n * sizeof(HitRec)));
-  HitRec* const d_h = (HitRec*)(d_buf + ray_bytes);
-  HIP_TRY(c, hipMemcpy(d_buf, rays8, ray_bytes, hipMemcpyHostToDevice));
-  HIP_TRY(c, hipEventCreate(&e0)); HIP_TRY(c, hipEventCreate(&e1));
+  if (q.n == 0) return RT_OK;
+  struct Staging {   // every exit path below releases the temporaries
+    char* buf = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~Staging() { if (buf) hipFree(buf); if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); }
+  } st;
+  HIP_TRY(c, hipMalloc((void**)&st.buf, total_bytes));
+  HIP_TRY(c, hipMemcpy(st.buf, records, record_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipEventCreate(&st.e0)); HIP_TRY(c, hipEventCreate(&st.e1));
+  q.records = st.buf; q.t0 = st.e0; q.t1 = st.e1;
+  for (const HostOutput& o : outs) if (o.host) q.*o.field = st.buf + o.offset;
   LaunchCfg cfg = c->cfg;
-  if (c->stack_need > 120) cfg.packet = 0;   // (see enqueue_frame)
-  r = enqueue_query(c, c->stream, cfg, Walk::Plain, n, d_buf, any_hit != 0, counting != 0, nullptr, 0u, d_h, nullptr, e0, e1); if (r) return r;
+  if (q.walk == Walk::Plain && c->stack_need > 120) cfg.packet = 0;   // (see enqueue_frame)
+  r = enqueue_query(c, c->stream, cfg, q); if (r) return r;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipMemcpy(out, d_h, n * sizeof(HitRec), hipMemcpyDeviceToHost));
+  for (const HostOutput& o : outs) if (o.host) HIP_TRY(c, hipMemcpy(o.host, st.buf + o.offset, o.bytes, hipMemcpyDeviceToHost));
   if (stats) {
-    if (counting) {
+    if (q.counting) {   // (an any-hit walk counts in the shadow words)
       uint32_t cnt[CNT_TAILS];
       HIP_TRY(c, hipMemcpy(cnt, c->d_q_counters, sizeof(cnt), hipMemcpyDeviceToHost));
-      memcpy(&stats->node_visits, &cnt[any_hit ? CNT_NODE_VISITS_SH : CNT_NODE_VISITS], 8);
-      memcpy(&stats->tri_tests, &cnt[any_hit ? CNT_TRI_TESTS_SH : CNT_TRI_TESTS], 8);
+      memcpy(&stats->node_visits, &cnt[q.any_hit ? CNT_NODE_VISITS_SH : CNT_NODE_VISITS], 8);
+      memcpy(&stats->tri_tests, &cnt[q.any_hit ? CNT_TRI_TESTS_SH : CNT_TRI_TESTS], 8);
     }
-    float ms = 0.f; hipEventElapsedTime(&ms, e0, e1);
-    if (any_hit) stats->ms_trace_shadow = ms; else stats->ms_trace_closest = ms;
-    stats->closest_rays = any_hit ? 0 : n; stats->rays_shadow = any_hit ? n : 0;
+    float ms = 0.f; hipEventElapsedTime(&ms, st.e0, st.e1);
+    if (q.any_hit) stats->ms_trace_shadow = ms; else stats->ms_trace_closest = ms;
+    if (q.walk == Walk::Plain) { stats->closest_rays = q.any_hit ? 0 : q.n; stats->rays_shadow = q.any_hit ? q.n : 0; }
     stats->bvh_node_bytes = c->cfg.variant == 1 ? sizeof(Bvh4Node) : c->cfg.variant == 2 ? sizeof(WideNodeQ) : sizeof(BvhNodeQ); stats->bvh_tri_bytes = sizeof(TriPacket);
   }
   return RT_OK;
 }
 
-namespace {
 // every non-NULL pointer is device memory of the context's GPU (`what` names them in the message)
 int check_device_pointers(rt_ctx* c, const std::string& name, const char* what, std::initializer_list<const void*> ptrs) {
   HIP_TRY(c, hipSetDevice(c->device));
@@ -2414,29 +2447,44 @@ int check_device_pointers(rt_ctx* c, const std::string& name, const char* what, 
   }
   return RT_OK;
 }
-}  // namespace
 
-namespace {
+// Vulkan's valid-usage rules for rayQueryInitializeEXT's flags (the per-ray words cannot be checked without a host round trip)
+int ray_flag_arguments(rt_ctx* c, const std::string& name, uint32_t ray_flags, uint32_t cull_mask) {
+  if ((ray_flags & ~0x3FFu) != 0u || cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": ray_flags has bits outside 0x3FF or cull_mask is above 0xFF");
+  const uint32_t opacity = ray_flags & (RT_RAY_FLAG_OPAQUE | RT_RAY_FLAG_NO_OPAQUE | RT_RAY_FLAG_CULL_OPAQUE | RT_RAY_FLAG_CULL_NO_OPAQUE);
+  if ((opacity & (opacity - 1u)) != 0u) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": at most one of OPAQUE, NO_OPAQUE, CULL_OPAQUE and CULL_NO_OPAQUE");
+  const uint32_t facing = RT_RAY_FLAG_CULL_BACK_FACING | RT_RAY_FLAG_CULL_FRONT_FACING;
+  if ((ray_flags & facing) == facing) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": CULL_BACK_FACING with CULL_FRONT_FACING");
+  if ((ray_flags & RT_RAY_FLAG_SKIP_TRIANGLES) && (ray_flags & (RT_RAY_FLAG_SKIP_AABBS | facing)))
+    return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": SKIP_TRIANGLES with SKIP_AABBS or a facing cull");
+  return RT_OK;
+}
+
 // The body of rt_intersect_device and rt_intersect_device_flags (their own argument checks come first): the checks of a device call,
-// then the query on the caller's stream.  packet_trace does not apply to device queries.
-int intersect_device(rt_ctx* c, size_t n, const void* d_rays8, bool any_hit, bool flags, const void* words, uint32_t query_word, void* d_hits,
-                     void* d_attr, void* hip_stream) {
-  const char* const name = flags ? "rt_intersect_device_flags" : "rt_intersect_device";
-  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + " needs trace_variant 0");
-  if (n) {
-    if (!d_rays8 || !d_hits) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null ray/hit pointers");
-    if (((uintptr_t)d_rays8 & 15u) || ((uintptr_t)d_hits & 3u) || ((uintptr_t)d_attr & 15u))
-      return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": rays and attributes must be 16-byte aligned, hits 4-byte aligned");
-    { int q = check_device_pointers(c, name, flags ? "rays, ray words, hits and attributes" : "rays, hits and attributes", {d_rays8, d_hits, d_attr, words}); if (q) return q; }
+// then the query on the caller's stream.
+int intersect_device(rt_ctx* c, const Query& q, void* hip_stream) {
+  const bool flags = q.walk == Walk::Flags;
+  const std::string name = flags ? "rt_intersect_device_flags" : "rt_intersect_device";
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, name + " needs trace_variant 0");
+  if (q.n) {
+    if (!q.records || !q.hits) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null ray/hit pointers");
+    if (((uintptr_t)q.records & 15u) || ((uintptr_t)q.hits & 3u) || ((uintptr_t)q.attr & 15u))
+      return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": rays and attributes must be 16-byte aligned, hits 4-byte aligned");
+    { int w = check_device_pointers(c, name, flags ? "rays, ray words, hits and attributes" : "rays, hits and attributes", {q.records, q.hits, q.attr, q.ray_words}); if (w) return w; }
   }
-  HIP_TRY(c, hipSetDevice(c->device));
-  int r = ready_to_trace(c); if (r) return r;
-  if (n == 0) return RT_OK;
-  LaunchCfg cfg = c->cfg;
-  cfg.packet = 0;
-  return enqueue_query(c, hip_stream ? (hipStream_t)hip_stream : c->stream, cfg, flags ? Walk::Flags : Walk::Plain, n, d_rays8, any_hit, false, words, query_word, d_hits, d_attr);
+  return device_query(c, q, hip_stream);
 }
 }  // namespace
+
+// A blocking ray query from host memory: the rays (32 B each), then the hits.
+int rt_intersect(rt_ctx* c, size_t n, const float* rays8, int any_hit, rt_hit* out, int counting, rt_stats* stats) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  if ((!rays8 || !out) && n) return fail(c, RT_ERR_INVALID_ARGUMENT, "null ray/hit pointers");
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, "too many rays for one call");
+  const size_t ray_bytes = n * 8 * sizeof(float), hit_bytes = n * sizeof(HitRec);
+  Query q; q.walk = Walk::Plain; q.n = n; q.any_hit = any_hit != 0; q.counting = counting != 0;
+  return blocking_query(c, q, rays8, ray_bytes, ray_bytes + hit_bytes, {{&Query::hits, ray_bytes, out, hit_bytes}}, stats);
+}
 
 // VK_KHR_ray_query for device-resident rays: rt_intersect's traversal (k_trace<MODE_QUERY>: the one-lane BVH2 walk with the far-ray logic)
 // on the caller's rays, hits and surfaces, ordered on the caller's stream.  Nothing is copied, nothing waits on the host, and no frame
@@ -2447,7 +2495,8 @@ int rt_intersect_device(rt_ctx* c, size_t n, const void* d_rays8, int any_hit, v
   if (!c) return RT_ERR_INVALID_ARGUMENT;
   if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, "too many rays for one call");
   if (any_hit && d_attr) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device: hit attributes are for closest-hit queries only (any_hit skips the closest-hit shader)");
-  return intersect_device(c, n, d_rays8, any_hit != 0, false, nullptr, 0u, d_hits, d_attr, hip_stream);
+  Query q; q.walk = Walk::Plain; q.n = n; q.records = d_rays8; q.any_hit = any_hit != 0; q.hits = d_hits; q.attr = d_attr;
+  return intersect_device(c, q, hip_stream);
 }
 
 // rt_intersect_device with ray flags and cull masks, per call and per ray (rayQueryInitializeEXT's rayFlags and cullMask): the same
@@ -2456,18 +2505,11 @@ int rt_intersect_device_flags(rt_ctx* c, size_t n, const void* d_rays8, const vo
                               void* d_attr, void* hip_stream) {
   if (!c) return RT_ERR_INVALID_ARGUMENT;
   if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, "too many rays for one call");
-  // Vulkan's valid-usage rules for rayQueryInitializeEXT's flags (the per-ray words cannot be checked without a host round trip)
-  if ((ray_flags & ~0x3FFu) != 0u || cull_mask > 0xFFu)
-    return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device_flags: ray_flags has bits outside 0x3FF or cull_mask is above 0xFF");
-  const uint32_t opacity = ray_flags & (RT_RAY_FLAG_OPAQUE | RT_RAY_FLAG_NO_OPAQUE | RT_RAY_FLAG_CULL_OPAQUE | RT_RAY_FLAG_CULL_NO_OPAQUE);
-  if ((opacity & (opacity - 1u)) != 0u)
-    return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device_flags: at most one of OPAQUE, NO_OPAQUE, CULL_OPAQUE and CULL_NO_OPAQUE");
-  const uint32_t facing = RT_RAY_FLAG_CULL_BACK_FACING | RT_RAY_FLAG_CULL_FRONT_FACING;
-  if ((ray_flags & facing) == facing) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device_flags: CULL_BACK_FACING with CULL_FRONT_FACING");
-  if ((ray_flags & RT_RAY_FLAG_SKIP_TRIANGLES) && (ray_flags & (RT_RAY_FLAG_SKIP_AABBS | facing)))
-    return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device_flags: SKIP_TRIANGLES with SKIP_AABBS or a facing cull");
+  { int w = ray_flag_arguments(c, "rt_intersect_device_flags", ray_flags, cull_mask); if (w) return w; }
   if (n && ((uintptr_t)d_ray_words & 3u)) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_intersect_device_flags: ray words must be 4-byte aligned");
-  return intersect_device(c, n, d_rays8, false, true, n ? d_ray_words : nullptr, (cull_mask << 24) | ray_flags, d_hits, d_attr, hip_stream);
+  Query q; q.walk = Walk::Flags; q.n = n; q.records = d_rays8; q.ray_words = n ? d_ray_words : nullptr; q.query_word = (cull_mask << 24) | ray_flags;
+  q.hits = d_hits; q.attr = d_attr;
+  return intersect_device(c, q, hip_stream);
 }
 
 // All hits along a ray (rayQueryProceedEXT's candidate loop in data form): the flag checks of rt_intersect_device_flags, the checks and
@@ -2475,126 +2517,70 @@ int rt_intersect_device_flags(rt_ctx* c, size_t n, const void* d_rays8, const vo
 int rt_intersect_device_hits(rt_ctx* c, size_t n, const void* d_rays8, const void* d_ray_words, uint32_t ray_flags, uint32_t cull_mask, uint32_t max_hits,
                              void* d_hits, void* d_attr, void* d_counts, void* hip_stream) {
   if (!c) return RT_ERR_INVALID_ARGUMENT;
-  const char* const name = "rt_intersect_device_hits";
+  const std::string name = "rt_intersect_device_hits";
   if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, "too many rays for one call");
-  if (max_hits > 16u) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": max_hits must be 0..16");
-  if ((uint64_t)n * max_hits >= 0xFFFFFF00ull)
-    return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": n * max_hits must be below 0xFFFFFF00 (32-bit record indices)");
+  if (max_hits > 16u) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": max_hits must be 0..16");
+  if ((uint64_t)n * max_hits >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": n * max_hits must be below 0xFFFFFF00 (32-bit record indices)");
   if (max_hits == 0u && (d_hits || d_attr || !d_counts))
-    return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": max_hits 0 counts only: d_hits and d_attr must be NULL, d_counts non-NULL");
+    return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": max_hits 0 counts only: d_hits and d_attr must be NULL, d_counts non-NULL");
   if (ray_flags & RT_RAY_FLAG_TERMINATE_ON_FIRST_HIT)
-    return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": TERMINATE_ON_FIRST_HIT in ray_flags (a multi-hit query has no first-hit form)");
-  if ((ray_flags & ~0x3FFu) != 0u || cull_mask > 0xFFu)
-    return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": ray_flags has bits outside 0x3FF or cull_mask is above 0xFF");
-  const uint32_t opacity = ray_flags & (RT_RAY_FLAG_OPAQUE | RT_RAY_FLAG_NO_OPAQUE | RT_RAY_FLAG_CULL_OPAQUE | RT_RAY_FLAG_CULL_NO_OPAQUE);
-  if ((opacity & (opacity - 1u)) != 0u)
-    return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": at most one of OPAQUE, NO_OPAQUE, CULL_OPAQUE and CULL_NO_OPAQUE");
-  const uint32_t facing = RT_RAY_FLAG_CULL_BACK_FACING | RT_RAY_FLAG_CULL_FRONT_FACING;
-  if ((ray_flags & facing) == facing) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": CULL_BACK_FACING with CULL_FRONT_FACING");
-  if ((ray_flags & RT_RAY_FLAG_SKIP_TRIANGLES) && (ray_flags & (RT_RAY_FLAG_SKIP_AABBS | facing)))
-    return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": SKIP_TRIANGLES with SKIP_AABBS or a facing cull");
-  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + " needs trace_variant 0");
+    return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": TERMINATE_ON_FIRST_HIT in ray_flags (a multi-hit query has no first-hit form)");
+  { int w = ray_flag_arguments(c, name, ray_flags, cull_mask); if (w) return w; }
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, name + " needs trace_variant 0");
   if (n) {
-    if (!d_rays8 || (max_hits && !d_hits)) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null ray/hit pointers");
+    if (!d_rays8 || (max_hits && !d_hits)) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null ray/hit pointers");
     if (((uintptr_t)d_rays8 & 15u) || ((uintptr_t)d_hits & 3u) || ((uintptr_t)d_attr & 15u) || ((uintptr_t)d_ray_words & 3u) || ((uintptr_t)d_counts & 3u))
-      return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": rays and attributes must be 16-byte aligned, ray words, hits and counts 4-byte aligned");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const void* ptrs[5] = {d_rays8, d_ray_words, d_hits, d_attr, d_counts};
-    for (const void* p : ptrs) {
-      if (!p) continue;
-      hipPointerAttribute_t at{};
-      const bool ok = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == c->device;
-      (void)hipGetLastError();   // (a host pointer leaves an error behind)
-      if (!ok) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": rays, ray words, hits, attributes and counts must be device memory of the context's GPU (" +
-                                                           std::to_string(c->device) + ")");
-    }
+      return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": rays and attributes must be 16-byte aligned, ray words, hits and counts 4-byte aligned");
+    { int w = check_device_pointers(c, name, "rays, ray words, hits, attributes and counts", {d_rays8, d_ray_words, d_hits, d_attr, d_counts}); if (w) return w; }
   }
-  HIP_TRY(c, hipSetDevice(c->device));
-  int r = ready_to_trace(c); if (r) return r;
-  if (n == 0) return RT_OK;
-  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-  r = query_workspace(c, s); if (r) return r;
-  launch_query_hits(scene_dev(c), (const float4*)d_rays8, (const uint32_t*)d_ray_words, (cull_mask << 24) | ray_flags, (uint32_t)n, max_hits, (HitRec*)d_hits,
-                    (float4*)d_attr, (uint32_t*)d_counts, c->d_q_ovf, c->d_q_counters, c->cfg, s);
-  return query_done(c, s);
+  Query q; q.walk = Walk::Hits; q.n = n; q.records = d_rays8; q.ray_words = d_ray_words; q.query_word = (cull_mask << 24) | ray_flags; q.max_hits = max_hits;
+  q.hits = d_hits; q.attr = d_attr; q.counts = d_counts;
+  return device_query(c, q, hip_stream);
 }
 
 // The nearest surface point of every query point: the checks and ordering of a device query (rt_intersect_device), then k_closest_scale and
 // k_closest_point over the caller's records (enqueue_query), k_hit_attr and k_closest_side for the attributes.
 int rt_closest_point_device(rt_ctx* c, size_t n, const void* d_points4, uint32_t cull_mask, void* d_hits, void* d_attr, void* hip_stream) {
   if (!c) return RT_ERR_INVALID_ARGUMENT;
-  const char* const name = "rt_closest_point_device";
+  const std::string name = "rt_closest_point_device";
   if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, "too many points for one call");
-  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": cull_mask is above 0xFF");
-  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + " needs trace_variant 0");
+  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": cull_mask is above 0xFF");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, name + " needs trace_variant 0");
   if (n) {
-    if (!d_points4 || !d_hits) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null point/hit pointers");
+    if (!d_points4 || !d_hits) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null point/hit pointers");
     if (((uintptr_t)d_points4 & 15u) || ((uintptr_t)d_hits & 3u) || ((uintptr_t)d_attr & 15u))
-      return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": points and attributes must be 16-byte aligned, hits 4-byte aligned");
-    { int q = check_device_pointers(c, name, "points, hits and attributes", {d_points4, d_hits, d_attr}); if (q) return q; }
+      return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": points and attributes must be 16-byte aligned, hits 4-byte aligned");
+    { int w = check_device_pointers(c, name, "points, hits and attributes", {d_points4, d_hits, d_attr}); if (w) return w; }
   }
-  HIP_TRY(c, hipSetDevice(c->device));
-  int r = ready_to_trace(c); if (r) return r;
-  if (n == 0) return RT_OK;
-  return enqueue_query(c, hip_stream ? (hipStream_t)hip_stream : c->stream, c->cfg, Walk::Closest, n, d_points4, false, false, nullptr, cull_mask, d_hits, d_attr);
+  Query q; q.walk = Walk::Closest; q.n = n; q.records = d_points4; q.cull_mask = cull_mask; q.hits = d_hits; q.attr = d_attr;
+  return device_query(c, q, hip_stream);
 }
 
-// The blocking host form, as rt_intersect is to rt_intersect_device: the records copied in, the same enqueue on the context's stream,
-// the hits copied out; with counting the instrumented walk, whose node visits and triangle tests come back in stats.
+// The blocking host form, as rt_intersect is to rt_intersect_device: the points (16 B each), then the hits.
 int rt_closest_point(rt_ctx* c, size_t n, const float* points4, uint32_t cull_mask, rt_hit* out, int counting, rt_stats* stats) {
   if (!c) return RT_ERR_INVALID_ARGUMENT;
   if ((!points4 || !out) && n) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_closest_point: null point/hit pointers");
   if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, "too many points for one call");
   if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_closest_point: cull_mask is above 0xFF");
   if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_closest_point needs trace_variant 0");
-  HIP_TRY(c, hipSetDevice(c->device));
-  { int q = quiesce(c); if (q) return q; }   // (as rt_intersect)
-  int r = ready_to_trace(c); if (r) return r;
-  if (stats) memset(stats, 0, sizeof(*stats));
-  if (n == 0) return RT_OK;
-  const size_t pt_bytes = n * 4 * sizeof(float);
-  char* d_buf = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  struct Guard {   // every exit path below releases the temporaries
-    char*& buf; hipEvent_t &a, &b;
-    ~Guard() { if (buf) hipFree(buf); if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
-  } guard{d_buf, e0, e1};
-  HIP_TRY(c, hipMalloc((void**)&d_buf, pt_bytes + n * sizeof(HitRec)));
-  HitRec* const d_h = (HitRec*)(d_buf + pt_bytes);
-  HIP_TRY(c, hipMemcpy(d_buf, points4, pt_bytes, hipMemcpyHostToDevice));
-  HIP_TRY(c, hipEventCreate(&e0)); HIP_TRY(c, hipEventCreate(&e1));
-  r = enqueue_query(c, c->stream, c->cfg, Walk::Closest, n, d_buf, false, counting != 0, nullptr, cull_mask, d_h, nullptr, e0, e1); if (r) return r;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipMemcpy(out, d_h, n * sizeof(HitRec), hipMemcpyDeviceToHost));
-  if (stats) {
-    if (counting) {
-      uint32_t cnt[CNT_TAILS];
-      HIP_TRY(c, hipMemcpy(cnt, c->d_q_counters, sizeof(cnt), hipMemcpyDeviceToHost));
-      memcpy(&stats->node_visits, &cnt[CNT_NODE_VISITS], 8);
-      memcpy(&stats->tri_tests, &cnt[CNT_TRI_TESTS], 8);
-    }
-    float ms = 0.f; hipEventElapsedTime(&ms, e0, e1);
-    stats->ms_trace_closest = ms;
-    stats->bvh_node_bytes = sizeof(BvhNodeQ); stats->bvh_tri_bytes = sizeof(TriPacket);
-  }
-  return RT_OK;
+  const size_t pt_bytes = n * 4 * sizeof(float), hit_bytes = n * sizeof(HitRec);
+  Query q; q.walk = Walk::Closest; q.n = n; q.cull_mask = cull_mask; q.counting = counting != 0;
+  return blocking_query(c, q, points4, pt_bytes, pt_bytes + hit_bytes, {{&Query::hits, pt_bytes, out, hit_bytes}}, stats);
 }
 
 namespace {
 // the argument rules rt_overlap_boxes_device and rt_overlap_boxes share (pointers aside)
-int overlap_arguments(rt_ctx* c, const char* name, size_t n, uint32_t cull_mask, uint32_t flags, uint32_t max_ids, const void* ids, const void* counts) {
-  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": too many boxes for one call");
-  if (max_ids > 16u) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": max_ids must be 0..16");
-  if ((uint64_t)n * max_ids >= 0xFFFFFF00ull)
-    return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": n * max_ids must be below 0xFFFFFF00 (32-bit record indices)");
-  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": cull_mask is above 0xFF");
-  if ((flags & ~RT_OVERLAP_ANY) != 0u) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": unknown flag bits");
-  if ((flags & RT_OVERLAP_ANY) && max_ids != 0u) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": RT_OVERLAP_ANY needs max_ids 0");
-  if (!ids && !counts) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": neither ids nor counts given");
-  if (max_ids == 0u && (ids || !counts))
-    return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": max_ids 0 counts only: the ids must be NULL, the counts non-NULL");
-  if (max_ids != 0u && !ids) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null id pointer with max_ids above 0");
-  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + " needs trace_variant 0");
+int overlap_arguments(rt_ctx* c, const std::string& name, size_t n, uint32_t cull_mask, uint32_t flags, uint32_t max_ids, const void* ids, const void* counts) {
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": too many boxes for one call");
+  if (max_ids > 16u) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": max_ids must be 0..16");
+  if ((uint64_t)n * max_ids >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": n * max_ids must be below 0xFFFFFF00 (32-bit record indices)");
+  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": cull_mask is above 0xFF");
+  if ((flags & ~RT_OVERLAP_ANY) != 0u) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": unknown flag bits");
+  if ((flags & RT_OVERLAP_ANY) && max_ids != 0u) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": RT_OVERLAP_ANY needs max_ids 0");
+  if (!ids && !counts) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": neither ids nor counts given");
+  if (max_ids == 0u && (ids || !counts)) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": max_ids 0 counts only: the ids must be NULL, the counts non-NULL");
+  if (max_ids != 0u && !ids) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null id pointer with max_ids above 0");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, name + " needs trace_variant 0");
   return RT_OK;
 }
 }  // namespace
@@ -2604,139 +2590,71 @@ int overlap_arguments(rt_ctx* c, const char* name, size_t n, uint32_t cull_mask,
 int rt_overlap_boxes_device(rt_ctx* c, size_t n, const void* d_boxes8, uint32_t cull_mask, uint32_t flags, uint32_t max_ids, void* d_ids, void* d_counts,
                             void* hip_stream) {
   if (!c) return RT_ERR_INVALID_ARGUMENT;
-  const char* const name = "rt_overlap_boxes_device";
-  { int q = overlap_arguments(c, name, n, cull_mask, flags, max_ids, d_ids, d_counts); if (q) return q; }
+  const std::string name = "rt_overlap_boxes_device";
+  { int w = overlap_arguments(c, name, n, cull_mask, flags, max_ids, d_ids, d_counts); if (w) return w; }
   if (n) {
-    if (!d_boxes8) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null box pointer");
+    if (!d_boxes8) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null box pointer");
     if (((uintptr_t)d_boxes8 & 15u) || ((uintptr_t)d_ids & 3u) || ((uintptr_t)d_counts & 3u))
-      return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": boxes must be 16-byte aligned, ids and counts 4-byte aligned");
-    { int q = check_device_pointers(c, name, "boxes, ids and counts", {d_boxes8, d_ids, d_counts}); if (q) return q; }
+      return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": boxes must be 16-byte aligned, ids and counts 4-byte aligned");
+    { int w = check_device_pointers(c, name, "boxes, ids and counts", {d_boxes8, d_ids, d_counts}); if (w) return w; }
   }
-  HIP_TRY(c, hipSetDevice(c->device));
-  int r = ready_to_trace(c); if (r) return r;
-  if (n == 0) return RT_OK;
-  return enqueue_query(c, hip_stream ? (hipStream_t)hip_stream : c->stream, c->cfg, Walk::Overlap, n, d_boxes8, (flags & RT_OVERLAP_ANY) != 0u, false, nullptr,
-                       cull_mask, d_ids, nullptr, nullptr, nullptr, max_ids, d_counts);
+  Query q; q.walk = Walk::Overlap; q.n = n; q.records = d_boxes8; q.cull_mask = cull_mask; q.overlap_any = (flags & RT_OVERLAP_ANY) != 0u; q.max_ids = max_ids;
+  q.ids = d_ids; q.counts = d_counts;
+  return device_query(c, q, hip_stream);
 }
 
-// The blocking host form, as rt_closest_point is to rt_closest_point_device: the records copied in, the same enqueue on the context's
-// stream, the rows and counts copied out; with counting the instrumented walk, whose node visits and triangle tests come back in stats.
+// The blocking host form, as rt_closest_point is to rt_closest_point_device: the boxes (32 B each), then the counts, then the rows.
 int rt_overlap_boxes(rt_ctx* c, size_t n, const float* boxes8, uint32_t cull_mask, uint32_t flags, uint32_t max_ids, int32_t* ids, uint32_t* counts,
                      int counting, rt_stats* stats) {
   if (!c) return RT_ERR_INVALID_ARGUMENT;
-  const char* const name = "rt_overlap_boxes";
-  { int q = overlap_arguments(c, name, n, cull_mask, flags, max_ids, ids, counts); if (q) return q; }
-  if (!boxes8 && n) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null box pointer");
-  HIP_TRY(c, hipSetDevice(c->device));
-  { int q = quiesce(c); if (q) return q; }   // (as rt_intersect)
-  int r = ready_to_trace(c); if (r) return r;
-  if (stats) memset(stats, 0, sizeof(*stats));
-  if (n == 0) return RT_OK;
-  // one allocation: the boxes (32 B each), then the counts, then the rows
+  const std::string name = "rt_overlap_boxes";
+  { int w = overlap_arguments(c, name, n, cull_mask, flags, max_ids, ids, counts); if (w) return w; }
+  if (!boxes8 && n) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null box pointer");
   const size_t box_bytes = n * 8 * sizeof(float), count_bytes = n * sizeof(uint32_t), id_bytes = n * max_ids * 2 * sizeof(int32_t);
-  char* d_buf = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  struct Guard {   // every exit path below releases the temporaries
-    char*& buf; hipEvent_t &a, &b;
-    ~Guard() { if (buf) hipFree(buf); if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
-  } guard{d_buf, e0, e1};
-  HIP_TRY(c, hipMalloc((void**)&d_buf, box_bytes + count_bytes + id_bytes));
-  uint32_t* const d_c = counts ? (uint32_t*)(d_buf + box_bytes) : nullptr;
-  void* const d_i = max_ids ? (void*)(d_buf + box_bytes + count_bytes) : nullptr;
-  HIP_TRY(c, hipMemcpy(d_buf, boxes8, box_bytes, hipMemcpyHostToDevice));
-  HIP_TRY(c, hipEventCreate(&e0)); HIP_TRY(c, hipEventCreate(&e1));
-  r = enqueue_query(c, c->stream, c->cfg, Walk::Overlap, n, d_buf, (flags & RT_OVERLAP_ANY) != 0u, counting != 0, nullptr, cull_mask, d_i, nullptr, e0, e1,
-                    max_ids, d_c);
-  if (r) return r;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (d_c) HIP_TRY(c, hipMemcpy(counts, d_c, count_bytes, hipMemcpyDeviceToHost));
-  if (d_i) HIP_TRY(c, hipMemcpy(ids, d_i, id_bytes, hipMemcpyDeviceToHost));
-  if (stats) {
-    if (counting) {
-      uint32_t cnt[CNT_TAILS];
-      HIP_TRY(c, hipMemcpy(cnt, c->d_q_counters, sizeof(cnt), hipMemcpyDeviceToHost));
-      memcpy(&stats->node_visits, &cnt[CNT_NODE_VISITS], 8);
-      memcpy(&stats->tri_tests, &cnt[CNT_TRI_TESTS], 8);
-    }
-    float ms = 0.f; hipEventElapsedTime(&ms, e0, e1);
-    stats->ms_trace_closest = ms;
-    stats->bvh_node_bytes = sizeof(BvhNodeQ); stats->bvh_tri_bytes = sizeof(TriPacket);
-  }
-  return RT_OK;
+  Query q; q.walk = Walk::Overlap; q.n = n; q.cull_mask = cull_mask; q.overlap_any = (flags & RT_OVERLAP_ANY) != 0u; q.max_ids = max_ids; q.counting = counting != 0;
+  return blocking_query(c, q, boxes8, box_bytes, box_bytes + count_bytes + id_bytes,
+                        {{&Query::counts, box_bytes, counts, count_bytes}, {&Query::ids, box_bytes + count_bytes, ids, id_bytes}}, stats);
 }
 
 // The first contact of every moving sphere: the checks and ordering of a device query (rt_closest_point_device), then k_closest_scale and
 // k_sweep_spheres over the caller's records (enqueue_query), k_hit_attr and k_sweep_side for the attributes.
 int rt_sweep_spheres_device(rt_ctx* c, size_t n, const void* d_sweeps8, uint32_t cull_mask, void* d_hits, void* d_attr, void* hip_stream) {
   if (!c) return RT_ERR_INVALID_ARGUMENT;
-  const char* const name = "rt_sweep_spheres_device";
-  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": too many sweeps for one call");
-  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": cull_mask is above 0xFF");
-  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + " needs trace_variant 0");
+  const std::string name = "rt_sweep_spheres_device";
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": too many sweeps for one call");
+  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": cull_mask is above 0xFF");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, name + " needs trace_variant 0");
   if (n) {
-    if (!d_sweeps8 || !d_hits) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null sweep/hit pointers");
+    if (!d_sweeps8 || !d_hits) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null sweep/hit pointers");
     if (((uintptr_t)d_sweeps8 & 15u) || ((uintptr_t)d_hits & 3u) || ((uintptr_t)d_attr & 15u))
-      return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": sweeps and attributes must be 16-byte aligned, hits 4-byte aligned");
-    { int q = check_device_pointers(c, name, "sweeps, hits and attributes", {d_sweeps8, d_hits, d_attr}); if (q) return q; }
+      return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": sweeps and attributes must be 16-byte aligned, hits 4-byte aligned");
+    { int w = check_device_pointers(c, name, "sweeps, hits and attributes", {d_sweeps8, d_hits, d_attr}); if (w) return w; }
   }
-  HIP_TRY(c, hipSetDevice(c->device));
-  int r = ready_to_trace(c); if (r) return r;
-  if (n == 0) return RT_OK;
-  return enqueue_query(c, hip_stream ? (hipStream_t)hip_stream : c->stream, c->cfg, Walk::Sweep, n, d_sweeps8, false, false, nullptr, cull_mask, d_hits, d_attr);
+  Query q; q.walk = Walk::Sweep; q.n = n; q.records = d_sweeps8; q.cull_mask = cull_mask; q.hits = d_hits; q.attr = d_attr;
+  return device_query(c, q, hip_stream);
 }
 
-// The blocking host form, as rt_closest_point is to rt_closest_point_device: the records copied in, the same enqueue on the context's
-// stream, the hits copied out; with counting the instrumented walk, whose node visits and triangle tests come back in stats.
+// The blocking host form, as rt_closest_point is to rt_closest_point_device: the sweeps (32 B each), then the hits.
 int rt_sweep_spheres(rt_ctx* c, size_t n, const float* sweeps8, uint32_t cull_mask, rt_hit* out, int counting, rt_stats* stats) {
   if (!c) return RT_ERR_INVALID_ARGUMENT;
-  const char* const name = "rt_sweep_spheres";
-  if ((!sweeps8 || !out) && n) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null sweep/hit pointers");
-  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": too many sweeps for one call");
-  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": cull_mask is above 0xFF");
-  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + " needs trace_variant 0");
-  HIP_TRY(c, hipSetDevice(c->device));
-  { int q = quiesce(c); if (q) return q; }   // (as rt_intersect)
-  int r = ready_to_trace(c); if (r) return r;
-  if (stats) memset(stats, 0, sizeof(*stats));
-  if (n == 0) return RT_OK;
-  // one allocation: the sweeps (32 B each), then the hits
-  const size_t sweep_bytes = n * 8 * sizeof(float);
-  char* d_buf = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  struct Guard {   // every exit path below releases the temporaries
-    char*& buf; hipEvent_t &a, &b;
-    ~Guard() { if (buf) hipFree(buf); if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
-  } guard{d_buf, e0, e1};
-  HIP_TRY(c, hipMalloc((void**)&d_buf, sweep_bytes + n * sizeof(HitRec)));
-  HitRec* const d_h = (HitRec*)(d_buf + sweep_bytes);
-  HIP_TRY(c, hipMemcpy(d_buf, sweeps8, sweep_bytes, hipMemcpyHostToDevice));
-  HIP_TRY(c, hipEventCreate(&e0)); HIP_TRY(c, hipEventCreate(&e1));
-  r = enqueue_query(c, c->stream, c->cfg, Walk::Sweep, n, d_buf, false, counting != 0, nullptr, cull_mask, d_h, nullptr, e0, e1); if (r) return r;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipMemcpy(out, d_h, n * sizeof(HitRec), hipMemcpyDeviceToHost));
-  if (stats) {
-    if (counting) {
-      uint32_t cnt[CNT_TAILS];
-      HIP_TRY(c, hipMemcpy(cnt, c->d_q_counters, sizeof(cnt), hipMemcpyDeviceToHost));
-      memcpy(&stats->node_visits, &cnt[CNT_NODE_VISITS], 8);
-      memcpy(&stats->tri_tests, &cnt[CNT_TRI_TESTS], 8);
-    }
-    float ms = 0.f; hipEventElapsedTime(&ms, e0, e1);
-    stats->ms_trace_closest = ms;
-    stats->bvh_node_bytes = sizeof(BvhNodeQ); stats->bvh_tri_bytes = sizeof(TriPacket);
-  }
-  return RT_OK;
+  const std::string name = "rt_sweep_spheres";
+  if ((!sweeps8 || !out) && n) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null sweep/hit pointers");
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": too many sweeps for one call");
+  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": cull_mask is above 0xFF");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, name + " needs trace_variant 0");
+  const size_t sweep_bytes = n * 8 * sizeof(float), hit_bytes = n * sizeof(HitRec);
+  Query q; q.walk = Walk::Sweep; q.n = n; q.cull_mask = cull_mask; q.counting = counting != 0;
+  return blocking_query(c, q, sweeps8, sweep_bytes, sweep_bytes + hit_bytes, {{&Query::hits, sweep_bytes, out, hit_bytes}}, stats);
 }
 
 namespace {
 // the argument rules rt_point_inside_device, rt_point_inside and rt_signed_distance_device share (pointers aside)
-int inside_arguments(rt_ctx* c, const char* name, size_t n, uint32_t cull_mask, uint32_t n_dirs, bool with_counts) {
-  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": too many points for one call");
-  if (n_dirs != 1u && n_dirs != 3u && n_dirs != 5u) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": n_dirs must be 1, 3 or 5");
-  if (with_counts && (uint64_t)n * n_dirs >= 0xFFFFFF00ull)
-    return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": n * n_dirs must be below 0xFFFFFF00 (32-bit record indices)");
-  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": cull_mask is above 0xFF");
-  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + " needs trace_variant 0");
+int inside_arguments(rt_ctx* c, const std::string& name, size_t n, uint32_t cull_mask, uint32_t n_dirs, bool with_counts) {
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": too many points for one call");
+  if (n_dirs != 1u && n_dirs != 3u && n_dirs != 5u) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": n_dirs must be 1, 3 or 5");
+  if (with_counts && (uint64_t)n * n_dirs >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": n * n_dirs must be below 0xFFFFFF00 (32-bit record indices)");
+  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": cull_mask is above 0xFF");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, name + " needs trace_variant 0");
   return RT_OK;
 }
 }  // namespace
@@ -2745,63 +2663,29 @@ int inside_arguments(rt_ctx* c, const char* name, size_t n, uint32_t cull_mask, 
 // caller's records (enqueue_query, Walk::Inside).
 int rt_point_inside_device(rt_ctx* c, size_t n, const void* d_points4, uint32_t cull_mask, uint32_t n_dirs, void* d_inside, void* d_counts, void* hip_stream) {
   if (!c) return RT_ERR_INVALID_ARGUMENT;
-  const char* const name = "rt_point_inside_device";
-  { int q = inside_arguments(c, name, n, cull_mask, n_dirs, d_counts != nullptr); if (q) return q; }
+  const std::string name = "rt_point_inside_device";
+  { int w = inside_arguments(c, name, n, cull_mask, n_dirs, d_counts != nullptr); if (w) return w; }
   if (n) {
-    if (!d_points4 || !d_inside) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null point/word pointers");
+    if (!d_points4 || !d_inside) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null point/word pointers");
     if (((uintptr_t)d_points4 & 15u) || ((uintptr_t)d_inside & 3u) || ((uintptr_t)d_counts & 3u))
-      return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": points must be 16-byte aligned, words and counts 4-byte aligned");
-    { int q = check_device_pointers(c, name, "points, words and counts", {d_points4, d_inside, d_counts}); if (q) return q; }
+      return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": points must be 16-byte aligned, words and counts 4-byte aligned");
+    { int w = check_device_pointers(c, name, "points, words and counts", {d_points4, d_inside, d_counts}); if (w) return w; }
   }
-  HIP_TRY(c, hipSetDevice(c->device));
-  int r = ready_to_trace(c); if (r) return r;
-  if (n == 0) return RT_OK;
-  return enqueue_query(c, hip_stream ? (hipStream_t)hip_stream : c->stream, c->cfg, Walk::Inside, n, d_points4, false, false, nullptr, cull_mask, nullptr, nullptr,
-                       nullptr, nullptr, n_dirs, d_counts, d_inside);
+  Query q; q.walk = Walk::Inside; q.n = n; q.records = d_points4; q.cull_mask = cull_mask; q.n_dirs = n_dirs; q.words = d_inside; q.counts = d_counts;
+  return device_query(c, q, hip_stream);
 }
 
-// The blocking host form, as rt_closest_point is to rt_closest_point_device: the points copied in, the same enqueue on the context's
-// stream, the words and counts copied out; with counting the instrumented walk, whose node visits and triangle tests come back in stats.
+// The blocking host form, as rt_closest_point is to rt_closest_point_device: the points (16 B each), then the words, then the counts.
 int rt_point_inside(rt_ctx* c, size_t n, const float* points4, uint32_t cull_mask, uint32_t n_dirs, uint32_t* inside, uint32_t* counts, int counting,
                     rt_stats* stats) {
   if (!c) return RT_ERR_INVALID_ARGUMENT;
-  const char* const name = "rt_point_inside";
-  if ((!points4 || !inside) && n) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null point/word pointers");
-  { int q = inside_arguments(c, name, n, cull_mask, n_dirs, counts != nullptr); if (q) return q; }
-  HIP_TRY(c, hipSetDevice(c->device));
-  { int q = quiesce(c); if (q) return q; }   // (as rt_intersect)
-  int r = ready_to_trace(c); if (r) return r;
-  if (stats) memset(stats, 0, sizeof(*stats));
-  if (n == 0) return RT_OK;
-  // one allocation: the points (16 B each), then the words, then the counts
+  const std::string name = "rt_point_inside";
+  if ((!points4 || !inside) && n) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null point/word pointers");
+  { int w = inside_arguments(c, name, n, cull_mask, n_dirs, counts != nullptr); if (w) return w; }
   const size_t pt_bytes = n * 4 * sizeof(float), word_bytes = n * sizeof(uint32_t), count_bytes = counts ? n * n_dirs * sizeof(uint32_t) : 0;
-  char* d_buf = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  struct Guard {   // every exit path below releases the temporaries
-    char*& buf; hipEvent_t &a, &b;
-    ~Guard() { if (buf) hipFree(buf); if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
-  } guard{d_buf, e0, e1};
-  HIP_TRY(c, hipMalloc((void**)&d_buf, pt_bytes + word_bytes + count_bytes));
-  uint32_t* const d_w = (uint32_t*)(d_buf + pt_bytes);
-  uint32_t* const d_c = counts ? (uint32_t*)(d_buf + pt_bytes + word_bytes) : nullptr;
-  HIP_TRY(c, hipMemcpy(d_buf, points4, pt_bytes, hipMemcpyHostToDevice));
-  HIP_TRY(c, hipEventCreate(&e0)); HIP_TRY(c, hipEventCreate(&e1));
-  r = enqueue_query(c, c->stream, c->cfg, Walk::Inside, n, d_buf, false, counting != 0, nullptr, cull_mask, nullptr, nullptr, e0, e1, n_dirs, d_c, d_w); if (r) return r;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipMemcpy(inside, d_w, word_bytes, hipMemcpyDeviceToHost));
-  if (counts) HIP_TRY(c, hipMemcpy(counts, d_c, count_bytes, hipMemcpyDeviceToHost));
-  if (stats) {
-    if (counting) {
-      uint32_t cnt[CNT_TAILS];
-      HIP_TRY(c, hipMemcpy(cnt, c->d_q_counters, sizeof(cnt), hipMemcpyDeviceToHost));
-      memcpy(&stats->node_visits, &cnt[CNT_NODE_VISITS], 8);
-      memcpy(&stats->tri_tests, &cnt[CNT_TRI_TESTS], 8);
-    }
-    float ms = 0.f; hipEventElapsedTime(&ms, e0, e1);
-    stats->ms_trace_closest = ms;
-    stats->bvh_node_bytes = sizeof(BvhNodeQ); stats->bvh_tri_bytes = sizeof(TriPacket);
-  }
-  return RT_OK;
+  Query q; q.walk = Walk::Inside; q.n = n; q.cull_mask = cull_mask; q.n_dirs = n_dirs; q.counting = counting != 0;
+  return blocking_query(c, q, points4, pt_bytes, pt_bytes + word_bytes + count_bytes,
+                        {{&Query::words, pt_bytes, inside, word_bytes}, {&Query::counts, pt_bytes + word_bytes, counts, count_bytes}}, stats);
 }
 
 // Signed distance: rt_closest_point_device's checks, then one enqueue_query under one ordering: k_closest_scale and k_closest_point into
@@ -2809,19 +2693,16 @@ int rt_point_inside(rt_ctx* c, size_t n, const float* points4, uint32_t cull_mas
 int rt_signed_distance_device(rt_ctx* c, size_t n, const void* d_points4, uint32_t cull_mask, uint32_t n_dirs, void* d_hits, void* d_attr, void* d_inside,
                               void* hip_stream) {
   if (!c) return RT_ERR_INVALID_ARGUMENT;
-  const char* const name = "rt_signed_distance_device";
-  { int q = inside_arguments(c, name, n, cull_mask, n_dirs, false); if (q) return q; }
+  const std::string name = "rt_signed_distance_device";
+  { int w = inside_arguments(c, name, n, cull_mask, n_dirs, false); if (w) return w; }
   if (n) {
-    if (!d_points4 || !d_hits) return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": null point/hit pointers");
+    if (!d_points4 || !d_hits) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null point/hit pointers");
     if (((uintptr_t)d_points4 & 15u) || ((uintptr_t)d_hits & 3u) || ((uintptr_t)d_attr & 15u) || ((uintptr_t)d_inside & 3u))
-      return fail(c, RT_ERR_INVALID_ARGUMENT, std::string(name) + ": points and attributes must be 16-byte aligned, hits and words 4-byte aligned");
-    { int q = check_device_pointers(c, name, "points, hits, attributes and words", {d_points4, d_hits, d_attr, d_inside}); if (q) return q; }
+      return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": points and attributes must be 16-byte aligned, hits and words 4-byte aligned");
+    { int w = check_device_pointers(c, name, "points, hits, attributes and words", {d_points4, d_hits, d_attr, d_inside}); if (w) return w; }
   }
-  HIP_TRY(c, hipSetDevice(c->device));
-  int r = ready_to_trace(c); if (r) return r;
-  if (n == 0) return RT_OK;
-  return enqueue_query(c, hip_stream ? (hipStream_t)hip_stream : c->stream, c->cfg, Walk::Inside, n, d_points4, false, false, nullptr, cull_mask, d_hits, d_attr,
-                       nullptr, nullptr, n_dirs, nullptr, d_inside);
+  Query q; q.walk = Walk::Inside; q.n = n; q.records = d_points4; q.cull_mask = cull_mask; q.n_dirs = n_dirs; q.hits = d_hits; q.attr = d_attr; q.words = d_inside;
+  return device_query(c, q, hip_stream);
 }
 
 // Custom ray generation: the caller's primary rays (n_points * n_samples records, sample-major) through the frame's bounce pipeline —
@@ -2844,16 +2725,7 @@ int rt_shade_rays_device(rt_ctx* c, size_t n_points, uint32_t n_samples, const v
   if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_shade_rays_device needs trace_variant 0");
   if (c->uni.max_bounce_count + 2 > (uint32_t)CNT_MAX_BOUNCES) return fail(c, RT_ERR_INVALID_ARGUMENT, "maxBounceCount too large (the frame's limit)");
   HIP_TRY(c, hipSetDevice(c->device));
-  if (n) {
-    const void* ptrs[3] = {d_rays8, d_sample_rgba, d_point_rgba};
-    for (const void* p : ptrs) {
-      if (!p) continue;
-      hipPointerAttribute_t at{};
-      const bool ok = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == c->device;
-      (void)hipGetLastError();   // (a host pointer leaves an error behind)
-      if (!ok) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_shade_rays_device: rays and outputs must be device memory of the context's GPU (" + std::to_string(c->device) + ")");
-    }
-  }
+  if (n) { int q = check_device_pointers(c, "rt_shade_rays_device", "rays and outputs", {d_rays8, d_sample_rgba, d_point_rgba}); if (q) return q; }
   if (!c->have_uni) return fail(c, RT_ERR_NOT_READY, "rt_set_uniforms has not been called");
   int r = ready_to_trace(c); if (r) return r;
   if (n == 0) return RT_OK;

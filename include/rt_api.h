@@ -484,6 +484,40 @@ int rt_overlap_boxes_device(rt_ctx* ctx, size_t n, const void* d_boxes8, uint32_
 int rt_overlap_boxes(rt_ctx* ctx, size_t n, const float* boxes8_host, uint32_t cull_mask, uint32_t flags,
                      uint32_t max_ids, int32_t* ids_host, uint32_t* counts_host, int counting, rt_stats* stats);
 
+/* Triangle overlaps: for every query triangle the triangles of the scene that cut or touch it (Embree's rtcCollide, FCL's mesh collision
+ * with the scene as one side), for cloth and tools whose vertices live in device memory, a robot link against its environment,
+ * self-collision through the cull mask, and the first step of cutting and CSG.
+ * Triangles: d_tris12 holds n records of 48 B (P0.x, P0.y, P0.z, w3, P1.x, P1.y, P1.z, w7, P2.x, P2.y, P2.z, w11), 16-B aligned, memory
+ * of ctx's GPU: a closed world-space triangle; words 3, 7 and 11 are ignored.  A record with a non-finite vertex component is invalid:
+ * its count is 0 and it lists nothing.  A zero-area query (a segment, a point) is valid and answered by the same arithmetic.
+ * Candidates C(query): the triangles of every instance with (mask & cull_mask) != 0 that the canonical predicate below does not separate
+ * from the query.  Both sets are closed: touching counts.  Instance flags, opacity and facing play no part; cull_mask is how a caller
+ * leaves out the instance the query triangles came from.
+ * d_counts, d_ids, max_ids, RT_OVERLAP_ANY in flags, the pruning without d_counts: exactly as for rt_overlap_boxes_device.
+ * Canonical predicate (DESIGN.md §5 "Triangle overlaps" has every operation in order): binary32, nothing fused except inside dot3 /
+ * cross3 / xform_point / xform_vec, min / max are fminf / fmaxf.  A, B, C as for rt_overlap_boxes_device (a non-finite A, B
+ * or C: never a candidate); the bounds of A, B, C against the bounds of P0, P1, P2 on every axis; then, centred on P0 (p1 = P1 - P0,
+ * p2 = P2 - P0, a = A - P0, b = B - P0, c = C - P0), with the edges g0 = p1, g1 = p2 - p1, g2 = p2 and f0 = b - a, f1 = c - b, f2 = a - c
+ * and the normals n = cross3(g0, g2), m = cross3(f0, f1), seventeen axes L in this order: n, m, the nine cross3(g_i, f_j) i-major, the
+ * three cross3(n, g_i), the three cross3(m, f_j).  On each the query projects to 0, dot3(L, p1), dot3(L, p2) and the candidate to
+ * dot3(L, a), dot3(L, b), dot3(L, c); the pair is separated if the query's minimum is greater than the candidate's maximum or its maximum
+ * less than the candidate's minimum.  Every comparison is strict: a tie is not a separation, and a zero axis separates nothing.  The
+ * predicate depends on the query record, the instance record and the packet only, never on the tree.  One exception to "never on the
+ * tree": a zero-area triangle has an incomplete axis set, and a pair of two zero-area triangles that nothing but their bounds holds
+ * together (a point beside a segment, say) may be left out, because the walk need not come near it; a pair in which either triangle
+ * has an area is always decided by the predicate.
+ * Stream ordering, the TLAS and scene of the call, the workspace, RT_ERR_NOT_READY, n == 0 (nothing is enqueued) and the
+ * RT_ERR_INVALID_ARGUMENT list: as for rt_overlap_boxes_device, with d_tris12 in the place of d_boxes8. */
+int rt_overlap_triangles_device(rt_ctx* ctx, size_t n, const void* d_tris12, uint32_t cull_mask, uint32_t flags,
+                                uint32_t max_ids, void* d_ids, void* d_counts, void* hip_stream);
+/* The blocking host form, as rt_overlap_boxes is to rt_overlap_boxes_device: ids_host (n x max_ids pairs; NULL with max_ids 0) and
+ * counts_host (n; optional unless max_ids is 0) are copied back.  counting != 0 runs the instrumented walk and fills stats->node_visits
+ * and stats->tri_tests (node visits and triangle-triangle tests of the whole call; packets are counted before the test, so with counts
+ * requested both equal rt_overlap_boxes' on the queries' bounding boxes); stats may be NULL.  The timing and size fields as for
+ * rt_overlap_boxes. */
+int rt_overlap_triangles(rt_ctx* ctx, size_t n, const float* tris12_host, uint32_t cull_mask, uint32_t flags,
+                         uint32_t max_ids, int32_t* ids_host, uint32_t* counts_host, int counting, rt_stats* stats);
+
 /* Sphere sweeps: for every record the first contact of a sphere that moves along a direction (PhysX's sweep query), for continuous
  * collision detection, character controllers, camera booms, clearance along a path and thick-beam sensors.
  * Sweeps: d_sweeps8 holds n records of 32 B (o.x, o.y, o.z, r, d.x, d.y, d.z, tmax), 16-B aligned, memory of ctx's GPU: a ray's layout

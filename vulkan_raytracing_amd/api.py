@@ -74,7 +74,7 @@ INSIDE_DIRS = ((0.36, 0.48, 0.8), (-0.8, 0.36, -0.48), (0.48, -0.8, -0.36), (-0.
 
 EXPORTS = ["rt_create", "rt_create_frame_slot", "rt_destroy", "rt_upload_geometry", "rt_build_blas", "rt_set_instances", "rt_set_instances_device", "rt_refit_blas_device", "rt_set_materials", "rt_set_instance_types", "rt_set_uniforms", "rt_set_skybox",
            "rt_trace", "rt_trace_async", "rt_trace_wait", "rt_trace_shard", "rt_set_batch", "rt_trace_shard_batch", "rt_assemble_shards", "rt_shard_rows", "rt_synchronize", "rt_get_stats", "rt_set_timing", "rt_intersect",
-           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_sweep_spheres_device", "rt_sweep_spheres", "rt_point_inside_device", "rt_point_inside", "rt_signed_distance_device", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_host_blas", "rt_debug_snapshot", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
+           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_overlap_triangles_device", "rt_overlap_triangles", "rt_sweep_spheres_device", "rt_sweep_spheres", "rt_point_inside_device", "rt_point_inside", "rt_signed_distance_device", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_host_blas", "rt_debug_snapshot", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
 
 _LIBS = {}
 
@@ -128,6 +128,8 @@ def lib(variant=None):
         L.rt_signed_distance_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
         L.rt_overlap_boxes_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]
         L.rt_overlap_boxes.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_int, C.POINTER(RtStats)]
+        L.rt_overlap_triangles_device.argtypes = L.rt_overlap_boxes_device.argtypes
+        L.rt_overlap_triangles.argtypes = L.rt_overlap_boxes.argtypes
         L.rt_shade_rays_device.argtypes = [vp, C.c_size_t, C.c_uint32, vp, vp, vp, vp]
         L.rt_last_error.argtypes = [vp]
         L.rt_last_error.restype = C.c_char_p
@@ -534,8 +536,13 @@ class RtContext:
         (inst, prim) of them in ascending order, (-1, -1) past the last.  counts=False lets the walk stop once a row is full.  any=True
         answers occupancy (max_ids 0): count is 0 or 1.  out = (ids, count) reuses such buffers (None where not asked for).  See
         include/rt_api.h."""
+        return self._overlap_device(boxes, "overlap_boxes", 8, "box", "boxes", max_ids, cull_mask, any, counts, stream, out)
+
+    def _overlap_device(self, boxes, name, cols, noun, nouns, max_ids, cull_mask, any, counts, stream, out):
+        """overlap_boxes_device and overlap_triangles_device: the checks, the buffers and the call rt_<name>_device on `stream`"""
         import torch
-        self._check_rays(boxes, "overlap_boxes_device", 8, "box")
+        self._check_rays(boxes, name + "_device", cols, noun)
+        fn = getattr(self.L, "rt_%s_device" % name)
         k = int(max_ids)
         if not 0 <= k <= 16:
             raise ValueError("max_ids must be 0..16, got %d" % k)
@@ -560,15 +567,14 @@ class RtContext:
                 if sh is None:
                     bufs[i] = None
                 elif t is None or t.dtype != torch.int32 or tuple(t.shape) != sh or not t.is_contiguous() or t.device != boxes.device:
-                    raise ValueError("out %s must be a contiguous int32 %s tensor on the boxes' device" % (what, sh))
+                    raise ValueError("out %s must be a contiguous int32 %s tensor on the %s' device" % (what, sh, nouns))
         ids, count = bufs
 
         def call(run):
             ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
-            return self.L.rt_overlap_boxes_device(self.h, n, ptr(boxes), int(cull_mask) & 0xFFFFFFFF, OVERLAP_ANY if any else 0, k, ptr(ids), ptr(count),
-                                                  C.c_void_p(run.cuda_stream))
+            return fn(self.h, n, ptr(boxes), int(cull_mask) & 0xFFFFFFFF, OVERLAP_ANY if any else 0, k, ptr(ids), ptr(count), C.c_void_p(run.cuda_stream))
         if n:
-            self._on_stream(stream, (boxes, ids, count), call, "rt_overlap_boxes_device")
+            self._on_stream(stream, (boxes, ids, count), call, "rt_%s_device" % name)
         return BoxOverlaps(ids, count)
 
     def overlap_boxes(self, boxes8, max_ids=0, cull_mask=0xFF, any=False, counts=True, counting=False):
@@ -582,6 +588,26 @@ class RtContext:
         self._chk(self.L.rt_overlap_boxes(self.h, n, _p(boxes8), int(cull_mask) & 0xFFFFFFFF, OVERLAP_ANY if any else 0, k & 0xFFFFFFFF,
                                           _p(ids) if ids is not None else None, _p(cnt) if cnt is not None else None, int(counting), C.byref(st)),
                   "rt_overlap_boxes")
+        return cnt, ids, st
+
+    def overlap_triangles_device(self, tris, max_ids=0, cull_mask=0xFF, any=False, counts=True, stream=None, out=None):
+        """rt_overlap_triangles_device: the triangles of the scene that cut or touch every query triangle.  `tris` is a contiguous float32
+        torch tensor (n, 12) on this context's GPU (P0.xyz, ignored, P1.xyz, ignored, P2.xyz, ignored per row: a closed world-space
+        triangle; triangle_records builds such rows from a mesh), read in the order of `stream`.  Every other argument and the BoxOverlaps
+        result as for overlap_boxes_device; cull_mask is how the instance the queries came from is left out.  See include/rt_api.h."""
+        return self._overlap_device(tris, "overlap_triangles", 12, "triangle", "triangles", max_ids, cull_mask, any, counts, stream, out)
+
+    def overlap_triangles(self, tris12, max_ids=0, cull_mask=0xFF, any=False, counts=True, counting=False):
+        """rt_overlap_triangles: the blocking host form -> (counts uint32 (n,) or None, ids int32 (n, max_ids, 2) or None, RtStats; with
+        counting its node_visits / tri_tests are filled)"""
+        tris12 = np.ascontiguousarray(tris12, np.float32).reshape(-1, 12)
+        n, k = len(tris12), int(max_ids)
+        cnt = np.zeros(n, np.uint32) if counts else None
+        ids = np.zeros((n, k, 2), np.int32) if k else None
+        st = RtStats()
+        self._chk(self.L.rt_overlap_triangles(self.h, n, _p(tris12), int(cull_mask) & 0xFFFFFFFF, OVERLAP_ANY if any else 0, k & 0xFFFFFFFF,
+                                              _p(ids) if ids is not None else None, _p(cnt) if cnt is not None else None, int(counting), C.byref(st)),
+                  "rt_overlap_triangles")
         return cnt, ids, st
 
     def intersect_device_hits(self, rays, max_hits, ray_flags=0, cull_mask=0xFF, words=None, attributes=False, counts=True, stream=None, out=None):
@@ -824,6 +850,26 @@ class BoxOverlaps:
         """(counts as (n,) uint32, ids as (n, max_ids, 2) int32), None where not asked for; synchronises"""
         return (self.count.cpu().numpy().view(np.uint32) if self.count is not None else None,
                 self.ids.cpu().numpy() if self.ids is not None else None)
+
+
+def triangle_records(vertices, faces):
+    """the (nf, 12) float32 records of overlap_triangles_device / overlap_triangles (P0.xyz, 0, P1.xyz, 0, P2.xyz, 0 per row) of the
+    triangles `faces` (nf, 3) indexes in `vertices` (nv, 3).  torch tensors stay on their device (torch indexing, no host copy); anything
+    else goes through numpy."""
+    try:
+        import torch
+        is_t = isinstance(vertices, torch.Tensor)
+    except ImportError:
+        is_t = False
+    if is_t:
+        f = torch.as_tensor(faces, device=vertices.device).reshape(-1, 3).long()
+        rec = torch.zeros((f.shape[0], 3, 4), dtype=torch.float32, device=vertices.device)
+        rec[:, :, :3] = vertices.reshape(-1, 3).to(torch.float32)[f]
+        return rec.reshape(-1, 12)
+    f = np.asarray(faces.cpu() if hasattr(faces, "cpu") else faces).reshape(-1, 3).astype(np.int64)
+    rec = np.zeros((len(f), 3, 4), np.float32)
+    rec[:, :, :3] = np.asarray(vertices, np.float32).reshape(-1, 3)[f]
+    return rec.reshape(-1, 12)
 
 
 def check_builders(verts6, idx):

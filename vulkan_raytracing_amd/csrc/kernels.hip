@@ -2371,7 +2371,9 @@ void launch_resolve_points(const float4* sample_color, float4* out, uint32_t n_p
 
 #include "kernels_overlap.inc"   // k_overlap_boxes: the triangles that touch every query box (rt_overlap_boxes_device)
 
-#include "kernels_sweep.inc"   // k_sweep_spheres, k_sweep_side: the first contact of every moving sphere (rt_sweep_spheres_device)
+#include "kernels_triangles.inc"   // k_collide_triangles: the triangles that cut every query triangle (rt_overlap_triangles_device)
+
+#include "kernels_sweep.inc"  // k_sweep_spheres, k_sweep_side: the first contact of every moving sphere (rt_sweep_spheres_device)
 
 #include "kernels_inside.inc"   // k_point_inside, k_sign_distance: inside / outside by a vote of crossing parities (rt_point_inside_device, rt_signed_distance_device)
 

@@ -82,6 +82,36 @@ __device__ __forceinline__ bool box_touches(uint32_t wx, uint32_t wy, uint32_t w
   return !(bl.x > hi.x) && !(bh.x < lo.x) && !(bl.y > hi.y) && !(bh.y < lo.y) && !(bl.z > hi.z) && !(bh.z < lo.z);
 }
 
+// Entering instance I (k_overlap_boxes and k_collide_triangles alike): the dequantisation of its BLAS, and the inflated world box
+// [qlo, qhi] replaced by the query of that tree (the head of this file).  s: the instance's entry of k_closest_scale's array.
+__device__ __forceinline__ void overlap_enter_instance(const InstanceDev* I, float s, F3& qlo, F3& qhi, F3& q_lo, F3& q_scale) {
+  const float INF = __builtin_inff();
+  const float* w = I->w2o;
+  q_lo = mk3(I->q_lo[0], I->q_lo[1], I->q_lo[2]); q_scale = mk3(I->q_scale[0], I->q_scale[1], I->q_scale[2]);
+  // the object-space bound of the inflated world box's corners
+  F3 mn = mk3(INF, INF, INF), mx = mk3(-INF, -INF, -INF);
+  for (int k = 0; k < 8; k++) {
+    const F3 p = xform_point(w, mk3((k & 1) ? qhi.x : qlo.x, (k & 2) ? qhi.y : qlo.y, (k & 4) ? qhi.z : qlo.z));
+    mn = mk3(fminf(mn.x, p.x), fminf(mn.y, p.y), fminf(mn.z, p.z)); mx = mk3(fmaxf(mx.x, p.x), fmaxf(mx.y, p.y), fmaxf(mx.z, p.z));
+  }
+  // magnitudes: the mesh's planes, the terms of the corners' rows (they may cancel)
+  const F3 cm = mk3(fmaxf(__builtin_fabsf(qlo.x), __builtin_fabsf(qhi.x)), fmaxf(__builtin_fabsf(qlo.y), __builtin_fabsf(qhi.y)),
+                    fmaxf(__builtin_fabsf(qlo.z), __builtin_fabsf(qhi.z)));
+  float om = 0.f;
+  for (int k = 0; k < 3; k++) {
+    om = fmaxf(om, fmaxf(__builtin_fabsf(I->q_lo[k]), __builtin_fabsf(__builtin_fmaf(65535.0f, I->q_scale[k], I->q_lo[k]))));
+    om = fmaxf(om, __builtin_fabsf(w[4 * k]) * cm.x + __builtin_fabsf(w[4 * k + 1]) * cm.y + __builtin_fabsf(w[4 * k + 2]) * cm.z + __builtin_fabsf(w[4 * k + 3]));
+  }
+  // (fmaxf drops a NaN term: the sum of the corner bounds brings it back)
+  const float chk = om + ((mn.x + mn.y + mn.z) + (mx.x + mx.y + mx.z)) * 0.0f;
+  if (s > 0.0f && chk <= 3.0e38f) {
+    const float so = OB_ABS * om;
+    qlo = mk3(mn.x - so, mn.y - so, mn.z - so); qhi = mk3(mx.x + so, mx.y + so, mx.z + so);
+  } else {   // a singular or non-finite transform, an unbounded slack: the instance's boxes do not prune
+    qlo = mk3(-INF, -INF, -INF); qhi = mk3(INF, INF, INF);
+  }
+}
+
 template <bool COUNT>
 __device__ __forceinline__ void overlap_body(const OverlapArgs& a) {
   __shared__ int s_stack[4][STACK2_LDS][64];
@@ -89,7 +119,6 @@ __device__ __forceinline__ void overlap_body(const OverlapArgs& a) {
   WalkFeed feed;
   const uint32_t K = a.k;
   const bool prune = a.counts == nullptr;
-  const float INF = __builtin_inff();
 
   bool need = true;
   uint32_t bx = 0, count = 0;
@@ -191,31 +220,7 @@ __device__ __forceinline__ void overlap_body(const OverlapArgs& a) {
       const int ii = ~cur;
       const InstanceDev* I = a.sc.inst + ii;
       if ((I->mask & a.cull_mask & 0xFFu) != 0u && !(prune && K != 0u && count >= K && ii > last_inst)) {
-        const float s = a.inst_scale[1 + ii];
-        const float* w = I->w2o;
-        q_lo = mk3(I->q_lo[0], I->q_lo[1], I->q_lo[2]); q_scale = mk3(I->q_scale[0], I->q_scale[1], I->q_scale[2]);
-        // the object-space bound of the inflated world box's corners
-        F3 mn = mk3(INF, INF, INF), mx = mk3(-INF, -INF, -INF);
-        for (int k = 0; k < 8; k++) {
-          const F3 p = xform_point(w, mk3((k & 1) ? qhi.x : qlo.x, (k & 2) ? qhi.y : qlo.y, (k & 4) ? qhi.z : qlo.z));
-          mn = mk3(fminf(mn.x, p.x), fminf(mn.y, p.y), fminf(mn.z, p.z)); mx = mk3(fmaxf(mx.x, p.x), fmaxf(mx.y, p.y), fmaxf(mx.z, p.z));
-        }
-        // magnitudes: the mesh's planes, the terms of the corners' rows (they may cancel)
-        const F3 cm = mk3(fmaxf(__builtin_fabsf(qlo.x), __builtin_fabsf(qhi.x)), fmaxf(__builtin_fabsf(qlo.y), __builtin_fabsf(qhi.y)),
-                          fmaxf(__builtin_fabsf(qlo.z), __builtin_fabsf(qhi.z)));
-        float om = 0.f;
-        for (int k = 0; k < 3; k++) {
-          om = fmaxf(om, fmaxf(__builtin_fabsf(I->q_lo[k]), __builtin_fabsf(__builtin_fmaf(65535.0f, I->q_scale[k], I->q_lo[k]))));
-          om = fmaxf(om, __builtin_fabsf(w[4 * k]) * cm.x + __builtin_fabsf(w[4 * k + 1]) * cm.y + __builtin_fabsf(w[4 * k + 2]) * cm.z + __builtin_fabsf(w[4 * k + 3]));
-        }
-        // (fmaxf drops a NaN term: the sum of the corner bounds brings it back)
-        const float chk = om + ((mn.x + mn.y + mn.z) + (mx.x + mx.y + mx.z)) * 0.0f;
-        if (s > 0.0f && chk <= 3.0e38f) {
-          const float so = OB_ABS * om;
-          qlo = mk3(mn.x - so, mn.y - so, mn.z - so); qhi = mk3(mx.x + so, mx.y + so, mx.z + so);
-        } else {   // a singular or non-finite transform, an unbounded slack: the instance's boxes do not prune
-          qlo = mk3(-INF, -INF, -INF); qhi = mk3(INF, INF, INF);
-        }
+        overlap_enter_instance(I, a.inst_scale[1 + ii], qlo, qhi, q_lo, q_scale);
         st.push(REF_MARK);
         cur_inst = ii; cur = I->blas_root;
       } else cur = st.pop();

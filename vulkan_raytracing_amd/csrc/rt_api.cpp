@@ -2308,6 +2308,7 @@ enum class Walk {
   Hits,      // rt_intersect_device_hits: the max_hits nearest hits of every ray and their number
   Closest,   // rt_closest_point*: the nearest surface point (the per-instance scales are made first, in the workspace)
   Overlap,   // rt_overlap_boxes*: the triangles that touch every box (the same scales first)
+  Triangles, // rt_overlap_triangles*: the triangles that cut every query triangle (the same scales first; the fields of Overlap)
   Sweep,     // rt_sweep_spheres*: the first contact of every moving sphere (the same scales first)
   Inside     // rt_point_inside*: the inside / outside vote; with hits, rt_signed_distance_device: the closest-point walk into hits (and
              // attr) first, the vote with the counter block's cursor initialised again, then the sign pass over hits
@@ -2315,7 +2316,7 @@ enum class Walk {
 struct Query {
   Walk walk = Walk::Plain;
   size_t n = 0;
-  const void* records = nullptr;     // n ray, point, box or sweep records
+  const void* records = nullptr;     // n ray, point, box, sweep or triangle records
   const void* ray_words = nullptr;   // Flags, Hits: n per-ray words, or none
   uint32_t query_word = 0;           // Flags, Hits: the call's ray flags | cull mask << 24
   uint32_t cull_mask = 0;            // Closest, Overlap, Sweep, Inside
@@ -2352,7 +2353,7 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q
   if (q.counting) HIP_TRY(c, hipMemsetAsync(c->d_q_counters, 0, CNT_WORDS * sizeof(uint32_t), s));
   const SceneDev sc = scene_dev(c);
   if (q.t0) HIP_TRY(c, hipEventRecord(q.t0, s));
-  if (closest || sweep || q.walk == Walk::Overlap) launch_closest_scale(sc, c->d_q_scale, s);
+  if (closest || sweep || q.walk == Walk::Overlap || q.walk == Walk::Triangles) launch_closest_scale(sc, c->d_q_scale, s);
   switch (q.walk) {
     case Walk::Plain: launch_query(sc, records, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, q.any_hit, q.counting, cfg, s); break;
     case Walk::Flags: launch_query_flags(sc, records, (const uint32_t*)q.ray_words, q.query_word, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, cfg, s); break;
@@ -2363,6 +2364,9 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q
     case Walk::Closest: launch_closest_point(sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s); break;
     case Walk::Overlap:
       launch_overlap_boxes(sc, records, q.cull_mask, c->d_q_scale, q.overlap_any, q.max_ids, q.ids, (uint32_t*)q.counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
+      break;
+    case Walk::Triangles:
+      launch_collide_triangles(sc, records, q.cull_mask, c->d_q_scale, q.overlap_any, q.max_ids, q.ids, (uint32_t*)q.counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
       break;
     case Walk::Sweep: launch_sweep_spheres(sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s); break;
     case Walk::Inside:
@@ -2569,9 +2573,10 @@ int rt_closest_point(rt_ctx* c, size_t n, const float* points4, uint32_t cull_ma
 }
 
 namespace {
-// the argument rules rt_overlap_boxes_device and rt_overlap_boxes share (pointers aside)
-int overlap_arguments(rt_ctx* c, const std::string& name, size_t n, uint32_t cull_mask, uint32_t flags, uint32_t max_ids, const void* ids, const void* counts) {
-  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": too many boxes for one call");
+// the argument rules rt_overlap_boxes*, and rt_overlap_triangles* with what = "triangles", share (pointers aside)
+int overlap_arguments(rt_ctx* c, const std::string& name, size_t n, uint32_t cull_mask, uint32_t flags, uint32_t max_ids, const void* ids, const void* counts,
+                      const char* what = "boxes") {
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": too many " + what + " for one call");
   if (max_ids > 16u) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": max_ids must be 0..16");
   if ((uint64_t)n * max_ids >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": n * max_ids must be below 0xFFFFFF00 (32-bit record indices)");
   if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": cull_mask is above 0xFF");
@@ -2614,6 +2619,37 @@ int rt_overlap_boxes(rt_ctx* c, size_t n, const float* boxes8, uint32_t cull_mas
   Query q; q.walk = Walk::Overlap; q.n = n; q.cull_mask = cull_mask; q.overlap_any = (flags & RT_OVERLAP_ANY) != 0u; q.max_ids = max_ids; q.counting = counting != 0;
   return blocking_query(c, q, boxes8, box_bytes, box_bytes + count_bytes + id_bytes,
                         {{&Query::counts, box_bytes, counts, count_bytes}, {&Query::ids, box_bytes + count_bytes, ids, id_bytes}}, stats);
+}
+
+// The triangles that cut every query triangle: rt_overlap_boxes_device's checks and ordering, then k_closest_scale and k_collide_triangles
+// over the caller's records (48 B each) into the caller's rows and counts (enqueue_query).
+int rt_overlap_triangles_device(rt_ctx* c, size_t n, const void* d_tris12, uint32_t cull_mask, uint32_t flags, uint32_t max_ids, void* d_ids, void* d_counts,
+                                void* hip_stream) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const std::string name = "rt_overlap_triangles_device";
+  { int w = overlap_arguments(c, name, n, cull_mask, flags, max_ids, d_ids, d_counts, "triangles"); if (w) return w; }
+  if (n) {
+    if (!d_tris12) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null triangle pointer");
+    if (((uintptr_t)d_tris12 & 15u) || ((uintptr_t)d_ids & 3u) || ((uintptr_t)d_counts & 3u))
+      return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": triangles must be 16-byte aligned, ids and counts 4-byte aligned");
+    { int w = check_device_pointers(c, name, "triangles, ids and counts", {d_tris12, d_ids, d_counts}); if (w) return w; }
+  }
+  Query q; q.walk = Walk::Triangles; q.n = n; q.records = d_tris12; q.cull_mask = cull_mask; q.overlap_any = (flags & RT_OVERLAP_ANY) != 0u; q.max_ids = max_ids;
+  q.ids = d_ids; q.counts = d_counts;
+  return device_query(c, q, hip_stream);
+}
+
+// The blocking host form, as rt_overlap_boxes is to rt_overlap_boxes_device: the triangles (48 B each), then the counts, then the rows.
+int rt_overlap_triangles(rt_ctx* c, size_t n, const float* tris12, uint32_t cull_mask, uint32_t flags, uint32_t max_ids, int32_t* ids, uint32_t* counts,
+                         int counting, rt_stats* stats) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const std::string name = "rt_overlap_triangles";
+  { int w = overlap_arguments(c, name, n, cull_mask, flags, max_ids, ids, counts, "triangles"); if (w) return w; }
+  if (!tris12 && n) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null triangle pointer");
+  const size_t tri_bytes = n * 12 * sizeof(float), count_bytes = n * sizeof(uint32_t), id_bytes = n * max_ids * 2 * sizeof(int32_t);
+  Query q; q.walk = Walk::Triangles; q.n = n; q.cull_mask = cull_mask; q.overlap_any = (flags & RT_OVERLAP_ANY) != 0u; q.max_ids = max_ids; q.counting = counting != 0;
+  return blocking_query(c, q, tris12, tri_bytes, tri_bytes + count_bytes + id_bytes,
+                        {{&Query::counts, tri_bytes, counts, count_bytes}, {&Query::ids, tri_bytes + count_bytes, ids, id_bytes}}, stats);
 }
 
 // The first contact of every moving sphere: the checks and ordering of a device query (rt_closest_point_device), then k_closest_scale and

@@ -208,6 +208,10 @@ void launch_closest_side(const SceneDev& sc, const float4* points, const HitRec*
 // (launch_closest_scale fills it first); chunk cursor, counters (counting) and spill area as for launch_query_hits.
 void launch_overlap_boxes(const SceneDev& sc, const float4* boxes, uint32_t cull_mask, const float* inst_scale, bool any, uint32_t k, void* ids, uint32_t* counts,
                           uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
+// rt_overlap_triangles_device: the triangles that the canonical triangle-triangle predicate does not separate from every query triangle
+// (48 bytes: P0.xyz, w3, P1.xyz, w7, P2.xyz, w11) (kernels_triangles.inc); every other argument as for launch_overlap_boxes.
+void launch_collide_triangles(const SceneDev& sc, const float4* tris, uint32_t cull_mask, const float* inst_scale, bool any, uint32_t k, void* ids, uint32_t* counts,
+                              uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
 // rt_sweep_spheres_device: the first contact of every moving sphere (32 bytes: o.xyz, r, d.xyz, tmax) with the instances the cull mask
 // admits, into hits[n] (kernels_sweep.inc).  inst_scale as for launch_closest_point (launch_closest_scale fills it first); chunk cursor,
 // counters (counting) and spill area as for launch_query_hits.

@@ -52,9 +52,19 @@ resource-usage-tlas:
 resource-usage-blas-refit:
 	$(HIPCC) $(HIPFLAGS) -c -Rpass-analysis=kernel-resource-usage -o /dev/null $(CSRC)/blas_refit.hip
 
+# the host builder under AddressSanitizer and UBSan (float-cast-overflow included) over the box sets a bad instance record can produce:
+# a stand-alone host program (tests/native/builder_sanitize.cpp links csrc/bvh_build.cpp directly; g++ only, no GPU, nothing preloaded);
+# test_host_builder_is_clean_under_the_sanitizers (tests/test_instance_records.py) runs it and expects a clean exit
+SANFLAGS := -O1 -g -std=c++17 -pthread -Wall -fsanitize=address,undefined -fsanitize=float-cast-overflow -fno-sanitize-recover=all -fno-omit-frame-pointer
+build/builder_sanitize: tests/native/builder_sanitize.cpp $(CSRC)/bvh_build.cpp $(CSRC)/bvh_build.h $(CSRC)/rt_device.h
+	@mkdir -p build
+	g++ $(SANFLAGS) -I$(CSRC) -Iinclude -o $@ tests/native/builder_sanitize.cpp $(CSRC)/bvh_build.cpp
+sanitize-builder: build/builder_sanitize
+	RT_BUILD_THREADS=1 ./build/builder_sanitize
+
 clean:
-	rm -f $(PKG)/*.so; rm -rf $(OBJDIR); $(MAKE) -C oracle clean
-.PHONY: all oracle clean resource-usage resource-usage-alt resource-usage-tlas resource-usage-blas-refit alt
+	rm -f $(PKG)/*.so; rm -rf $(OBJDIR) build/builder_sanitize; $(MAKE) -C oracle clean
+.PHONY: all oracle clean resource-usage resource-usage-alt resource-usage-tlas resource-usage-blas-refit alt sanitize-builder
 
 # host-side library (OBJ/MTL ingest, camera, animation, stand-in mesh, JPEG decode) — g++ only
 HOSTSRC := $(CSRC)/host_shim.cpp host/fly_camera.cpp host/standin.cpp host/standin_limbs.cpp $(wildcard host/jpeg_decode.cpp)

@@ -156,7 +156,23 @@ int rt_build_blas(rt_ctx* ctx, int mesh);
  * UPDATE mode, src=dst); it requires the same instance count as the last build.  Never waits for the frame in flight: the
  * instance records and TLAS nodes are double-buffered, the new set travels on the context's stream (pinned staging) and
  * the next frame is ordered behind it; only the frame before the last is waited for, if it is still running (the reference
- * allocates buffers and blocks on a fence here every frame, src/main.cpp:672-696, 752-778). */
+ * allocates buffers and blocks on a fence here every frame, src/main.cpp:672-696, 752-778).
+ *
+ * Bad records (the same for rt_set_instances_device, whose records no host ever sees, and for every frame of rt_set_batch).  None of
+ * them is an error — the call returns RT_OK — and none of them changes what any OTHER instance answers: every other instance keeps its
+ * index, objectIndex, type and results, bit for bit.
+ *   VOID record: one of the 12 transform entries is not finite (NaN, +-inf: a simulation that blew up, a 0xFF-filled slot), or the
+ *     padded world box of the instance has a coordinate of magnitude >= 1e37 (a body that flew off; FLT_MAX / 34).  In every frame and
+ *     every query the record behaves exactly like the same record with mask 0: never entered, never a candidate, whatever the cull
+ *     mask.  It adds nothing to the TLAS bounds, the centroid bounds or the quantisation; its box is that of an empty mesh.
+ *   NON-INVERTIBLE record: the transform is finite and its inverse (gl_WorldToObjectEXT, binary64 cofactors rounded once) has an entry
+ *     that is not finite — a singular matrix (a flattened body, a zero-filled slot), a scale below about 3e-39 whose inverse overflows
+ *     binary32.  No ray ever hits it: frames, rt_intersect*, rt_intersect_device_flags / _hits, rt_point_inside*, the vote of
+ *     rt_signed_distance_device, rt_shade_rays_device.  The world-space queries (rt_closest_point*, rt_sweep_spheres*,
+ *     rt_overlap_boxes*, rt_overlap_triangles*) keep answering over the o2w image of its triangles, as their own sections say.
+ *   FAR record: finite and below the limit (a translation of 1e30) is a VALID record.  Nothing is promised about hitting it (binary32
+ *     has no resolution left out there, and the TLAS planes are 1e30 / 65530 apart); the rest of the scene answers bit for bit as
+ *     without it, more slowly: the closest hit does not depend on the tree. */
 int rt_set_instances(rt_ctx* ctx, const rt_instance* instances, int n, int update);
 
 /* createTLAS with a DEVICE instance buffer (src/main.cpp:538-793: the reference's instance buffer is device memory and the TLAS is
@@ -169,6 +185,9 @@ int rt_set_instances(rt_ctx* ctx, const rt_instance* instances, int n, int updat
  * build is back on the host (the reference waits on its fence inside createTLAS, :772-778); it does not wait for the frame in
  * flight: records and TLAS are double-buffered exactly as for rt_set_instances.  Frames and hit records are bit-identical to
  * those of rt_set_instances with the same records (the closest hit does not depend on the tree).
+ * Void, non-invertible and far records are treated as rt_set_instances documents them, by the same two tests on the device: a record
+ * a physics kernel left non-finite or singular costs the scene nothing but that record, in builds and in refits (a refit with the
+ * record good again restores the state of the original build bit for bit).
  * 1 <= n <= 1048576.  RT_ERR_INVALID_ARGUMENT: a NULL pointer, n out of range, an unknown mesh index, trace_variant != 0, an
  * update whose previous build came from rt_set_instances / rt_set_batch (and an rt_set_instances update after this call);
  * RT_ERR_NOT_READY: an instance of a mesh whose BLAS is not built.  After an error the context's TLAS is invalid until the next
@@ -246,7 +265,9 @@ int rt_trace_shard(rt_ctx* ctx, int width, int height, int band_rows, int shard,
  * instances + k * n, each frame a createTLAS(update) of the same topology, src/main.cpp:2848-2861), uniforms = n_frames blocks — the camera
  * (position, right, up, forward), the light's position and its intensity may differ from frame to frame; maxBounceCount, samplesPerPixel and
  * the two object types are the batch's: a block that differs from block 0 in one of them is refused (RT_ERR_INVALID_ARGUMENT, the context
- * keeps its state); the two informational offset fields are not compared.  update as in rt_set_instances.
+ * keeps its state); the two informational offset fields are not compared.  update as in rt_set_instances.  Void, non-invertible and far
+ * records as in rt_set_instances: the frames share ONE quantisation, and a void record of one frame adds nothing to it, so it changes no
+ * other frame either.
  * While the context holds a batch of more than one frame its uniforms are the batch's: rt_set_uniforms returns RT_ERR_NOT_READY and changes
  * nothing; rt_set_instances (back to single frames) comes first, then rt_set_uniforms.  The frames of a batch are walked by the one-lane
  * kernels whatever "packet_trace" says.

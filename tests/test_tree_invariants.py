@@ -117,8 +117,10 @@ def check(snap, inst_mesh, prim_counts, n_reached=None, frames=1):
 
 # ---- CPU: the validator can fail ------------------------------------------------------------------------------------------------------
 
-def synthetic():
-    """Two meshes with triangles, one without, five instances and a two-frame batch, quantised by the documented rule (lower planes
+def synthetic(void=None, leak=False):
+    """void: a record (of mesh 0 or 1) made VOID as the library leaves it — a NaN in its transform, mask word 0, no box in its leaf, out
+    of the bounds; leak: its box, had the NaN been dropped and a 1e37 translation kept, counted into the bounds all the same.
+    Two meshes with triangles, one without, five instances and a two-frame batch, quantised by the documented rule (lower planes
     rounded down, upper planes up, one whole quantum further out).  Mesh 0: node 0 -> (node 1: leaves A = packets 0, 1 and B = 2, 3;
     node 2: leaves C = 4 and D = 5, two coincident triangles).  Mesh 1: one leaf of two triangles under a synthetic single-child root.
     Per frame: instances 0, 2 of mesh 0, 1, 3 of mesh 1, 4 of the empty mesh 2; TLAS ((0, 1), (2, (3, 4))), the leaf of instance 4
@@ -172,6 +174,11 @@ def synthetic():
     for k in range(K):
         boxes[k * n + 4] = boxes[k * n + 3]
     valid = [b for b in boxes if b is not None]
+    if void is not None:
+        inst[void]["o2w"][5] = np.nan
+        inst[void]["mask"] = 0
+        boxes[void] = None
+        valid = [b for b in boxes if b is not None] + ([(np.full(3, 1e37), np.full(3, 1.0001e37))] if leak else [])
     t_lo, t_s = tr.quant_params(np.min([b[0] for b in valid], axis=0), np.max([b[1] for b in valid], axis=0))
     base, stride = 8 + 2048, 4
     tlas = np.concatenate([tr.build_tree(((0, 1), (2, (3, 4))), lambda j, k=k: boxes[k * n + j], lambda j, k=k: k * n + j, t_lo, t_s, 1, base + k * stride)
@@ -254,12 +261,36 @@ def _d_frame(s):
     s["tlas_nodes"][4 + 3]["child"][1] = ~4                                     # frame 1's leaf of its empty instance 9 names record 4 of frame 0
 
 
+def _d_void_leaked(s):
+    return synthetic(void=2, leak=True)[0]                                      # record 2 is void, and the bounds were taken as if it were not
+
+
+def _d_box_none(s):
+    s["tlas_nodes"][1]["w"][0:3] = 0xFFFFFFFF                                   # node 1 = (0, 1): the good record 0 drawn with BOX_NONE (the last quantum)
+
+
+def _d_void_mask(s):
+    s = synthetic(void=2)[0]                                                    # record 2 is void and out of the bounds, but its mask stayed
+    s["instances"][2]["mask"] = 0xFF
+    return s
+
+
+def _d_root_order(s):
+    s["instances"]["mask"][[0, 1]] = 0                                          # records 0 and 1 masked out by the caller, their subtree dropped ...
+    nd = s["tlas_nodes"][0]                                                     # ... as the FIRST child of frame 0's root
+    nd["w"][0:3] = tr.INVERTED
+    nd["child"][0] = nd["child"][1]
+
+
 DEFECTS = [("an upper plane one quantum below a vertex", _d_upper, "blas_hi"), ("a lower plane one quantum above a vertex", _d_lower, "blas_lo"),
            ("a link redirected to an ancestor", _d_ancestor, "blas_node_twice"), ("a packet in two leaves", _d_packet_twice, "packet_twice"),
            ("a packet in no leaf", _d_packet_none, "packet_unreached"), ("e1 off by one ulp", _d_e1, "packet_bits"),
            ("a TLAS leaf box shrunk below a corner", _d_tlas_box, "tlas_containment"), ("an instance in two leaves", _d_inst_twice, "instance_twice"),
            ("an instance with triangles in no leaf", _d_inst_none, "instance_unreached"), ("a frontier box removed", _d_frontier, "frontier"),
-           ("InstanceDev.q_scale one ulp off the mesh table", _d_q_scale, "record_fields"), ("a leaf of frame 1 naming a record of frame 0", _d_frame, "tlas_leaf_range")]
+           ("InstanceDev.q_scale one ulp off the mesh table", _d_q_scale, "record_fields"), ("a leaf of frame 1 naming a record of frame 0", _d_frame, "tlas_leaf_range"),
+           ("a void record that leaked into the bounds", _d_void_leaked, "tlas_bounds"), ("a good record given BOX_NONE", _d_box_none, "tlas_containment"),
+           ("a void record that kept its mask", _d_void_mask, "void_record"),
+           ("the root's absent child in the first slot", _d_root_order, "tlas_root_order")]
 
 
 def test_validator_accepts_a_clean_snapshot():
@@ -272,9 +303,16 @@ def test_validator_accepts_a_clean_snapshot():
 @pytest.mark.parametrize("name,seed,kind", DEFECTS, ids=[d[2] + str(i) for i, d in enumerate(DEFECTS)])
 def test_validator_reports_each_seeded_defect_as_its_own_kind(name, seed, kind):
     snap, inst_mesh = synthetic()
-    seed(snap)
+    snap = seed(snap) or snap                                                   # (a seed may build the defective snapshot itself)
     viol, _ = tr.validate(snap, inst_mesh)
     assert list(clean(viol)) == [kind], (name, clean(viol))
+
+
+def test_validator_accepts_a_void_record():
+    """the same snapshot with record 2 void as the library leaves it: mask word 0, no box, out of the bounds"""
+    snap, inst_mesh = synthetic(void=2)
+    viol, reached = tr.validate(snap, inst_mesh)
+    assert clean(viol) == {} and reached["instances"] == [3, 4], (clean(viol), reached)
 
 
 def _frac(x):

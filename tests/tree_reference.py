@@ -39,6 +39,10 @@ KINDS = (
     "tlas_containment",      # a corner of the instance's transformed bounds outside the boxes on its path
     "record_fields",         # an InstanceDev field differs from the mesh table's current entry
     "tlas_depth",
+    "void_record",           # a void record (void_records below) whose mask word is not 0, or whose leaf is drawn with another box than BOX_NONE
+    "tlas_bounds",           # the TLAS dequantisation is not finite, or spans more than the records that are not void need
+    "tlas_root_order",       # the root of a frame's TLAS has an absent (inverted) FIRST child beside a present second one: k_raygen and the ray
+                             # generation of rt_shade_rays_device recognise the absent child of the root by its repeated link and take it to be child 1
 )
 
 _EPS = np.finfo(np.float64).eps
@@ -116,10 +120,43 @@ def _bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-def validate(snap, inst_mesh):
+INST_BOX_LIMIT = np.float32(1e37)
+
+
+def padded_world_box(o2w, lo, hi):
+    """instance_world_box (csrc/rt_api.cpp, k_inst_records) in numpy: the eight corners of the mesh bounds through o2w in binary64,
+    rounded to binary32, min / max that drop a NaN, padded by 1e-5 of the largest magnitude + 1e-30 in binary32.  o2w (n, 12), lo and
+    hi (n, 3) -> (lo, hi) float32 (n, 3)"""
+    f = np.float32
+    M = np.asarray(o2w, f).astype(np.float64).reshape(-1, 3, 4)
+    corner = np.array([[(c >> a) & 1 for a in range(3)] for c in range(8)], bool)
+    p = np.where(corner[None], np.asarray(hi, f).astype(np.float64)[:, None, :], np.asarray(lo, f).astype(np.float64)[:, None, :])   # (n, 8, 3)
+    with np.errstate(all="ignore"):
+        v = ((M[:, None, :, 0] * p[:, :, None, 0] + M[:, None, :, 1] * p[:, :, None, 1]) + M[:, None, :, 2] * p[:, :, None, 2]) + M[:, None, :, 3]
+        v32 = v.astype(f)                                                                     # (n, 8, 3)
+        wlo = np.fmin(f(3.0e38), np.fmin.reduce(v32, axis=1))
+        whi = np.fmax(f(-3.0e38), np.fmax.reduce(v32, axis=1))
+        mag = np.fmax(f(0), np.fmax.reduce(np.abs(v).astype(f).reshape(len(M), -1), axis=1))
+        pad = (f(1e-5) * mag + f(1e-30)).astype(f)
+        return (wlo - pad[:, None]).astype(f), (whi + pad[:, None]).astype(f)
+
+
+def void_records(inst, meshes, inst_mesh):
+    """(n,) bool: the records of meshes with triangles that the contract calls void (include/rt_api.h, rt_set_instances): an entry of
+    the transform that is not finite, or a padded world box with a coordinate of magnitude 1e37 or more"""
+    mt = meshes[np.asarray(inst_mesh, np.int64)]
+    o2w = np.asarray(inst["o2w"], np.float32).reshape(-1, 12)
+    lo, hi = padded_world_box(o2w, mt["lo"], mt["hi"])
+    with np.errstate(invalid="ignore"):
+        inside = (np.abs(lo) < INST_BOX_LIMIT).all(axis=1) & (np.abs(hi) < INST_BOX_LIMIT).all(axis=1)
+    return (mt["prim_count"] > 0) & ~(np.isfinite(o2w).all(axis=1) & inside)
+
+
+def validate(snap, inst_mesh, blas=True):
     """snap: a snapshot (RtContext.debug_snapshot / link_meshes); inst_mesh: the mesh index of every instance record (all frames of a
     batch).  Returns (violations, reached): violations maps every kind of KINDS to a count; reached holds what the walk visited —
-    packets[m], nodes[m], leaves[m], levels[m] per mesh with triangles, instances[k] and tlas_levels[k] per frame."""
+    packets[m], nodes[m], leaves[m], levels[m] per mesh with triangles, instances[k] and tlas_levels[k] per frame.  blas=False checks the
+    records and the TLAS only (for a snapshot whose meshes an earlier call has validated: a new set of instances leaves them alone)."""
     out = {k: 0 for k in KINDS}
     reached = {"packets": {}, "nodes": {}, "leaves": {}, "levels": {}, "instances": [], "tlas_levels": []}
     meshes, inst, packets = snap["meshes"], snap["instances"], snap["packets"]
@@ -155,6 +192,8 @@ def validate(snap, inst_mesh):
         used = np.unique(tri)
         vp = np.stack([pos[6 * used + a] for a in range(3)], axis=1)         # referenced positions
         mesh_bounds[m] = (vp.min(axis=0), vp.max(axis=0))
+        if not blas:
+            continue
 
         refs, llo, lhi, levels, n_nodes, shape_ok = _walk(bn, 0, int(M["blas_root"]), 0, n_blas, visited, out, "blas", n_blas + 2)
         first, cnt = refs >> 3, (refs & 7) + 1
@@ -211,22 +250,31 @@ def validate(snap, inst_mesh):
     t_lo, t_s = np.asarray(snap["tlas_q_lo"], np.float32).astype(np.float64), np.asarray(snap["tlas_q_scale"], np.float32).astype(np.float64)
     tvisited = np.zeros(len(tn), bool)
     has_tris = meshes["prim_count"][inst_mesh] > 0
+    # ---- void records: mask word 0, nothing of them in the bounds ----
+    void = void_records(inst, meshes, inst_mesh)
+    out["void_record"] += int((void & (inst["mask"] != 0)).sum())
+    out["tlas_bounds"] += _bounds_excess(inst, meshes, inst_mesh, has_tris & ~void, t_lo, t_s)
     for k in range(K):
         root = base + k * stride
+        if 0 <= root - base < len(tn):
+            rw = tn["w"][root - base].astype(np.int64).reshape(2, 3)
+            absent = ((rw & 0xFFFF) > (rw >> 16)).any(axis=1)
+            out["tlas_root_order"] += int(absent[0] and not absent[1])
         refs, llo, lhi, levels, _, shape_ok = _walk(tn, base, root, root, root + count, tvisited, out, "tlas", len(tn) + 2)
         in_frame = (refs >= k * n) & (refs < (k + 1) * n)
         out["tlas_leaf_range"] += int((~in_frame).sum())
         refs, llo, lhi = refs[in_frame], llo[in_frame], lhi[in_frame]
         times = np.bincount(refs - k * n, minlength=n)
         out["instance_twice"] += int((times > 1).sum())
-        need = has_tris[k * n:(k + 1) * n] & (inst["mask"][k * n:(k + 1) * n] != 0)
+        need = has_tris[k * n:(k + 1) * n] & (inst["mask"][k * n:(k + 1) * n] != 0) & ~void[k * n:(k + 1) * n]   # (a void record: "void_record")
         if shape_ok:
             out["instance_unreached"] += int((need & (times == 0)).sum())
             if levels > TLAS_MAX_DEPTH:
                 out["tlas_depth"] += 1
         reached["instances"].append(int((has_tris[k * n:(k + 1) * n] & (times > 0)).sum()))
         reached["tlas_levels"].append(levels)
-        sel = has_tris[refs]
+        out["void_record"] += int((void[refs] & (llo != 65535).any(axis=1)).sum())                  # (BOX_NONE lies above every plane)
+        sel = has_tris[refs] & ~void[refs]
         refs, llo, lhi = refs[sel], llo[sel], lhi[sel]
         if not len(refs):
             continue
@@ -239,6 +287,30 @@ def validate(snap, inst_mesh):
         out["tlas_containment"] += int((cmp_plane(img, 0.0, t_lo, llo[:, None, :], t_s) < 0).sum())
         out["tlas_containment"] += int((cmp_plane(img, 0.0, t_lo, lhi[:, None, :], t_s) > 0).sum())
     return out, reached
+
+
+def _bounds_excess(inst, meshes, inst_mesh, valid, t_lo, t_s):
+    """The number of axes on which the dequantisation (t_lo, t_s) is not finite or spans more than the `valid` records need by the
+    documented rule.  With [L, H] the union of their world boxes, each padded by at most 1.01e-5 of its largest magnitude + 2e-30:
+    q_scale <= s = (H - L)(1 + 1e-6) / 65530 (1e-30 for H = L), q_lo = lo - 2 q_scale >= L - 2 s and the last plane q_lo + 65535
+    q_scale = lo + 65533 q_scale <= (their smallest lo) + 65533 s, each up to the binary32 rounding of the two numbers (below 1e-6 (|L| + |H|)).  A box
+    that is not one of theirs and reaches the bounds (a void record's, an empty mesh's 3e38) breaks this by orders of magnitude."""
+    t_lo, t_s = np.asarray(t_lo, np.float64), np.asarray(t_s, np.float64)
+    bad = ~(np.isfinite(t_lo) & np.isfinite(t_s) & (t_s > 0))
+    if valid.any():
+        mt = meshes[np.asarray(inst_mesh, np.int64)[valid]]
+        lo, hi = padded_world_box(np.asarray(inst["o2w"], np.float32).reshape(-1, 12)[valid], mt["lo"], mt["hi"])
+        lo, hi = lo.astype(np.float64), hi.astype(np.float64)
+        grow = 1e-7 * np.maximum(np.abs(lo), np.abs(hi)).max(axis=1, keepdims=True) + 1e-30          # (the pad itself is inside lo / hi)
+        L, H, first = (lo - grow).min(axis=0), (hi + grow).max(axis=0), lo.min(axis=0)
+    else:
+        L = H = first = np.zeros(3)
+    s = np.maximum((H - L) * (1.0 + 1e-6) / 65530.0, 1e-30)
+    slack = 1e-6 * (np.abs(L) + np.abs(H)) + 1e-29
+    with np.errstate(all="ignore"):
+        top = t_lo + 65535.0 * t_s
+        bad |= ~(t_lo >= L - 3.0 * s - slack) | ~(top <= first + 65534.0 * s + slack)
+    return int(bad.sum())
 
 
 # ---- snapshots assembled by hand (the self-test of the validator, host-built trees without a GPU) --------------------------------------

@@ -28,9 +28,18 @@ struct Ref {
 inline void box_reset(Aabb& b) {
   for (int k = 0; k < 3; k++) { b.lo[k] = BIG; b.hi[k] = -BIG; }
 }
+// An ABSENT box (box_valid below: lo[0] >= 1e37 — the box of an empty mesh or of a void instance record, lo = hi = 3e38, and the reset
+// box) adds nothing: its upper planes must not reach the boxes above it, which bvh2_bounds takes into the quantisation.
 inline void box_grow(Aabb& b, const Aabb& o) {
+  if (!(o.lo[0] < 1e37f)) return;
   for (int k = 0; k < 3; k++) { b.lo[k] = std::min(b.lo[k], o.lo[k]); b.hi[k] = std::max(b.hi[k], o.hi[k]); }
 }
+// ... and a node over absent boxes only stores the absent box in its documented form (rt_device.h: lo = hi = 3e38)
+inline void box_close(Aabb& b) {
+  if (!(b.lo[0] < 1e37f)) for (int k = 0; k < 3; k++) { b.lo[k] = BIG; b.hi[k] = BIG; }
+}
+// the bin of a centroid at (c - lo) * scale: clamped in floating point, so that no value (NaN, inf, beyond int) is ever converted
+inline int bin_of(float x) { return x >= 0.f ? (x < (float)(NBINS - 1) ? (int)x : NBINS - 1) : 0; }
 inline float half_area(const Aabb& b) {
   float dx = b.hi[0] - b.lo[0], dy = b.hi[1] - b.lo[1], dz = b.hi[2] - b.lo[2];
   if (dx < 0.f || dy < 0.f || dz < 0.f) return 0.f;
@@ -108,6 +117,7 @@ struct Builder {
       for (int t = 1; t < nt; t++) { box_grow(bounds, pb[t]); box_grow(cb, pc[t]); }
     }
     BuildNode& node = out->topo[me];
+    box_close(bounds);
     node.box = bounds; node.first = first;
     if (count <= 1) { node.count = count; lc.leaves++; return false; }
 
@@ -152,8 +162,7 @@ struct Builder {
         for (uint32_t i = f; i < f + n; i++)
           for (int a = 0; a < 3; a++) {
             if (!live[a]) continue;
-            int b = (int)((refs[i].c[a] - cb.lo[a]) * scale[a]);
-            b = b < 0 ? 0 : (b >= NBINS ? NBINS - 1 : b);
+            const int b = bin_of((refs[i].c[a] - cb.lo[a]) * scale[a]);
             B.cnt[a][b]++; box_grow(B.bb[a][b], refs[i].box);
           }
       });
@@ -194,9 +203,7 @@ struct Builder {
     } else if (best_axis >= 0) {
       const float sc = scale[best_axis], lo = cb.lo[best_axis]; const int ax = best_axis, bbin = best_bin;
       auto left = [&](const Ref& r) {
-        int b = (int)((r.c[ax] - lo) * sc);
-        b = b < 0 ? 0 : (b >= NBINS ? NBINS - 1 : b);
-        return b <= bbin;
+        return bin_of((r.c[ax] - lo) * sc) <= bbin;
       };
       if (nt > 1) {   // stable scatter through tmp: lefts of all chunks, then rights of all chunks
         std::vector<uint32_t> nl((size_t)nt + 1, 0), nr((size_t)nt + 1, 0);
@@ -375,6 +382,7 @@ static void refit_rec(const Aabb* prim_boxes, BuiltBvh& bvh, int ti) {
   if (t.left < 0) {
     box_reset(t.box);
     for (uint32_t i = t.first; i < t.first + t.count; i++) box_grow(t.box, prim_boxes[bvh.order[i]]);
+    box_close(t.box);
     return;
   }
   refit_rec(prim_boxes, bvh, t.left);
@@ -382,6 +390,7 @@ static void refit_rec(const Aabb* prim_boxes, BuiltBvh& bvh, int ti) {
   box_reset(t.box);
   box_grow(t.box, bvh.topo[t.left].box);
   box_grow(t.box, bvh.topo[t.right].box);
+  box_close(t.box);
   int e = bvh.emit_of[ti];
   if (e >= 0) {
     set_child_box(bvh.nodes[e], 0, bvh.topo[t.left].box);
@@ -527,7 +536,11 @@ void quantize_bvh2_in(const BuiltBvh& bvh, std::vector<BvhNodeQ>& out, const flo
     const BvhNode& n = bvh.nodes[i];
     float c0[6] = {n.a[0], n.a[1], n.a[2], n.a[3], n.c[0], n.c[1]}, c1[6] = {n.b[0], n.b[1], n.b[2], n.b[3], n.c[2], n.c[3]};
     int32_t r0 = n.child0, r1 = n.child1;
-    const bool v0 = valid(c0), v1 = valid(c1);
+    bool v0 = valid(c0), v1 = valid(c1);
+    // An absent child is always the SECOND one: k_raygen and the ray generation of rt_shade_rays_device recognise the absent child of
+    // the root by its repeated link and take it to be child 1.  A refit can leave the first child absent (the TLAS update in which the
+    // record of child 0 turns void, or its mesh empty): the children change places, which no walk depends on.
+    if (!v0 && v1) { for (int k = 0; k < 6; k++) std::swap(c0[k], c1[k]); std::swap(r0, r1); std::swap(v0, v1); }
     // The absent child of a synthetic single-child root (one-instance TLAS, single-leaf BLAS) gets an INVERTED box
     // (lower plane 0xFFFF, upper plane 0): no ray can enter it, so the sibling is never visited twice.  Its link
     // repeats the sibling's so that every link in the array stays a valid reference for the tree walkers.

@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void k_closest_scale(const InstanceDev* __rest
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
   const float* m = inst[i].o2w;
-  if ((inst[i].mask & 0xFFu) != 0u) {   // (an empty mesh has mask 0 and no bounds)
+  if (((inst[i].mask >> INST_WORLD_MASK_SHIFT) & 0xFFu) != 0u) {   // (an empty mesh and a void record have mask 0 and no bounds)
     const float* ql = inst[i].q_lo; const float* qs = inst[i].q_scale;
     float bm[3], mw = 0.f;
     for (int k = 0; k < 3; k++) bm[k] = fmaxf(__builtin_fabsf(ql[k]), __builtin_fabsf(__builtin_fmaf(65535.0f, qs[k], ql[k])));
@@ -201,7 +201,7 @@ __device__ __forceinline__ void closest_body(const ClosestArgs& a) {
       // ---- TLAS leaf: enter the instance if the call's mask lets it (point -> object space, the slack of both spaces in object units)
       const int ii = ~cur;
       const InstanceDev* I = a.sc.inst + ii;
-      if ((I->mask & a.cull_mask & 0xFFu) != 0u) {
+      if (((I->mask >> INST_WORLD_MASK_SHIFT) & a.cull_mask & 0xFFu) != 0u) {
         const float s = a.inst_scale[1 + ii];
         const float* w = I->w2o; const float* o = I->o2w;
         q = xform_point(w, wp);

@@ -219,7 +219,7 @@ __device__ __forceinline__ void overlap_body(const OverlapArgs& a) {
       // ---- TLAS leaf: enter the instance if the call's mask lets it and, when pruning, the row could still take one of its triangles
       const int ii = ~cur;
       const InstanceDev* I = a.sc.inst + ii;
-      if ((I->mask & a.cull_mask & 0xFFu) != 0u && !(prune && K != 0u && count >= K && ii > last_inst)) {
+      if (((I->mask >> INST_WORLD_MASK_SHIFT) & a.cull_mask & 0xFFu) != 0u && !(prune && K != 0u && count >= K && ii > last_inst)) {
         overlap_enter_instance(I, a.inst_scale[1 + ii], qlo, qhi, q_lo, q_scale);
         st.push(REF_MARK);
         cur_inst = ii; cur = I->blas_root;

@@ -239,7 +239,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a) {
       // ---- TLAS leaf: enter the instance if the call's mask lets it (the path -> object space, the inflation in object units)
       const int ii = ~cur;
       const InstanceDev* I = a.sc.inst + ii;
-      if ((I->mask & a.cull_mask & 0xFFu) != 0u) {
+      if (((I->mask >> INST_WORLD_MASK_SHIFT) & a.cull_mask & 0xFFu) != 0u) {
         const float s = a.inst_scale[1 + ii];
         const float* w = I->w2o; const float* o = I->o2w;
         q = xform_point(w, wo);

@@ -153,6 +153,7 @@ struct rt_ctx {
 
   // instances / TLAS (binding 0) of this slot
   std::vector<rt_instance> h_inst;
+  std::vector<uint8_t> h_inst_no_rays;   // per record of h_inst: no ray enters it (mask 0, empty mesh, void record, w2o not finite)
   std::vector<uint32_t> inst_types;   // rt_set_instance_types: per-instance object type (empty: src/shader.rgen:96's two-way switch)
   BuiltBvh tlas;
   Bvh4 tlas4;
@@ -363,6 +364,18 @@ Aabb instance_world_box(const float o2w[12], const Aabb& b) {
   float pad = 1e-5f * mag + 1e-30f;
   for (int k = 0; k < 3; k++) { w.lo[k] -= pad; w.hi[k] += pad; }
   return w;
+}
+
+// What a caller's record is (rt_api.h, rt_set_instances; k_inst_records of tlas_gpu.hip applies the same two tests).  VOID: an entry of
+// the transform is not finite, or the padded world box has a coordinate of magnitude INST_BOX_LIMIT or more (the box of an empty mesh
+// is one): the record is that of an empty mesh, mask word 0 and BOX_NONE.  NO_RAYS: the transform is finite and w2o is not (a singular
+// matrix, a scale whose inverse overflows binary32): the world-space queries keep it, no ray enters it.
+enum { REC_OK = 0, REC_NO_RAYS = 1, REC_VOID = 2 };
+int instance_record_state(const float o2w[12], const float w2o[12], const Aabb& box) {
+  bool fin = true, inv = true, inside = true;
+  for (int k = 0; k < 12; k++) { fin = fin && std::fabs(o2w[k]) <= 3.4028234e38f; inv = inv && std::fabs(w2o[k]) <= 3.4028234e38f; }
+  for (int k = 0; k < 3; k++) inside = inside && std::fabs(box.lo[k]) < INST_BOX_LIMIT && std::fabs(box.hi[k]) < INST_BOX_LIMIT;
+  return (!fin || !inside) ? REC_VOID : inv ? REC_OK : REC_NO_RAYS;
 }
 
 }  // namespace
@@ -790,9 +803,10 @@ bool far_possible(const rt_ctx* c, const UniformsDev& u) {
       if (!((double)u.position[k] >= c->dev_g_lo[k] && (double)u.position[k] <= c->dev_g_hi[k])) return true;
     return c->dev_far;
   }
-  for (const rt_instance& in : c->h_inst) {
+  for (size_t i = 0; i < c->h_inst.size(); i++) {
+    const rt_instance& in = c->h_inst[i];
     const Mesh& m = S->meshes[in.mesh];
-    if (!m.range.prim_count) continue;
+    if (!m.range.prim_count || c->h_inst_no_rays[i]) continue;   // (no ray enters an empty mesh, a void record, one without a finite w2o, a mask of 0)
     float w2o[12];
     invert_affine(in.transform, w2o);
     smin = std::min({(double)m.q_scale[0], (double)m.q_scale[1], (double)m.q_scale[2]});
@@ -1595,6 +1609,7 @@ static int set_instances_frames(rt_ctx* c, const rt_instance* inst, int n, int u
   // has to be called again) instead of half old, half new
   c->tlas_valid = false;
   c->h_inst.assign(inst, inst + total);
+  c->h_inst_no_rays.assign((size_t)total, 0);
   c->n_inst = total; c->inst_source = INST_HOST;
   std::vector<InstanceDev> inst_dev(total);
   std::vector<Aabb> boxes(total);
@@ -1613,6 +1628,12 @@ static int set_instances_frames(rt_ctx* c, const rt_instance* inst, int n, int u
     d.type = (size_t)(i % n) < c->inst_types.size() ? c->inst_types[i % n] : TYPE_BY_OBJECT_INDEX;
     d.cover_first = m.cover_first; d.cover_count = m.range.prim_count ? m.cover_count : 0u; d.pad = 0;
     boxes[i] = instance_world_box(d.o2w, m.bounds);
+    const int state = instance_record_state(d.o2w, d.w2o, boxes[i]);
+    if (state == REC_VOID) {   // the record of an empty mesh: it enters no bounds and nothing enters it
+      d.mask = 0u;
+      for (int k = 0; k < 3; k++) boxes[i].lo[k] = boxes[i].hi[k] = 3.0e38f;
+    } else if (state == REC_NO_RAYS) d.mask &= ~0xFFu;
+    c->h_inst_no_rays[i] = (d.mask & 0xFFu) == 0u;
   }
   // frame 0 builds (or refits) the context's TLAS; the other frames of a batch are refits of that topology to their own boxes
   std::vector<BuiltBvh> frame_trees;

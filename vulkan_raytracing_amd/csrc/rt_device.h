@@ -81,7 +81,10 @@ struct alignas(16) InstanceDev {
   float w2o[12];        // gl_WorldToObjectEXT, row-major 3x4 (inverse evaluated in binary64, rounded once)
   float o2w[12];        // gl_ObjectToWorldEXT, row-major 3x4 (rt_instance::transform)
   int32_t blas_root;    // global index of the mesh's root node in blas_nodes
-  uint32_t mask;        // bits 0-7: instance mask (frames trace with the ray mask 0xFF); bits 8-11: instance flags (INST_FLAG_*, for ray queries only)
+  uint32_t mask;        // bits 0-7: instance mask as RAYS see it (frames trace with the ray mask 0xFF; 0 for a record whose w2o is not finite);
+                        // bits 8-11: instance flags (INST_FLAG_*, for ray queries only); bits 16-23: the mask as the WORLD-SPACE queries see it
+                        // (closest point, sweep, box and triangle overlaps: they need o2w only).  The whole word is 0 for an empty mesh and
+                        // for a void record ("Instance records")
   int32_t custom_index; // gl_InstanceCustomIndexEXT
   uint32_t first_float; // vertexOffset of src/shader.rchit:55 (floats)
   uint32_t first_index; // 3*primitive offset of src/shader.rchit:54 (uint32s)
@@ -118,8 +121,10 @@ static_assert(sizeof(MaterialDev) == 48, "MaterialDev must be 48 bytes");
 // query (MODE_QUERY_FLAGS) reads them; every other reader masks the word with 0xFF, so frames ignore them as the reference's pipeline does.
 constexpr uint32_t INST_FLAG_FACING_CULL_DISABLE = 0x1u, INST_FLAG_FLIP_FACING = 0x2u, INST_FLAG_FORCE_OPAQUE = 0x4u, INST_FLAG_FORCE_NO_OPAQUE = 0x8u;
 constexpr uint32_t instance_mask_word(uint32_t custom_index_and_mask, uint32_t sbt_offset_and_flags) {   // (constexpr: host and device code)
-  return (custom_index_and_mask >> 24) | (((sbt_offset_and_flags >> 24) & 0xFu) << 8);
+  return (custom_index_and_mask >> 24) | (((sbt_offset_and_flags >> 24) & 0xFu) << 8) | ((custom_index_and_mask >> 24) << 16);
 }
+constexpr uint32_t INST_WORLD_MASK_SHIFT = 16;   // InstanceDev::mask >> INST_WORLD_MASK_SHIFT: what a world-space query's cull mask is tested against
+constexpr float INST_BOX_LIMIT = 1e37f;          // a padded world box with a coordinate of this magnitude or more makes its record void
 // The per-ray word of MODE_QUERY_FLAGS (rt_intersect_device_flags): bits 0-9 the ray flags (RT_RAY_FLAG_*, the SPIR-V RayFlags values),
 // bits 24-31 the cull mask.  Bits 10-11 hold the facing cull of the instance the ray is in, set when the ray enters it.
 constexpr uint32_t QF_OPAQUE = 0x1u, QF_NO_OPAQUE = 0x2u, QF_TERMINATE = 0x4u, QF_CULL_BACK = 0x10u, QF_CULL_FRONT = 0x20u, QF_CULL_OPAQUE = 0x40u,

@@ -104,11 +104,21 @@ __global__ __launch_bounds__(256) void k_inst_records(const RecDev* rec, int n, 
         const float pad = 1e-5f * mag + 1e-30f;
         for (int k = 0; k < 3; k++) { w.lo[k] -= pad; w.hi[k] += pad; }
       }
+      // instance_record_state (rt_api.cpp), the same two tests: a VOID record (an entry of the transform that is not finite, or a
+      // padded box reaching INST_BOX_LIMIT) is the record of an empty mesh — mask word 0, BOX_NONE, nothing of it enters the bounds;
+      // a record whose w2o is not finite keeps its world-space mask only, so no ray is ever transformed by that w2o
+      bool fin = true, inv = true, inside = true;
+      for (int k = 0; k < 12; k++) { fin = fin && __builtin_fabsf(r.transform[k]) <= 3.4028234e38f; inv = inv && __builtin_fabsf(d.w2o[k]) <= 3.4028234e38f; }
+      for (int k = 0; k < 3; k++) inside = inside && __builtin_fabsf(w.lo[k]) < INST_BOX_LIMIT && __builtin_fabsf(w.hi[k]) < INST_BOX_LIMIT;
+      if (!fin || !inside) {   // (an empty mesh arrives here as it is: mask 0, BOX_NONE)
+        d.mask = 0u;
+        for (int k = 0; k < 3; k++) { w.lo[k] = BOX_NONE; w.hi[k] = BOX_NONE; }
+      } else if (!inv) d.mask &= ~0xFFu;
       if (m.built) atomicMax(&s_levels, m.levels);
     }
     out[i] = d;
     boxes[i] = w;
-    if (w.lo[0] < 1e37f)   // (boxes of empty meshes stay out of the bounds, as bvh2_bounds leaves them out)
+    if (w.lo[0] < INST_BOX_LIMIT)   // (boxes of empty meshes and of void records stay out of the bounds, as bvh2_bounds leaves them out)
       for (int k = 0; k < 3; k++) {
         atomicMin(&s_b[k], f2ord(w.lo[k])); atomicMax(&s_b[3 + k], f2ord(w.hi[k]));
         const float cen = 0.5f * w.lo[k] + 0.5f * w.hi[k];
@@ -220,7 +230,7 @@ __global__ __launch_bounds__(256) void k_tlas_emit(const Box* inst_boxes, const 
 __global__ __launch_bounds__(256) void k_tlas_far(const RecDev* rec, int n, const TlasMeshDev* meshes, int n_meshes, const InstanceDev* inst, TlasSummary* s) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   int far = 0;
-  if (i < n && rec[i].mesh < (uint64_t)n_meshes && meshes[rec[i].mesh].prim_count) {
+  if (i < n && rec[i].mesh < (uint64_t)n_meshes && meshes[rec[i].mesh].prim_count && (inst[i].mask & 0xFFu) != 0u) {   // (no ray enters the others)
     const TlasMeshDev& m = meshes[rec[i].mesh];
     const double K = 0.99 * 2097152.0;
     double lo[3], hi[3];

@@ -54,7 +54,8 @@ resource-usage-blas-refit:
 
 # the host builder under AddressSanitizer and UBSan (float-cast-overflow included) over the box sets a bad instance record can produce:
 # a stand-alone host program (tests/native/builder_sanitize.cpp links csrc/bvh_build.cpp directly; g++ only, no GPU, nothing preloaded);
-# test_host_builder_is_clean_under_the_sanitizers (tests/test_instance_records.py) runs it and expects a clean exit
+# test_host_builder_is_clean_under_the_sanitizers (tests/test_instance_records.py) runs it and expects a clean exit; so does
+# tests/test_bad_vertices.py for its second part, build_blas + quantize_bvh2 over triangle meshes with bad vertex positions
 SANFLAGS := -O1 -g -std=c++17 -pthread -Wall -fsanitize=address,undefined -fsanitize=float-cast-overflow -fno-sanitize-recover=all -fno-omit-frame-pointer
 build/builder_sanitize: tests/native/builder_sanitize.cpp $(CSRC)/bvh_build.cpp $(CSRC)/bvh_build.h $(CSRC)/rt_device.h
 	@mkdir -p build

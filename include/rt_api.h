@@ -143,12 +143,29 @@ int rt_create_frame_slot(rt_ctx* parent, rt_ctx** out_ctx);
 void rt_destroy(rt_ctx* ctx);
 
 /* buildBuffer for the shared vertex and index buffers (src/main.cpp:1684-1697, 1713-1726).
- * verts6 = interleaved [px py pz nx ny nz] (src/main.cpp:1673-1682), idx = object-local uint32. */
+ * verts6 = interleaved [px py pz nx ny nz] (src/main.cpp:1673-1682), idx = object-local uint32.
+ *
+ * Bad vertices (for rt_upload_geometry + rt_build_blas with every builder, the vertices on the host or, after a refit, on the device
+ * only).  A vertex position is a caller-supplied input like an instance record (rt_set_instances, "bad records") and has its
+ * degenerate forms specified: a NaN from a skinning kernel or an overflowed literal costs the triangles that name it and nothing else.
+ *   BAD TRIANGLE: one of the nine position coordinates of its three vertices is not finite, or has magnitude >= 1e37 (the limit of an
+ *     instance's box: a larger coordinate in the mesh bounds would void every instance of the mesh).  It is not an error:
+ *     rt_upload_geometry and rt_build_blas return RT_OK.  A bad triangle is INACTIVE for every builder and every consumer: never hit,
+ *     never a candidate of any query, and it adds nothing to any node box, to the mesh bounds, to the centroid bounds or to the
+ *     dequantisation of the mesh.  Every other triangle keeps its primitive index, its material and its answers, bit for bit.
+ *     A mesh whose triangles are all bad behaves like a mesh without triangles: its instances are never entered (rt_set_instances over
+ *     them is RT_OK).  Normals are not part of this: a normal that is not finite changes the shading of its own hits only.
+ *   FAR vertices: a finite coordinate below the limit (1e30) is valid.  The mesh answers bit for bit as over the vertices as they are,
+ *     only more slowly (its boxes collapse into a few quanta); the closest hit does not depend on the tree.  Its
+ *     instances are subject to the box limit of rt_set_instances like any other.
+ *   rt_refit_blas_device keeps its rule: a position in the NEW vertices that is not finite is RT_ERR_INVALID_ARGUMENT and the mesh
+ *     counts as not built.  A later rt_build_blas builds over those vertices under the rule above.  A refit with all-finite vertices
+ *     over a mesh built with inactive triangles makes them active: frames and hits are those of a fresh build over the new vertices. */
 int rt_upload_geometry(rt_ctx* ctx, const float* verts6, size_t n_floats, const uint32_t* idx, size_t n_idx,
                        const rt_mesh_range* ranges, int n_meshes);
 
 /* createBLASGeometry + createBLAS + createBLASScratchBuffer + buildBLAS (src/main.cpp:305-536, called
- * :1734-1799).  Synchronous like the reference's fence wait (:525-527). */
+ * :1734-1799).  Synchronous like the reference's fence wait (:525-527).  Bad vertex positions are no error: see rt_upload_geometry. */
 int rt_build_blas(rt_ctx* ctx, int mesh);
 
 /* createInstance + createTLAS (src/main.cpp:538-793; called :1818-1835 with update=false and every

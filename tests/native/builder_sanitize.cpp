@@ -5,9 +5,13 @@
 // NaN centroids, among finite boxes and alone, at 1, 2, 300 and 5000 boxes (the exact sweep below 13 references, the binned split
 // above).  It checks what has to hold whatever the boxes are: every primitive in exactly one leaf, every link inside the arrays, every
 // quantised plane a 16-bit value.  The sanitizers check the rest.
+// Then build_blas + quantize_bvh2 over triangle meshes with bad vertex positions (include/rt_api.h, rt_upload_geometry): every
+// coordinate class of tests/bad_vertex_cases.py at 1, 2, 13, 300, 20 000 and 40 000 triangles, on 1 and 8 threads.
 #include <cmath>
 #include <cstdint>
+#include <algorithm>
 #include <cstdio>
+#include <cstdlib>
 #include <limits>
 #include <vector>
 
@@ -121,6 +125,50 @@ void run(const std::vector<Aabb>& boxes, const std::vector<Aabb>& refit_to, cons
   }
 }
 
+// ---- triangle meshes with bad vertex positions (include/rt_api.h, rt_upload_geometry; tests/bad_vertex_cases.py): build_blas + quantize_bvh2
+struct CoordClass { const char* name; float value; bool whole_vertex; bool plus_minus; };
+const CoordClass coord_classes[] = {
+    {"NaN in y", NANF, false, false}, {"a NaN vertex", NANF, true, false}, {"+inf in y", INF, false, false}, {"-inf in y", -INF, false, false},
+    {"a +inf vertex", INF, true, false}, {"a -inf vertex", -INF, true, false}, {"+inf and -inf in one triangle", INF, false, true},
+    {"3e38 in y", 3.0e38f, false, false}, {"1e37 in y", 1.0e37f, false, false}, {"just below 1e37 in y", 9.9999993e36f, false, false},
+    {"1e30 in y", 1.0e30f, false, false}};
+
+int meshes = 0;
+void run_mesh(uint32_t n_tris, const CoordClass& cc, int pattern, int threads) {
+  // n_tris random triangles over 2 n_tris vertices (shared vertices: one bad vertex makes a fan of triangles bad)
+  const uint32_t nv = 2 * n_tris + 1;
+  std::vector<float> v(6ull * nv, 0.f);
+  for (uint32_t i = 0; i < nv; i++) for (int k = 0; k < 3; k++) v[6ull * i + k] = (rnd() - 0.5f) * 20.f;
+  std::vector<uint32_t> idx(3ull * n_tris);
+  for (uint32_t t = 0; t < n_tris; t++) {
+    const float c = rnd() * (float)(nv - 3);
+    for (int k = 0; k < 3; k++) idx[3ull * t + k] = (uint32_t)c + (uint32_t)k;
+  }
+  auto chosen = [&](uint32_t i) { return pattern == 0 ? i == idx[0] : pattern == 1 ? i % 40 == 17 % std::min(40u, nv) : pattern == 2 ? i < nv / 3 + 1 : true; };
+  for (uint32_t i = 0; i < nv; i++) {
+    if (!chosen(i)) continue;
+    if (cc.whole_vertex) for (int k = 0; k < 3; k++) v[6ull * i + k] = cc.value; else v[6ull * i + 1] = cc.value;
+  }
+  if (cc.plus_minus) for (uint32_t t = 0; t < n_tris; t++) if (chosen(idx[3ull * t])) v[6ull * idx[3ull * t + 1] + 1] = -INF;
+  char th[8]; snprintf(th, sizeof(th), "%d", threads);
+  setenv("RT_BUILD_THREADS", th, 1);
+  BuiltBvh t; std::vector<TriPacket> tris;
+  build_blas(v.data(), idx.data(), n_tris, t, tris);
+  check_tree(t, n_tris, 4, cc.name);
+  expect(tris.size() == n_tris, "packet count", cc.name, n_tris, 4);
+  // the bounds hold no coordinate of a bad triangle: finite and below the limit, or empty
+  bool fin = true;
+  for (int k = 0; k < 3; k++) fin = fin && ((t.bounds.lo[k] > t.bounds.hi[k]) || (std::fabs(t.bounds.lo[k]) < 1e37f && std::fabs(t.bounds.hi[k]) < 1e37f));
+  expect(fin, "the mesh bounds hold a bad coordinate", cc.name, n_tris, 4);
+  std::vector<BvhNodeQ> q; float q_lo[3], q_scale[3];
+  quantize_bvh2(t, q, q_lo, q_scale, true);
+  for (int k = 0; k < 3; k++) expect(std::isfinite(q_lo[k]) && std::isfinite(q_scale[k]) && q_scale[k] > 0.f && std::isfinite(q_lo[k] + 65535.f * q_scale[k]), "the frame is not finite", cc.name, n_tris, 4);
+  expect(q.size() == t.nodes.size() && bvh2_levels(q.data(), q.size(), 0) >= 1, "the quantised links are no tree", cc.name, n_tris, 4);
+  Bvh4 t4; collapse_bvh4(t, true, false, t4);
+  expect(!t4.nodes.empty(), "no BVH4 root", cc.name, n_tris, 4);
+  meshes++;
+}
+
 }  // namespace
 
 int main() {
@@ -146,5 +194,15 @@ int main() {
     sets += 2;
   }
   printf("builder_sanitize: %d box sets, %d failures\n", sets, failures);
+  // 40 000 triangles reach the threaded passes of the builder (two times Builder::PAR_MIN references); there the two patterns that
+  // leave work for them
+  for (uint32_t n : {1u, 2u, 13u, 300u, 20000u, 40000u})
+    for (const CoordClass& cc : coord_classes)
+      for (int pattern = 0; pattern < 4; pattern++)
+        for (int threads : {1, 8}) {
+          if (n == 40000u && pattern != 1 && pattern != 2) continue;
+          run_mesh(n, cc, pattern, threads);
+        }
+  printf("builder_sanitize: %d triangle meshes, %d failures\n", meshes, failures);
   return failures ? 1 : 0;
 }

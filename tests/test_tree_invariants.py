@@ -117,8 +117,10 @@ def check(snap, inst_mesh, prim_counts, n_reached=None, frames=1):
 
 # ---- CPU: the validator can fail ------------------------------------------------------------------------------------------------------
 
-def synthetic(void=None, leak=False):
-    """void: a record (of mesh 0 or 1) made VOID as the library leaves it — a NaN in its transform, mask word 0, no box in its leaf, out
+def synthetic(void=None, leak=False, bad_tri=False):
+    """bad_tri: triangle 5 of mesh 0 (leaf D, coincident with triangle 4) gets a NaN into the y of its three vertices and is INACTIVE
+    as the library leaves it — its packet holds the NaN, its leaf keeps its link under inverted planes, bounds and frame are those of
+    the other five.  void: a record (of mesh 0 or 1) made VOID as the library leaves it — a NaN in its transform, mask word 0, no box in its leaf, out
     of the bounds; leak: its box, had the NaN been dropped and a 1e37 translation kept, counted into the bounds all the same.
     Two meshes with triangles, one without, five instances and a two-frame batch, quantised by the documented rule (lower planes
     rounded down, upper planes up, one whole quantum further out).  Mesh 0: node 0 -> (node 1: leaves A = packets 0, 1 and B = 2, 3;
@@ -130,6 +132,8 @@ def synthetic(void=None, leak=False):
     t0[4:] += [3.0, 0.5, -0.25]
     t0[5] = t0[4]
     t1 = rng.uniform(-2, -1, size=(2, 3, 3))
+    if bad_tri:
+        t0[5, :, 1] = np.nan
     m0, m1 = _mesh(t0.reshape(-1, 3), np.arange(18).reshape(-1, 3)), _mesh(t1.reshape(-1, 3), np.arange(6).reshape(-1, 3))
     verts, idx, ranges = pack([m0, m1], empty_last=True)
     packets = np.zeros(8, api.TRI_PACKET_DTYPE)
@@ -137,10 +141,12 @@ def synthetic(void=None, leak=False):
     nodes, cover = [], []
     for m, ((v, i), topo, nn, nt) in enumerate([(m0, (([0, 1], [2, 3]), ([4], [5])), 0, 0), (m1, ([0, 1],), 4, 6)]):   # mesh 1 starts on a line of four nodes
         P = v[:, :3][i.astype(np.int64)].reshape(-1, 3, 3)
-        lo, hi = P.reshape(-1, 3).min(axis=0), P.reshape(-1, 3).max(axis=0)
+        lo, hi = tr.active_bounds(P)
         q_lo, q_s = tr.quant_params(lo, hi)
-        nd = tr.build_tree(topo, lambda leaf: (P[leaf].reshape(-1, 3).min(axis=0), P[leaf].reshape(-1, 3).max(axis=0)),
-                           lambda leaf: ((leaf[0] + nt) << 3) | (len(leaf) - 1), q_lo, q_s, margin=1, first=nn)
+        box = lambda leaf: tr.active_bounds(P[leaf]) if tr.active_triangles(P[leaf]).any() else None
+        nd = tr.build_tree(topo, box, lambda leaf: ((leaf[0] + nt) << 3) | (len(leaf) - 1), q_lo, q_s, margin=1, first=nn, keep_links=True)
+        if len(nd) == 1 and len(topo) == 1:
+            nd[0]["child"][1] = nd[0]["child"][0]                                # (the absent child of the synthetic root repeats its sibling's link)
         for p in range(len(P)):
             packets[nt + p] = (P[p, 0], P[p, 1] - P[p, 0], P[p, 2] - P[p, 0], p, (0, 0))
         first_cover = len(cover)
@@ -282,6 +288,34 @@ def _d_root_order(s):
     nd["child"][0] = nd["child"][1]
 
 
+def _bad(seed):
+    """the seed applied to the snapshot with the inactive triangle"""
+    def f(_):
+        s = synthetic(bad_tri=True)[0]
+        seed(s)
+        return s
+    return f
+
+
+def _d_frame_inf(s):
+    s["meshes"][0]["q_scale"][1] = np.inf                                        # what one infinite coordinate made of the frame before the contract
+    s["instances"]["q_scale"][[0, 2, 5, 7], 1] = np.inf
+
+
+def _d_bounds(s):
+    s["meshes"][0]["hi"][0] = np.nextafter(s["meshes"][0]["hi"][0], np.float32(np.inf))   # one ulp beyond the active triangles
+
+
+def _d_blas_frame(s):
+    q = np.nextafter(s["meshes"][0]["q_lo"][2], np.float32(-np.inf))
+    s["meshes"][0]["q_lo"][2] = q
+    s["instances"]["q_lo"][[0, 2, 5, 7], 2] = q
+
+
+def _d_active_absent(s):
+    s["blas_nodes"][2]["w"][0:3] = tr.INVERTED                                   # leaf C holds the active triangle 4: inverted planes, its own link
+
+
 DEFECTS = [("an upper plane one quantum below a vertex", _d_upper, "blas_hi"), ("a lower plane one quantum above a vertex", _d_lower, "blas_lo"),
            ("a link redirected to an ancestor", _d_ancestor, "blas_node_twice"), ("a packet in two leaves", _d_packet_twice, "packet_twice"),
            ("a packet in no leaf", _d_packet_none, "packet_unreached"), ("e1 off by one ulp", _d_e1, "packet_bits"),
@@ -290,7 +324,12 @@ DEFECTS = [("an upper plane one quantum below a vertex", _d_upper, "blas_hi"), (
            ("InstanceDev.q_scale one ulp off the mesh table", _d_q_scale, "record_fields"), ("a leaf of frame 1 naming a record of frame 0", _d_frame, "tlas_leaf_range"),
            ("a void record that leaked into the bounds", _d_void_leaked, "tlas_bounds"), ("a good record given BOX_NONE", _d_box_none, "tlas_containment"),
            ("a void record that kept its mask", _d_void_mask, "void_record"),
-           ("the root's absent child in the first slot", _d_root_order, "tlas_root_order")]
+           ("the root's absent child in the first slot", _d_root_order, "tlas_root_order"),
+           # bad vertices (appended: the ids of the cases above carry their position in the table)
+           ("a frame that is not finite", _bad(_d_frame_inf), "blas_not_finite"), ("mesh bounds one ulp beyond the active triangles", _bad(_d_bounds), "blas_bounds"),
+           ("q_lo one ulp off the documented frame", _bad(_d_blas_frame), "blas_frame"),
+           ("an active triangle under inverted planes with a link of their own", _bad(_d_active_absent), "blas_inverted_link"),
+           ("the same in a mesh without inactive triangles", _d_active_absent, "blas_inverted_link")]
 
 
 def test_validator_accepts_a_clean_snapshot():
@@ -306,6 +345,16 @@ def test_validator_reports_each_seeded_defect_as_its_own_kind(name, seed, kind):
     snap = seed(snap) or snap                                                   # (a seed may build the defective snapshot itself)
     viol, _ = tr.validate(snap, inst_mesh)
     assert list(clean(viol)) == [kind], (name, clean(viol))
+
+
+def test_validator_accepts_an_inactive_triangle():
+    """the same snapshot with triangle 5 of mesh 0 inactive as the library leaves it: reached or not, in no box, out of bounds and frame"""
+    snap, inst_mesh = synthetic(bad_tri=True)
+    viol, reached = tr.validate(snap, inst_mesh)
+    assert clean(viol) == {} and reached["active"] == {0: 5, 1: 2} and reached["inactive"] == {0: 1, 1: 0} and reached["packets"][0] == 6, (clean(viol), reached)
+    snap["blas_nodes"][2]["child"][1] = snap["blas_nodes"][2]["child"][0]       # ... and with its leaf dropped from the tree
+    viol, reached = tr.validate(snap, inst_mesh)
+    assert clean(viol) == {} and reached["active"] == {0: 5, 1: 2} and reached["packets"][0] == 5, (clean(viol), reached)
 
 
 def test_validator_accepts_a_void_record():

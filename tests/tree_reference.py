@@ -19,16 +19,21 @@ KINDS = (
     # BLAS
     "blas_node_twice",       # a node slot reached twice (within a mesh or across meshes)
     "blas_link_range",       # an interior link outside [0, n_blas_nodes)
-    "blas_inverted_link",    # a child with inverted planes whose link does not repeat its sibling's
+    "blas_inverted_link",    # a child with inverted planes whose link does not repeat its sibling's AND leads to an active triangle (a subtree
+                             # of inactive triangles only keeps its link under inverted planes: a refit over good vertices revives it)
     "blas_leaf_range",       # a leaf whose packets do not lie inside the packet array
     "packet_twice",          # a packet reached more than once
-    "packet_unreached",      # a mesh reaches fewer packets than it has triangles
+    "packet_unreached",      # a mesh reaches fewer packets of active triangles than it has active triangles (an inactive one may be reached or not)
     "prim_permutation",      # the prim values of a mesh's packets are not a permutation of 0..prim_count-1
     "packet_bits",           # v0 / e1 / e2 differ from verts[idx[3p]], fl32(v1 - v0), fl32(v2 - v0)
     "blas_lo",               # a lower plane on the path lies above a vertex of the triangle
     "blas_hi",               # an upper plane on the path lies below a vertex of the triangle
     "frontier",              # a vertex of the mesh lies in none of its frontier boxes
     "blas_depth",            # interior levels differ from the mesh table's, or exceed BLAS_MAX_DEPTH
+    # bad vertices (include/rt_api.h, rt_upload_geometry): a triangle with a position coordinate that is not finite or reaches 1e37 is INACTIVE
+    "blas_not_finite",       # a q_lo or q_scale of a mesh (mesh table or record) that is not finite or not positive, or a last plane that is not finite
+    "blas_bounds",           # the mesh table's lo / hi are not exactly the bounds of the mesh's ACTIVE triangles (none: lo > hi)
+    "blas_frame",            # q_lo / q_scale are not bit for bit the documented function of those bounds (the host rule or the device rule)
     # TLAS
     "tlas_node_twice",
     "tlas_link_range",       # an interior link outside the frame's node range
@@ -71,27 +76,30 @@ def cmp_plane(a, b, q_lo, q, s):
     return out.reshape(shape)
 
 
-def _walk(nodes, first_global, root, lo_ok, hi_ok, visited, out, prefix, max_iter):
+def _walk(nodes, first_global, root, lo_ok, hi_ok, visited, out, prefix, max_iter, follow_absent=False):
     """Level-by-level walk of one tree.  nodes[i] is global node first_global + i; links must stay inside [lo_ok, hi_ok); visited is the
     shared per-slot flag array of `nodes`.  Every entered child carries the intersection (in quanta) of the child boxes on its path.
-    Returns (leaf refs, leaf lo (n, 3), leaf hi (n, 3), interior levels, nodes visited, shape_ok)."""
+    follow_absent (a BLAS): a child with inverted planes and a link of its own is entered all the same, as ABSENT — what lies below it
+    is in no box; the caller decides whether that is a violation (an active triangle there) — and is not counted as an inverted link here.
+    Returns (leaf refs, leaf lo (n, 3), leaf hi (n, 3), interior levels, nodes visited, shape_ok, leaf absent (n,) bool)."""
     bad0 = out[prefix + "_node_twice"] + out[prefix + "_link_range"] + out[prefix + "_inverted_link"]
     cur = np.array([root], np.int64)
     blo = np.zeros((1, 3), np.int64)
     bhi = np.full((1, 3), 65535, np.int64)
-    leaves, llo, lhi = [], [], []
+    dead = np.zeros(1, bool)
+    leaves, llo, lhi, ldead = [], [], [], []
     levels = n_visited = 0
     for _ in range(max_iter):
         ok = (cur >= lo_ok) & (cur < hi_ok)
         out[prefix + "_link_range"] += int((~ok).sum())
-        cur, blo, bhi = cur[ok], blo[ok], bhi[ok]
+        cur, blo, bhi, dead = cur[ok], blo[ok], bhi[ok], dead[ok]
         loc = cur - first_global
         _, first_at = np.unique(loc, return_index=True)
         fresh = np.zeros(len(loc), bool)
         fresh[first_at] = True
         fresh &= ~visited[loc]
         out[prefix + "_node_twice"] += int((~fresh).sum())
-        cur, blo, bhi, loc = cur[fresh], blo[fresh], bhi[fresh], loc[fresh]
+        cur, blo, bhi, loc, dead = cur[fresh], blo[fresh], bhi[fresh], loc[fresh], dead[fresh]
         if not len(cur):
             break
         visited[loc] = True
@@ -101,19 +109,22 @@ def _walk(nodes, first_global, root, lo_ok, hi_ok, visited, out, prefix, max_ite
         ch = nodes["child"][loc].astype(np.int64)
         qlo, qhi = w & 0xFFFF, w >> 16
         inverted = (qlo > qhi).any(axis=2)                                  # (n, 2)
-        out[prefix + "_inverted_link"] += int((inverted & (ch != ch[:, ::-1])).sum())
+        own = inverted & (ch != ch[:, ::-1])
+        if not follow_absent:
+            out[prefix + "_inverted_link"] += int(own.sum())
         nlo = np.maximum(blo[:, None, :], qlo)
         nhi = np.minimum(bhi[:, None, :], qhi)
-        enter = ~inverted
+        enter = ~inverted | (own if follow_absent else False)
+        ndead = (dead[:, None] | inverted)[enter]
         ref, nlo, nhi = ch[enter], nlo[enter], nhi[enter]
         leaf = ref < 0
-        leaves.append(~ref[leaf]); llo.append(nlo[leaf]); lhi.append(nhi[leaf])
-        cur, blo, bhi = ref[~leaf], nlo[~leaf], nhi[~leaf]
+        leaves.append(~ref[leaf]); llo.append(nlo[leaf]); lhi.append(nhi[leaf]); ldead.append(ndead[leaf])
+        cur, blo, bhi, dead = ref[~leaf], nlo[~leaf], nhi[~leaf], ndead[~leaf]
     else:
         out[prefix + "_node_twice"] += 1                                    # (cannot happen: every slot is entered once)
     shape_ok = out[prefix + "_node_twice"] + out[prefix + "_link_range"] + out[prefix + "_inverted_link"] == bad0
     cat = lambda xs, shape: np.concatenate(xs) if xs else np.zeros(shape, np.int64)
-    return cat(leaves, (0,)), cat(llo, (0, 3)), cat(lhi, (0, 3)), levels, n_visited, shape_ok
+    return cat(leaves, (0,)), cat(llo, (0, 3)), cat(lhi, (0, 3)), levels, n_visited, shape_ok, (np.concatenate(ldead) if ldead else np.zeros(0, bool))
 
 
 def _bits(a):
@@ -141,6 +152,37 @@ def padded_world_box(o2w, lo, hi):
         return (wlo - pad[:, None]).astype(f), (whi + pad[:, None]).astype(f)
 
 
+BAD_COORD_LIMIT = INST_BOX_LIMIT
+
+
+def active_triangles(P):
+    """P (n, 3 corners, 3 axes) float32 -> (n,) bool: every one of the nine coordinates finite and of magnitude below BAD_COORD_LIMIT
+    (include/rt_api.h, rt_upload_geometry: the others are BAD triangles, inactive in every builder and consumer)"""
+    with np.errstate(invalid="ignore"):
+        return (np.abs(np.asarray(P, np.float32)) < BAD_COORD_LIMIT).reshape(len(P), -1).all(axis=1)
+
+
+def active_bounds(P):
+    """(lo, hi) float32 over the vertices of the active triangles of P; none: the empty box (3e38, -3e38)"""
+    A = np.asarray(P, np.float32)[active_triangles(P)].reshape(-1, 3)
+    if not len(A):
+        return np.full(3, 3.0e38, np.float32), np.full(3, -3.0e38, np.float32)
+    return A.min(axis=0), A.max(axis=0)
+
+
+def frame_rules(lo, hi):
+    """the two documented dequantisations of a mesh with bounds [lo, hi] (an empty box counts as [0, 0]), as (q_lo, q_scale) float32
+    pairs: the host's (quant_params of csrc/bvh_build.cpp: 65530 quanta of the extent times 1 + 1e-6 in binary64, two quanta below) and
+    the device builders' and the refit's (csrc/blas_quant.h: 65520 quanta of the extent times 1.00001 in binary32, four quanta below)"""
+    f = np.float32
+    lo, hi = np.asarray(lo, f), np.asarray(hi, f)
+    if (lo > hi).any():
+        lo = hi = np.zeros(3, f)
+    ext = (hi - lo).astype(f)
+    scale = np.where(ext > 0, ((ext * f(1.00001)).astype(f) / f(65520.0)).astype(f), f(1e-30)).astype(f)
+    return quant_params(lo, hi), ((lo - (f(4.0) * scale).astype(f)).astype(f), scale)
+
+
 def void_records(inst, meshes, inst_mesh):
     """(n,) bool: the records of meshes with triangles that the contract calls void (include/rt_api.h, rt_set_instances): an entry of
     the transform that is not finite, or a padded world box with a coordinate of magnitude 1e37 or more"""
@@ -158,7 +200,7 @@ def validate(snap, inst_mesh, blas=True):
     packets[m], nodes[m], leaves[m], levels[m] per mesh with triangles, instances[k] and tlas_levels[k] per frame.  blas=False checks the
     records and the TLAS only (for a snapshot whose meshes an earlier call has validated: a new set of instances leaves them alone)."""
     out = {k: 0 for k in KINDS}
-    reached = {"packets": {}, "nodes": {}, "leaves": {}, "levels": {}, "instances": [], "tlas_levels": []}
+    reached = {"packets": {}, "active": {}, "inactive": {}, "nodes": {}, "leaves": {}, "levels": {}, "instances": [], "tlas_levels": []}
     meshes, inst, packets = snap["meshes"], snap["instances"], snap["packets"]
     inst_mesh = np.asarray(inst_mesh, np.int64)
     assert len(inst_mesh) == len(inst)
@@ -189,25 +231,44 @@ def validate(snap, inst_mesh, blas=True):
         tri = idx[fi:fi + 3 * pc].astype(np.int64).reshape(-1, 3)
         pos = verts[ff:].reshape(-1)                                         # position of vertex v: pos[6v : 6v + 3]
         P = np.stack([pos[6 * tri + a] for a in range(3)], axis=2)           # (pc, 3 corners, 3 axes) float32
-        used = np.unique(tri)
-        vp = np.stack([pos[6 * used + a] for a in range(3)], axis=1)         # referenced positions
-        mesh_bounds[m] = (vp.min(axis=0), vp.max(axis=0))
+        active = active_triangles(P)
+        used = np.unique(tri[active])
+        vp = np.stack([pos[6 * used + a] for a in range(3)], axis=1)         # positions the active triangles reference
+        mesh_bounds[m] = active_bounds(P)
         if not blas:
             continue
 
-        refs, llo, lhi, levels, n_nodes, shape_ok = _walk(bn, 0, int(M["blas_root"]), 0, n_blas, visited, out, "blas", n_blas + 2)
+        # ---- the frame: finite, and exactly that of the active triangles ----
+        not_finite = 0
+        with np.errstate(all="ignore"):
+            for src_ in ([M] + [inst[u] for u in users]):
+                fl, fs = src_["q_lo"].astype(np.float64), src_["q_scale"].astype(np.float64)
+                not_finite += int((~(np.isfinite(fl) & np.isfinite(fs) & (fs > 0) & np.isfinite((fl + 65535.0 * fs).astype(np.float32)))).sum())
+        out["blas_not_finite"] += not_finite
+        if not_finite:
+            continue                                                         # (no plane of this mesh is a number: nothing below can be decided)
+        # (as numbers: all of them are finite or the empty box's 3e38, and a minimum over -0 and +0 has either sign)
+        out["blas_bounds"] += int((M["lo"] != mesh_bounds[m][0]).sum() + (M["hi"] != mesh_bounds[m][1]).sum())
+        rules = frame_rules(*mesh_bounds[m])
+        if not any((_bits(M["q_lo"]) == _bits(r[0])).all() and (_bits(M["q_scale"]) == _bits(r[1])).all() for r in rules):
+            out["blas_frame"] += 1
+
+        refs, llo, lhi, levels, n_nodes, shape_ok, ldead = _walk(bn, 0, int(M["blas_root"]), 0, n_blas, visited, out, "blas", n_blas + 2, follow_absent=True)
         first, cnt = refs >> 3, (refs & 7) + 1
         in_range = first + cnt <= n_pk
         out["blas_leaf_range"] += int((~in_range).sum())
-        first, cnt, llo, lhi = first[in_range], cnt[in_range], llo[in_range], lhi[in_range]
+        first, cnt, llo, lhi, ldead = first[in_range], cnt[in_range], llo[in_range], lhi[in_range], ldead[in_range]
         leaf_of = np.repeat(np.arange(len(first)), cnt)
         pk = np.repeat(first, cnt) + (np.arange(len(leaf_of)) - np.repeat(np.cumsum(cnt) - cnt, cnt))
         upk, ucnt = np.unique(pk, return_counts=True)
         out["packet_twice"] += int(((ucnt > 1) | (pk_count[upk] > 0)).sum())      # within this mesh, or already reached from another
         pk_count[upk] += ucnt
         reached["packets"][m], reached["nodes"][m], reached["leaves"][m], reached["levels"][m] = len(upk), n_nodes, len(refs), levels
+        uprim = packets["prim"][upk].astype(np.int64)
+        n_active_reached = int(active[uprim[uprim < pc]].sum())
+        reached["active"][m], reached["inactive"][m] = n_active_reached, int(pc - active.sum())
         if shape_ok:
-            out["packet_unreached"] += max(0, pc - len(upk))
+            out["packet_unreached"] += max(0, int(active.sum()) - n_active_reached)
             if levels != int(M["levels"]) or levels > BLAS_MAX_DEPTH:
                 out["blas_depth"] += 1
         prim = packets["prim"][upk].astype(np.int64)
@@ -220,9 +281,15 @@ def validate(snap, inst_mesh, blas=True):
         pk, leaf_of, prim_all = pk[okp], leaf_of[okp], prim_all[okp]
         T = P[prim_all]                                                      # (n, 3, 3)
         rec = packets[pk]
-        bad = (_bits(rec["v0"]) != _bits(T[:, 0])).any(axis=1) | (_bits(rec["e1"]) != _bits(T[:, 1] - T[:, 0])).any(axis=1) | \
-              (_bits(rec["e2"]) != _bits(T[:, 2] - T[:, 0])).any(axis=1)
+        with np.errstate(all="ignore"):                                      # (a NaN edge of an inactive triangle is a NaN: its payload is the processor's)
+            differs = lambda got, want: ((_bits(got) != _bits(want)) & ~(np.isnan(got) & np.isnan(want))).any(axis=1)
+            bad = differs(rec["v0"], T[:, 0]) | differs(rec["e1"], T[:, 1] - T[:, 0]) | differs(rec["e2"], T[:, 2] - T[:, 0])
         out["packet_bits"] += int(bad.sum())
+        # an inverted child that keeps a link of its own may hold inactive triangles only
+        act = active[prim_all]
+        out["blas_inverted_link"] += int(np.unique(leaf_of[act & ldead[leaf_of]]).size)
+        act &= ~ldead[leaf_of]                                               # containment: the active triangles (those below an absent child are counted above)
+        pk, leaf_of, T, rec = pk[act], leaf_of[act], T[act], rec[act]
 
         # containment along the path: the three buffer positions, and the exact v0, v0 + e1, v0 + e2 of the packet
         v0 = rec["v0"].astype(np.float64)
@@ -260,7 +327,7 @@ def validate(snap, inst_mesh, blas=True):
             rw = tn["w"][root - base].astype(np.int64).reshape(2, 3)
             absent = ((rw & 0xFFFF) > (rw >> 16)).any(axis=1)
             out["tlas_root_order"] += int(absent[0] and not absent[1])
-        refs, llo, lhi, levels, _, shape_ok = _walk(tn, base, root, root, root + count, tvisited, out, "tlas", len(tn) + 2)
+        refs, llo, lhi, levels, _, shape_ok, _ = _walk(tn, base, root, root, root + count, tvisited, out, "tlas", len(tn) + 2)
         in_frame = (refs >= k * n) & (refs < (k + 1) * n)
         out["tlas_leaf_range"] += int((~in_frame).sum())
         refs, llo, lhi = refs[in_frame], llo[in_frame], lhi[in_frame]
@@ -342,11 +409,12 @@ def world_box(o2w, lo, hi):
     return img.min(axis=0), img.max(axis=0)
 
 
-def build_tree(topo, leaf_box, leaf_ref, q_lo, q_scale, margin=1, first=0):
+def build_tree(topo, leaf_box, leaf_ref, q_lo, q_scale, margin=1, first=0, keep_links=False):
     """BvhNodeQ records of the tree `topo`: an interior node is a tuple of one or two children, anything else is a leaf.  leaf_box(leaf)
     gives (lo, hi) or None for a leaf without a box (its planes are inverted and its link repeats the sibling's, as quantize_bvh2_in
     leaves it); leaf_ref(leaf) the value a leaf link names.  Interior links are first + index.  A root that is a leaf gets the synthetic
-    single-child root."""
+    single-child root.  keep_links: a child without a box keeps its own link under the inverted planes (a BLAS child over inactive
+    triangles only, as quantize_bvh2 with keep_links and the device builders leave it)."""
     from vulkan_raytracing_amd.api import NODEQ_DTYPE
     if not isinstance(topo, tuple):
         topo = (topo,)
@@ -366,6 +434,7 @@ def build_tree(topo, leaf_box, leaf_ref, q_lo, q_scale, margin=1, first=0):
             b = box_of(c)
             if b is not None:
                 w[3 * k:3 * k + 3] = quantise_box(b[0], b[1], q_lo, q_scale, margin)
+            if b is not None or keep_links:
                 link[k] = first + emit(c) if isinstance(c, tuple) else ~int(leaf_ref(c))
         if link[0] is None:
             link[0] = link[1]
@@ -405,20 +474,22 @@ def link_meshes(parts, transforms=None):
         ch = nd["child"].astype(np.int64)
         ref = ~ch
         nd["child"] = np.where(ch >= 0, ch + nn, ~((((ref >> 3) + nt) << 3) | (ref & 7))).astype(np.int32)
-        pos = v.reshape(-1, 6)[np.unique(ix), :3]
-        lo, hi = pos.min(axis=0), pos.max(axis=0)
+        lo, hi = active_bounds(v.reshape(-1, 6)[ix.astype(np.int64), :3].reshape(-1, 3, 3))
         meshes[m] = (nn, 0, nf, ni, m, 1, len(ix) // 3, 1, levels, q_lo, q_scale, lo, hi)
         M = np.eye(4, dtype=np.float32)[:3].reshape(12) if transforms is None else np.asarray(transforms[m], np.float32).reshape(12)
         inst[m]["o2w"] = M
         inst[m]["w2o"] = np.linalg.inv(np.vstack([M.reshape(3, 4).astype(np.float64), [0, 0, 0, 1]]))[:3].reshape(12).astype(np.float32)
         for f in ("blas_root", "first_float", "first_index", "cover_first", "cover_count", "q_lo", "q_scale"):
             inst[m][f] = meshes[m][f]
-        inst[m]["mask"] = 0xFF
+        with np.errstate(all="ignore"):                                          # (every triangle inactive, or bounds that reach the instance limit: a void record)
+            plo, phi = padded_world_box(M[None], lo[None], hi[None])
+            inst[m]["mask"] = 0xFF if ((np.abs(plo) < INST_BOX_LIMIT).all() and (np.abs(phi) < INST_BOX_LIMIT).all()) else 0
         cover.append(np.concatenate([lo, hi]))
         nodes.append(nd); packets.append(pk); verts.append(v); idx.append(ix)
         nn += len(nd); nt += len(pk); nf += len(v); ni += len(ix)
-    boxes = [world_box(inst[m]["o2w"], meshes[m]["lo"], meshes[m]["hi"]) for m in range(n)]
-    t_lo, t_s = quant_params(np.min([b[0] for b in boxes], axis=0), np.max([b[1] for b in boxes], axis=0))
+    boxes = [world_box(inst[m]["o2w"], meshes[m]["lo"], meshes[m]["hi"]) if inst[m]["mask"] else None for m in range(n)]
+    some = [b for b in boxes if b is not None] or [(np.zeros(3), np.zeros(3))]
+    t_lo, t_s = quant_params(np.min([b[0] for b in some], axis=0), np.max([b[1] for b in some], axis=0))
     base = nn + 8
     tlas = build_tree(balanced(range(n)), lambda i: boxes[i], lambda i: i, t_lo, t_s, margin=1, first=base)
     snap = {"n_blas_nodes": nn, "tlas_base": base, "tlas_node_count": len(tlas), "tlas_stride": 0, "batch_k": 1, "inst_per_frame": n,

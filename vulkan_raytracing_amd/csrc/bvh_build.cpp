@@ -38,6 +38,11 @@ inline void box_grow(Aabb& b, const Aabb& o) {
 inline void box_close(Aabb& b) {
   if (!(b.lo[0] < 1e37f)) for (int k = 0; k < 3; k++) { b.lo[k] = BIG; b.hi[k] = BIG; }
 }
+// The box of a BAD triangle (rt_api.h, rt_upload_geometry: a position coordinate that is not finite or reaches 1e37) is the reset box
+// as it stands, lo = 3e38 and hi = -3e38: box_grow ignores it.  build_blas puts these references behind the others and under a child
+// of the root of their own (Builder::forced_mid), so no node and no leaf holds active and inactive triangles together: the tree over
+// the active ones is the tree of a mesh without the others, and a packet whose numbers are finite (1e37) is in no box a walk enters.
+inline bool box_is_reset(const Aabb& b) { return !(b.lo[0] < 1e37f) && b.hi[0] < -1e37f; }
 // the bin of a centroid at (c - lo) * scale: clamped in floating point, so that no value (NaN, inf, beyond int) is ever converted
 inline int bin_of(float x) { return x >= 0.f ? (x < (float)(NBINS - 1) ? (int)x : NBINS - 1) : 0; }
 inline float half_area(const Aabb& b) {
@@ -65,6 +70,7 @@ struct Builder {
   float trav_cost = 1.0f;   // SAH: cost of visiting an interior node relative to one triangle test
   BuiltBvh* out;
   int threads = 1;
+  uint32_t forced_mid = 0;   // > 0: the root splits its references at this position whatever the SAH says (build_blas: the inactive ones last)
   // Node numbers, leaf count and depth are kept per task (one cache line hammered by every thread at every node made eight
   // threads slower than one): a subtree over c references owns the next 2c - 2 node numbers below its root, reserved in one step.
   struct Local { int next = 0; uint32_t leaves = 0; int depth = 0; };
@@ -120,6 +126,12 @@ struct Builder {
     box_close(bounds);
     node.box = bounds; node.first = first;
     if (count <= 1) { node.count = count; lc.leaves++; return false; }
+    if (depth == 0 && forced_mid > 0 && forced_mid < count) {   // the root of a mesh with inactive triangles: the active references, then the others
+      L = Task{lc.next++, first, forced_mid, 1};
+      R = Task{lc.next++, first + forced_mid, count - forced_mid, 1};
+      node.left = L.node; node.right = R.node;
+      return true;
+    }
 
     // ---- best SAH split over 3 axes: NBINS bins each, or — for the few references of the bottom levels, where a bin grid is
     // mostly empty bins to reset and merge — every split position of the references sorted by centroid (the exact sweep)
@@ -334,7 +346,8 @@ static int build_threads() {
   return std::max(1, std::min(n, 16));
 }
 
-static void build_bvh_impl(const Aabb* prim_boxes, uint32_t n, int max_leaf, int max_depth, bool direct_ids, BuiltBvh& out, float trav_cost = 1.0f) {
+static void build_bvh_impl(const Aabb* prim_boxes, uint32_t n, int max_leaf, int max_depth, bool direct_ids, BuiltBvh& out, float trav_cost = 1.0f,
+                           bool separate_reset = false) {
   out = BuiltBvh{};
   box_reset(out.bounds);
   Builder b;
@@ -347,6 +360,11 @@ static void build_bvh_impl(const Aabb* prim_boxes, uint32_t n, int max_leaf, int
     b.refs[i].box = prim_boxes[i]; b.refs[i].id = i;
     for (int k = 0; k < 3; k++) b.refs[i].c[k] = 0.5f * prim_boxes[i].lo[k] + 0.5f * prim_boxes[i].hi[k];
     box_grow(out.bounds, prim_boxes[i]);
+  }
+  if (separate_reset) {   // (stable: the order of either kind stays that of the primitives, for every thread count)
+    auto mid = std::stable_partition(b.refs.begin(), b.refs.end(), [](const Ref& r) { return !box_is_reset(r.box); });
+    b.forced_mid = (uint32_t)(mid - b.refs.begin());
+    if (b.forced_mid == n) b.forced_mid = 0;
   }
   b.threads = n >= 2 * Builder::PAR_MIN ? build_threads() : 1;
   const bool timing = getenv("RT_BUILD_TIMING") != nullptr;
@@ -364,7 +382,7 @@ static void build_bvh_impl(const Aabb* prim_boxes, uint32_t n, int max_leaf, int
     set_child_box(root, 0, n ? out.topo[0].box : missing_box());
     set_child_box(root, 1, missing_box());
     root.child0 = n ? em.leaf_ref(out.topo[0]) : ~0;
-    root.child1 = ~0;
+    root.child1 = root.child0;   // (the absent child repeats its sibling's link: no second way to the leaf, whatever a refit makes of the planes)
     out.nodes.push_back(root);
   } else {
     em.emit(0);
@@ -516,14 +534,14 @@ void quant_params(const double lo_in[3], const double hi_in[3], float q_lo[3], f
   }
 }
 
-void quantize_bvh2(const BuiltBvh& bvh, std::vector<BvhNodeQ>& out, float q_lo[3], float q_scale[3]) {
+void quantize_bvh2(const BuiltBvh& bvh, std::vector<BvhNodeQ>& out, float q_lo[3], float q_scale[3], bool keep_links) {
   double lo[3] = {3e38, 3e38, 3e38}, hi[3] = {-3e38, -3e38, -3e38};
   bvh2_bounds(bvh, lo, hi);
   quant_params(lo, hi, q_lo, q_scale);
-  quantize_bvh2_in(bvh, out, q_lo, q_scale);
+  quantize_bvh2_in(bvh, out, q_lo, q_scale, keep_links);
 }
 
-void quantize_bvh2_in(const BuiltBvh& bvh, std::vector<BvhNodeQ>& out, const float q_lo[3], const float q_scale[3]) {
+void quantize_bvh2_in(const BuiltBvh& bvh, std::vector<BvhNodeQ>& out, const float q_lo[3], const float q_scale[3], bool keep_links) {
   auto valid = box_valid;
   // the kernel uses the float values: the doubles are re-derived from them so that rounding of base/scale
   // cannot make a box non-conservative
@@ -540,13 +558,17 @@ void quantize_bvh2_in(const BuiltBvh& bvh, std::vector<BvhNodeQ>& out, const flo
     // An absent child is always the SECOND one: k_raygen and the ray generation of rt_shade_rays_device recognise the absent child of
     // the root by its repeated link and take it to be child 1.  A refit can leave the first child absent (the TLAS update in which the
     // record of child 0 turns void, or its mesh empty): the children change places, which no walk depends on.
-    if (!v0 && v1) { for (int k = 0; k < 6; k++) std::swap(c0[k], c1[k]); std::swap(r0, r1); std::swap(v0, v1); }
+    // keep_links (a BLAS): a child over bad triangles only is absent as well, with the same inverted box, but stays where it is and keeps
+    // its link — the BLAS refit reads the tree from the links (blas_refit.hip) and gives the child a box again once its vertices are good.
+    if (!keep_links && !v0 && v1) { for (int k = 0; k < 6; k++) std::swap(c0[k], c1[k]); std::swap(r0, r1); std::swap(v0, v1); }
     // The absent child of a synthetic single-child root (one-instance TLAS, single-leaf BLAS) gets an INVERTED box
     // (lower plane 0xFFFF, upper plane 0): no ray can enter it, so the sibling is never visited twice.  Its link
     // repeats the sibling's so that every link in the array stays a valid reference for the tree walkers.
     const uint32_t kNever = 0x0000FFFFu;
-    if (!v1) r1 = r0;
-    if (!v0) r0 = r1;
+    if (!keep_links) {
+      if (!v1) r1 = r0;
+      if (!v0) r0 = r1;
+    }
     BvhNodeQ q{};
     for (int k = 0; k < 3; k++) {
       q.w[k] = v0 ? (qdn(c0[2 * k], k) | (qup(c0[2 * k + 1], k) << 16)) : kNever;
@@ -600,7 +622,12 @@ void build_blas(const float* verts6, const uint32_t* idx, uint32_t n_prims, Buil
   std::vector<Aabb> boxes(n_prims);
   for (uint32_t p = 0; p < n_prims; p++) {
     Aabb b; box_reset(b);
+    bool ok = true;   // the first thing that happens to a position: a BAD triangle (rt_api.h) keeps the reset box and is inactive
     for (int c = 0; c < 3; c++) {
+      const float* v = verts6 + 6ull * idx[3ull * p + c];
+      for (int k = 0; k < 3; k++) ok = ok && std::fabs(v[k]) < BAD_COORD_LIMIT;
+    }
+    for (int c = 0; c < 3 && ok; c++) {
       const float* v = verts6 + 6ull * idx[3ull * p + c];
       for (int k = 0; k < 3; k++) { b.lo[k] = std::min(b.lo[k], v[k]); b.hi[k] = std::max(b.hi[k], v[k]); }
     }
@@ -610,7 +637,7 @@ void build_blas(const float* verts6, const uint32_t* idx, uint32_t n_prims, Buil
   int max_leaf = 4; float trav_cost = 1.0f;
   if (const char* e = getenv("RT_BVH_MAX_LEAF")) { int v = atoi(e); if (v >= 1 && v <= 8) max_leaf = v; }
   if (const char* e = getenv("RT_BVH_TRAV_COST")) { float v = (float)atof(e); if (v > 0.f) trav_cost = v; }
-  build_bvh_impl(boxes.data(), n_prims, max_leaf, BLAS_MAX_DEPTH, false, bvh, trav_cost);
+  build_bvh_impl(boxes.data(), n_prims, max_leaf, BLAS_MAX_DEPTH, false, bvh, trav_cost, true);
   tris.resize(n_prims);
   for (uint32_t i = 0; i < n_prims; i++) {
     uint32_t p = bvh.order[i];

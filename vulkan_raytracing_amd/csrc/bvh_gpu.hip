@@ -29,6 +29,9 @@
 namespace rt {
 namespace {
 
+// false for the empty box of an inactive triangle (k_tri_boxes), lo = 3e38 and hi = -3e38
+__device__ __forceinline__ bool box_live(const Box& b) { return b.lo[0] <= b.hi[0]; }
+
 // per triangle: box, centroid bounds (block-reduced, then 6 atomics per block)
 __global__ __launch_bounds__(256) void k_tri_boxes(const float* verts6, const uint32_t* idx, uint32_t n, Box* boxes, uint32_t* cbounds) {
   __shared__ uint32_t s_b[6];
@@ -36,17 +39,26 @@ __global__ __launch_bounds__(256) void k_tri_boxes(const float* verts6, const ui
   __syncthreads();
   const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p < n) {
+    // The first thing that happens to a position is the test of rt_api.h ("bad vertices"): a triangle with a coordinate that is not
+    // finite or reaches BAD_COORD_LIMIT is inactive.  It keeps the empty box, which every fminf / fmaxf union below ignores and which
+    // quantises to inverted planes; its centroid is 0 by the arithmetic wherever one is formed (a finite number for every bin and
+    // Morton code), and box_live keeps it out of every centroid bound.
     Box b;
     for (int k = 0; k < 3; k++) { b.lo[k] = 3.0e38f; b.hi[k] = -3.0e38f; }
+    float pos[9]; bool ok = true;
     for (int c = 0; c < 3; c++) {
       const float* v = verts6 + 6ull * idx[3ull * p + c];
-      for (int k = 0; k < 3; k++) { b.lo[k] = fminf(b.lo[k], v[k]); b.hi[k] = fmaxf(b.hi[k], v[k]); }
+      for (int k = 0; k < 3; k++) { pos[3 * c + k] = v[k]; ok = ok && __builtin_fabsf(v[k]) < BAD_COORD_LIMIT; }
     }
+    if (ok)
+      for (int c = 0; c < 3; c++)
+        for (int k = 0; k < 3; k++) { b.lo[k] = fminf(b.lo[k], pos[3 * c + k]); b.hi[k] = fmaxf(b.hi[k], pos[3 * c + k]); }
     boxes[p] = b;
-    for (int k = 0; k < 3; k++) {
-      const float cen = 0.5f * b.lo[k] + 0.5f * b.hi[k];
-      atomicMin(&s_b[k], f2ord(cen)); atomicMax(&s_b[3 + k], f2ord(cen));
-    }
+    if (ok)
+      for (int k = 0; k < 3; k++) {
+        const float cen = 0.5f * b.lo[k] + 0.5f * b.hi[k];
+        atomicMin(&s_b[k], f2ord(cen)); atomicMax(&s_b[3 + k], f2ord(cen));
+      }
   }
   __syncthreads();
   if (threadIdx.x < 3) atomicMin(&cbounds[threadIdx.x], s_b[threadIdx.x]);
@@ -137,7 +149,8 @@ __global__ void k_quant_params(const Box* node_boxes, float* qparams /* lo[3], s
   if (threadIdx.x >= 3) return;
   const int k = threadIdx.x;
   const float lo = node_boxes[0].lo[k], hi = node_boxes[0].hi[k];
-  blas_quant_axis_params(lo, hi, &qparams[k], &qparams[3 + k]);   // (blas_quant.h, shared with the refit)
+  const bool none = lo > hi;   // every triangle inactive: the frame of an empty mesh (quant_params of bvh_build.cpp), the bounds stay empty
+  blas_quant_axis_params(none ? 0.f : lo, none ? 0.f : hi, &qparams[k], &qparams[3 + k]);   // (blas_quant.h, shared with the refit)
   qparams[6 + k] = lo; qparams[9 + k] = hi;
 }
 
@@ -232,7 +245,11 @@ __global__ __launch_bounds__(256) void k_ploc_nn(const Cluster* c, int m, int r,
   const int lo = max(0, i - r), hi = min(m - 1, i + r);
   for (int j = lo; j <= hi; j++) {
     if (j == i) continue;
-    const float a = merged_area(me, c[j].box);
+    // two clusters of inactive triangles have no area to compare (their empty boxes would give inf or NaN, and one pair a round would
+    // merge: a chain as deep as the run is long): position i pairs with i ^ 1, every other inactive neighbour costs a little more —
+    // symmetric, so a mutual pair exists every round, and a run of such clusters halves every round
+    const Box o = c[j].box;
+    const float a = (!box_live(me) && !box_live(o)) ? (j == (i ^ 1) ? 0.0f : 1e-30f) : merged_area(me, o);
     if (a < best) { best = a; bj = j; }     // ascending j: ties keep the smaller index, so the choice is deterministic
   }
   nn[i] = bj;
@@ -268,7 +285,8 @@ __global__ void k_quant_params_ploc(const PlocNode* nodes, int root, float* qpar
   if (threadIdx.x >= 3) return;
   const int k = threadIdx.x;
   const float lo = fminf(nodes[root].b0.lo[k], nodes[root].b1.lo[k]), hi = fmaxf(nodes[root].b0.hi[k], nodes[root].b1.hi[k]);
-  blas_quant_axis_params(lo, hi, &qparams[k], &qparams[3 + k]);
+  const bool none = lo > hi;   // (as k_quant_params)
+  blas_quant_axis_params(none ? 0.f : lo, none ? 0.f : hi, &qparams[k], &qparams[3 + k]);
   qparams[6 + k] = lo; qparams[9 + k] = hi;
 }
 
@@ -340,8 +358,10 @@ __global__ __launch_bounds__(256) void k_sah_bins_init(uint32_t* bins, uint32_t 
 }
 
 __device__ __forceinline__ int sah_bin_of(float c, float lo, float scale) {
-  int b = (int)((c - lo) * scale);
-  return b < 0 ? 0 : (b >= SAH_BINS ? SAH_BINS - 1 : b);
+  // clamped in floating point, as bin_of of bvh_build.cpp: no NaN, infinity or value beyond int is ever converted (a denormal extent
+  // makes scale infinite)
+  const float x = (c - lo) * scale;
+  return x >= 0.f ? (x < (float)(SAH_BINS - 1) ? (int)x : SAH_BINS - 1) : 0;
 }
 struct SahFrame { float lo[3], scale[3]; bool live[3]; };
 __device__ __forceinline__ SahFrame sah_frame(const uint32_t* cb) {
@@ -495,7 +515,8 @@ __global__ __launch_bounds__(64) void k_sah_split(const Box* tri_boxes, const ui
       ids_next[seg.x + i] = id[q]; pos_node_next[seg.x + i] = i < nl ? left : right;
       box_add(i < nl ? lbx : rbx, bx[q]);
       uint32_t* c = i < nl ? cl : cr;
-      for (int k = 0; k < 3; k++) { const uint32_t o = f2ord(cen[q][k]); c[k] = min(c[k], o); c[3 + k] = max(c[3 + k], o); }
+      if (box_live(bx[q]))
+        for (int k = 0; k < 3; k++) { const uint32_t o = f2ord(cen[q][k]); c[k] = min(c[k], o); c[3 + k] = max(c[3 + k], o); }
     }
     for (int k = 0; k < 6; k++) { ncb[6 * (size_t)left + k] = cl[k]; ncb[6 * (size_t)right + k] = cr[k]; }
   }
@@ -547,7 +568,8 @@ __global__ __launch_bounds__(256) void k_sah_scatter(const Box* tri_boxes, const
     const uint32_t id = ids[p];
     ids_next[np] = id; pos_node_next[np] = l ? kids.x : kids.y;
     const Box b = tri_boxes[id];
-    for (int k = 0; k < 3; k++) { o[k] = f2ord(0.5f * b.lo[k] + 0.5f * b.hi[k]); o[3 + k] = o[k]; }
+    if (box_live(b))   // (an inactive triangle keeps the neutral words: it moves, and adds nothing to the bounds)
+      for (int k = 0; k < 3; k++) { o[k] = f2ord(0.5f * b.lo[k] + 0.5f * b.hi[k]); o[3 + k] = o[k]; }
   }
   const int node_first = __builtin_amdgcn_readfirstlane(node);
   const bool wave_uniform = __ballot(!moves || node != node_first) == 0ull;   // (the whole wave is active here)

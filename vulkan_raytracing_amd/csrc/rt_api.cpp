@@ -461,7 +461,7 @@ int link_blas(rt_ctx* c) {
   for (size_t mi = 0; mi < S->meshes.size(); mi++) {
     Mesh& m = S->meshes[mi];
     if (!m.built) continue;
-    if (!m.gpu_built) quantize_bvh2(m.bvh, m.qnodes, m.q_lo, m.q_scale);
+    if (!m.gpu_built) quantize_bvh2(m.bvh, m.qnodes, m.q_lo, m.q_scale, true);
     laid[mi] = line_layout ? treelet_layout(m.qnodes) : m.qnodes;
     if (getenv("RT_BUILD_TIMING")) fprintf(stderr, "[link_blas] mesh %zu: %zu nodes, %zu slots in the cache-line layout\n", mi, m.qnodes.size(), laid[mi].size());
     gap_from[mi] = nn;
@@ -522,7 +522,9 @@ int link_blas(rt_ctx* c) {
         for (int ax = 0; ax < 3; ax++) {
           const uint32_t w = q.w[3 * k + ax];
           const uint32_t pl = w & 0xFFFFu, ph = w >> 16;
-          if (pl > ph) return;   // the absent child of a synthetic single-child root
+          // (inverted planes: a child over inactive triangles only, kept in the cut for the refit that revives them — until then the
+          // point at plane 0, which lies inside the mesh's frame and holds nothing)
+          if (pl > ph) { lo[ax] = hi[ax] = m.q_lo[ax]; continue; }
           lo[ax] = m.q_lo[ax] + (float)pl * m.q_scale[ax]; hi[ax] = m.q_lo[ax] + (float)ph * m.q_scale[ax];
           const float pad = 1e-6f * (std::fabs(lo[ax]) + std::fabs(hi[ax]));
           lo[ax] -= pad; hi[ax] += pad;
@@ -551,7 +553,12 @@ int link_blas(rt_ctx* c) {
         const int32_t ch[2] = {q.child0, q.child1};
         for (int k = 0; k < 2; k++) {
           const float ar = area_of(q, k);
-          if (ar < 0.0f) continue;   // the absent child of a synthetic single-child root
+          if (ar < 0.0f) {
+            // the absent child of a synthetic single-child root repeats its sibling's link; one with a link of its own holds inactive
+            // triangles only (rt_api.h, "bad vertices"): it is never opened, and a refit re-emits its box from the planes it then has
+            if (ch[k] != ch[k ^ 1]) closed.push_back(Open{0.0f, n, k, ch[k]});
+            continue;
+          }
           const Open o{ar, n, k, ch[k]};
           if (ch[k] >= 0) open.push(o); else closed.push_back(o);
         }
@@ -1996,16 +2003,22 @@ int rt_debug_check_builders(const float* verts6, size_t n_floats, const uint32_t
   BuiltBvh bvh; std::vector<TriPacket> tris; Bvh4 b4; std::vector<BvhNodeQ> q; float q_lo[3], q_scale[3];
   build_blas(verts6, idx, n, bvh, tris);
   collapse_bvh4(bvh, true, false, b4);
-  quantize_bvh2(bvh, q, q_lo, q_scale);
+  quantize_bvh2(bvh, q, q_lo, q_scale, true);
   uint64_t violations = 0, reached = 0, max_leaf = 0;
   std::vector<uint8_t> seen(n, 0);
-  auto tri_box = [&](uint32_t leaf_pos, Aabb& b) {
-    const TriPacket& t = tris[leaf_pos];
-    for (int k = 0; k < 3; k++) {
-      float a = t.v0[k], c1 = t.v0[k] + t.e1[k], c2 = t.v0[k] + t.e2[k];
-      b.lo[k] = std::min(a, std::min(c1, c2)); b.hi[k] = std::max(a, std::max(c1, c2));
+  // the box of a triangle from its three buffer positions, which the builder's boxes contain exactly (min / max round nothing).  The
+  // packet's v0 + e1 is another number: fl(v0 + fl(v1 - v0)) misses v1 by up to an ulp of the LARGER of the two, the whole of a small
+  // coordinate beside one of 1e30.  Returns false for a bad triangle (rt_api.h): inactive, contained in no box.
+  auto tri_box = [&](uint32_t prim, Aabb& b) {
+    bool ok = true;
+    for (int k = 0; k < 3; k++) { b.lo[k] = 3.0e38f; b.hi[k] = -3.0e38f; }
+    for (int c = 0; c < 3; c++) {
+      const float* v = verts6 + 6ull * idx[3ull * prim + c];
+      for (int k = 0; k < 3; k++) { ok = ok && std::fabs(v[k]) < BAD_COORD_LIMIT; b.lo[k] = std::min(b.lo[k], v[k]); b.hi[k] = std::max(b.hi[k], v[k]); }
     }
+    return ok;
   };
+  const bool synthetic_root = bvh.topo.empty() || bvh.topo[0].left < 0;
   // walk the float BVH2 and its quantized twin together
   struct Item { int32_t ref; Aabb box; int depth; };
   std::vector<Item> stack;
@@ -2023,9 +2036,18 @@ int rt_debug_check_builders(const float* verts6, size_t n_floats, const uint32_t
       for (int w = 0; w < 2; w++) {
         Aabb cb = child_box(nd, w);
         const int32_t ref = w ? nd.child1 : nd.child0;
-        if (cb.lo[0] > 1e37f) continue;   // missing child of a synthetic root
+        if (cb.lo[0] > 1e37f) {
+          // an absent child: the missing one of a synthetic root, or a subtree of bad triangles — inverted planes under its own link,
+          // walked for its packets with the box nothing lies in
+          if (synthetic_root && w == 1) continue;
+          for (int k = 0; k < 3; k++) if ((nq.w[(w ? 3 : 0) + k] & 0xFFFFu) <= (nq.w[(w ? 3 : 0) + k] >> 16)) violations++;
+          if ((w ? nq.child1 : nq.child0) != ref) violations++;
+          Aabb none; for (int k = 0; k < 3; k++) { none.lo[k] = 3e38f; none.hi[k] = -3e38f; }
+          stack.push_back({ref, none, it.depth + 1});
+          continue;
+        }
         for (int k = 0; k < 3; k++) {
-          if (cb.lo[k] < it.box.lo[k] - 1e-4f || cb.hi[k] > it.box.hi[k] + 1e-4f) violations++;      // child inside parent
+          if (cb.lo[k] < it.box.lo[k] || cb.hi[k] > it.box.hi[k]) violations++;                      // child inside parent, exactly
           const uint32_t wq = nq.w[(w ? 3 : 0) + k];
           const double qlo = (double)q_lo[k] + (double)(wq & 0xFFFFu) * q_scale[k], qhi = (double)q_lo[k] + (double)(wq >> 16) * q_scale[k];
           if (qlo > cb.lo[k] || qhi < cb.hi[k]) violations++;                                         // quantized box contains the float box
@@ -2040,8 +2062,9 @@ int rt_debug_check_builders(const float* verts6, size_t n_floats, const uint32_t
         if (first + k >= n) { violations++; continue; }
         const uint32_t prim = tris[first + k].prim;
         if (prim >= n || seen[prim]) violations++; else { seen[prim] = 1; reached++; }
-        Aabb tb; tri_box(first + k, tb);
-        for (int a = 0; a < 3; a++) if (tb.lo[a] < it.box.lo[a] - 1e-4f || tb.hi[a] > it.box.hi[a] + 1e-4f) violations++;   // triangle inside its leaf box
+        Aabb tb;
+        if (prim >= n || !tri_box(prim, tb)) continue;
+        for (int a = 0; a < 3; a++) if (tb.lo[a] < it.box.lo[a] || tb.hi[a] > it.box.hi[a]) violations++;   // an active triangle inside its leaf box, exactly
       }
     }
   }
@@ -2070,7 +2093,7 @@ int rt_debug_host_blas(const float* verts6, size_t n_floats, const uint32_t* idx
   for (size_t k = 0; k < n_idx; k++) if ((size_t)idx[k] * 6 + 5 >= n_floats) return RT_ERR_INVALID_ARGUMENT;
   BuiltBvh bvh; std::vector<TriPacket> tris; std::vector<BvhNodeQ> q; float q_lo[3], q_scale[3];
   build_blas(verts6, idx, n, bvh, tris);
-  quantize_bvh2(bvh, q, q_lo, q_scale);
+  quantize_bvh2(bvh, q, q_lo, q_scale, true);
   if (q.size() * sizeof(BvhNodeQ) > nodes_capacity_bytes || tris.size() * sizeof(TriPacket) > packets_capacity_bytes) return RT_ERR_INVALID_ARGUMENT;
   memcpy(nodes, q.data(), q.size() * sizeof(BvhNodeQ));
   memcpy(packets, tris.data(), tris.size() * sizeof(TriPacket));

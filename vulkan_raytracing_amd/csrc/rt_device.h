@@ -125,6 +125,9 @@ constexpr uint32_t instance_mask_word(uint32_t custom_index_and_mask, uint32_t s
 }
 constexpr uint32_t INST_WORLD_MASK_SHIFT = 16;   // InstanceDev::mask >> INST_WORLD_MASK_SHIFT: what a world-space query's cull mask is tested against
 constexpr float INST_BOX_LIMIT = 1e37f;          // a padded world box with a coordinate of this magnitude or more makes its record void
+// A triangle with a position coordinate that is not finite or of this magnitude or more is BAD (rt_api.h, rt_upload_geometry): inactive
+// in every builder.  The same number as INST_BOX_LIMIT: a larger coordinate in the mesh bounds would void every instance of the mesh.
+constexpr float BAD_COORD_LIMIT = INST_BOX_LIMIT;
 // The per-ray word of MODE_QUERY_FLAGS (rt_intersect_device_flags): bits 0-9 the ray flags (RT_RAY_FLAG_*, the SPIR-V RayFlags values),
 // bits 24-31 the cull mask.  Bits 10-11 hold the facing cull of the instance the ray is in, set when the ray enters it.
 constexpr uint32_t QF_OPAQUE = 0x1u, QF_NO_OPAQUE = 0x2u, QF_TERMINATE = 0x4u, QF_CULL_BACK = 0x10u, QF_CULL_FRONT = 0x20u, QF_CULL_OPAQUE = 0x40u,

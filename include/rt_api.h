@@ -487,6 +487,44 @@ int rt_closest_point_device(rt_ctx* ctx, size_t n, const void* d_points4, uint32
  * stats->node_visits and stats->tri_tests (boxes-pair visits and point-triangle tests of the whole call); stats may be NULL. */
 int rt_closest_point(rt_ctx* ctx, size_t n, const float* points4_host, uint32_t cull_mask, rt_hit* out_host, int counting, rt_stats* stats);
 
+/* The K nearest triangles of every query point and the number of triangles within its radius: rt_closest_point_device's list form, as
+ * rt_intersect_device_hits is rt_intersect_device_flags'.  For contact manifolds (a sphere or particle against the scene needs every
+ * triangle within its radius), PhysX's overlapSphere count, a stable normal / material / object id near vertices and edges (blend or
+ * vote over the few nearest triangles) and k-nearest surface samples.
+ * Points: rt_closest_point_device's records (x, y, z, r_max), 16-B aligned: one buffer feeds both calls.
+ * Candidates C(p): every triangle of every instance with (mask & cull_mask) != 0 is tested; it is a candidate when its canonical d2
+ * (rt_closest_point_device, DESIGN.md §5 "Closest points") is not NaN and d2 <= r_max * r_max (the product rounded to binary32).  This is
+ * exactly the set rt_closest_point_device takes its minimum from: the bound is inclusive, and with r_max = +inf a d2 of +inf is a
+ * candidate, as it is there.  Instance flags, opacity and facing play no part; void and non-invertible instance records behave as
+ * they do for rt_closest_point_device.
+ *  - d_hits: n x max_hits rt_hit, point-major (entry j of point i at i * max_hits + j), 4-B aligned.  A row holds the max_hits smallest
+ *    candidates by the key (d2, inst, prim) ascending.  The order is d2's, not t's: two different d2 can round to the same sqrtf, and
+ *    then (inst, prim) must not reorder them.  In each entry t = sqrtf(d2), u and v the nearest point's barycentrics of B and C.  Entry 0
+ *    is rt_closest_point_device's record byte for byte; an (inst, prim) appears at most once.  Entries past min(|C|, max_hits) are the
+ *    miss form: t = r_max as given (bit pattern kept), u = v = 0, prim = inst = -1;
+ *  - d_counts (optional): n uint32, 4-B aligned: |C(p)|, not capped at max_hits.  Without it the walk may stop looking beyond the
+ *    max_hits-th entry's d2 once the row is full; the rows are the same either way.  With it and r_max = +inf the walk visits every
+ *    admitted triangle of the scene: that is the caller's choice;
+ *  - max_hits 1..16, or 0 = count only: then d_hits and d_attr must be NULL and d_counts non-NULL.  That form is the sphere-overlap
+ *    count.  Occupancy ("anything within r") is rt_closest_point_device's inst >= 0 and needs no flag here;
+ *  - d_attr (optional): n x max_hits rt_hit_attr, 16-B aligned, in the same order: what rt_closest_point_device gives for that
+ *    (inst, prim, u, v) and that point: P, N, objectIndex and the side word in `reserved`; a miss is zeros, -1 and 0.
+ * Invalid records (a non-finite coordinate, a negative or NaN r_max): a row of miss forms and a count of 0.
+ * Stream ordering without host synchronisation, the TLAS and scene of the call, the query workspace, queries and shading calls of one
+ * context one after another, RT_ERR_NOT_READY and n == 0 (nothing is enqueued): as for rt_closest_point_device.
+ * RT_ERR_INVALID_ARGUMENT: a NULL or misaligned pointer, a pointer that is not memory of ctx's GPU, n >= 0xFFFFFF00 or
+ * n x max_hits >= 0xFFFFFF00 (the kernels index records with 32 bits), cull_mask > 0xFF, max_hits > 16, max_hits == 0 with d_hits or
+ * d_attr or without d_counts, trace_variant != 0. */
+int rt_closest_point_device_hits(rt_ctx* ctx, size_t n, const void* d_points4, uint32_t cull_mask, uint32_t max_hits,
+                                 void* d_hits, void* d_attr, void* d_counts, void* hip_stream);
+/* The blocking host form, as rt_closest_point is to rt_closest_point_device: the records are copied to the device, queried on the
+ * context's stream (same workspace and ordering) and hits_host (n x max_hits records; NULL with max_hits 0) and counts_host (n; optional
+ * unless max_hits is 0) copied back.  counting != 0 runs the instrumented walk and fills stats->node_visits and stats->tri_tests; stats
+ * may be NULL.  As rt_closest_point does, the call also reports the walk's device time in stats->ms_trace_closest and the node and
+ * packet sizes in stats->bvh_node_bytes / bvh_tri_bytes; every other field is 0. */
+int rt_closest_point_hits(rt_ctx* ctx, size_t n, const float* points4_host, uint32_t cull_mask, uint32_t max_hits,
+                          rt_hit* hits_host, uint32_t* counts_host, int counting, rt_stats* stats);
+
 /* Box overlaps: for every query box the triangles of the scene that touch it (PhysX's overlap query, an occupancy test per voxel), for
  * voxelisation and occupancy grids, broad-phase collision against the live scene, region selection and "is this cell empty" tests.
  * Boxes: d_boxes8 holds n records of 32 B (lo.x, lo.y, lo.z, w3, hi.x, hi.y, hi.z, w7), 16-B aligned, memory of ctx's GPU: a closed

@@ -74,7 +74,7 @@ INSIDE_DIRS = ((0.36, 0.48, 0.8), (-0.8, 0.36, -0.48), (0.48, -0.8, -0.36), (-0.
 
 EXPORTS = ["rt_create", "rt_create_frame_slot", "rt_destroy", "rt_upload_geometry", "rt_build_blas", "rt_set_instances", "rt_set_instances_device", "rt_refit_blas_device", "rt_set_materials", "rt_set_instance_types", "rt_set_uniforms", "rt_set_skybox",
            "rt_trace", "rt_trace_async", "rt_trace_wait", "rt_trace_shard", "rt_set_batch", "rt_trace_shard_batch", "rt_assemble_shards", "rt_shard_rows", "rt_synchronize", "rt_get_stats", "rt_set_timing", "rt_intersect",
-           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_overlap_triangles_device", "rt_overlap_triangles", "rt_sweep_spheres_device", "rt_sweep_spheres", "rt_point_inside_device", "rt_point_inside", "rt_signed_distance_device", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_host_blas", "rt_debug_snapshot", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
+           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_closest_point_device_hits", "rt_closest_point_hits", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_overlap_triangles_device", "rt_overlap_triangles", "rt_sweep_spheres_device", "rt_sweep_spheres", "rt_point_inside_device", "rt_point_inside", "rt_signed_distance_device", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_host_blas", "rt_debug_snapshot", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
 
 _LIBS = {}
 
@@ -121,6 +121,8 @@ def lib(variant=None):
         L.rt_intersect_device_hits.argtypes = [vp, C.c_size_t, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
         L.rt_closest_point_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, vp, vp]
         L.rt_closest_point.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, C.c_int, C.POINTER(RtStats)]
+        L.rt_closest_point_device_hits.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+        L.rt_closest_point_hits.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_int, C.POINTER(RtStats)]
         L.rt_sweep_spheres_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, vp, vp]
         L.rt_sweep_spheres.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, C.c_int, C.POINTER(RtStats)]
         L.rt_point_inside_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
@@ -632,6 +634,59 @@ class RtContext:
                 raise ValueError("words must be int32 or uint32, not %s" % words.dtype)
             if words.device != rays.device or not words.is_contiguous() or tuple(words.shape) != (n,):
                 raise ValueError("words must be a contiguous (n,) tensor on the rays' device")
+        stream, hits, attr, count = self._row_buffers(rays, k, attributes, counts, stream, out)
+
+        def call(run):
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+            return self.L.rt_intersect_device_hits(self.h, n, ptr(rays), ptr(words) if n else None, int(ray_flags) & 0xFFFFFFFF, int(cull_mask) & 0xFFFFFFFF,
+                                                   k, ptr(hits), ptr(attr), ptr(count), C.c_void_p(run.cuda_stream))
+        if n:
+            self._on_stream(stream, (rays, words, hits, attr, count), call, "rt_intersect_device_hits")
+        return RayHits(hits, attr, count, n, k)
+
+    def closest_point_device_hits(self, points, max_hits, cull_mask=0xFF, attributes=False, counts=True, stream=None, out=None):
+        """rt_closest_point_device_hits: the max_hits nearest triangles of every query point in (d2, inst, prim) order, and the number of
+        triangles within the point's radius.  points as for closest_point_device ((n, 4): x, y, z, r_max); max_hits 1..16, or 0 for
+        counts only (the sphere-overlap count).  Read and written in the order of `stream`, with no host synchronisation.  Returns a
+        RayHits of views over one int32 (n, max_hits, 5) hits buffer (t the distance; entry 0 is closest_point_device's record; entries
+        past a point's candidates have prim = inst = -1 and t = r_max), with attributes=True one int32 (n, max_hits, 8) attribute buffer
+        (hit_kind: the side of the triangle's plane the point lies on), with counts=True (required when max_hits is 0) one int32 (n,)
+        count buffer.  counts=False lets the walk prune beyond the max_hits-th entry.  out = (hits, attr, count) reuses such buffers
+        (None where not asked for).  See include/rt_api.h."""
+        self._check_rays(points, "closest_point_device_hits", 4, "point")
+        k = int(max_hits)
+        if not 0 <= k <= 16:
+            raise ValueError("max_hits must be 0..16, got %d" % k)
+        if k == 0 and (attributes or not counts):
+            raise ValueError("max_hits 0 counts only: counts=True and attributes=False")
+        n = points.shape[0]
+        stream, hits, attr, count = self._row_buffers(points, k, attributes, counts, stream, out)
+
+        def call(run):
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+            return self.L.rt_closest_point_device_hits(self.h, n, ptr(points), int(cull_mask) & 0xFFFFFFFF, k, ptr(hits), ptr(attr), ptr(count),
+                                                       C.c_void_p(run.cuda_stream))
+        if n:
+            self._on_stream(stream, (points, hits, attr, count), call, "rt_closest_point_device_hits")
+        return RayHits(hits, attr, count, n, k)
+
+    def closest_point_hits(self, points4, max_hits, cull_mask=0xFF, counts=True, counting=False):
+        """rt_closest_point_hits: the blocking host form -> (HIT_DTYPE records (n, max_hits) or None, counts uint32 (n,) or None, RtStats;
+        with counting its node_visits / tri_tests are filled)"""
+        points4 = np.ascontiguousarray(points4, np.float32).reshape(-1, 4)
+        n, k = len(points4), int(max_hits)
+        hits = np.zeros((n, k), HIT_DTYPE) if k else None
+        cnt = np.zeros(n, np.uint32) if counts else None
+        st = RtStats()
+        self._chk(self.L.rt_closest_point_hits(self.h, n, _p(points4), int(cull_mask) & 0xFFFFFFFF, k & 0xFFFFFFFF, _p(hits) if hits is not None else None,
+                                               _p(cnt) if cnt is not None else None, int(counting), C.byref(st)), "rt_closest_point_hits")
+        return hits, cnt, st
+
+    def _row_buffers(self, rays, k, attributes, counts, stream, out):
+        """the outputs of a list query over the n records of `rays`: int32 (n, k, 5) hits (k > 0), (n, k, 8) attributes and (n,) counts
+        where asked for, new or checked from out = (hits, attr, count) -> (the stream to run on, hits, attr, count)"""
+        import torch
+        n = rays.shape[0]
         cur = torch.cuda.current_stream(rays.device)
         if stream is None:
             stream = cur
@@ -649,15 +704,7 @@ class RtContext:
                     bufs[i] = None
                 elif t is None or t.dtype != torch.int32 or tuple(t.shape) != sh or not t.is_contiguous() or t.device != rays.device:
                     raise ValueError("out %s must be a contiguous int32 %s tensor on the rays' device" % (what, sh))
-        hits, attr, count = bufs
-
-        def call(run):
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
-            return self.L.rt_intersect_device_hits(self.h, n, ptr(rays), ptr(words) if n else None, int(ray_flags) & 0xFFFFFFFF, int(cull_mask) & 0xFFFFFFFF,
-                                                   k, ptr(hits), ptr(attr), ptr(count), C.c_void_p(run.cuda_stream))
-        if n:
-            self._on_stream(stream, (rays, words, hits, attr, count), call, "rt_intersect_device_hits")
-        return RayHits(hits, attr, count, n, k)
+        return (stream, *bufs)
 
     def shade_rays_device(self, rays, samples=1, per_sample=True, points=True, stream=None, out=None):
         """rt_shade_rays_device: the frame's shading of caller-generated primary rays.  `rays` is a contiguous float32 torch tensor

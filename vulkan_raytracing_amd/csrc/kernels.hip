@@ -2369,6 +2369,8 @@ void launch_resolve_points(const float4* sample_color, float4* out, uint32_t n_p
 
 #include "kernels_closest.inc"   // k_closest_point, k_closest_side: the nearest surface point of every query point (rt_closest_point_device)
 
+#include "kernels_closest_hits.inc"   // k_closest_hits, k_closest_hits_side: the K nearest triangles of every query point and their count (rt_closest_point_device_hits)
+
 #include "kernels_overlap.inc"   // k_overlap_boxes: the triangles that touch every query box (rt_overlap_boxes_device)
 
 #include "kernels_triangles.inc"   // k_collide_triangles: the triangles that cut every query triangle (rt_overlap_triangles_device)

@@ -114,6 +114,27 @@ __device__ __forceinline__ float box_bound(uint32_t wx, uint32_t wy, uint32_t wz
   return (dx * dx + dy * dy + dz * dz) * scale2;
 }
 
+// The entry of instance I (s: its scale of k_closest_scale) by the closest-family point walks (k_closest_point, k_closest_hits): the
+// world point wp into object space (q), the dequantisation of the mesh's tree, and the slack of both spaces in object units
+// (w_slack: the walk's world-space slack) with the factor on the squared bound.
+__device__ __forceinline__ void closest_enter_instance(const InstanceDev* I, float s, F3 wp, float w_slack, F3& q, F3& q_lo, F3& q_scale, float& slack, float& scale2) {
+  const float* w = I->w2o; const float* o = I->o2w;
+  q = xform_point(w, wp);
+  q_lo = mk3(I->q_lo[0], I->q_lo[1], I->q_lo[2]); q_scale = mk3(I->q_scale[0], I->q_scale[1], I->q_scale[2]);
+  // magnitudes: the mesh's planes, the terms of q's rows (they may cancel), the terms of o2w's rows over the mesh's bounds
+  const F3 bm = mk3(fmaxf(__builtin_fabsf(q_lo.x), __builtin_fabsf(__builtin_fmaf(65535.0f, q_scale.x, q_lo.x))),
+                    fmaxf(__builtin_fabsf(q_lo.y), __builtin_fabsf(__builtin_fmaf(65535.0f, q_scale.y, q_lo.y))),
+                    fmaxf(__builtin_fabsf(q_lo.z), __builtin_fabsf(__builtin_fmaf(65535.0f, q_scale.z, q_lo.z))));
+  const F3 ap = mk3(__builtin_fabsf(wp.x), __builtin_fabsf(wp.y), __builtin_fabsf(wp.z));
+  float om = fmaxf(fmaxf(bm.x, bm.y), bm.z), wm = w_slack;
+  for (int r = 0; r < 3; r++) {
+    om = fmaxf(om, __builtin_fabsf(w[4 * r]) * ap.x + __builtin_fabsf(w[4 * r + 1]) * ap.y + __builtin_fabsf(w[4 * r + 2]) * ap.z + __builtin_fabsf(w[4 * r + 3]));
+    wm = fmaxf(wm, CP_ABS * (__builtin_fabsf(o[4 * r]) * bm.x + __builtin_fabsf(o[4 * r + 1]) * bm.y + __builtin_fabsf(o[4 * r + 2]) * bm.z + __builtin_fabsf(o[4 * r + 3])));
+  }
+  slack = CP_ABS * om + wm / s;   // (s == 0: an infinite slack, every bound 0)
+  scale2 = CP_REL * (s * s);
+}
+
 template <bool COUNT>
 __device__ __forceinline__ void closest_body(const ClosestArgs& a) {
   __shared__ int s_stack[4][STACK2_LDS][64];
@@ -202,22 +223,7 @@ __device__ __forceinline__ void closest_body(const ClosestArgs& a) {
       const int ii = ~cur;
       const InstanceDev* I = a.sc.inst + ii;
       if (((I->mask >> INST_WORLD_MASK_SHIFT) & a.cull_mask & 0xFFu) != 0u) {
-        const float s = a.inst_scale[1 + ii];
-        const float* w = I->w2o; const float* o = I->o2w;
-        q = xform_point(w, wp);
-        q_lo = mk3(I->q_lo[0], I->q_lo[1], I->q_lo[2]); q_scale = mk3(I->q_scale[0], I->q_scale[1], I->q_scale[2]);
-        // magnitudes: the mesh's planes, the terms of q's rows (they may cancel), the terms of o2w's rows over the mesh's bounds
-        const F3 bm = mk3(fmaxf(__builtin_fabsf(q_lo.x), __builtin_fabsf(__builtin_fmaf(65535.0f, q_scale.x, q_lo.x))),
-                          fmaxf(__builtin_fabsf(q_lo.y), __builtin_fabsf(__builtin_fmaf(65535.0f, q_scale.y, q_lo.y))),
-                          fmaxf(__builtin_fabsf(q_lo.z), __builtin_fabsf(__builtin_fmaf(65535.0f, q_scale.z, q_lo.z))));
-        const F3 ap = mk3(__builtin_fabsf(wp.x), __builtin_fabsf(wp.y), __builtin_fabsf(wp.z));
-        float om = fmaxf(fmaxf(bm.x, bm.y), bm.z), wm = w_slack;
-        for (int r = 0; r < 3; r++) {
-          om = fmaxf(om, __builtin_fabsf(w[4 * r]) * ap.x + __builtin_fabsf(w[4 * r + 1]) * ap.y + __builtin_fabsf(w[4 * r + 2]) * ap.z + __builtin_fabsf(w[4 * r + 3]));
-          wm = fmaxf(wm, CP_ABS * (__builtin_fabsf(o[4 * r]) * bm.x + __builtin_fabsf(o[4 * r + 1]) * bm.y + __builtin_fabsf(o[4 * r + 2]) * bm.z + __builtin_fabsf(o[4 * r + 3])));
-        }
-        slack = CP_ABS * om + wm / s;   // (s == 0: an infinite slack, every bound 0)
-        scale2 = CP_REL * (s * s);
+        closest_enter_instance(I, a.inst_scale[1 + ii], wp, w_slack, q, q_lo, q_scale, slack, scale2);
         st.push(REF_MARK);
         cur_inst = ii; cur = I->blas_root;
       } else cur = st.pop();
@@ -240,25 +246,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_CLOSEST_
 // The side of the reported triangle's plane the query point lies on, into word 7 of its rt_hit_attr (after k_hit_attr): front when
 // s = dot(cross(e1, e2), xform_point(w2o, p) - v0) < 0, e1 / e2 / v0 from the vertex buffer as k_hit_kind forms them, inverted by
 // FLIP_FACING; 0 on a miss.  The kind k_hit_kind reports for a ray from the point that hits that triangle.
+__device__ __forceinline__ uint32_t closest_side_word(const SceneDev& sc, const float4* __restrict__ point, const HitRec h) {
+  if (h.inst < 0) return 0u;
+  const InstanceDev* I = sc.inst + h.inst;
+  const float4 r = *point;
+  const F3 po = xform_point(I->w2o, mk3(r.x, r.y, r.z));
+  const uint32_t* ix = sc.idx + I->first_index + 3u * (uint32_t)h.prim;
+  const float* vb = sc.verts + I->first_float;
+  const float* p0 = vb + 6u * ix[0]; const float* p1 = vb + 6u * ix[1]; const float* p2 = vb + 6u * ix[2];
+  const F3 e1 = mk3(p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]), e2 = mk3(p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]);
+  const float s = dot3(cross3(e1, e2), mk3(po.x - p0[0], po.y - p0[1], po.z - p0[2]));
+  const bool front = ((s < 0.0f) == FRONT_IS_DET_NEGATIVE) != (((I->mask >> 8) & INST_FLAG_FLIP_FACING) != 0u);
+  return front ? 0xFEu : 0xFFu;
+}
 __global__ __launch_bounds__(256) void k_closest_side(SceneDev sc, const float4* __restrict__ points, const HitRec* __restrict__ hits, uint32_t* __restrict__ attr,
                                                      uint32_t n) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
-  const HitRec h = hits[i];
-  uint32_t kind = 0u;
-  if (h.inst >= 0) {
-    const InstanceDev* I = sc.inst + h.inst;
-    const float4 r = points[i];
-    const F3 po = xform_point(I->w2o, mk3(r.x, r.y, r.z));
-    const uint32_t* ix = sc.idx + I->first_index + 3u * (uint32_t)h.prim;
-    const float* vb = sc.verts + I->first_float;
-    const float* p0 = vb + 6u * ix[0]; const float* p1 = vb + 6u * ix[1]; const float* p2 = vb + 6u * ix[2];
-    const F3 e1 = mk3(p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]), e2 = mk3(p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]);
-    const float s = dot3(cross3(e1, e2), mk3(po.x - p0[0], po.y - p0[1], po.z - p0[2]));
-    const bool front = ((s < 0.0f) == FRONT_IS_DET_NEGATIVE) != (((I->mask >> 8) & INST_FLAG_FLIP_FACING) != 0u);
-    kind = front ? 0xFEu : 0xFFu;
-  }
-  attr[8u * (size_t)i + 7u] = kind;
+  attr[8u * (size_t)i + 7u] = closest_side_word(sc, points + i, hits[i]);
 }
 
 void launch_closest_scale(const SceneDev& sc, float* inst_scale, hipStream_t s) {

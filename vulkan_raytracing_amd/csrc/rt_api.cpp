@@ -2351,6 +2351,7 @@ enum class Walk {
   Flags,     // rt_intersect_device_flags: the flag-aware walk (MODE_QUERY_FLAGS) and k_hit_kind behind the attributes
   Hits,      // rt_intersect_device_hits: the max_hits nearest hits of every ray and their number
   Closest,   // rt_closest_point*: the nearest surface point (the per-instance scales are made first, in the workspace)
+  ClosestHits, // rt_closest_point*_hits: the max_hits nearest triangles of every point and their number (the same scales first)
   Overlap,   // rt_overlap_boxes*: the triangles that touch every box (the same scales first)
   Triangles, // rt_overlap_triangles*: the triangles that cut every query triangle (the same scales first; the fields of Overlap)
   Sweep,     // rt_sweep_spheres*: the first contact of every moving sphere (the same scales first)
@@ -2363,15 +2364,15 @@ struct Query {
   const void* records = nullptr;     // n ray, point, box, sweep or triangle records
   const void* ray_words = nullptr;   // Flags, Hits: n per-ray words, or none
   uint32_t query_word = 0;           // Flags, Hits: the call's ray flags | cull mask << 24
-  uint32_t cull_mask = 0;            // Closest, Overlap, Sweep, Inside
+  uint32_t cull_mask = 0;            // Closest, ClosestHits, Overlap, Sweep, Inside
   bool any_hit = false;              // Plain
   bool overlap_any = false;          // Overlap: RT_OVERLAP_ANY
-  uint32_t max_hits = 0;             // Hits: records per row of hits
+  uint32_t max_hits = 0;             // Hits, ClosestHits: records per row of hits
   uint32_t max_ids = 0;              // Overlap: entries per row of ids
   uint32_t n_dirs = 0;               // Inside
-  void* hits = nullptr;              // hit records (Hits: n rows; Overlap: none; Inside: the signed distances, or none)
+  void* hits = nullptr;              // hit records (Hits, ClosestHits: n rows; Overlap: none; Inside: the signed distances, or none)
   void* ids = nullptr;               // Overlap: n rows of (inst, prim)
-  void* counts = nullptr;            // Hits, Overlap: n counts; Inside: n * n_dirs crossing counts (optional)
+  void* counts = nullptr;            // Hits, ClosestHits, Overlap: n counts; Inside: n * n_dirs crossing counts (optional)
   void* words = nullptr;             // Inside: n vote words (null with hits: the workspace's)
   void* attr = nullptr;              // the hit attributes (optional)
   bool counting = false;             // the instrumented walk (Hits and Flags have none): its counts start from a zeroed counter block
@@ -2397,7 +2398,7 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q
   if (q.counting) HIP_TRY(c, hipMemsetAsync(c->d_q_counters, 0, CNT_WORDS * sizeof(uint32_t), s));
   const SceneDev sc = scene_dev(c);
   if (q.t0) HIP_TRY(c, hipEventRecord(q.t0, s));
-  if (closest || sweep || q.walk == Walk::Overlap || q.walk == Walk::Triangles) launch_closest_scale(sc, c->d_q_scale, s);
+  if (closest || sweep || q.walk == Walk::ClosestHits || q.walk == Walk::Overlap || q.walk == Walk::Triangles) launch_closest_scale(sc, c->d_q_scale, s);
   switch (q.walk) {
     case Walk::Plain: launch_query(sc, records, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, q.any_hit, q.counting, cfg, s); break;
     case Walk::Flags: launch_query_flags(sc, records, (const uint32_t*)q.ray_words, q.query_word, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, cfg, s); break;
@@ -2406,6 +2407,10 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q
                         c->d_q_counters, cfg, s);
       break;
     case Walk::Closest: launch_closest_point(sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s); break;
+    case Walk::ClosestHits:   // (with k_hit_attr and k_closest_hits_side over the rows for the attributes)
+      launch_closest_hits(sc, records, q.cull_mask, c->d_q_scale, n, q.max_hits, (HitRec*)q.hits, (float4*)q.attr, (uint32_t*)q.counts, c->d_q_ovf, c->d_q_counters,
+                          q.counting, cfg, s);
+      break;
     case Walk::Overlap:
       launch_overlap_boxes(sc, records, q.cull_mask, c->d_q_scale, q.overlap_any, q.max_ids, q.ids, (uint32_t*)q.counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
       break;
@@ -2419,7 +2424,7 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q
       break;
   }
   if (q.t1) HIP_TRY(c, hipEventRecord(q.t1, s));
-  if (q.attr && q.walk != Walk::Hits) {
+  if (q.attr && q.walk != Walk::Hits && q.walk != Walk::ClosestHits) {
     launch_hit_attr(sc, (const HitRec*)q.hits, (float4*)q.attr, n, s);
     if (flags) launch_hit_kind(sc, records, (const HitRec*)q.hits, (float4*)q.attr, n, s);
     if (closest) launch_closest_side(sc, records, (const HitRec*)q.hits, (float4*)q.attr, n, s);
@@ -2614,6 +2619,52 @@ int rt_closest_point(rt_ctx* c, size_t n, const float* points4, uint32_t cull_ma
   const size_t pt_bytes = n * 4 * sizeof(float), hit_bytes = n * sizeof(HitRec);
   Query q; q.walk = Walk::Closest; q.n = n; q.cull_mask = cull_mask; q.counting = counting != 0;
   return blocking_query(c, q, points4, pt_bytes, pt_bytes + hit_bytes, {{&Query::hits, pt_bytes, out, hit_bytes}}, stats);
+}
+
+namespace {
+// the argument rules rt_closest_point_device_hits and rt_closest_point_hits share (pointers aside)
+int closest_hits_arguments(rt_ctx* c, const std::string& name, size_t n, uint32_t cull_mask, uint32_t max_hits, const void* hits, const void* attr, const void* counts) {
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, "too many points for one call");
+  if (max_hits > 16u) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": max_hits must be 0..16");
+  if ((uint64_t)n * max_hits >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": n * max_hits must be below 0xFFFFFF00 (32-bit record indices)");
+  if (max_hits == 0u && (hits || attr || !counts))
+    return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": max_hits 0 counts only: the hits and attributes must be NULL, the counts non-NULL");
+  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": cull_mask is above 0xFF");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, name + " needs trace_variant 0");
+  return RT_OK;
+}
+}  // namespace
+
+// The K nearest triangles of every query point: rt_closest_point_device's checks and ordering with rt_intersect_device_hits' rows and
+// counts, then k_closest_scale and k_closest_hits over the caller's records (enqueue_query), k_hit_attr and k_closest_hits_side over
+// the rows for the attributes.
+int rt_closest_point_device_hits(rt_ctx* c, size_t n, const void* d_points4, uint32_t cull_mask, uint32_t max_hits, void* d_hits, void* d_attr, void* d_counts,
+                                 void* hip_stream) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const std::string name = "rt_closest_point_device_hits";
+  { int w = closest_hits_arguments(c, name, n, cull_mask, max_hits, d_hits, d_attr, d_counts); if (w) return w; }
+  if (n) {
+    if (!d_points4 || (max_hits && !d_hits)) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null point/hit pointers");
+    if (((uintptr_t)d_points4 & 15u) || ((uintptr_t)d_hits & 3u) || ((uintptr_t)d_attr & 15u) || ((uintptr_t)d_counts & 3u))
+      return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": points and attributes must be 16-byte aligned, hits and counts 4-byte aligned");
+    { int w = check_device_pointers(c, name, "points, hits, attributes and counts", {d_points4, d_hits, d_attr, d_counts}); if (w) return w; }
+  }
+  Query q; q.walk = Walk::ClosestHits; q.n = n; q.records = d_points4; q.cull_mask = cull_mask; q.max_hits = max_hits;
+  q.hits = d_hits; q.attr = d_attr; q.counts = d_counts;
+  return device_query(c, q, hip_stream);
+}
+
+// The blocking host form, as rt_closest_point is to rt_closest_point_device: the points (16 B each), then the counts, then the rows.
+int rt_closest_point_hits(rt_ctx* c, size_t n, const float* points4, uint32_t cull_mask, uint32_t max_hits, rt_hit* hits, uint32_t* counts, int counting,
+                          rt_stats* stats) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const std::string name = "rt_closest_point_hits";
+  { int w = closest_hits_arguments(c, name, n, cull_mask, max_hits, hits, nullptr, counts); if (w) return w; }
+  if (n && (!points4 || (max_hits && !hits))) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null point/hit pointers");
+  const size_t pt_bytes = n * 4 * sizeof(float), count_bytes = n * sizeof(uint32_t), hit_bytes = n * max_hits * sizeof(HitRec);
+  Query q; q.walk = Walk::ClosestHits; q.n = n; q.cull_mask = cull_mask; q.max_hits = max_hits; q.counting = counting != 0;
+  return blocking_query(c, q, points4, pt_bytes, pt_bytes + count_bytes + hit_bytes,
+                        {{&Query::counts, pt_bytes, counts, count_bytes}, {&Query::hits, pt_bytes + count_bytes, hits, hit_bytes}}, stats);
 }
 
 namespace {

@@ -202,6 +202,12 @@ void launch_closest_point(const SceneDev& sc, const float4* points, uint32_t cul
                           uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
 // the side of the reported triangle's plane every point lies on (0xFE front, 0xFF back, 0 miss) into word 7 of its rt_hit_attr (after launch_hit_attr)
 void launch_closest_side(const SceneDev& sc, const float4* points, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s);
+// rt_closest_point_device_hits: the k (0..16) nearest candidates of every point (launch_closest_point's records and candidates), sorted by
+// (d2, inst, prim), into hits (n * k records, point-major, t = sqrtf(d2); the rest of a row in the miss form), their number into counts
+// (optional: without it the walk prunes by the k-th entry's d2), and with attr (k >= 1) the rt_hit_attr of every record with its side
+// word (kernels_closest_hits.inc).  inst_scale, chunk cursor, counters (counting) and spill area as for launch_closest_point.
+void launch_closest_hits(const SceneDev& sc, const float4* points, uint32_t cull_mask, const float* inst_scale, uint32_t n, uint32_t k, HitRec* hits, float4* attr,
+                         uint32_t* counts, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
 // rt_overlap_boxes_device: the triangles that touch every query box (32 bytes: lo.xyz, w3, hi.xyz, w7) among the instances the cull mask
 // admits (kernels_overlap.inc): the k smallest (inst, prim) of each box into ids[n * k] (8 bytes each; k == 0: none), their number into
 // counts[n] (or null: the walk prunes); any: counts of 0 or 1, a box ends at its first candidate.  inst_scale as for launch_closest_point

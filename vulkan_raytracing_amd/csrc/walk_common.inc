@@ -1,5 +1,5 @@
 // walk_common.inc — included by kernels.hip before kernels_hits.inc (product and alt translation units alike).
-// The skeleton of a record-level walk (k_query_hits, k_closest_point, k_overlap_boxes, k_sweep_spheres, k_point_inside): one lane per
+// The skeleton of a record-level walk (k_query_hits, k_closest_point, k_closest_hits, k_overlap_boxes, k_sweep_spheres, k_point_inside): one lane per
 // record, the quantised BVH2 of the TLAS and, inside an instance, of its BLAS.  What every such walk does the same way lives here; its
 // node test, child order, leaf body, instance entry and exit, finish step, args struct and register budget stay in its own file.
 // The frame kernels and k_trace have a stack of their own (the fast_step row) and use none of this.

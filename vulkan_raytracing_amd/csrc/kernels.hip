@@ -436,6 +436,22 @@ __global__ __launch_bounds__(256) void k_cover(SceneDev sc, CoverViews views, ui
   const float* bx = sc.cover_boxes + 6u * (size_t)(I->cover_first + b);
   float x0 = 3e38f, x1 = -3e38f, y0 = 3e38f, y1 = -3e38f, az_min = 3e38f;
   bool all = false;
+  // Where the box stands relative to the view point is known only as well as binary32 holds world coordinates: the corner w below is
+  // rounded at the magnitude of w, and the walk this mask must not contradict moves the ray's origin into object space (w2o * cam + t',
+  // rounded at |w2o| |cam| + |t'| object units; o2w carries that back to world units: eo).  Both are a few 2^-24 of those magnitudes and
+  // do not shrink with the distance w - cam, so in front of a close-up far from the origin they are whole pixels.
+  float eo[3];
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    eo[i] = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      const float* r = I->w2o + 4 * j;
+      eo[i] += __builtin_fabsf(I->o2w[4 * i + j]) * (__builtin_fabsf(r[0] * a.cam[0]) + __builtin_fabsf(r[1] * a.cam[1]) + __builtin_fabsf(r[2] * a.cam[2]) + __builtin_fabsf(r[3]));
+    }
+    if (!(eo[i] < 3e38f)) eo[i] = 0.0f;   // (a record without a finite inverse: no ray enters it, rt_api.h)
+  }
+  float ex = 0.0f, ey = 0.0f;   // what those roundings can move a corner by, in pixels
 #pragma unroll
   for (int k = 0; k < 8; k++) {
     const F3 p = mk3(bx[(k & 1) ? 3 : 0], bx[(k & 2) ? 4 : 1], bx[(k & 4) ? 5 : 2]);
@@ -444,16 +460,26 @@ __global__ __launch_bounds__(256) void k_cover(SceneDev sc, CoverViews views, ui
     const float ax = a.inv[0] * v.x + a.inv[1] * v.y + a.inv[2] * v.z;
     const float ay = a.inv[3] * v.x + a.inv[4] * v.y + a.inv[5] * v.z;
     const float az = a.inv[6] * v.x + a.inv[7] * v.y + a.inv[8] * v.z;
-    if (!(az > 1e-20f)) { all = true; continue; }
+    const float c4 = 4.0f * 5.9604645e-8f;   // 4 x 2^-24
+    const float dx = c4 * (eo[0] + __builtin_fabsf(w.x) + __builtin_fabsf(a.cam[0])), dy = c4 * (eo[1] + __builtin_fabsf(w.y) + __builtin_fabsf(a.cam[1])),
+                dz = c4 * (eo[2] + __builtin_fabsf(w.z) + __builtin_fabsf(a.cam[2]));
+    const float ea = __builtin_fabsf(a.inv[0]) * dx + __builtin_fabsf(a.inv[1]) * dy + __builtin_fabsf(a.inv[2]) * dz;
+    const float eb = __builtin_fabsf(a.inv[3]) * dx + __builtin_fabsf(a.inv[4]) * dy + __builtin_fabsf(a.inv[5]) * dz;
+    const float ec = __builtin_fabsf(a.inv[6]) * dx + __builtin_fabsf(a.inv[7]) * dy + __builtin_fabsf(a.inv[8]) * dz;
+    if (!(az > 1e-20f) || !(az > 2.0f * ec)) { all = true; continue; }   // at, behind or not safely in front of the camera plane
     az_min = fminf(az_min, az);
     const float ux = a.kf * ax / az, uy = a.kf * ay / az;
     const float px = (ux + 1.0f) * 0.5f * (float)a.width, py = (1.0f - uy) * 0.5f * (float)a.height;
     if (!(__builtin_fabsf(px) < 1e9f) || !(__builtin_fabsf(py) < 1e9f)) { all = true; continue; }
     x0 = fminf(x0, px); x1 = fmaxf(x1, px); y0 = fminf(y0, py); y1 = fmaxf(y1, py);
+    // d(kf a / c) <= (kf da + |u| dc) / (c - dc)
+    ex = fmaxf(ex, 0.5f * (float)a.width * (a.kf * ea + __builtin_fabsf(ux) * ec) / (az - ec));
+    ey = fmaxf(ey, 0.5f * (float)a.height * (a.kf * eb + __builtin_fabsf(uy) * ec) / (az - ec));
   }
+  if (!(ex < 1e9f) || !(ey < 1e9f)) all = true;
   if (!all) {
-    // one pixel of margin on every side, and a relative one for the rounding of the projection
-    float mx = 1.0f + 1e-4f * (__builtin_fabsf(x0) + __builtin_fabsf(x1)), my = 1.0f + 1e-4f * (__builtin_fabsf(y0) + __builtin_fabsf(y1));
+    // one pixel of margin on every side, a relative one for the rounding of the projection, and what the world coordinates cannot resolve
+    float mx = 1.0f + 1e-4f * (__builtin_fabsf(x0) + __builtin_fabsf(x1)) + ex, my = 1.0f + 1e-4f * (__builtin_fabsf(y0) + __builtin_fabsf(y1)) + ey;
     if (a.apex_radius > 0.0f) {
       // rays that pass within apex_radius of the view point instead of through it (shadow rays at the light): a point of the box
       // at depth az is then seen up to apex_radius (1 + |u|) / (az - apex_radius) away in u, u = kf ax / az (orthonormal light bases)

@@ -186,7 +186,7 @@ int rt_build_blas(rt_ctx* ctx, int mesh);
  *     that is not finite — a singular matrix (a flattened body, a zero-filled slot), a scale below about 3e-39 whose inverse overflows
  *     binary32.  No ray ever hits it: frames, rt_intersect*, rt_intersect_device_flags / _hits, rt_point_inside*, the vote of
  *     rt_signed_distance_device, rt_shade_rays_device.  The world-space queries (rt_closest_point*, rt_sweep_spheres*,
- *     rt_overlap_boxes*, rt_overlap_triangles*) keep answering over the o2w image of its triangles, as their own sections say.
+ *     rt_overlap_boxes*, rt_overlap_triangles*, rt_closest_segment*) keep answering over the o2w image of its triangles, as their own sections say.
  *   FAR record: finite and below the limit (a translation of 1e30) is a VALID record.  Nothing is promised about hitting it (binary32
  *     has no resolution left out there, and the TLAS planes are 1e30 / 65530 apart); the rest of the scene answers bit for bit as
  *     without it, more slowly: the closest hit does not depend on the tree. */
@@ -632,6 +632,52 @@ int rt_sweep_spheres_device(rt_ctx* ctx, size_t n, const void* d_sweeps8, uint32
  * stats->ms_trace_closest and the node and packet sizes in stats->bvh_node_bytes / bvh_tri_bytes; every other field is 0. */
 int rt_sweep_spheres(rt_ctx* ctx, size_t n, const float* sweeps8_host, uint32_t cull_mask,
                      rt_hit* out_host, int counting, rt_stats* stats);
+
+/* Closest points of segments: for every record the nearest pair of a point of a line segment and a point of the scene's surface
+ * (PhysX's overlapCapsule and computePenetration, FCL's capsule distance): a capsule is a segment with a radius, so this is the
+ * clearance of a robot link, the penetration depth and direction of a character's capsule, the nearest surface point of a cloth or
+ * rope edge.
+ * Records: d_segs8 holds n records of 32 B (P0.x, P0.y, P0.z, r_max, P1.x, P1.y, P1.z, w7), 16-B aligned, memory of ctx's GPU: the
+ * closed world-space segment P0..P1 and the search radius r_max >= 0 (+inf allowed); word 7 is ignored.  P0 == P1 is valid (below).
+ * Candidates: every triangle of every instance with (mask & cull_mask) != 0.  Instance flags, opacity and facing play no part; void and
+ * non-invertible instance records behave as they do for rt_closest_point_device.
+ * d_hits: n rt_hit, 4-B aligned.  Record i is the candidate with the smallest key (d2, inst, prim) among those whose canonical d2 below
+ * is not NaN and is <= r_max * r_max (the product rounded to binary32; inclusive, as for closest points): t = sqrtf(d2), u and v the
+ * barycentrics (of vertices B and C) of the triangle's point of the nearest pair, prim and inst the triangle.
+ * d_params (optional): n floats, 4-B aligned: s in [0, 1], the segment's point of the nearest pair being P0 + s (P1 - P0); 0 on a miss.
+ * No candidate: the miss record t = r_max as given (bit pattern kept), u = v = 0, prim = inst = -1, s = 0; the same for a non-finite
+ * endpoint coordinate, a negative or a NaN r_max.  t is never NaN unless r_max was.
+ * Canonical d2 (DESIGN.md §5 "Closest points of segments" has every operation in order): binary32, world space, nothing fused except
+ * inside dot3 / cross3 / xform_point / xform_vec, IEEE divisions, clamp(x) = fminf(fmaxf(x, 0), 1) with NaN and -0 giving
+ * +0.  a = xform_point(I.o2w, v0), ab = xform_vec(I.o2w, e1), ac = xform_vec(I.o2w, e2), d = P1 - P0.  Every feature proposes a pair of
+ * a segment point and a triangle point and its d2 is the distance computed between the two, never an assumed 0: (1) rt_closest_point_device's
+ * sequence for p = P0, s = 0; (2) the same for p = P1, s = 1; (3) only when the endpoints lie strictly on opposite sides of the
+ * triangle's plane (h0 = dot3(n, P0 - a), h1 = dot3(n, P1 - a), n = cross3(ab, ac)): the same for the crossing X = P0 + s d,
+ * s = clamp(h0 / (h0 - h1)); (4) the edges AB, AC, BC by Ericson, Real-Time Collision Detection §5.1.9 with exact-zero tests in place of
+ * its epsilons.  A later feature replaces an earlier one only when its d2 is strictly smaller; a feature with a NaN d2 is skipped, a
+ * triangle all of whose features are NaN is never a candidate.  The value depends on the record, the instance record and the packet
+ * only, never on the tree.
+ * Points: a record whose endpoints compare equal in all three components is answered by feature (1) alone: its rt_hit is
+ * rt_closest_point_device's record for (P0, r_max) byte for byte, and s = 0.
+ * Pierced triangles: a triangle the segment passes through reports the rounding residue of feature (3), a t around 2^-24 of the scene's
+ * magnitude, not an exact 0: compare t with a radius or a tolerance.  Among several pierced triangles the key decides, not the order
+ * along the segment; the first triangle along a segment is a ray query (rt_intersect_device).
+ * d_attr (optional): n rt_hit_attr, 16-B aligned: what rt_closest_point_device gives for (inst, prim, u, v) — P the surface point, N the
+ * interpolated shading normal, objectIndex; a miss zeros and -1.  `reserved` is the side of the triangle's plane the segment's point
+ * P0 + s d lies on (per component one product and one sum), by rt_closest_point_device's rule (FLIP_FACING included), 0 on a miss.
+ * Stream ordering without host synchronisation, the TLAS and scene of the call, the query workspace, queries and shading calls of one
+ * context one after another, RT_ERR_NOT_READY and n == 0 (nothing is enqueued): as for rt_closest_point_device.
+ * RT_ERR_INVALID_ARGUMENT: a NULL pointer (d_attr and d_params aside), a misaligned pointer, a pointer that is not memory of ctx's GPU,
+ * n >= 0xFFFFFF00, cull_mask > 0xFF, trace_variant != 0. */
+int rt_closest_segment_device(rt_ctx* ctx, size_t n, const void* d_segs8, uint32_t cull_mask,
+                              void* d_hits, void* d_attr, void* d_params, void* hip_stream);
+/* The blocking host form, as rt_closest_point is to rt_closest_point_device: the records are copied to the device, walked on the
+ * context's stream (same workspace and ordering) and the hits and, with params_host, the parameters copied back.  counting != 0 runs
+ * the instrumented walk and fills stats->node_visits and stats->tri_tests; stats may be NULL.  As rt_closest_point does, the call also
+ * reports the walk's device time in stats->ms_trace_closest and the node and packet sizes in stats->bvh_node_bytes / bvh_tri_bytes;
+ * every other field is 0. */
+int rt_closest_segment(rt_ctx* ctx, size_t n, const float* segs8_host, uint32_t cull_mask,
+                       rt_hit* out_host, float* params_host, int counting, rt_stats* stats);
 
 /* Inside / outside: for every point, is it enclosed by the scene's surfaces (Open3D's compute_occupancy and compute_signed_distance),
  * for signed distance fields, penetration tests, occupancy and voxel filling.  The answer is a vote over the crossing parities of a few

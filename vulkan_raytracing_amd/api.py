@@ -74,7 +74,7 @@ INSIDE_DIRS = ((0.36, 0.48, 0.8), (-0.8, 0.36, -0.48), (0.48, -0.8, -0.36), (-0.
 
 EXPORTS = ["rt_create", "rt_create_frame_slot", "rt_destroy", "rt_upload_geometry", "rt_build_blas", "rt_set_instances", "rt_set_instances_device", "rt_refit_blas_device", "rt_set_materials", "rt_set_instance_types", "rt_set_uniforms", "rt_set_skybox",
            "rt_trace", "rt_trace_async", "rt_trace_wait", "rt_trace_shard", "rt_set_batch", "rt_trace_shard_batch", "rt_assemble_shards", "rt_shard_rows", "rt_synchronize", "rt_get_stats", "rt_set_timing", "rt_intersect",
-           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_closest_point_device_hits", "rt_closest_point_hits", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_overlap_triangles_device", "rt_overlap_triangles", "rt_sweep_spheres_device", "rt_sweep_spheres", "rt_point_inside_device", "rt_point_inside", "rt_signed_distance_device", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_host_blas", "rt_debug_snapshot", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
+           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_closest_point_device_hits", "rt_closest_point_hits", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_overlap_triangles_device", "rt_overlap_triangles", "rt_sweep_spheres_device", "rt_sweep_spheres", "rt_closest_segment_device", "rt_closest_segment", "rt_point_inside_device", "rt_point_inside", "rt_signed_distance_device", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_host_blas", "rt_debug_snapshot", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
 
 _LIBS = {}
 
@@ -125,6 +125,8 @@ def lib(variant=None):
         L.rt_closest_point_hits.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_int, C.POINTER(RtStats)]
         L.rt_sweep_spheres_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, vp, vp]
         L.rt_sweep_spheres.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, C.c_int, C.POINTER(RtStats)]
+        L.rt_closest_segment_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, vp, vp, vp]
+        L.rt_closest_segment.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, vp, C.c_int, C.POINTER(RtStats)]
         L.rt_point_inside_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
         L.rt_point_inside.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_int, C.POINTER(RtStats)]
         L.rt_signed_distance_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
@@ -453,6 +455,50 @@ class RtContext:
         st = RtStats()
         self._chk(self.L.rt_sweep_spheres(self.h, len(sweeps8), _p(sweeps8), int(cull_mask) & 0xFFFFFFFF, _p(out), int(counting), C.byref(st)), "rt_sweep_spheres")
         return out, st
+
+    def closest_segment_device(self, segments, cull_mask=0xFF, attributes=False, params=False, stream=None, out=None):
+        """rt_closest_segment_device: the nearest pair of every segment and the scene's surface.  `segments` is a contiguous float32 torch
+        tensor (n, 8) on this context's GPU (P0.xyz, r_max, P1.xyz, ignored per row: the closed world-space segment P0..P1 and a search
+        radius, inf allowed; capsule_records packs it), read in the order of `stream` like intersect_device's rays.  Returns a RayQuery:
+        t the distance, u / v the barycentrics of the triangle's point of the nearest pair, prim / inst the triangle (a miss: t = r_max,
+        prim = inst = -1); with attributes=True position is that surface point, normal the shading normal there and hit_kind the side of
+        the triangle's plane the segment's point lies on; with params=True its `s` is a float32 (n,) tensor, the segment's point of the
+        pair being P0 + s (P1 - P0) (0 on a miss), else None.  out = (hits, attr) or (hits, attr, s) reuses buffers.  A pierced
+        triangle reports a rounding residue, not an exact 0.  See include/rt_api.h."""
+        import torch
+        self._check_rays(segments, "closest_segment_device", 8, "segment")
+        n = segments.shape[0]
+        s = None
+        if out is not None and len(out) == 3:
+            s, out = out[2], tuple(out[:2])
+            if params and (s is None or s.dtype != torch.float32 or tuple(s.shape) != (n,) or not s.is_contiguous() or s.device != segments.device):
+                raise ValueError("out s must be a contiguous float32 (n,) tensor on the segments' device")
+        if not params:
+            s = None
+        elif s is None:
+            s = torch.empty((n,), dtype=torch.float32, device=segments.device)
+
+        def call(run, hits, attr):
+            if s is not None:
+                s.record_stream(run)
+            return self.L.rt_closest_segment_device(self.h, n, C.c_void_p(segments.data_ptr()), int(cull_mask) & 0xFFFFFFFF, C.c_void_p(hits.data_ptr()),
+                                                    C.c_void_p(attr.data_ptr()) if attr is not None else None,
+                                                    C.c_void_p(s.data_ptr()) if s is not None else None, C.c_void_p(run.cuda_stream))
+        hits, attr = self._device_query(segments, attributes, stream, out, (), call, "rt_closest_segment_device")
+        res = RayQuery(hits, attr, hit_kind=True)
+        res.s = s
+        return res
+
+    def closest_segment(self, segs8, cull_mask=0xFF, params=False, counting=False):
+        """rt_closest_segment: the blocking host form -> (HIT_DTYPE records, RtStats; with counting its node_visits / tri_tests are
+        filled), or with params=True (records, s float32 (n,), RtStats)"""
+        segs8 = np.ascontiguousarray(segs8, np.float32).reshape(-1, 8)
+        out = np.zeros(len(segs8), HIT_DTYPE)
+        s = np.zeros(len(segs8), np.float32) if params else None
+        st = RtStats()
+        self._chk(self.L.rt_closest_segment(self.h, len(segs8), _p(segs8), int(cull_mask) & 0xFFFFFFFF, _p(out), _p(s) if s is not None else None,
+                                            int(counting), C.byref(st)), "rt_closest_segment")
+        return (out, s, st) if params else (out, st)
 
     def point_inside_device(self, points, n_dirs=3, cull_mask=0xFF, counts=False, stream=None, out=None):
         """rt_point_inside_device: is every point enclosed by the scene's surfaces?  `points` is closest_point_device's tensor, a contiguous
@@ -917,6 +963,30 @@ def triangle_records(vertices, faces):
     rec = np.zeros((len(f), 3, 4), np.float32)
     rec[:, :, :3] = np.asarray(vertices, np.float32).reshape(-1, 3)[f]
     return rec.reshape(-1, 12)
+
+
+def capsule_records(p0, p1, r_max):
+    """the (n, 8) float32 records of closest_segment_device / closest_segment (P0.xyz, r_max, P1.xyz, 0 per row) of the segments from
+    `p0` (n, 3) to `p1` (n, 3) with the search radii `r_max` ((n,) or a scalar; for a capsule, at least its radius).  torch tensors stay
+    on their device; anything else goes through numpy."""
+    try:
+        import torch
+        is_t = isinstance(p0, torch.Tensor)
+    except ImportError:
+        is_t = False
+    if is_t:
+        a = p0.reshape(-1, 3).to(torch.float32)
+        rec = torch.zeros((a.shape[0], 8), dtype=torch.float32, device=a.device)
+        rec[:, 0:3] = a
+        rec[:, 4:7] = torch.as_tensor(p1, device=a.device).reshape(-1, 3).to(torch.float32)
+        rec[:, 3] = torch.as_tensor(r_max, device=a.device).to(torch.float32)
+        return rec
+    a = np.asarray(p0, np.float32).reshape(-1, 3)
+    rec = np.zeros((len(a), 8), np.float32)
+    rec[:, 0:3] = a
+    rec[:, 4:7] = np.asarray(p1, np.float32).reshape(-1, 3)
+    rec[:, 3] = np.asarray(r_max, np.float32)
+    return rec
 
 
 def check_builders(verts6, idx):

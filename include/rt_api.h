@@ -186,7 +186,7 @@ int rt_build_blas(rt_ctx* ctx, int mesh);
  *     that is not finite — a singular matrix (a flattened body, a zero-filled slot), a scale below about 3e-39 whose inverse overflows
  *     binary32.  No ray ever hits it: frames, rt_intersect*, rt_intersect_device_flags / _hits, rt_point_inside*, the vote of
  *     rt_signed_distance_device, rt_shade_rays_device.  The world-space queries (rt_closest_point*, rt_sweep_spheres*,
- *     rt_overlap_boxes*, rt_overlap_triangles*, rt_closest_segment*) keep answering over the o2w image of its triangles, as their own sections say.
+ *     rt_overlap_boxes*, rt_overlap_triangles*, rt_closest_segment*, rt_closest_triangle*) keep answering over the o2w image of its triangles, as their own sections say.
  *   FAR record: finite and below the limit (a translation of 1e30) is a VALID record.  Nothing is promised about hitting it (binary32
  *     has no resolution left out there, and the TLAS planes are 1e30 / 65530 apart); the rest of the scene answers bit for bit as
  *     without it, more slowly: the closest hit does not depend on the tree. */
@@ -678,6 +678,60 @@ int rt_closest_segment_device(rt_ctx* ctx, size_t n, const void* d_segs8, uint32
  * every other field is 0. */
 int rt_closest_segment(rt_ctx* ctx, size_t n, const float* segs8_host, uint32_t cull_mask,
                        rt_hit* out_host, float* params_host, int counting, rt_stats* stats);
+
+/* Closest points of triangles: for every record the nearest pair of a point of a query triangle and a point of the scene's surface
+ * (FCL's distance beside collide, PQP's TriDist, the mesh-mesh closest points of Bullet and PhysX): the distance half of
+ * rt_overlap_triangles_device, for geometry that lives in device memory: the clearance of a tool or link mesh, cloth-to-body proximity
+ * per face (its vertex-face and edge-edge pairs alike), the minimum separation of a whole mesh as the minimum over its records.
+ * Records: d_tris12 holds n records of 48 B (P0.xyz, w3, P1.xyz, w7, P2.xyz, w11), 16-B aligned, memory of ctx's GPU:
+ * rt_overlap_triangles_device's record, a closed world-space triangle.  Word 3 is the search radius r_max >= 0 (+inf allowed); words 7
+ * and 11 are ignored.  One buffer feeds both triangle queries: the overlap query ignores word 3.  Degenerate triangles (a segment, a
+ * point) are valid (below).
+ * Candidates: every triangle of every instance with (mask & cull_mask) != 0.  Instance flags, opacity and facing play no part; void and
+ * non-invertible instance records behave as they do for rt_closest_point_device.
+ * d_hits: n rt_hit, 4-B aligned.  Record i is the candidate with the smallest key (d2, inst, prim) among those whose canonical d2 below
+ * is not NaN and is <= r_max * r_max (the product rounded to binary32; inclusive, as for closest points): t = sqrtf(d2), u and v the
+ * barycentrics (of vertices B and C) of the scene triangle's point of the nearest pair, prim and inst the scene triangle.
+ * d_params (optional): n x 2 floats, 4-B aligned: (qu, qv), the barycentrics of the query's point of the nearest pair, which is
+ * P0 + qu (P1 - P0) + qv (P2 - P0); both are in [0, 1] and never carry a sign bit; 0, 0 on a miss.
+ * No candidate: the miss record t = r_max as given (bit pattern kept), u = v = 0, prim = inst = -1, qu = qv = 0; the same for a
+ * non-finite vertex coordinate, a negative or a NaN r_max.  t is never NaN unless r_max was.
+ * Canonical d2 (DESIGN.md §5 "Closest points of triangles" has every operation in order): binary32, world space, nothing fused except
+ * inside dot3 / cross3 / xform_point / xform_vec, IEEE divisions, clamp as for rt_closest_segment_device.
+ * a = xform_point(I.o2w, v0), ab = xform_vec(I.o2w, e1), ac = xform_vec(I.o2w, e2), b = a + ab, c = a + ac; g0 = P1 - P0, g2 = P2 - P0.
+ * Every feature proposes a pair of a query point and a scene point and its d2 is the distance computed between the two, never an assumed
+ * 0.  In this order: (1) rt_closest_point_device's sequence for p = P0, P1, P2, (qu, qv) = (0, 0), (1, 0), (0, 1); (2) for the query's
+ * edges (P0, P1), (P1, P2), (P2, P0), feature (3) of rt_closest_segment_device (only when the ends lie strictly on opposite sides of
+ * the scene triangle's plane: the same sequence for the crossing X = Pi + s (Pj - Pi)), (qu, qv) = (s, 0), (1 - s, s), (0, 1 - s);
+ * (3) for each of those edges in turn, feature (4) of rt_closest_segment_device against AB, AC, BC, nine pairs, (qu, qv) from s as in
+ * (2); (4) the same point sequence for V = a, b, c against the query triangle (P0, g0, g2), (u, v) = (0, 0), (1, 0), (0, 1), (qu, qv) the
+ * clamp of what it returns; (5) the form of (2) with the roles exchanged: normal cross3(g0, g2), heights from P0, the scene's edges
+ * (a, b), (a, c), (b, c) as differences of those points, the crossing against (P0, g0, g2); (u, v) = (s, 0), (0, s), (1 - s, s), (qu, qv)
+ * as in (4).  A later feature replaces an earlier one only when its d2 is strictly smaller; a feature with a NaN d2 is skipped, a
+ * triangle all of whose features are NaN is never a candidate.  The value depends on the record, the instance record and the packet
+ * only, never on the tree.
+ * Points: a record with P0 == P1 == P2 in all components is answered by feature (1) for P0 alone: its rt_hit is
+ * rt_closest_point_device's record for (P0, r_max) byte for byte, and qu = qv = 0.
+ * Edges: features (1) to (3) are the union of rt_closest_segment_device's features for the three records (Pi, r_max, Pj) of the edges
+ * above, so d2 never exceeds the d2 of any of the three and t <= t_edge holds exactly; when the winning feature is one of (1) to (3) the
+ * record equals the best of the three edge records in (t, inst, prim, u, v).  A record with two equal vertices is not promised the
+ * bytes of a segment record.
+ * Pierced and touching triangles: a scene triangle that cuts or touches the query triangle reports the rounding residue of a crossing
+ * feature, a t around 2^-24 of the scene's magnitude, not an exact 0: compare t with a tolerance, or ask rt_overlap_triangles_device.
+ * Among several the key decides.
+ * d_attr (optional): n rt_hit_attr, 16-B aligned: what rt_closest_point_device gives for (inst, prim, u, v) — P the surface point, N the
+ * interpolated shading normal, objectIndex; a miss zeros and -1.  `reserved` is the side of the scene triangle's plane the query's
+ * point (P0 + qu g0) + qv g2 lies on (per component two products and two sums in that order), by rt_closest_point_device's rule
+ * (FLIP_FACING included), 0 on a miss.
+ * Stream ordering without host synchronisation, the TLAS and scene of the call, the query workspace, queries and shading calls of one
+ * context one after another, RT_ERR_NOT_READY and n == 0 (nothing is enqueued): as for rt_closest_point_device.
+ * RT_ERR_INVALID_ARGUMENT: a NULL pointer (d_attr and d_params aside), a misaligned pointer, a pointer that is not memory of ctx's GPU,
+ * n >= 0xFFFFFF00, cull_mask > 0xFF, trace_variant != 0. */
+int rt_closest_triangle_device(rt_ctx* ctx, size_t n, const void* d_tris12, uint32_t cull_mask,
+                               void* d_hits, void* d_attr, void* d_params, void* hip_stream);
+/* The blocking host form, as rt_closest_segment is to rt_closest_segment_device; params_host, when given, takes n x 2 floats. */
+int rt_closest_triangle(rt_ctx* ctx, size_t n, const float* tris12_host, uint32_t cull_mask,
+                        rt_hit* out_host, float* params_host, int counting, rt_stats* stats);
 
 /* Inside / outside: for every point, is it enclosed by the scene's surfaces (Open3D's compute_occupancy and compute_signed_distance),
  * for signed distance fields, penetration tests, occupancy and voxel filling.  The answer is a vote over the crossing parities of a few

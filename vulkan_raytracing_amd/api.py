@@ -74,7 +74,7 @@ INSIDE_DIRS = ((0.36, 0.48, 0.8), (-0.8, 0.36, -0.48), (0.48, -0.8, -0.36), (-0.
 
 EXPORTS = ["rt_create", "rt_create_frame_slot", "rt_destroy", "rt_upload_geometry", "rt_build_blas", "rt_set_instances", "rt_set_instances_device", "rt_refit_blas_device", "rt_set_materials", "rt_set_instance_types", "rt_set_uniforms", "rt_set_skybox",
            "rt_trace", "rt_trace_async", "rt_trace_wait", "rt_trace_shard", "rt_set_batch", "rt_trace_shard_batch", "rt_assemble_shards", "rt_shard_rows", "rt_synchronize", "rt_get_stats", "rt_set_timing", "rt_intersect",
-           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_closest_point_device_hits", "rt_closest_point_hits", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_overlap_triangles_device", "rt_overlap_triangles", "rt_sweep_spheres_device", "rt_sweep_spheres", "rt_closest_segment_device", "rt_closest_segment", "rt_point_inside_device", "rt_point_inside", "rt_signed_distance_device", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_host_blas", "rt_debug_snapshot", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
+           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_closest_point_device_hits", "rt_closest_point_hits", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_overlap_triangles_device", "rt_overlap_triangles", "rt_sweep_spheres_device", "rt_sweep_spheres", "rt_closest_segment_device", "rt_closest_segment", "rt_closest_triangle_device", "rt_closest_triangle", "rt_point_inside_device", "rt_point_inside", "rt_signed_distance_device", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_host_blas", "rt_debug_snapshot", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
 
 _LIBS = {}
 
@@ -127,6 +127,8 @@ def lib(variant=None):
         L.rt_sweep_spheres.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, C.c_int, C.POINTER(RtStats)]
         L.rt_closest_segment_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, vp, vp, vp]
         L.rt_closest_segment.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, vp, C.c_int, C.POINTER(RtStats)]
+        L.rt_closest_triangle_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, vp, vp, vp]
+        L.rt_closest_triangle.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, vp, C.c_int, C.POINTER(RtStats)]
         L.rt_point_inside_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
         L.rt_point_inside.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_int, C.POINTER(RtStats)]
         L.rt_signed_distance_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
@@ -500,6 +502,51 @@ class RtContext:
                                             int(counting), C.byref(st)), "rt_closest_segment")
         return (out, s, st) if params else (out, st)
 
+    def closest_triangle_device(self, tris, cull_mask=0xFF, attributes=False, params=False, stream=None, out=None):
+        """rt_closest_triangle_device: the nearest pair of every query triangle and the scene's surface.  `tris` is
+        overlap_triangles_device's tensor, a contiguous float32 (n, 12) on this context's GPU (P0.xyz, r_max, P1.xyz, ignored, P2.xyz,
+        ignored per row: a closed world-space triangle and a search radius, inf allowed; triangle_records(..., r_max=) packs it), read
+        in the order of `stream` like intersect_device's rays.  Returns a RayQuery: t the distance, u / v the barycentrics of the scene
+        triangle's point of the nearest pair, prim / inst the scene triangle (a miss: t = r_max, prim = inst = -1); with
+        attributes=True position is that surface point, normal the shading normal there and hit_kind the side of the scene triangle's
+        plane the query's point lies on; with params=True its `quv` is a float32 (n, 2) tensor, the query's point of the pair being
+        P0 + qu (P1 - P0) + qv (P2 - P0) (0, 0 on a miss), else None.  out = (hits, attr) or (hits, attr, quv) reuses buffers.  A
+        scene triangle that cuts the query reports a rounding residue, not an exact 0.  See include/rt_api.h."""
+        import torch
+        self._check_rays(tris, "closest_triangle_device", 12, "triangle")
+        n = tris.shape[0]
+        quv = None
+        if out is not None and len(out) == 3:
+            quv, out = out[2], tuple(out[:2])
+            if params and (quv is None or quv.dtype != torch.float32 or tuple(quv.shape) != (n, 2) or not quv.is_contiguous() or quv.device != tris.device):
+                raise ValueError("out quv must be a contiguous float32 (n, 2) tensor on the triangles' device")
+        if not params:
+            quv = None
+        elif quv is None:
+            quv = torch.empty((n, 2), dtype=torch.float32, device=tris.device)
+
+        def call(run, hits, attr):
+            if quv is not None:
+                quv.record_stream(run)
+            return self.L.rt_closest_triangle_device(self.h, n, C.c_void_p(tris.data_ptr()), int(cull_mask) & 0xFFFFFFFF, C.c_void_p(hits.data_ptr()),
+                                                     C.c_void_p(attr.data_ptr()) if attr is not None else None,
+                                                     C.c_void_p(quv.data_ptr()) if quv is not None else None, C.c_void_p(run.cuda_stream))
+        hits, attr = self._device_query(tris, attributes, stream, out, (), call, "rt_closest_triangle_device", cols=12, checked=True)
+        res = RayQuery(hits, attr, hit_kind=True)
+        res.quv = quv
+        return res
+
+    def closest_triangle(self, tris12, cull_mask=0xFF, params=False, counting=False):
+        """rt_closest_triangle: the blocking host form -> (HIT_DTYPE records, RtStats; with counting its node_visits / tri_tests are
+        filled), or with params=True (records, (qu, qv) float32 (n, 2), RtStats)"""
+        tris12 = np.ascontiguousarray(tris12, np.float32).reshape(-1, 12)
+        out = np.zeros(len(tris12), HIT_DTYPE)
+        quv = np.zeros((len(tris12), 2), np.float32) if params else None
+        st = RtStats()
+        self._chk(self.L.rt_closest_triangle(self.h, len(tris12), _p(tris12), int(cull_mask) & 0xFFFFFFFF, _p(out), _p(quv) if quv is not None else None,
+                                             int(counting), C.byref(st)), "rt_closest_triangle")
+        return (out, quv, st) if params else (out, st)
+
     def point_inside_device(self, points, n_dirs=3, cull_mask=0xFF, counts=False, stream=None, out=None):
         """rt_point_inside_device: is every point enclosed by the scene's surfaces?  `points` is closest_point_device's tensor, a contiguous
         float32 (n, 4) on this context's GPU (x, y, z, ignored per row), read in the order of `stream` like intersect_device's rays.  The
@@ -828,10 +875,12 @@ class RtContext:
         if run is not stream:
             stream.wait_stream(run)
 
-    def _device_query(self, rays, attributes, stream, out, inputs, call, name, cols=8):
-        """the common part of intersect_device*: checks, output buffers, the null-stream detour; call(run_stream, hits, attr) -> status"""
+    def _device_query(self, rays, attributes, stream, out, inputs, call, name, cols=8, checked=False):
+        """the common part of intersect_device*: checks (unless the caller has run _check_rays itself: checked=True), output buffers, the
+        null-stream detour; call(run_stream, hits, attr) -> status"""
         import torch
-        self._check_rays(rays, "closest_point_device" if cols == 4 else "intersect_device", cols, "point" if cols == 4 else "ray")
+        if not checked:
+            self._check_rays(rays, "closest_point_device" if cols == 4 else "intersect_device", cols, "point" if cols == 4 else "ray")
         n = rays.shape[0]
         cur = torch.cuda.current_stream(rays.device)
         if stream is None:
@@ -945,10 +994,11 @@ class BoxOverlaps:
                 self.ids.cpu().numpy() if self.ids is not None else None)
 
 
-def triangle_records(vertices, faces):
-    """the (nf, 12) float32 records of overlap_triangles_device / overlap_triangles (P0.xyz, 0, P1.xyz, 0, P2.xyz, 0 per row) of the
-    triangles `faces` (nf, 3) indexes in `vertices` (nv, 3).  torch tensors stay on their device (torch indexing, no host copy); anything
-    else goes through numpy."""
+def triangle_records(vertices, faces, r_max=0.0):
+    """the (nf, 12) float32 records of overlap_triangles_device / overlap_triangles and closest_triangle_device / closest_triangle
+    (P0.xyz, r_max, P1.xyz, 0, P2.xyz, 0 per row) of the triangles `faces` (nf, 3) indexes in `vertices` (nv, 3).  `r_max` (a scalar or
+    (nf,)) is the search radius of the closest-triangle query; the overlap query ignores it.  torch tensors stay on their device (torch
+    indexing, no host copy); anything else goes through numpy."""
     try:
         import torch
         is_t = isinstance(vertices, torch.Tensor)
@@ -958,10 +1008,12 @@ def triangle_records(vertices, faces):
         f = torch.as_tensor(faces, device=vertices.device).reshape(-1, 3).long()
         rec = torch.zeros((f.shape[0], 3, 4), dtype=torch.float32, device=vertices.device)
         rec[:, :, :3] = vertices.reshape(-1, 3).to(torch.float32)[f]
+        rec[:, 0, 3] = torch.as_tensor(r_max, device=vertices.device).to(torch.float32)
         return rec.reshape(-1, 12)
     f = np.asarray(faces.cpu() if hasattr(faces, "cpu") else faces).reshape(-1, 3).astype(np.int64)
     rec = np.zeros((len(f), 3, 4), np.float32)
     rec[:, :, :3] = np.asarray(vertices, np.float32).reshape(-1, 3)[f]
+    rec[:, 0, 3] = np.asarray(r_max.cpu() if hasattr(r_max, "cpu") else r_max, np.float32)
     return rec.reshape(-1, 12)
 
 

@@ -2407,6 +2407,8 @@ void launch_resolve_points(const float4* sample_color, float4* out, uint32_t n_p
 
 #include "kernels_segment.inc"   // k_closest_segment, k_segment_side: the nearest surface point of every segment (rt_closest_segment_device)
 
+#include "kernels_triangle.inc"   // k_closest_triangle, k_triangle_side: the nearest pair of every query triangle and the surface (rt_closest_triangle_device)
+
 int tail_blocks_per_cu() {
   // the smallest over the instantiations: any of them may be the one in flight (counting; 4-ary records in the alt build)
   int n = 1 << 30, v = 0;

@@ -302,8 +302,9 @@ struct rt_ctx {
   size_t q_ovf_alloc = 0;          // int32 entries of d_q_ovf
   float* d_q_scale = nullptr;      // rt_closest_point*: 1 + n_inst floats of launch_closest_scale, part of the query workspace
   size_t q_scale_alloc = 0;        // floats of d_q_scale
-  uint32_t* d_q_words = nullptr;   // rt_signed_distance_device without d_inside: the vote words; rt_closest_segment_device with d_attr and without
-                                   // d_params: the parameters k_segment_side reads; part of the query workspace
+  uint32_t* d_q_words = nullptr;   // rt_signed_distance_device without d_inside: the vote words; rt_closest_segment_device and
+                                   // rt_closest_triangle_device with d_attr and without d_params: the parameters k_segment_side (one per
+                                   // record) and k_triangle_side (two) read; part of the query workspace
   size_t q_words_alloc = 0;        // words of d_q_words
   hipEvent_t ev_query[2] = {nullptr, nullptr};
   bool ev_query_valid[2] = {false, false};
@@ -2357,6 +2358,7 @@ enum class Walk {
   Triangles, // rt_overlap_triangles*: the triangles that cut every query triangle (the same scales first; the fields of Overlap)
   Sweep,     // rt_sweep_spheres*: the first contact of every moving sphere (the same scales first)
   Segment,   // rt_closest_segment*: the nearest surface point of every segment and its parameter (the same scales first)
+  Triangle,  // rt_closest_triangle*: the nearest pair of every query triangle and the surface, and its (qu, qv) (the same scales first)
   Inside     // rt_point_inside*: the inside / outside vote; with hits, rt_signed_distance_device: the closest-point walk into hits (and
              // attr) first, the vote with the counter block's cursor initialised again, then the sign pass over hits
 };
@@ -2366,7 +2368,7 @@ struct Query {
   const void* records = nullptr;     // n ray, point, box, sweep or triangle records
   const void* ray_words = nullptr;   // Flags, Hits: n per-ray words, or none
   uint32_t query_word = 0;           // Flags, Hits: the call's ray flags | cull mask << 24
-  uint32_t cull_mask = 0;            // Closest, ClosestHits, Overlap, Sweep, Segment, Inside
+  uint32_t cull_mask = 0;            // Closest, ClosestHits, Overlap, Sweep, Segment, Triangle, Inside
   bool any_hit = false;              // Plain
   bool overlap_any = false;          // Overlap: RT_OVERLAP_ANY
   uint32_t max_hits = 0;             // Hits, ClosestHits: records per row of hits
@@ -2376,33 +2378,35 @@ struct Query {
   void* ids = nullptr;               // Overlap: n rows of (inst, prim)
   void* counts = nullptr;            // Hits, ClosestHits, Overlap: n counts; Inside: n * n_dirs crossing counts (optional)
   void* words = nullptr;             // Inside: n vote words (null with hits: the workspace's)
-  void* params = nullptr;            // Segment: n parameters s (optional; null with attr: the workspace's words hold them)
+  void* params = nullptr;            // Segment: n parameters s; Triangle: n pairs (qu, qv) (optional; null with attr: the workspace's words hold them)
   void* attr = nullptr;              // the hit attributes (optional)
   bool counting = false;             // the instrumented walk (Hits and Flags have none): its counts start from a zeroed counter block
   hipEvent_t t0 = nullptr, t1 = nullptr;   // recorded around the walk (optional)
 };
 int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q) {
   const bool flags = q.walk == Walk::Flags, sweep = q.walk == Walk::Sweep, inside = q.walk == Walk::Inside, segment = q.walk == Walk::Segment;
+  const bool triangle = q.walk == Walk::Triangle;
   const bool closest = q.walk == Walk::Closest || (inside && q.hits);
   const uint32_t n = (uint32_t)q.n;
   const float4* const records = (const float4*)q.records;
   { int r = query_workspace(c, s); if (r) return r; }
   uint32_t* words = (uint32_t*)q.words;
-  if (segment) words = (uint32_t*)q.params;
-  if ((inside && !words) || (segment && !words && q.attr)) {   // (signed distance without d_inside; segment attributes without d_params)
-    if (q.n > c->q_words_alloc) {
+  if (segment || triangle) words = (uint32_t*)q.params;
+  if ((inside && !words) || ((segment || triangle) && !words && q.attr)) {   // (signed distance without d_inside; segment and triangle attributes without d_params)
+    const size_t need = triangle ? 2 * q.n : q.n;
+    if (need > c->q_words_alloc) {
       { int w = wait_queries(c, c); if (w) return w; }
       if (c->d_q_words) HIP_TRY(c, hipFree(c->d_q_words));
       c->d_q_words = nullptr; c->q_words_alloc = 0;
-      HIP_TRY(c, hipMalloc((void**)&c->d_q_words, q.n * sizeof(uint32_t)));
-      c->q_words_alloc = q.n;
+      HIP_TRY(c, hipMalloc((void**)&c->d_q_words, need * sizeof(uint32_t)));
+      c->q_words_alloc = need;
     }
     words = c->d_q_words;
   }
   if (q.counting) HIP_TRY(c, hipMemsetAsync(c->d_q_counters, 0, CNT_WORDS * sizeof(uint32_t), s));
   const SceneDev sc = scene_dev(c);
   if (q.t0) HIP_TRY(c, hipEventRecord(q.t0, s));
-  if (closest || sweep || segment || q.walk == Walk::ClosestHits || q.walk == Walk::Overlap || q.walk == Walk::Triangles) launch_closest_scale(sc, c->d_q_scale, s);
+  if (closest || sweep || segment || triangle || q.walk == Walk::ClosestHits || q.walk == Walk::Overlap || q.walk == Walk::Triangles) launch_closest_scale(sc, c->d_q_scale, s);
   switch (q.walk) {
     case Walk::Plain: launch_query(sc, records, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, q.any_hit, q.counting, cfg, s); break;
     case Walk::Flags: launch_query_flags(sc, records, (const uint32_t*)q.ray_words, q.query_word, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, cfg, s); break;
@@ -2425,6 +2429,9 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q
     case Walk::Segment:
       launch_closest_segment(sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, (float*)words, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
       break;
+    case Walk::Triangle:
+      launch_closest_triangle(sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, (float*)words, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
+      break;
     case Walk::Inside:
       if (closest) launch_closest_point(sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, false, cfg, s);
       launch_point_inside(sc, records, q.cull_mask, q.n_dirs, words, (uint32_t*)q.counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
@@ -2437,6 +2444,7 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q
     if (closest) launch_closest_side(sc, records, (const HitRec*)q.hits, (float4*)q.attr, n, s);
     if (sweep) launch_sweep_side(sc, records, (const HitRec*)q.hits, (float4*)q.attr, n, s);
     if (segment) launch_segment_side(sc, records, (const float*)words, (const HitRec*)q.hits, (float4*)q.attr, n, s);
+    if (triangle) launch_triangle_side(sc, records, (const float*)words, (const HitRec*)q.hits, (float4*)q.attr, n, s);
   }
   if (inside && q.hits) launch_sign_distance(records, words, (HitRec*)q.hits, n, s);   // (after the attributes: they read the records)
   return query_done(c, s);
@@ -2816,6 +2824,39 @@ int rt_closest_segment(rt_ctx* c, size_t n, const float* segs8, uint32_t cull_ma
   Query q; q.walk = Walk::Segment; q.n = n; q.cull_mask = cull_mask; q.counting = counting != 0;
   return blocking_query(c, q, segs8, seg_bytes, seg_bytes + hit_bytes + par_bytes,
                         {{&Query::hits, seg_bytes, out, hit_bytes}, {&Query::params, seg_bytes + hit_bytes, params, par_bytes}}, stats);
+}
+
+// The nearest pair of every query triangle and the surface: the checks and ordering of a device query (rt_closest_point_device), then
+// k_closest_scale and k_closest_triangle over the caller's records (enqueue_query), k_hit_attr and k_triangle_side for the attributes.
+int rt_closest_triangle_device(rt_ctx* c, size_t n, const void* d_tris12, uint32_t cull_mask, void* d_hits, void* d_attr, void* d_params, void* hip_stream) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const std::string name = "rt_closest_triangle_device";
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": too many triangles for one call");
+  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": cull_mask is above 0xFF");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, name + " needs trace_variant 0");
+  if (n) {
+    if (!d_tris12 || !d_hits) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null triangle/hit pointers");
+    if (((uintptr_t)d_tris12 & 15u) || ((uintptr_t)d_hits & 3u) || ((uintptr_t)d_attr & 15u) || ((uintptr_t)d_params & 3u))
+      return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": triangles and attributes must be 16-byte aligned, hits and parameters 4-byte aligned");
+    { int w = check_device_pointers(c, name, "triangles, hits, attributes and parameters", {d_tris12, d_hits, d_attr, d_params}); if (w) return w; }
+  }
+  Query q; q.walk = Walk::Triangle; q.n = n; q.records = d_tris12; q.cull_mask = cull_mask; q.hits = d_hits; q.attr = d_attr; q.params = d_params;
+  return device_query(c, q, hip_stream);
+}
+
+// The blocking host form, as rt_closest_segment is to rt_closest_segment_device: the triangles (48 B each), then the hits, then the
+// parameters (two floats each).
+int rt_closest_triangle(rt_ctx* c, size_t n, const float* tris12, uint32_t cull_mask, rt_hit* out, float* params, int counting, rt_stats* stats) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const std::string name = "rt_closest_triangle";
+  if ((!tris12 || !out) && n) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null triangle/hit pointers");
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": too many triangles for one call");
+  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": cull_mask is above 0xFF");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, name + " needs trace_variant 0");
+  const size_t tri_bytes = n * 12 * sizeof(float), hit_bytes = n * sizeof(HitRec), par_bytes = n * 2 * sizeof(float);
+  Query q; q.walk = Walk::Triangle; q.n = n; q.cull_mask = cull_mask; q.counting = counting != 0;
+  return blocking_query(c, q, tris12, tri_bytes, tri_bytes + hit_bytes + par_bytes,
+                        {{&Query::hits, tri_bytes, out, hit_bytes}, {&Query::params, tri_bytes + hit_bytes, params, par_bytes}}, stats);
 }
 
 namespace {

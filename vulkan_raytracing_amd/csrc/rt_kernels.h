@@ -240,6 +240,13 @@ void launch_closest_segment(const SceneDev& sc, const float4* segs, uint32_t cul
                             int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
 // the side of the reported triangle's plane the segment's point P0 + params[i] (P1 - P0) lies on (launch_closest_side's rule and word)
 void launch_segment_side(const SceneDev& sc, const float4* segs, const float* params, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s);
+// rt_closest_triangle_device: the nearest pair of every query triangle (48 bytes: P0.xyz, r_max, P1.xyz, ignored, P2.xyz, ignored) and the
+// surface of the instances the cull mask admits, into hits[n] and, when given, the barycentrics (qu, qv) of the query's point into
+// params[2 n] (kernels_triangle.inc).  The other arguments as for launch_closest_segment.
+void launch_closest_triangle(const SceneDev& sc, const float4* tris, uint32_t cull_mask, const float* inst_scale, HitRec* hits, float* params, uint32_t n,
+                             int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
+// the side of the reported triangle's plane the query's point (P0 + qu (P1 - P0)) + qv (P2 - P0) lies on (launch_closest_side's rule and word)
+void launch_triangle_side(const SceneDev& sc, const float4* tris, const float* params, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s);
 // rt_shade_rays_device: k_ray_ingest replaces k_raygen for the caller's n rays (32 bytes each, o.xyz, w3, d.xyz, tmax; sample id = record
 // index): sky colours of the rays that miss the TLAS and (0, 0, 0, 0) for invalid records into f.sample_color, the others into bounce queue 0
 // (workgroup b appends to shard b % 8: f.shard_cap >= 256 * ceil(ray_ingest_block_count(n) / 8)).  f.counters must be zero.

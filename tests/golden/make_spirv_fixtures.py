@@ -21,7 +21,10 @@ compares HIP frames with the recorded pixels.
 
 Run in the authoring container (needs /root/reference, does not travel to the GPU box):
     python tests/golden/make_spirv_fixtures.py
-writes tests/golden/spirv_fixtures.npz (+ .json with the scene list).
+writes tests/golden/spirv_fixtures.npz (+ .json with the scene list): the reference's shipped configurations.
+    python tests/golden/make_spirv_fixtures.py --set edge
+writes tests/golden/spirv_fixtures_edge.npz (+ .json): the cases the reference never ships (edge_scene_list), small frames,
+replayed by tests/test_spirv_edge.py on the CPU and on the GPU.
 """
 import json
 import os
@@ -229,10 +232,114 @@ def scene_list():
     ]
 
 
-def choose_pixels(env, W, H, n, seed):
-    """70 % of the pixels where geometry is (found with a coarse oracle pre-pass of primary rays), 30 % anywhere."""
+def affine(linear, translation):
+    """the row-major 3x4 transform of an instance record from a 3x3 linear part and a translation"""
+    m = np.zeros((3, 4), np.float32)
+    m[:, 0:3], m[:, 3] = np.asarray(linear, np.float64), np.asarray(translation, np.float64)
+    return m.reshape(12)
+
+
+def rot_y(angle):
+    c, s = np.cos(angle), np.sin(angle)
+    return np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]])
+
+
+# shear, unequal scales and a reflection at once: det = -1.0185 (teapot), -0.96 (cube)
+SHEAR_MIRROR_TEAPOT = np.array([[-1.2, 0.5, 0.0], [0.0, 0.8, 0.25], [0.3, 0.0, 1.1]])
+SHEAR_MIRROR_CUBE = np.array([[1.5, 0.6, 0.0], [0.0, -0.9, 0.4], [0.5, 0.0, 0.8]])
+INSIDE_TEAPOT = (0.0, 0.9, 0.0)     # a point in the teapot's body (the mesh spans x -3..3.43, y 0..3.15, z -2..2)
+
+
+def edge_scene_list():
+    """(key, description, workload factory, W, H, n) — what the reference never ships: sheared / mirrored / anisotropic instance
+    transforms, cameras and lights inside a mesh, object types outside 0..2, spp other than 1 and 4, cameras whose basis is neither
+    unit, orthogonal nor upright, and a ring of both meshes under mixed transforms.  n None records the whole frame, otherwise
+    choose_pixels picks n pixels.  Every instance keeps custom index == mesh (src/shader.rchit:52 reads the custom index)."""
+    teapot, cube = os.path.join(RES, "teapot.obj"), os.path.join(RES, "cube.obj")
+    sky_test = os.path.join(RES, "skybox_texture_test")
+    eye = np.eye(3)
+
+    def scene(key, instances, W, H, sky=sky_test, **uniforms):
+        def make():
+            g = host.SceneGeometry([teapot, cube])
+            u = host.default_uniforms(orbiting_object_primitive_offset=g.orbiting_primitive_offset, orbiting_object_vertex_offset=g.orbiting_vertex_offset)
+            for k, v in uniforms.items():
+                if k in ("position", "right", "up", "forward"):
+                    u[0][k][0:3] = v
+                else:
+                    u[0][k] = v
+            inst = np.zeros(len(instances), workloads.INSTANCE_DTYPE)
+            for i, (mesh, lin, tr) in enumerate(instances):
+                inst[i] = host.make_instance(affine(lin, tr), mesh, mesh)
+            w = workloads.Workload(key, [teapot, cube], inst, u, sky, W, H, key)
+            w._geom = g
+            return w
+        return make
+
+    # the teapot's body is nearly a sphere about the camera: rays meet it head-on and leave.  Towards the spout they enter the spout's
+    # tube from the body and meet its wall obliquely: total internal reflection
+    AT_SPOUT = dict(forward=(0.944, 0.33, 0.0), up=(-0.33, 0.944, 0.0), right=(0.0, 0.0, 1.0))
+    T, C = 0, 1     # mesh (and custom index) of the teapot and of the cube
+    plain = [(T, eye, (0, 0, 0)), (C, rot_y(0.5), (4.0, 1.0, 3.0))]
+    ring = [(T, SHEAR_MIRROR_TEAPOT * 0.6, (0, -0.5, 0)),
+            (C, rot_y(0.3), (5.0, 0.0, 0.5)),
+            (C, SHEAR_MIRROR_CUBE * 0.7, (2.8, 3.0, 3.0)),
+            (T, rot_y(2.0) * 0.5, (-4.5, 2.0, 2.0)),
+            (C, np.diag([0.3, 1.6, 0.9]) @ rot_y(0.7), (-4.0, -1.5, 3.5)),
+            (C, rot_y(-0.4) @ np.diag([1.0, -1.0, 1.0]), (-1.5, -2.6, 5.0)),
+            (T, np.array([[0.5, 0.2, 0.0], [0.0, 0.5, 0.0], [0.0, 0.15, 0.5]]), (3.0, -3.5, 4.0))]
+    roll = 0.4
+    return [
+        ("sheared_mirrored_glass", "glass teapot under shear, unequal scales and a reflection (det < 0) + rigid mirror cube, depth 5, spp 7",
+         scene("sheared_mirrored_glass", [(T, SHEAR_MIRROR_TEAPOT, (0, -0.5, 0)), (C, rot_y(0.6), (4.5, 1.5, 2.0))], 48, 27,
+               center_object_type=2, orbiting_object_type=1, max_bounce_count=5, samples_per_pixel=7), 48, 27, 100),
+        ("anisotropic_diffuse", "diffuse teapot scaled (1e-2, 1, 3) and turned to face the camera + diffuse cube, lit: the normal through w2o, the shadow origin P + 0.01 N",
+         scene("anisotropic_diffuse", [(T, rot_y(1.25) @ np.diag([1e-2, 1.0, 3.0]), (0, -1.5, 0)), (C, rot_y(0.5), (3.0, 2.0, 4.0))], 64, 36,
+               center_object_type=0, orbiting_object_type=0, max_bounce_count=1, samples_per_pixel=1, light_position=(6.0, 5.0, 9.0)), 64, 36, 600),
+        ("sheared_mirrored_glass_cube", "glass cube under shear and a reflection in front of a diffuse teapot, depth 6, odd frame size",
+         scene("sheared_mirrored_glass_cube", [(T, eye, (0, -1.0, 0)), (C, SHEAR_MIRROR_CUBE * 1.4, (1.0, 1.0, 8.0))], 37, 23,
+               center_object_type=0, orbiting_object_type=2, max_bounce_count=6, samples_per_pixel=2), 37, 23, None),
+        ("inside_glass", "camera inside the glass teapot: outwards hits, total internal reflection; mirror cube outside, depth 8, spp 3",
+         scene("inside_glass", [(T, eye, (0, 0, 0)), (C, rot_y(0.4), (7.0, 3.0, 0.5))], 48, 27, position=INSIDE_TEAPOT, **AT_SPOUT,
+               center_object_type=2, orbiting_object_type=1, max_bounce_count=8, samples_per_pixel=3), 48, 27, 130),
+        ("inside_diffuse", "camera inside the diffuse teapot: every primary hit is a back face",
+         scene("inside_diffuse", [(T, eye, (0, 0, 0)), (C, rot_y(0.4), (0.5, 1.0, -7.0))], 48, 27, position=INSIDE_TEAPOT,
+               center_object_type=0, orbiting_object_type=0, max_bounce_count=2, samples_per_pixel=1), 48, 27, None),
+        ("inside_mirror", "camera inside the mirror teapot, depth 9",
+         scene("inside_mirror", [(T, eye, (0, 0, 0)), (C, rot_y(0.4), (0.5, 1.0, -7.0))], 48, 27, position=INSIDE_TEAPOT,
+               center_object_type=1, orbiting_object_type=0, max_bounce_count=9, samples_per_pixel=1), 48, 27, 120),
+        ("unknown_types", "centre type 3, orbiting type 7: the loop retraces the same ray until the bounce budget ends, depth 3",
+         scene("unknown_types", plain, 48, 27, center_object_type=3, orbiting_object_type=7, max_bounce_count=3, samples_per_pixel=1), 48, 27, 400),
+        ("light_inside", "the light inside the teapot, everything diffuse",
+         scene("light_inside", plain, 64, 36, center_object_type=0, orbiting_object_type=0, max_bounce_count=1, samples_per_pixel=1,
+               light_position=INSIDE_TEAPOT), 64, 36, 500),
+        ("light_close", "the light 0.1 in front of a cube face (tmax comparable to the 0.01 offset), everything diffuse",
+         scene("light_close", [(T, eye, (0, -1.0, 0)), (C, eye * 1.5, (0.0, 1.0, 8.0))], 64, 36, center_object_type=0, orbiting_object_type=0,
+               max_bounce_count=1, samples_per_pixel=1, light_position=(0.3, 1.2, 9.6), position=(1.0, 2.0, 15.0)), 64, 36, 500),
+        ("intensity_0", "lightIntensity 0, everything diffuse",
+         scene("intensity_0", plain, 48, 27, center_object_type=0, orbiting_object_type=0, max_bounce_count=1, samples_per_pixel=1, light_intensity=0.0), 48, 27, 300),
+        ("intensity_3p5", "lightIntensity 3.5, everything diffuse",
+         scene("intensity_3p5", plain, 48, 27, center_object_type=0, orbiting_object_type=0, max_bounce_count=1, samples_per_pixel=1, light_intensity=3.5), 48, 27, 300),
+        ("depth0_spp1", "mirror teapot + glass cube with maxBounceCount 0: the budget ends at the first hit",
+         scene("depth0_spp1", plain, 48, 27, center_object_type=1, orbiting_object_type=2, max_bounce_count=0, samples_per_pixel=1), 48, 27, 400),
+        ("spp5", "glass teapot + diffuse cube, depth 3, spp 5",
+         scene("spp5", plain, 48, 27, center_object_type=2, orbiting_object_type=0, max_bounce_count=3, samples_per_pixel=5), 48, 27, 100),
+        ("spp16", "diffuse teapot + mirror cube, depth 2, spp 16: pow(0.9, float(i)) up to i = 15",
+         scene("spp16", plain, 48, 27, center_object_type=0, orbiting_object_type=1, max_bounce_count=2, samples_per_pixel=16), 48, 27, 70),
+        ("rolled_anamorphic_camera", "right, up and forward rolled about the view axis, of unequal length and not orthogonal; mirror teapot + diffuse cube",
+         scene("rolled_anamorphic_camera", plain, 64, 36, center_object_type=1, orbiting_object_type=0, max_bounce_count=2, samples_per_pixel=2,
+               position=(1.0, 2.0, 18.0), right=(1.3 * np.cos(roll), 1.3 * np.sin(roll), 0.2), up=(-0.7 * np.sin(roll) - 0.25 * np.cos(roll), 0.7 * np.cos(roll) - 0.25 * np.sin(roll), -0.1),
+               forward=(0.06, -0.05, -1.2)), 64, 36, 250),
+        ("ring", "seven instances of both meshes: rigid, sheared, mirrored, anisotropic; glass teapots + diffuse cubes, depth 4, spp 2",
+         scene("ring", ring, 96, 54, center_object_type=2, orbiting_object_type=0, max_bounce_count=4, samples_per_pixel=2), 96, 54, 450),
+    ]
+
+
+def choose_pixels(env, W, H, n, seed, step=None):
+    """70 % of the pixels where geometry is (found with a coarse oracle pre-pass of primary rays; step 1 for the small frames of
+    the edge set: every pixel is a candidate), 30 % anywhere."""
     rng = np.random.default_rng(seed)
-    step = max(4, W // 160)
+    step = max(4, W // 160) if step is None else step
     xs, ys = np.meshgrid(np.arange(step // 2, W, step), np.arange(step // 2, H, step))
     rays = np.zeros((xs.size, 8), np.float32)
     for k, (x, y) in enumerate(zip(xs.ravel(), ys.ravel())):
@@ -251,26 +358,39 @@ def choose_pixels(env, W, H, n, seed):
     return sorted(chosen)
 
 
-def main():
+def main(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--set", choices=("base", "edge"), default="base", help="base: the shipped configurations (spirv_fixtures.*); "
+                    "edge: what the reference never ships (spirv_fixtures_edge.*, see edge_scene_list)")
+    args = ap.parse_args(argv)
     mods = load_modules()
     bounces, pixels, meta = [], [], []
     t0 = time.time()
-    for sid, (name, make, W, H, n) in enumerate(scene_list()):
+    if args.set == "base":
+        stem, seed0, step = "spirv_fixtures", 100, None
+        todo = [(None, name, make, W, H, n) for (name, make, W, H, n) in scene_list()]
+    else:
+        stem, seed0, step = "spirv_fixtures_edge", 200, 1
+        todo = [(key, "%s: %s" % (key, text), make, W, H, n) for (key, text, make, W, H, n) in edge_scene_list()]
+    for sid, (key, name, make, W, H, n) in enumerate(todo):
         wl = make()
         env = Env(mods, wl, W, H)
-        px = choose_pixels(env, W, H, n, seed=100 + sid)
+        px = choose_pixels(env, W, H, n, seed=seed0 + sid, step=step) if n is not None else [(x, y) for y in range(H) for x in range(W)]
         nb0 = len(bounces)
         for (x, y) in px:
             env.run_pixel(sid, x, y, bounces, pixels)
         meta.append(dict(id=sid, name=name, width=W, height=H, pixels=len(px), bounce_records=len(bounces) - nb0,
                          paths=[os.path.relpath(p, ROOT) for p in wl.paths], sky=os.path.relpath(wl.sky_dir, ROOT) if wl.sky_dir else None,
                          instances=[wl.instances[i].tobytes().hex() for i in range(len(wl.instances))], uniforms=wl.uniforms.tobytes().hex()))
+        if key is not None:
+            meta[-1]["key"] = key
         print("%-100s %4d pixels %6d bounce records  %.0f s" % (name[:100], len(px), len(bounces) - nb0, time.time() - t0), flush=True)
     b = np.array(bounces, BOUNCE_DTYPE)
     p = np.array(pixels, PIXEL_DTYPE)
-    np.savez_compressed(os.path.join(HERE, "spirv_fixtures.npz"), bounces=b, pixels=p)
-    with open(os.path.join(HERE, "spirv_fixtures.json"), "w") as fh:
-        json.dump(dict(generator="tests/golden/make_spirv_fixtures.py",
+    np.savez_compressed(os.path.join(HERE, stem + ".npz"), bounces=b, pixels=p)
+    with open(os.path.join(HERE, stem + ".json"), "w") as fh:
+        json.dump(dict(generator="tests/golden/make_spirv_fixtures.py" + ("" if args.set == "base" else " --set " + args.set),
                        source="interpreted /root/reference/shaders/{shader.rgen,shader.rchit,shader.rmiss,shader_shadow.rmiss}.spv (read as data)",
                        arithmetic="binary32 +,-,*,/ and OpDot literally (one rounding per operation, left to right, no contraction); GLSL.std.450 instructions "
                                   "in binary64 rounded once; traversal / inverse transform / cube sampling bound to the oracle",

@@ -177,6 +177,7 @@ class SpirvFixtureScene:
     def __init__(self, meta, bounces, pixels):
         self.meta, self.bounces, self.pixels = meta, bounces, pixels
         self.name, self.width, self.height = meta["name"], meta["width"], meta["height"]
+        self.key = meta.get("key")        # the edge set's short scene name
         self.paths = [os.path.join(ROOT, p) for p in meta["paths"]]
         self.instances = np.frombuffer(bytes.fromhex("".join(meta["instances"])), INSTANCE_DTYPE).copy()
         from vulkan_raytracing_amd.api import UNIFORMS_DTYPE
@@ -210,12 +211,16 @@ class SpirvFixtureScene:
         return S
 
 
-def load_spirv_fixtures():
+def load_spirv_fixtures(which="base"):
+    """which: "base" (spirv_fixtures.*: the reference's shipped configurations) or "edge" (spirv_fixtures_edge.*: sheared, inside,
+    unknown-type, odd-spp and rolled-camera cases; every scene's meta carries a short "key")"""
     import json
     gold = os.path.join(ROOT, "tests", "golden")
-    meta = json.load(open(os.path.join(gold, "spirv_fixtures.json")))
-    data = np.load(os.path.join(gold, "spirv_fixtures.npz"), allow_pickle=False)
-    for kind in ("standin", "limbs"):      # the generated meshes the cfg3 / cfg5 scenes name (deterministic generators)
-        host.armadillo_path(RES, kind=kind)
+    stem = {"base": "spirv_fixtures", "edge": "spirv_fixtures_edge"}[which]
+    meta = json.load(open(os.path.join(gold, stem + ".json")))
+    data = np.load(os.path.join(gold, stem + ".npz"), allow_pickle=False)
+    if which == "base":
+        for kind in ("standin", "limbs"):  # the generated meshes the cfg3 / cfg5 scenes name (deterministic generators)
+            host.armadillo_path(RES, kind=kind)
     b, p = data["bounces"], data["pixels"]
     return [SpirvFixtureScene(m, b[b["scene"] == m["id"]], p[p["scene"] == m["id"]]) for m in meta["scenes"]]

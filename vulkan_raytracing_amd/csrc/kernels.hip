@@ -1601,19 +1601,69 @@ struct ShadeArgs {
 // src/shader.rchit:50-96 up to the shading: the world position P and the shading normal N of the hit (u, v) on triangle `prim` of
 // instance I.  The one copy of this arithmetic: k_shade and k_tail shade with it, k_hit_attr hands it to ray queries.
 struct Surface { F3 P, N; };
+// ... from the triangle's three vertices (position, normal: 6 floats each) and the instance's two matrices, wherever they lie
+__device__ __forceinline__ Surface surface_at(const float* o2w, const float* w2o, const float* pa, const float* pb, const float* pc, float hu, float hv) {
+  const float bx = (1.0f - hu) - hv, by = hu, bz = hv;
+  const F3 pos = fma3(bz, mk3(pc[0], pc[1], pc[2]), fma3(by, mk3(pb[0], pb[1], pb[2]), mul3(mk3(pa[0], pa[1], pa[2]), bx)));
+  const F3 nrm = fma3(bz, mk3(pc[3], pc[4], pc[5]), fma3(by, mk3(pb[3], pb[4], pb[5]), mul3(mk3(pa[3], pa[4], pa[5]), bx)));
+  Surface s;
+  s.P = xform_point(o2w, pos);
+  s.N = normalize3(xform_normal(w2o, nrm));
+  return s;
+}
 __device__ __forceinline__ Surface hit_surface(const SceneDev& sc, const InstanceDev* I, uint32_t prim, float hu, float hv) {
   const uint32_t* ix = sc.idx + I->first_index + 3u * prim;
   const uint32_t ia = ix[0], ib = ix[1], ic = ix[2];
   const float* vb = sc.verts + I->first_float;
-  const float bx = (1.0f - hu) - hv, by = hu, bz = hv;
-  const float* pa = vb + 6u * ia; const float* pb = vb + 6u * ib; const float* pc = vb + 6u * ic;
-  const F3 pos = fma3(bz, mk3(pc[0], pc[1], pc[2]), fma3(by, mk3(pb[0], pb[1], pb[2]), mul3(mk3(pa[0], pa[1], pa[2]), bx)));
-  const F3 nrm = fma3(bz, mk3(pc[3], pc[4], pc[5]), fma3(by, mk3(pb[3], pb[4], pb[5]), mul3(mk3(pa[3], pa[4], pa[5]), bx)));
-  Surface s;
-  s.P = xform_point(I->o2w, pos);
-  s.N = normalize3(xform_normal(I->w2o, nrm));
-  return s;
+  return surface_at(I->o2w, I->w2o, vb + 6u * ia, vb + 6u * ib, vb + 6u * ic, hu, hv);
 }
+
+// a T read through the scalar constant cache: p is WAVE-UNIFORM and what it points at is not written while the kernel runs
+template <typename T> __device__ __forceinline__ T ld_const(const T* p) {
+  T v;
+  __builtin_memcpy(&v, (const __attribute__((address_space(4))) T*)p, sizeof(T));
+  return v;
+}
+// ... a pointer to device memory read that way, AS what it is.  A pointer that a kernel loads from its argument block by hand is generic to
+// the compiler, and every access through it a flat_* instruction (a 64-bit address per lane, both wait counters); loaded as a global
+// pointer, the accesses are global_* ones, with a scalar base where the pointer is wave-uniform.
+template <typename T> __device__ __forceinline__ T* ld_const_ptr(T* const* p) {
+  typedef __attribute__((address_space(1))) T* global_ptr;
+  const __attribute__((address_space(4))) void* const c = (const __attribute__((address_space(4))) void*)(const void*)p;
+  return (T*)*static_cast<const __attribute__((address_space(4))) global_ptr*>(c);
+}
+
+// REG shading (k_beam_shade): what a lane CARRIES from one sample row of its pixel to the next.  The samples of a pixel lie a fraction
+// of a pixel apart: nearly always in one instance and mostly in one triangle, so row j finds here what row j - 1 fetched — the fields of
+// the instance record that shading reads, and the triangle's three vertices — and fetches only what differs.  The caller may fill the
+// instance part for the whole wave from one scalar read when all hits of the run lie in one instance (beam_body).
+struct InstanceShade { float w2o[12], o2w[12]; int32_t custom_index; uint32_t first_float, first_index, type; };
+struct ShadeCarry {
+  int inst = -1;               // the instance R is of (-1: none yet)
+  uint32_t prim = ~0u;         // the primitive of `inst` v is of (~0: none yet)
+  InstanceShade R = {};        // (zeros, not nothing: an undefined value here would be one kept from kernel entry, across the walk)
+  float v[18] = {};            // vertices a, b, c: position, normal
+  __device__ __forceinline__ void set_instance(int ii, const InstanceShade& r) { inst = ii; prim = ~0u; R = r; }
+  __device__ __forceinline__ static InstanceShade fields_of(const InstanceDev& I) {
+    InstanceShade r;
+#pragma unroll
+    for (int k = 0; k < 12; k++) { r.w2o[k] = I.w2o[k]; r.o2w[k] = I.o2w[k]; }
+    r.custom_index = I.custom_index; r.first_float = I.first_float; r.first_index = I.first_index; r.type = I.type;
+    return r;
+  }
+  __device__ __forceinline__ void fetch(const SceneDev& sc, int ii, uint32_t pp) {
+    if (ii != inst) set_instance(ii, fields_of(sc.inst[ii]));
+    if (pp != prim) {
+      const uint32_t* ix = sc.idx + R.first_index + 3u * pp;
+      const uint32_t ia = ix[0], ib = ix[1], ic = ix[2];
+      const float* vb = sc.verts + R.first_float;
+      const float* pa = vb + 6u * ia; const float* pb = vb + 6u * ib; const float* pc = vb + 6u * ic;
+#pragma unroll
+      for (int k = 0; k < 6; k++) { v[k] = pa[k]; v[6 + k] = pb[k]; v[12 + k] = pc[k]; }
+      prim = pp;
+    }
+  }
+};
 
 // shade_slot, the per-slot part of shading (TILE, BATCH, RUNS: see shade_body): queue entry q of `shard` (in_range: it lies below the queue's tail) is shaded, its continuation ray goes to the
 // next bounce queue and its shadow ray to the shadow queue of the same shard.  WAVE-CONVERGENT: all 64 lanes of a wave call it together
@@ -1627,8 +1677,9 @@ template <bool PIN> __device__ __forceinline__ float4 ambient_default() {
   if constexpr (PIN) asm volatile("" : "+v"(r));
   return make_float4(r, 0.24f, r, 1.0f);
 }
-template <bool TILE, bool BATCH, bool RUNS, bool REG, typename A>
-__device__ __forceinline__ void shade_slot(const A& a, const int bounce, const uint32_t shard, const uint32_t q, const bool in_range, const int inst_r, const float4 h_r) {
+// REG: the instance fields and the vertices come through `carry` (ShadeCarry), which the caller keeps from row to row of a run.
+template <bool TILE, bool BATCH, bool RUNS, bool REG, typename A, typename RC = void>
+__device__ __forceinline__ void shade_slot(const A& a, const int bounce, const uint32_t shard, const uint32_t q, const bool in_range, const int inst_r, const float4 h_r, RC* carry = nullptr) {
   const auto& f = a.f;
   const auto& U = a.u;
   const int cur = bounce & 1, nxt = cur ^ 1;
@@ -1652,19 +1703,28 @@ __device__ __forceinline__ void shade_slot(const A& a, const int bounce, const u
       // src/shader.rchit:50-96
       float4 h = h_r;
       if constexpr (!REG) h = ld_stream(&f.hit_a[q]);
-      const InstanceDev* I = a.sc.inst + inst;
       const uint32_t prim = __float_as_uint(h.w);
-      const Surface S = hit_surface(a.sc, I, prim, h.y, h.z);
+      Surface S;
+      int objectIndex;
+      uint32_t inst_type, first_index;
+      if constexpr (REG) {
+        carry->fetch(a.sc, inst, prim);
+        S = surface_at(carry->R.o2w, carry->R.w2o, carry->v, carry->v + 6, carry->v + 12, h.y, h.z);
+        objectIndex = carry->R.custom_index; inst_type = carry->R.type; first_index = carry->R.first_index;
+      } else {
+        const InstanceDev* I = a.sc.inst + inst;
+        S = hit_surface(a.sc, I, prim, h.y, h.z);
+        objectIndex = I->custom_index; inst_type = I->type; first_index = I->first_index;
+      }
       const F3 P = S.P;
       F3 N = S.N;
-      const int objectIndex = I->custom_index;
       // src/shader.rgen:96, generalised (row n4): a per-instance type replaces the two-way switch when the host set one,
       // and an MTL material may fix its own type (illum)
-      uint32_t type = I->type != TYPE_BY_OBJECT_INDEX ? I->type : (objectIndex == 0 ? U.center_object_type : U.orbiting_object_type);
+      uint32_t type = inst_type != TYPE_BY_OBJECT_INDEX ? inst_type : (objectIndex == 0 ? U.center_object_type : U.orbiting_object_type);
       const MaterialDev* M = nullptr;
       uint32_t mat = MATERIAL_NONE;
       if (a.sc.n_materials != 0) {
-        mat = a.sc.prim_material[I->first_index / 3u + prim];
+        mat = a.sc.prim_material[first_index / 3u + prim];
         M = a.sc.materials + mat;
         if (M->type != TYPE_BY_INSTANCE) type = M->type;
       }

@@ -87,22 +87,44 @@ struct BeamShadeArgs {
   int width, rows, light_tiles, settle_dead_shadow_rays;
   BeamShadeUniforms u;
 };
-// what shade_slot reads of FrameDev at bounce 0 of such a frame, under the same names; made from the argument block inside the kernel
+// What shade_slot reads of FrameDev and SceneDev at bounce 0 of such a frame, under the same names; made from the argument block inside the
+// kernel, per run.  A pointer is a KargPtr: the PLACE of the pointer in the argument block, read (one scalar load that hits the constant
+// cache, ld_const_ptr: a pointer to device memory) where shading uses it — the queue of the next bounce where a mirror pushes a ray, the
+// cube map where a sample misses.  Read ahead of the rows, the pointers and uniforms of the epilogue are more words than a wave has
+// scalar registers beside the row loop's own, and the rest goes to lanes and comes back inside the loop.
+template <typename T> struct KargPtr {
+  T* const* at;       // its place in the block, or
+  T* held;            // (at == nullptr) the pointer itself, read ahead: what every row uses
+  __device__ __forceinline__ operator T*() const { return at != nullptr ? ld_const_ptr(at) : held; }
+};
 struct BeamShadeFrame {
-  float4* ray_o[2]; float4* ray_d[2];
-  float4* sh_o; float4* sh_d; float4* sh_c; uint32_t* sh_e;
-  float4* sample_color;
-  uint32_t* counters;
-  const EntryRec* light_entry;
+  KargPtr<float4> ray_o[2], ray_d[2];
+  KargPtr<float4> sh_o, sh_d, sh_c; KargPtr<uint32_t> sh_e;
+  KargPtr<float4> sample_color;
+  KargPtr<uint32_t> counters;
+  KargPtr<const EntryRec> light_entry;
   uint32_t shard_cap;
   int width, rows, light_tiles, settle_dead_shadow_rays;
   static constexpr int pixel_runs = 64;       // such a frame has pixel runs (one origin per run: the camera) and no shadow runs
   static constexpr uint32_t sh_base = 0u;
 };
-struct BeamShadeView { const SceneDev& sc; const BeamShadeFrame& f; const BeamShadeUniforms& u; };
+struct BeamShadeScene {
+  const BeamShadeArgs* ka;
+  int n_materials;
+  KargPtr<const MaterialDev> materials;
+  KargPtr<const uint32_t> prim_material;
+  __device__ __forceinline__ operator SceneDev() const {   // for sample_sky, ambient_of, ShadeCarry::fetch: what they do not read of it is not loaded
+    SceneDev s = ld_const(&ka->sc);
+    s.inst = ld_const_ptr(&ka->sc.inst); s.verts = ld_const_ptr(&ka->sc.verts); s.idx = ld_const_ptr(&ka->sc.idx); s.sky = ld_const_ptr(&ka->sc.sky);
+    s.materials = ld_const_ptr(&ka->sc.materials); s.prim_material = ld_const_ptr(&ka->sc.prim_material);
+    return s;
+  }
+};
+struct BeamShadeView { const BeamShadeScene& sc; const BeamShadeFrame& f; const BeamShadeUniforms& u; };
 
 template <bool COUNT, bool SHADE = false, typename Args = TraceArgs>
-__device__ __forceinline__ void beam_body(const Args& a, const uint32_t run) {
+__device__ __forceinline__ void beam_body(const Args& a_entry, const uint32_t run) {
+  const Args& a = a_entry;
   __shared__ int s_stack[4][STACK2_LDS + 1][64];
   __shared__ float s_best[4][16][64];    // ray j of lane l: rows 4 j .. 4 j + 3 = u, v, primitive, instance of its closest hit so far (t stays in a register)
   __shared__ float4 s_inst[LDS_INSTANCES ? LDS_INSTANCES : 1][5];
@@ -118,13 +140,27 @@ __device__ __forceinline__ void beam_body(const Args& a, const uint32_t run) {
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   int* const stk = &s_stack[wave][0][lane];
   float* const bst = &s_best[wave][0][lane];                // row r at bst[r * 64]
-  const char* const node_bytes = reinterpret_cast<const char*>(a.sc.blas_nodes);
   const uint32_t S = run >> 6;
   uint64_t cnt_nodes = 0, cnt_tris = 0, diag_iters = 0, diag_busy = 0;   // (counting builds: trips of the interior loop, lanes busy in them)
   const uint64_t diag_t0 = COUNT ? __builtin_readcyclecounter() : 0;
   uint32_t shard = blockIdx.x & (N_SHARDS - 1), tried = 0;
 
   for (;;) {
+    // k_beam_shade: the walk reads its arguments from the block again for every run (scalar loads that hit the constant cache), as the
+    // epilogue does.  Held in scalar registers from kernel entry they would be live across the epilogue, which has its own fifty words of
+    // pointers and uniforms there: together more than a wave has, and the allocator then spills the walk's into lanes and reads them
+    // back inside set_space and the leaf tests.
+    Args a_run;
+    if constexpr (SHADE) {
+      const Args* ka = (const Args*)__builtin_amdgcn_kernarg_segment_ptr();   // (the block is the kernel's first argument: offset 0)
+      asm volatile("" : "+s"(ka));
+      a_run = ld_const(ka);
+      a_run.sc.blas_nodes = ld_const_ptr(&ka->sc.blas_nodes); a_run.sc.tris = ld_const_ptr(&ka->sc.tris); a_run.sc.inst = ld_const_ptr(&ka->sc.inst);
+      a_run.ray_o = ld_const_ptr(&ka->ray_o); a_run.ray_d = ld_const_ptr(&ka->ray_d); a_run.tails = ld_const_ptr(&ka->tails); a_run.work = ld_const_ptr(&ka->work);
+      a_run.ovf_stack = ld_const_ptr(&ka->ovf_stack); a_run.entry = ld_const_ptr(&ka->entry);
+    }
+    const Args& a = SHADE ? a_run : a_entry;
+    const char* const node_bytes = reinterpret_cast<const char*>(a.sc.blas_nodes);
     // ---- the wave's next run (wave-uniform)
     uint32_t base = 0; bool got = false;
     while (tried < (uint32_t)N_SHARDS) {
@@ -351,17 +387,41 @@ __device__ __forceinline__ void beam_body(const Args& a, const uint32_t run) {
       // What shading reads of the argument block is read HERE, per run, through the kernarg pointer: named as `a.x` the compiler loads every
       // word at kernel entry and carries it across the walk in scalar registers the walk needs (68 of them spilled to lanes of two more
       // VGPRs); the empty asm keeps the loads below it.  A run's scalar loads hit the constant cache.
+      // The block is read as what it is, constant memory (ld_const: scalar loads), and the pointers it holds as what they are, pointers to
+      // device memory (ld_const_ptr): read as generic ones, every access of the epilogue would be a flat_* instruction.
       const BeamShadeArgs* ka = (const BeamShadeArgs*)__builtin_amdgcn_kernarg_segment_ptr();   // (the block is the kernel's first argument: offset 0)
       asm volatile("" : "+s"(ka));
-      const BeamShadeFrame sf{{const_cast<float4*>(ka->ray_o), ka->next_o}, {const_cast<float4*>(ka->ray_d), ka->next_d}, ka->sh_o, ka->sh_d, ka->sh_c, ka->sh_e, ka->sample_color,
-                              ka->counters, ka->light_entry, ka->shard_cap, ka->width, ka->rows, ka->light_tiles, ka->settle_dead_shadow_rays};
-      const BeamShadeView sv{ka->sc, sf, ka->u};
+      // The hits of a run mostly lie in ONE instance: then the fields of its record that shading reads are read once for the wave, through the
+      // scalar cache, and no row fetches them.  Otherwise a lane fetches the record of its own hit, and again only when a later row's differs.
+      ShadeCarry carry;
+      {
+        int first = -1; bool agree = true;
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; j++) {
+          const int ij = (alive >> j) & 1u ? __float_as_int(bst[(4u * j + 3u) * 64u]) : -1;
+          if (ij >= 0) { agree = agree && (first < 0 || ij == first); if (first < 0) first = ij; }
+        }
+        const uint64_t m_hit = __ballot(first >= 0);
+        if (m_hit != 0ull) {
+          const int one = __builtin_amdgcn_readlane(first, (int)__builtin_ctzll(m_hit));
+          if (__ballot(first >= 0 && !(agree && first == one)) == 0ull) carry.set_instance(one, ShadeCarry::fields_of(ld_const(ld_const_ptr(&ka->sc.inst) + one)));
+        }
+      }
+      asm volatile("" : "+s"(ka));   // (what follows is read after that: the record's words and the words below need not be in scalar registers together)
+      const BeamShadeFrame sf{{{const_cast<float4* const*>(&ka->ray_o), nullptr}, {&ka->next_o, nullptr}},
+                              {{nullptr, const_cast<float4*>(ld_const_ptr(&ka->ray_d))}, {&ka->next_d, nullptr}},
+                              {&ka->sh_o, nullptr}, {&ka->sh_d, nullptr}, {&ka->sh_c, nullptr}, {&ka->sh_e, nullptr},
+                              {nullptr, ld_const_ptr(&ka->sample_color)}, {nullptr, ld_const_ptr(&ka->counters)}, {&ka->light_entry, nullptr},
+                              ld_const(&ka->shard_cap), ld_const(&ka->width), ld_const(&ka->rows), ld_const(&ka->light_tiles), ld_const(&ka->settle_dead_shadow_rays)};
+      const BeamShadeScene sg{ka, ld_const(&ka->sc.n_materials), {&ka->sc.materials, nullptr}, {&ka->sc.prim_material, nullptr}};
+      const BeamShadeUniforms su = ld_const(&ka->u);
+      const BeamShadeView sv{sg, sf, su};
 #pragma nounroll
       for (uint32_t j = 0; j < S; j++) {
         const float tj = j == 0u ? bt0 : (j == 1u ? bt1 : (j == 2u ? bt2 : bt3));
         const float* const b = bst + 256u * j;   // rows 4 j .. 4 j + 3
         const int ij = (alive >> j) & 1u ? __float_as_int(b[192]) : HIT_DEAD;
-        shade_slot<false, false, false, true>(sv, 0, run_shard, v0 + 64u * j, true, ij, make_float4(tj, b[0], b[64], b[128]));
+        shade_slot<false, false, false, true>(sv, 0, run_shard, v0 + 64u * j, true, ij, make_float4(tj, b[0], b[64], b[128]), &carry);
       }
     } else {
     // ---- the hit records of the pixel's samples (a slot without a ray: HIT_DEAD)

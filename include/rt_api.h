@@ -241,7 +241,9 @@ typedef struct rt_material {
 } rt_material;
 #define RT_MATERIAL_TYPE_OF_INSTANCE 0xFFFFFFFFu   /* the surface's type is its instance's (rt_set_instance_types / the uniform block) */
 /* table[prim_material[g]] shades triangle g of the shared index buffer, g = first_index / 3 + gl_PrimitiveID (one entry per
- * triangle: n_prims = n_idx / 3).  Scene state, shared by all frame slots; n_materials == 0 removes the table.  With a table the
+ * triangle: n_prims = n_idx / 3).  Scene state, shared by all frame slots; n_materials == 0 removes the table, and so does
+ * rt_upload_geometry on any slot of the scene (the ids belong to the index buffer it replaces): frames are then shaded without a table
+ * until it is set again with one id per triangle of the new index buffer (any other n_prims: RT_ERR_INVALID_ARGUMENT).  With a table the
  * diffuse branch evaluates Iamb*ka, kd, ks, pow(., Ns) and the refractive branch Ni from the hit triangle's material. */
 int rt_set_materials(rt_ctx* ctx, const rt_material* table, int n_materials, const uint32_t* prim_material, size_t n_prims);
 /* types[i] in {0,1,2} for instance i of this context's next rt_set_instances (and of the current ones, re-issued at once);
@@ -249,7 +251,9 @@ int rt_set_materials(rt_ctx* ctx, const rt_material* table, int n_materials, con
 int rt_set_instance_types(rt_ctx* ctx, const uint32_t* types, int n);
 
 /* Uniform buffer copyData (src/main.cpp:1887-1889, 2901-2903).  RT_ERR_NOT_READY, with nothing changed, while the context holds a frame
- * batch (rt_set_batch with more than one frame): call rt_set_instances first. */
+ * batch (rt_set_batch with more than one frame): call rt_set_instances first.  The block is taken as it is; the calls that use it check
+ * it: a frame call or rt_shade_rays_device with samplesPerPixel 0 (frames) or maxBounceCount above 69 returns RT_ERR_INVALID_ARGUMENT,
+ * enqueues nothing and leaves a frame submitted before it, pending or not, as it was. */
 int rt_set_uniforms(rt_ctx* ctx, const rt_uniforms* u);
 
 /* Cube map creation + upload (src/main.cpp:2073-2412): 6 RGBA8 faces in the order

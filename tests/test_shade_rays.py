@@ -306,13 +306,13 @@ def test_argument_errors(ctx):
     assert _call(ctx, 1 << 24, 3, rays, so, po) == E
     assert _call(ctx, 1 << 62, 4, rays, so, po) == E
     u = sp.uniforms.copy()
-    u[0]["max_bounce_count"] = 71
+    u[0]["max_bounce_count"] = 70
     ctx.set_uniforms(u)
-    assert _call(ctx, 16, 1, rays, so, po) == E                        # maxBounceCount above the frame limit
+    assert _call(ctx, 16, 1, rays, so, po) == E                        # maxBounceCount above the frame limit (69)
     with pytest.raises(api.RtError) as e:
         ctx.trace(32, 16)
     assert e.value.code == E                                           # (the same limit as a frame's)
-    u[0]["max_bounce_count"] = 70
+    u[0]["max_bounce_count"] = 69
     ctx.set_uniforms(u)
     assert _call(ctx, 16, 1, rays, so, po) == 0
     torch.cuda.synchronize()

@@ -1016,9 +1016,8 @@ int enqueue_frame(rt_ctx* c, int W, int H, int band_rows, int shard, int n_shard
   if (K > 1) sc.batch_samples = (uint32_t)((size_t)u.samples_per_pixel * (size_t)rows * (size_t)W);
   const int n_inst1 = K > 1 ? sc.n_inst / K : sc.n_inst;   // instances of one frame
   const int frame_parity = again ? again->parity : c->parity;
-  if (!again) { c->last_frame = {W, H, band_rows, shard, n_shards, d_out, c->counting, sc, u, c->parity, c->inst_gen[c->parity], K, bt, c->batch_out_stride ? c->batch_out_stride : (uint32_t)((size_t)rows * W)}; c->frame_rerendered = false; }
   if (u.samples_per_pixel == 0) return fail(c, RT_ERR_INVALID_ARGUMENT, "samplesPerPixel must be >= 1");
-  if (u.max_bounce_count + 2 > (uint32_t)CNT_MAX_BOUNCES) return fail(c, RT_ERR_INVALID_ARGUMENT, "maxBounceCount too large (max 69)");
+  if (u.max_bounce_count > (uint32_t)BOUNCE_COUNT_LIMIT) return fail(c, RT_ERR_INVALID_ARGUMENT, "maxBounceCount too large (max 69)");
   const size_t tiles = (size_t)((W + 7) / 8) * (size_t)((rows + 7) / 8) * (size_t)K;
   const size_t samples = tiles * u.samples_per_pixel * 64;   // k_raygen threads
   if (samples >= 0xF0000000ull) return fail(c, RT_ERR_INVALID_ARGUMENT, "frame too large for 32-bit sample ids");
@@ -1033,6 +1032,8 @@ int enqueue_frame(rt_ctx* c, int W, int H, int band_rows, int shard, int n_shard
   const size_t shard_cap = std::max<size_t>(256, ((raygen_blocks + N_SHARDS - 1) / N_SHARDS) * 256) * (c->tile_blobs ? 2 : 1);
   const size_t capacity = shard_cap * N_SHARDS;
   int r = ensure_frame(c, capacity); if (r) return r;
+  // (only now: a call refused above leaves the frame submitted before it, which may still be pending, the one a re-render restores)
+  if (!again) { c->last_frame = {W, H, band_rows, shard, n_shards, d_out, c->counting, sc, u, c->parity, c->inst_gen[c->parity], K, bt, c->batch_out_stride ? c->batch_out_stride : (uint32_t)((size_t)rows * W)}; c->frame_rerendered = false; }
   FrameDev f = c->frame;
   // the counters of this frame were zeroed by the previous frame's k_resolve (or at allocation); this frame's k_resolve zeroes the other block
   f.counters = c->d_counters + (size_t)c->cnt_parity * CNT_WORDS; f.counters_next = c->d_counters + (size_t)(c->cnt_parity ^ 1) * CNT_WORDS;
@@ -2935,7 +2936,7 @@ int rt_shade_rays_device(rt_ctx* c, size_t n_points, uint32_t n_samples, const v
   if (((uintptr_t)d_rays8 | (uintptr_t)d_sample_rgba | (uintptr_t)d_point_rgba) & 15u)
     return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_shade_rays_device: rays and outputs must be 16-byte aligned");
   if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_shade_rays_device needs trace_variant 0");
-  if (c->uni.max_bounce_count + 2 > (uint32_t)CNT_MAX_BOUNCES) return fail(c, RT_ERR_INVALID_ARGUMENT, "maxBounceCount too large (the frame's limit)");
+  if (c->uni.max_bounce_count > (uint32_t)BOUNCE_COUNT_LIMIT) return fail(c, RT_ERR_INVALID_ARGUMENT, "maxBounceCount too large (the frame's limit: 69)");
   HIP_TRY(c, hipSetDevice(c->device));
   if (n) { int q = check_device_pointers(c, "rt_shade_rays_device", "rays and outputs", {d_rays8, d_sample_rgba, d_point_rgba}); if (q) return q; }
   if (!c->have_uni) return fail(c, RT_ERR_NOT_READY, "rt_set_uniforms has not been called");

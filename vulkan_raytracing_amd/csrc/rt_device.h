@@ -210,6 +210,7 @@ constexpr uint32_t CONT_FLAG = 0x80000000u;                        // | survivin
 constexpr int N_SHARDS = 8;
 constexpr int CNT_STRIDE = 32;                 // uint32 words between cursors: one 128-byte line each
 constexpr int CNT_MAX_BOUNCES = 72;            // bounce queues 0..71 (maxBounceCount <= 69)
+constexpr int BOUNCE_COUNT_LIMIT = 69;         // the limit frames and rt_shade_rays_device refuse beyond (include/rt_api.h: rt_set_uniforms)
 constexpr int Q_SHADOW = CNT_MAX_BOUNCES;      // queue id of the shadow-ray queue
 // pseudo-queues of the tile path (bounce 0 only).  The rays of tiles with a blob live in the SAME arrays as bounce queue 0, at the
 // top end of each shard's region, growing downwards (queue 0 grows upwards; a shard never holds more than shard_cap rays in all):

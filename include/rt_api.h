@@ -571,8 +571,9 @@ int rt_overlap_boxes(rt_ctx* ctx, size_t n, const float* boxes8_host, uint32_t c
  * of ctx's GPU: a closed world-space triangle; words 3, 7 and 11 are ignored.  A record with a non-finite vertex component is invalid:
  * its count is 0 and it lists nothing.  A zero-area query (a segment, a point) is valid and answered by the same arithmetic.
  * Candidates C(query): the triangles of every instance with (mask & cull_mask) != 0 that the canonical predicate below does not separate
- * from the query.  Both sets are closed: touching counts.  Instance flags, opacity and facing play no part; cull_mask is how a caller
- * leaves out the instance the query triangles came from.
+ * from the query.  Both sets are closed: touching counts.  Instance flags, opacity and facing play no part.  Query triangles that are
+ * triangles of the scene itself are better named by reference (rt_overlap_scene_triangles_device below), which leaves out their own
+ * instance by rule; for query triangles that are not in the scene, cull_mask is how a caller leaves out an instance they came from.
  * d_counts, d_ids, max_ids, RT_OVERLAP_ANY in flags, the pruning without d_counts: exactly as for rt_overlap_boxes_device.
  * Canonical predicate (DESIGN.md §5 "Triangle overlaps" has every operation in order): binary32, nothing fused except inside dot3 /
  * cross3 / xform_point / xform_vec, min / max are fminf / fmaxf.  A, B, C as for rt_overlap_boxes_device (a non-finite A, B
@@ -736,6 +737,60 @@ int rt_closest_triangle_device(rt_ctx* ctx, size_t n, const void* d_tris12, uint
 /* The blocking host form, as rt_closest_segment is to rt_closest_segment_device; params_host, when given, takes n x 2 floats. */
 int rt_closest_triangle(rt_ctx* ctx, size_t n, const float* tris12_host, uint32_t cull_mask,
                         rt_hit* out_host, float* params_host, int counting, rt_stats* stats);
+
+/* Triangles of the scene as the query, by (inst, prim) reference: the two triangle queries above asked about bodies of the scene
+ * itself ("does body 5 touch anything", "the clearance between link 3 and link 7") without a second copy of the mesh, without spending
+ * mask bits on self-exclusion, and for one pair of instances without walking the TLAS.
+ * References: d_refs4 holds n records of 16 B, 16-B aligned, memory of ctx's GPU; one buffer feeds all three calls. */
+typedef struct rt_tri_ref {
+  int32_t inst;     /* source instance: index into the context's current instance array */
+  int32_t prim;     /* source triangle: gl_PrimitiveID within that instance's mesh */
+  int32_t against;  /* RT_REF_AGAINST_OTHERS (-1): candidates from every instance except `inst`;
+                       >= 0: candidates from that instance only */
+  float   r_max;    /* search radius of rt_closest_scene_triangle_device; ignored by the overlap query */
+} rt_tri_ref;
+#define RT_REF_AGAINST_OTHERS (-1)
+/* The query triangle of a valid record is the world image of the source packet in the arithmetic of the candidate side: v0, v1, v2 from
+ * the scene's vertex buffer through the instance's mesh range (after rt_refit_blas_device: the refitted vertices), e1 = v1 - v0 and
+ * e2 = v2 - v0 each rounded once, P0 = xform_point(o2w, v0), P1 = P0 + xform_vec(o2w, e1), P2 = P0 + xform_vec(o2w, e2): exactly the
+ * (A, B, C) of the canonical predicates for that instance and packet.
+ * An invalid record is no error.  It is answered as the plain calls answer a record with a non-finite vertex: the overlap query gives
+ * count 0 and an empty row, the distance query the miss record with t = r_max as given.  A record is invalid when inst is outside
+ * [0, n_instances), prim is outside [0, triangles of the instance's mesh) (a mesh without triangles has no valid prim), against < -1 or
+ * against >= n_instances, the source triangle is a BAD TRIANGLE (rt_upload_geometry), or a coordinate of the world image is not finite
+ * (a source instance with a non-finite transform).  Nothing else about the source matters: its mask, its flags and cull_mask play no
+ * part in whether it may ask; a non-invertible or masked-out source with a finite image is a valid query.
+ * Candidates: those of the plain call for that world triangle (same predicate, same key, same cull_mask rule, same behaviour of void
+ * and non-invertible instances), restricted: with against == -1 the candidate's instance index must differ from inst; with
+ * against >= 0 it must equal against, and that instance must still be admitted by cull_mask.  against == inst is not special: the
+ * instance's own triangles are candidates, prim itself included.  The restriction removes candidates before the key's minimum or the
+ * row is formed; it never changes the test of a remaining pair.
+ * Role: the query side and the candidate side play different roles in the canonical sequences, so the record (a, i, against b) and the
+ * records of b against a are two different questions and may differ at ties.
+ *
+ * rt_scene_triangles_device writes the world triangles themselves: n records of 48 B in rt_overlap_triangles_device's layout into
+ * d_tris12 (16-B aligned, memory of ctx's GPU): words 0-2, 4-6, 8-10 = P0, P1, P2 (nine quiet NaNs, 0x7FC00000, for an invalid
+ * record), word 3 = r_max as given (bit pattern kept), word 7 = the bits of inst, word 11 = the bits of against.  The plain triangle
+ * calls ignore words 7 and 11, so the output feeds them directly, rt_overlap_boxes_device on its bounds, and drawing.
+ * Stream ordering, the TLAS and scene of the call, RT_ERR_NOT_READY and n == 0: as for rt_overlap_triangles_device.
+ * RT_ERR_INVALID_ARGUMENT: a NULL, misaligned or non-device pointer, n >= 0xFFFFFF00, trace_variant != 0. */
+int rt_scene_triangles_device(rt_ctx* ctx, size_t n, const void* d_refs4, void* d_tris12, void* hip_stream);
+/* rt_overlap_triangles_device with d_refs4 in the place of d_tris12: outputs, max_ids 0..16, RT_OVERLAP_ANY, the pruning without
+ * d_counts, the alignment rules, the RT_ERR_INVALID_ARGUMENT list, RT_ERR_NOT_READY, stream ordering without host synchronisation,
+ * n == 0 and the query workspace (which also holds the n x 48 B of expanded records; an allocation that fails is
+ * RT_ERR_OUT_OF_MEMORY and leaves the context as it was) are the plain call's.  Ids and counts name the candidate triangle. */
+int rt_overlap_scene_triangles_device(rt_ctx* ctx, size_t n, const void* d_refs4, uint32_t cull_mask, uint32_t flags,
+                                      uint32_t max_ids, void* d_ids, void* d_counts, void* hip_stream);
+/* The blocking host form, as rt_overlap_triangles is to rt_overlap_triangles_device; the expansion is inside the timed window. */
+int rt_overlap_scene_triangles(rt_ctx* ctx, size_t n, const rt_tri_ref* refs_host, uint32_t cull_mask, uint32_t flags,
+                               uint32_t max_ids, int32_t* ids_host, uint32_t* counts_host, int counting, rt_stats* stats);
+/* rt_closest_triangle_device with d_refs4 in the place of d_tris12, in the same way.  The hit names the candidate triangle; (qu, qv)
+ * and the side word of d_attr refer to the source triangle's world image. */
+int rt_closest_scene_triangle_device(rt_ctx* ctx, size_t n, const void* d_refs4, uint32_t cull_mask,
+                                     void* d_hits, void* d_attr, void* d_params, void* hip_stream);
+/* The blocking host form, as rt_closest_triangle is to rt_closest_triangle_device. */
+int rt_closest_scene_triangle(rt_ctx* ctx, size_t n, const rt_tri_ref* refs_host, uint32_t cull_mask,
+                              rt_hit* out_host, float* params_host, int counting, rt_stats* stats);
 
 /* Inside / outside: for every point, is it enclosed by the scene's surfaces (Open3D's compute_occupancy and compute_signed_distance),
  * for signed distance fields, penetration tests, occupancy and voxel filling.  The answer is a vote over the crossing parities of a few

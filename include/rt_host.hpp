@@ -229,6 +229,35 @@ class Renderer {
   rt_stats wait(const void*& pixels) { rt_stats st{}; check(rt_trace_wait(ctx_, &pixels, &st), "rt_trace_wait"); return st; }
   void setParam(const char* name, int value) { check(rt_set_param(ctx_, name, value), "rt_set_param"); }
   void setTiming(bool on) { check(rt_set_timing(ctx_, on ? 1 : 0), "rt_set_timing"); }
+  // Triangles of the scene as the query, by (inst, prim) reference (rt_tri_ref; against = RT_REF_AGAINST_OTHERS: every other body):
+  // the blocking host forms.  counts[i]: the scene triangles that cut or touch reference i; ids: maxIds (inst, prim) pairs per row.
+  rt_stats overlapSceneTriangles(const std::vector<rt_tri_ref>& refs, std::vector<uint32_t>& counts, std::vector<int32_t>* ids = nullptr, uint32_t maxIds = 0,
+                                 uint32_t cullMask = 0xFF) {
+    counts.resize(refs.size());
+    if (ids) ids->resize(refs.size() * maxIds * 2);
+    rt_stats st{};
+    check(rt_overlap_scene_triangles(ctx_, refs.size(), refs.data(), cullMask, 0, ids ? maxIds : 0, ids && maxIds ? ids->data() : nullptr, counts.data(), 0, &st),
+          "rt_overlap_scene_triangles");
+    return st;
+  }
+  // hits[i]: the nearest scene triangle to reference i within its r_max (a miss: inst = prim = -1, t = r_max); quv: the source's (qu, qv)
+  rt_stats closestSceneTriangle(const std::vector<rt_tri_ref>& refs, std::vector<rt_hit>& hits, std::vector<float>* quv = nullptr, uint32_t cullMask = 0xFF) {
+    hits.resize(refs.size());
+    if (quv) quv->resize(refs.size() * 2);
+    rt_stats st{};
+    check(rt_closest_scene_triangle(ctx_, refs.size(), refs.data(), cullMask, hits.data(), quv ? quv->data() : nullptr, 0, &st), "rt_closest_scene_triangle");
+    return st;
+  }
+  // the device forms, on device memory of this context's GPU, ordered on `stream` (see include/rt_api.h)
+  void sceneTrianglesDevice(size_t n, const void* dRefs4, void* dTris12, void* stream) {
+    check(rt_scene_triangles_device(ctx_, n, dRefs4, dTris12, stream), "rt_scene_triangles_device");
+  }
+  void overlapSceneTrianglesDevice(size_t n, const void* dRefs4, uint32_t cullMask, uint32_t flags, uint32_t maxIds, void* dIds, void* dCounts, void* stream) {
+    check(rt_overlap_scene_triangles_device(ctx_, n, dRefs4, cullMask, flags, maxIds, dIds, dCounts, stream), "rt_overlap_scene_triangles_device");
+  }
+  void closestSceneTriangleDevice(size_t n, const void* dRefs4, uint32_t cullMask, void* dHits, void* dAttr, void* dParams, void* stream) {
+    check(rt_closest_scene_triangle_device(ctx_, n, dRefs4, cullMask, dHits, dAttr, dParams, stream), "rt_closest_scene_triangle_device");
+  }
 
  private:
   void check(int r, const char* fn) { if (r) throwExceptionRtAPI(r, fn, ctx_); }

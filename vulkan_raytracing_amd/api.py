@@ -21,7 +21,7 @@ NODEQ_DTYPE = np.dtype([("w", np.uint32, 6), ("child", np.int32, 2)])
 TRI_PACKET_DTYPE = np.dtype([("v0", np.float32, 3), ("e1", np.float32, 3), ("e2", np.float32, 3), ("prim", np.uint32), ("pad", np.uint32, 2)])
 INSTANCE_DEV_DTYPE = np.dtype([("w2o", np.float32, 12), ("o2w", np.float32, 12), ("blas_root", np.int32), ("mask", np.uint32), ("custom_index", np.int32),
                                ("first_float", np.uint32), ("first_index", np.uint32), ("blas_root4", np.int32), ("q_lo", np.float32, 3), ("q_scale", np.float32, 3),
-                               ("type", np.uint32), ("cover_first", np.uint32), ("cover_count", np.uint32), ("pad", np.uint32)])
+                               ("type", np.uint32), ("cover_first", np.uint32), ("cover_count", np.uint32), ("prim_count", np.uint32)])
 TLAS_MESH_DTYPE = np.dtype([("blas_root", np.int32), ("blas_root4", np.int32), ("first_float", np.uint32), ("first_index", np.uint32),
                             ("cover_first", np.uint32), ("cover_count", np.uint32), ("prim_count", np.uint32), ("built", np.uint32), ("levels", np.int32),
                             ("q_lo", np.float32, 3), ("q_scale", np.float32, 3), ("lo", np.float32, 3), ("hi", np.float32, 3)])
@@ -68,13 +68,17 @@ INSTANCE_FLAG_FORCE_OPAQUE = 0x4
 INSTANCE_FLAG_FORCE_NO_OPAQUE = 0x8
 HIT_KIND_FRONT_FACING = 0xFE
 HIT_KIND_BACK_FACING = 0xFF
+# rt_tri_ref (include/rt_api.h): a triangle of the scene as the query of overlap_scene_triangles* / closest_scene_triangle*
+TRI_REF_DTYPE = np.dtype([("inst", np.int32), ("prim", np.int32), ("against", np.int32), ("r_max", np.float32)])
+assert TRI_REF_DTYPE.itemsize == 16
+REF_AGAINST_OTHERS = -1
 OVERLAP_ANY = 0x1   # rt_overlap_boxes_device: occupancy (counts of 0 or 1)
 # rt_point_inside_device: the direction table (RT_INSIDE_DIRS of include/rt_api.h; rounded to binary32, not normalised)
 INSIDE_DIRS = ((0.36, 0.48, 0.8), (-0.8, 0.36, -0.48), (0.48, -0.8, -0.36), (-0.6, -0.64, 0.48), (0.64, -0.48, 0.6))
 
 EXPORTS = ["rt_create", "rt_create_frame_slot", "rt_destroy", "rt_upload_geometry", "rt_build_blas", "rt_set_instances", "rt_set_instances_device", "rt_refit_blas_device", "rt_set_materials", "rt_set_instance_types", "rt_set_uniforms", "rt_set_skybox",
            "rt_trace", "rt_trace_async", "rt_trace_wait", "rt_trace_shard", "rt_set_batch", "rt_trace_shard_batch", "rt_assemble_shards", "rt_shard_rows", "rt_synchronize", "rt_get_stats", "rt_set_timing", "rt_intersect",
-           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_closest_point_device_hits", "rt_closest_point_hits", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_overlap_triangles_device", "rt_overlap_triangles", "rt_sweep_spheres_device", "rt_sweep_spheres", "rt_closest_segment_device", "rt_closest_segment", "rt_closest_triangle_device", "rt_closest_triangle", "rt_point_inside_device", "rt_point_inside", "rt_signed_distance_device", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_host_blas", "rt_debug_snapshot", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
+           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_closest_point_device_hits", "rt_closest_point_hits", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_overlap_triangles_device", "rt_overlap_triangles", "rt_sweep_spheres_device", "rt_sweep_spheres", "rt_closest_segment_device", "rt_closest_segment", "rt_closest_triangle_device", "rt_closest_triangle", "rt_scene_triangles_device", "rt_overlap_scene_triangles_device", "rt_overlap_scene_triangles", "rt_closest_scene_triangle_device", "rt_closest_scene_triangle", "rt_point_inside_device", "rt_point_inside", "rt_signed_distance_device", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_host_blas", "rt_debug_snapshot", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
 
 _LIBS = {}
 
@@ -136,6 +140,11 @@ def lib(variant=None):
         L.rt_overlap_boxes.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_int, C.POINTER(RtStats)]
         L.rt_overlap_triangles_device.argtypes = L.rt_overlap_boxes_device.argtypes
         L.rt_overlap_triangles.argtypes = L.rt_overlap_boxes.argtypes
+        L.rt_scene_triangles_device.argtypes = [vp, C.c_size_t, vp, vp, vp]
+        L.rt_overlap_scene_triangles_device.argtypes = L.rt_overlap_boxes_device.argtypes
+        L.rt_overlap_scene_triangles.argtypes = L.rt_overlap_boxes.argtypes
+        L.rt_closest_scene_triangle_device.argtypes = L.rt_closest_triangle_device.argtypes
+        L.rt_closest_scene_triangle.argtypes = L.rt_closest_triangle.argtypes
         L.rt_shade_rays_device.argtypes = [vp, C.c_size_t, C.c_uint32, vp, vp, vp, vp]
         L.rt_last_error.argtypes = [vp]
         L.rt_last_error.restype = C.c_char_p
@@ -633,10 +642,11 @@ class RtContext:
         include/rt_api.h."""
         return self._overlap_device(boxes, "overlap_boxes", 8, "box", "boxes", max_ids, cull_mask, any, counts, stream, out)
 
-    def _overlap_device(self, boxes, name, cols, noun, nouns, max_ids, cull_mask, any, counts, stream, out):
-        """overlap_boxes_device and overlap_triangles_device: the checks, the buffers and the call rt_<name>_device on `stream`"""
+    def _overlap_device(self, boxes, name, cols, noun, nouns, max_ids, cull_mask, any, counts, stream, out, int32=False):
+        """overlap_boxes_device, overlap_triangles_device and overlap_scene_triangles_device (int32 records): the checks, the buffers and
+        the call rt_<name>_device on `stream`"""
         import torch
-        self._check_rays(boxes, name + "_device", cols, noun)
+        self._check_rays(boxes, name + "_device", cols, noun, int32)
         fn = getattr(self.L, "rt_%s_device" % name)
         k = int(max_ids)
         if not 0 <= k <= 16:
@@ -689,7 +699,8 @@ class RtContext:
         """rt_overlap_triangles_device: the triangles of the scene that cut or touch every query triangle.  `tris` is a contiguous float32
         torch tensor (n, 12) on this context's GPU (P0.xyz, ignored, P1.xyz, ignored, P2.xyz, ignored per row: a closed world-space
         triangle; triangle_records builds such rows from a mesh), read in the order of `stream`.  Every other argument and the BoxOverlaps
-        result as for overlap_boxes_device; cull_mask is how the instance the queries came from is left out.  See include/rt_api.h."""
+        result as for overlap_boxes_device.  For triangles of the scene itself see overlap_scene_triangles_device; for others cull_mask is how an
+        instance the queries came from is left out.  See include/rt_api.h."""
         return self._overlap_device(tris, "overlap_triangles", 12, "triangle", "triangles", max_ids, cull_mask, any, counts, stream, out)
 
     def overlap_triangles(self, tris12, max_ids=0, cull_mask=0xFF, any=False, counts=True, counting=False):
@@ -704,6 +715,90 @@ class RtContext:
                                               _p(ids) if ids is not None else None, _p(cnt) if cnt is not None else None, int(counting), C.byref(st)),
                   "rt_overlap_triangles")
         return cnt, ids, st
+
+    def scene_triangles_device(self, refs, stream=None, out=None):
+        """rt_scene_triangles_device: the world triangles of (inst, prim) references.  `refs` is a contiguous int32 torch tensor (n, 4) on
+        this context's GPU (inst, prim, against, the bits of r_max per row; triangle_refs packs it), read in the order of `stream`.
+        Returns a float32 (n, 12) tensor in overlap_triangles_device's layout: P0.xyz, r_max, P1.xyz, the bits of inst, P2.xyz, the bits
+        of against; an invalid reference has nine NaNs.  out reuses such a tensor.  See include/rt_api.h."""
+        import torch
+        self._check_rays(refs, "scene_triangles_device", 4, "reference", True)
+        n = refs.shape[0]
+        cur = torch.cuda.current_stream(refs.device)
+        if stream is None:
+            stream = cur
+        if out is None:
+            out = torch.empty((n, 12), dtype=torch.float32, device=refs.device)
+            if stream != cur:   # (allocated for the current stream, written on `stream`)
+                out.record_stream(stream)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (n, 12) or not out.is_contiguous() or out.device != refs.device:
+            raise ValueError("out must be a contiguous float32 (n, 12) tensor on the references' device")
+
+        def call(run):
+            return self.L.rt_scene_triangles_device(self.h, n, C.c_void_p(refs.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(run.cuda_stream))
+        if n:
+            self._on_stream(stream, (refs, out), call, "rt_scene_triangles_device")
+        return out
+
+    def overlap_scene_triangles_device(self, refs, max_ids=0, cull_mask=0xFF, any=False, counts=True, stream=None, out=None):
+        """rt_overlap_scene_triangles_device: overlap_triangles_device asked about triangles of the scene itself.  `refs` is
+        scene_triangles_device's tensor (triangle_refs packs it): against = -1 takes candidates from every instance but the source's,
+        against >= 0 from that instance only.  Every other argument and the BoxOverlaps result as for overlap_triangles_device.  See
+        include/rt_api.h."""
+        return self._overlap_device(refs, "overlap_scene_triangles", 4, "reference", "references", max_ids, cull_mask, any, counts, stream, out, int32=True)
+
+    def overlap_scene_triangles(self, refs, max_ids=0, cull_mask=0xFF, any=False, counts=True, counting=False):
+        """rt_overlap_scene_triangles: the blocking host form (refs: TRI_REF_DTYPE records or (n, 4) int32 rows) -> (counts uint32 (n,) or
+        None, ids int32 (n, max_ids, 2) or None, RtStats; with counting its node_visits / tri_tests are filled)"""
+        refs = _host_refs(refs)
+        n, k = len(refs), int(max_ids)
+        cnt = np.zeros(n, np.uint32) if counts else None
+        ids = np.zeros((n, k, 2), np.int32) if k else None
+        st = RtStats()
+        self._chk(self.L.rt_overlap_scene_triangles(self.h, n, _p(refs), int(cull_mask) & 0xFFFFFFFF, OVERLAP_ANY if any else 0, k & 0xFFFFFFFF,
+                                                    _p(ids) if ids is not None else None, _p(cnt) if cnt is not None else None, int(counting), C.byref(st)),
+                  "rt_overlap_scene_triangles")
+        return cnt, ids, st
+
+    def closest_scene_triangle_device(self, refs, cull_mask=0xFF, attributes=False, params=False, stream=None, out=None):
+        """rt_closest_scene_triangle_device: closest_triangle_device asked about triangles of the scene itself.  `refs` is
+        scene_triangles_device's tensor (triangle_refs packs it, r_max the search radius).  The RayQuery names the candidate triangle;
+        quv and hit_kind refer to the source triangle's world image.  Every other argument as for closest_triangle_device.  See
+        include/rt_api.h."""
+        import torch
+        self._check_rays(refs, "closest_scene_triangle_device", 4, "reference", True)
+        n = refs.shape[0]
+        quv = None
+        if out is not None and len(out) == 3:
+            quv, out = out[2], tuple(out[:2])
+            if params and (quv is None or quv.dtype != torch.float32 or tuple(quv.shape) != (n, 2) or not quv.is_contiguous() or quv.device != refs.device):
+                raise ValueError("out quv must be a contiguous float32 (n, 2) tensor on the references' device")
+        if not params:
+            quv = None
+        elif quv is None:
+            quv = torch.empty((n, 2), dtype=torch.float32, device=refs.device)
+
+        def call(run, hits, attr):
+            if quv is not None:
+                quv.record_stream(run)
+            return self.L.rt_closest_scene_triangle_device(self.h, n, C.c_void_p(refs.data_ptr()), int(cull_mask) & 0xFFFFFFFF, C.c_void_p(hits.data_ptr()),
+                                                           C.c_void_p(attr.data_ptr()) if attr is not None else None,
+                                                           C.c_void_p(quv.data_ptr()) if quv is not None else None, C.c_void_p(run.cuda_stream))
+        hits, attr = self._device_query(refs, attributes, stream, out, (), call, "rt_closest_scene_triangle_device", cols=4, checked=True)
+        res = RayQuery(hits, attr, hit_kind=True)
+        res.quv = quv
+        return res
+
+    def closest_scene_triangle(self, refs, cull_mask=0xFF, params=False, counting=False):
+        """rt_closest_scene_triangle: the blocking host form (refs: TRI_REF_DTYPE records or (n, 4) int32 rows) -> (HIT_DTYPE records,
+        RtStats; with counting its node_visits / tri_tests are filled), or with params=True (records, (qu, qv) float32 (n, 2), RtStats)"""
+        refs = _host_refs(refs)
+        out = np.zeros(len(refs), HIT_DTYPE)
+        quv = np.zeros((len(refs), 2), np.float32) if params else None
+        st = RtStats()
+        self._chk(self.L.rt_closest_scene_triangle(self.h, len(refs), _p(refs), int(cull_mask) & 0xFFFFFFFF, _p(out), _p(quv) if quv is not None else None,
+                                                   int(counting), C.byref(st)), "rt_closest_scene_triangle")
+        return (out, quv, st) if params else (out, st)
 
     def intersect_device_hits(self, rays, max_hits, ray_flags=0, cull_mask=0xFF, words=None, attributes=False, counts=True, stream=None, out=None):
         """rt_intersect_device_hits: every candidate along each ray, the first max_hits of them in (t, inst, prim) order, and their number.
@@ -843,15 +938,16 @@ class RtContext:
             self._on_stream(stream, (rays, srgba, prgba), call, "rt_shade_rays_device")
         return srgba, prgba
 
-    def _check_rays(self, rays, name, cols=8, noun="ray"):
-        """the checks of a (n, 8) float32 ray tensor (or, with cols=4 and noun="point", a (n, 4) point tensor) on this context's GPU"""
+    def _check_rays(self, rays, name, cols=8, noun="ray", int32=False):
+        """the checks of a (n, 8) float32 ray tensor (or, with cols=4 and noun="point", a (n, 4) point tensor; with int32, an int32
+        tensor: the (n, 4) references of triangle_refs) on this context's GPU"""
         import torch
         if not isinstance(rays, torch.Tensor):
             raise TypeError("%s takes a torch tensor, got %s" % (name, type(rays).__name__))
         if rays.device.type != "cuda" or rays.device.index != self.device:
             raise ValueError("%s tensor must live on cuda:%d (the context's GPU), not %s" % (noun, self.device, rays.device))
-        if rays.dtype != torch.float32:
-            raise ValueError("%s tensor must be float32, not %s" % (noun, rays.dtype))
+        if rays.dtype != (torch.int32 if int32 else torch.float32):
+            raise ValueError("%s tensor must be %s, not %s" % (noun, "int32" if int32 else "float32", rays.dtype))
         if not rays.is_contiguous():
             raise ValueError("%s tensor must be contiguous" % noun)
         if rays.dim() != 2 or rays.shape[1] != cols:
@@ -1015,6 +1111,39 @@ def triangle_records(vertices, faces, r_max=0.0):
     rec[:, :, :3] = np.asarray(vertices, np.float32).reshape(-1, 3)[f]
     rec[:, 0, 3] = np.asarray(r_max.cpu() if hasattr(r_max, "cpu") else r_max, np.float32)
     return rec.reshape(-1, 12)
+
+
+def _host_refs(refs):
+    """host references as contiguous (n, 4) int32 rows: TRI_REF_DTYPE records or anything triangle_refs returns for numpy input"""
+    refs = np.asarray(refs)
+    if refs.dtype == TRI_REF_DTYPE:
+        return np.ascontiguousarray(refs).view(np.int32).reshape(-1, 4)
+    if refs.dtype != np.int32:
+        raise ValueError("references must be TRI_REF_DTYPE records or int32 rows, not %s" % refs.dtype)
+    return np.ascontiguousarray(refs).reshape(-1, 4)
+
+
+def triangle_refs(inst, prim, against=REF_AGAINST_OTHERS, r_max=float("inf")):
+    """the (n, 4) int32 rows (rt_tri_ref: inst, prim, against, the bits of r_max) of scene_triangles_device, overlap_scene_triangles* and
+    closest_scene_triangle*: triangle `prim` of instance `inst` as the query, against every other instance (against = -1) or against
+    that instance only.  inst, prim, against and r_max broadcast against each other ((n,) or scalars).  torch tensors stay on their
+    device; anything else goes through numpy (the rows then view as TRI_REF_DTYPE)."""
+    try:
+        import torch
+        dev = next((x.device for x in (inst, prim, against, r_max) if isinstance(x, torch.Tensor)), None)
+    except ImportError:
+        dev = None
+    if dev is not None:
+        i, p, a, r = torch.broadcast_tensors(*(torch.as_tensor(x, device=dev).reshape(-1) for x in (inst, prim, against, r_max)))
+        rec = torch.empty((i.shape[0], 4), dtype=torch.int32, device=dev)
+        rec[:, 0] = i.to(torch.int32); rec[:, 1] = p.to(torch.int32); rec[:, 2] = a.to(torch.int32)
+        rec[:, 3] = r.to(torch.float32).contiguous().view(torch.int32)
+        return rec
+    i, p, a, r = np.broadcast_arrays(*(np.asarray(x).reshape(-1) for x in (inst, prim, against, r_max)))
+    rec = np.empty((len(i), 4), np.int32)
+    rec[:, 0] = i.astype(np.int64).astype(np.int32); rec[:, 1] = p.astype(np.int64).astype(np.int32); rec[:, 2] = a.astype(np.int64).astype(np.int32)
+    rec[:, 3] = np.ascontiguousarray(r, np.float32).view(np.int32)
+    return rec
 
 
 def capsule_records(p0, p1, r_max):

@@ -2469,6 +2469,8 @@ void launch_resolve_points(const float4* sample_color, float4* out, uint32_t n_p
 
 #include "kernels_triangle.inc"   // k_closest_triangle, k_triangle_side: the nearest pair of every query triangle and the surface (rt_closest_triangle_device)
 
+#include "kernels_refs.inc"   // k_refs_expand, k_refs_collide, k_refs_nearest: the two triangle queries over (inst, prim) references (rt_*_scene_triangle*_device)
+
 int tail_blocks_per_cu() {
   // the smallest over the instantiations: any of them may be the one in flight (counting; 4-ary records in the alt build)
   int n = 1 << 30, v = 0;

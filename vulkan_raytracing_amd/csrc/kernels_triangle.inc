@@ -158,7 +158,9 @@ __device__ __forceinline__ bool triangle_box(uint32_t wx, uint32_t wy, uint32_t 
   return open;
 }
 
-template <bool COUNT>
+// REFS (kernels_refs.inc, rt_closest_scene_triangle_device): collide_body's two changes — a valid record with against >= 0 (word 11)
+// starts at that instance's TLAS leaf, one against the others passes over its source instance (word 7).  Everything else is shared.
+template <bool COUNT, bool REFS = false>
 __device__ __forceinline__ void triangle_body(const TriangleArgs& a) {
   __shared__ int s_stack[4][STACK2_LDS][64];
   WalkStack st(s_stack, a.ovf_stack, a.sc.ovf_stride);
@@ -216,6 +218,7 @@ __device__ __forceinline__ void triangle_body(const TriangleArgs& a) {
       world_space();
       cur_inst = -1;
       st.reset(); cur = valid ? a.sc.tlas_root : REF_DONE;
+      if (REFS && valid && (int)__float_as_uint(r2.w) >= 0) cur = ~(int)__float_as_uint(r2.w);   // (k_refs_expand: below n_inst)
       need = false;
     }
     if (__ballot(!need) == 0) break;   // every lane idle and the records used up
@@ -270,7 +273,12 @@ __device__ __forceinline__ void triangle_body(const TriangleArgs& a) {
       // ---- TLAS leaf: enter the instance if the call's mask lets it (the vertices -> object space, the slack of both spaces in object units)
       const int ii = ~cur;
       const InstanceDev* I = a.sc.inst + ii;
-      if (((I->mask >> INST_WORLD_MASK_SHIFT) & a.cull_mask & 0xFFu) != 0u) {
+      bool own = false;   // REFS: the source instance of a record against the others (words 7 and 11, read again)
+      if (REFS) {
+        const float4* qp = a.tris + 3u * (size_t)pt;
+        own = (int)__float_as_uint(qp[2].w) < 0 && ii == (int)__float_as_uint(qp[1].w);
+      }
+      if (((I->mask >> INST_WORLD_MASK_SHIFT) & a.cull_mask & 0xFFu) != 0u && !own) {
         // the closest-point walks' entry with the per-component largest magnitude of the vertices as the point (its slack formula reads
         // |wp| only; the object-space point it returns for that argument is not used), then the vertices themselves through w2o
         const F3 ap = mk3(fmaxf(fmaxf(__builtin_fabsf(w0.x), __builtin_fabsf(w1.x)), __builtin_fabsf(w2.x)),

@@ -71,7 +71,10 @@ __device__ __forceinline__ bool collide_tri(F3 wlo, F3 whi, F3 P0, F3 P1, F3 P2,
   return !sep;
 }
 
-template <bool COUNT>
+// REFS (kernels_refs.inc, rt_overlap_scene_triangles_device): the records are k_refs_expand's, words 7 and 11 the source instance and
+// `against`; a valid record with against >= 0 starts at that instance's TLAS leaf with nothing beneath it, so the TLAS is never walked,
+// and with against == -1 the TLAS-leaf branch passes over the source instance.  Everything else is shared.
+template <bool COUNT, bool REFS = false>
 __device__ __forceinline__ void collide_body(const CollideArgs& a) {
   __shared__ int s_stack[4][STACK2_LDS][64];
   WalkStack st(s_stack, a.ovf_stack, a.sc.ovf_stride);
@@ -112,6 +115,7 @@ __device__ __forceinline__ void collide_body(const CollideArgs& a) {
       world_space();
       cur_inst = -1; count = 0;
       st.reset(); cur = valid ? a.sc.tlas_root : REF_DONE;
+      if (REFS && valid && (int)__float_as_uint(r2.w) >= 0) cur = ~(int)__float_as_uint(r2.w);   // (k_refs_expand: below n_inst)
       row = a.ids + (size_t)bx * K;
       need = false;
     }
@@ -183,7 +187,12 @@ __device__ __forceinline__ void collide_body(const CollideArgs& a) {
       // ---- TLAS leaf: enter the instance if the call's mask lets it and, when pruning, the row could still take one of its triangles
       const int ii = ~cur;
       const InstanceDev* I = a.sc.inst + ii;
-      if (((I->mask >> INST_WORLD_MASK_SHIFT) & a.cull_mask & 0xFFu) != 0u && !(prune && K != 0u && count >= K && ii > last_inst)) {
+      bool own = false;   // REFS: the source instance of a record against the others (words 7 and 11, read again)
+      if (REFS) {
+        const float4* qp = a.tris + 3u * (size_t)bx;
+        own = (int)__float_as_uint(qp[2].w) < 0 && ii == (int)__float_as_uint(qp[1].w);
+      }
+      if (((I->mask >> INST_WORLD_MASK_SHIFT) & a.cull_mask & 0xFFu) != 0u && !(prune && K != 0u && count >= K && ii > last_inst) && !own) {
         overlap_enter_instance(I, a.inst_scale[1 + ii], qlo, qhi, q_lo, q_scale);
         st.push(REF_MARK);
         cur_inst = ii; cur = I->blas_root;

@@ -306,6 +306,9 @@ struct rt_ctx {
                                    // rt_closest_triangle_device with d_attr and without d_params: the parameters k_segment_side (one per
                                    // record) and k_triangle_side (two) read; part of the query workspace
   size_t q_words_alloc = 0;        // words of d_q_words
+  float4* d_q_tris = nullptr;      // rt_overlap_scene_triangles*, rt_closest_scene_triangle*: the 48-byte records k_refs_expand makes of the
+                                   // references, which the walk then reads; part of the query workspace
+  size_t q_tris_alloc = 0;         // records of d_q_tris
   hipEvent_t ev_query[2] = {nullptr, nullptr};
   bool ev_query_valid[2] = {false, false};
   int query_last = -1;             // parity of the last query (-1: none since the last host wait)
@@ -1486,6 +1489,7 @@ void rt_destroy(rt_ctx* c) {
   if (c->d_q_ovf) hipFree(c->d_q_ovf);
   if (c->d_q_scale) hipFree(c->d_q_scale);
   if (c->d_q_words) hipFree(c->d_q_words);
+  if (c->d_q_tris) hipFree(c->d_q_tris);
   for (int k = 0; k < 2; k++) if (c->ev_query[k]) hipEventDestroy(c->ev_query[k]);
   tlas_gpu_free(c->tgpu);
   for (auto e : c->ev_pool) hipEventDestroy(e);
@@ -1636,7 +1640,7 @@ static int set_instances_frames(rt_ctx* c, const rt_instance* inst, int n, int u
     d.first_float = (uint32_t)m.range.first_float;
     d.first_index = (uint32_t)m.range.first_index;
     d.type = (size_t)(i % n) < c->inst_types.size() ? c->inst_types[i % n] : TYPE_BY_OBJECT_INDEX;
-    d.cover_first = m.cover_first; d.cover_count = m.range.prim_count ? m.cover_count : 0u; d.pad = 0;
+    d.cover_first = m.cover_first; d.cover_count = m.range.prim_count ? m.cover_count : 0u; d.prim_count = m.range.prim_count;
     boxes[i] = instance_world_box(d.o2w, m.bounds);
     const int state = instance_record_state(d.o2w, d.w2o, boxes[i]);
     if (state == REC_VOID) {   // the record of an empty mesh: it enters no bounds and nothing enters it
@@ -2360,13 +2364,17 @@ enum class Walk {
   Sweep,     // rt_sweep_spheres*: the first contact of every moving sphere (the same scales first)
   Segment,   // rt_closest_segment*: the nearest surface point of every segment and its parameter (the same scales first)
   Triangle,  // rt_closest_triangle*: the nearest pair of every query triangle and the surface, and its (qu, qv) (the same scales first)
-  Inside     // rt_point_inside*: the inside / outside vote; with hits, rt_signed_distance_device: the closest-point walk into hits (and
+  Inside,    // rt_point_inside*: the inside / outside vote; with hits, rt_signed_distance_device: the closest-point walk into hits (and
              // attr) first, the vote with the counter block's cursor initialised again, then the sign pass over hits
+  Expand     // rt_scene_triangles_device: k_refs_expand alone, the references' 48-byte records into tris_out
 };
 struct Query {
   Walk walk = Walk::Plain;
   size_t n = 0;
   const void* records = nullptr;     // n ray, point, box, sweep or triangle records
+  bool refs = false;                 // Triangles, Triangle, Expand: the records are n references (rt_tri_ref).  k_refs_expand makes their
+                                     // 48-byte records first (Triangles, Triangle: in the workspace; the by-reference walks read them)
+  void* tris_out = nullptr;          // Expand: the n records of 48 bytes
   const void* ray_words = nullptr;   // Flags, Hits: n per-ray words, or none
   uint32_t query_word = 0;           // Flags, Hits: the call's ray flags | cull mask << 24
   uint32_t cull_mask = 0;            // Closest, ClosestHits, Overlap, Sweep, Segment, Triangle, Inside
@@ -2389,8 +2397,18 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q
   const bool triangle = q.walk == Walk::Triangle;
   const bool closest = q.walk == Walk::Closest || (inside && q.hits);
   const uint32_t n = (uint32_t)q.n;
-  const float4* const records = (const float4*)q.records;
+  const float4* records = (const float4*)q.records;
   { int r = query_workspace(c, s); if (r) return r; }
+  if (q.refs && q.walk != Walk::Expand) {   // the expanded records: a new area before the old one goes, so that a failure changes nothing
+    if (q.n > c->q_tris_alloc) {
+      { int w = wait_queries(c, c); if (w) return w; }
+      float4* grown = nullptr;
+      HIP_TRY(c, hipMalloc((void**)&grown, q.n * 3 * sizeof(float4)));
+      if (c->d_q_tris) (void)hipFree(c->d_q_tris);
+      c->d_q_tris = grown; c->q_tris_alloc = q.n;
+    }
+    records = c->d_q_tris;
+  }
   uint32_t* words = (uint32_t*)q.words;
   if (segment || triangle) words = (uint32_t*)q.params;
   if ((inside && !words) || ((segment || triangle) && !words && q.attr)) {   // (signed distance without d_inside; segment and triangle attributes without d_params)
@@ -2407,6 +2425,7 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q
   if (q.counting) HIP_TRY(c, hipMemsetAsync(c->d_q_counters, 0, CNT_WORDS * sizeof(uint32_t), s));
   const SceneDev sc = scene_dev(c);
   if (q.t0) HIP_TRY(c, hipEventRecord(q.t0, s));
+  if (q.refs) launch_refs_expand(sc, q.records, q.walk == Walk::Expand ? (float4*)q.tris_out : c->d_q_tris, n, c->scene->h_verts.size(), s);
   if (closest || sweep || segment || triangle || q.walk == Walk::ClosestHits || q.walk == Walk::Overlap || q.walk == Walk::Triangles) launch_closest_scale(sc, c->d_q_scale, s);
   switch (q.walk) {
     case Walk::Plain: launch_query(sc, records, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, q.any_hit, q.counting, cfg, s); break;
@@ -2424,19 +2443,22 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q
       launch_overlap_boxes(sc, records, q.cull_mask, c->d_q_scale, q.overlap_any, q.max_ids, q.ids, (uint32_t*)q.counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
       break;
     case Walk::Triangles:
-      launch_collide_triangles(sc, records, q.cull_mask, c->d_q_scale, q.overlap_any, q.max_ids, q.ids, (uint32_t*)q.counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
+      if (q.refs) launch_refs_collide(sc, records, q.cull_mask, c->d_q_scale, q.overlap_any, q.max_ids, q.ids, (uint32_t*)q.counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
+      else launch_collide_triangles(sc, records, q.cull_mask, c->d_q_scale, q.overlap_any, q.max_ids, q.ids, (uint32_t*)q.counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
       break;
     case Walk::Sweep: launch_sweep_spheres(sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s); break;
     case Walk::Segment:
       launch_closest_segment(sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, (float*)words, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
       break;
     case Walk::Triangle:
-      launch_closest_triangle(sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, (float*)words, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
+      if (q.refs) launch_refs_nearest(sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, (float*)words, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
+      else launch_closest_triangle(sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, (float*)words, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
       break;
     case Walk::Inside:
       if (closest) launch_closest_point(sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, false, cfg, s);
       launch_point_inside(sc, records, q.cull_mask, q.n_dirs, words, (uint32_t*)q.counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
       break;
+    case Walk::Expand: break;   // (the expansion above is the whole call)
   }
   if (q.t1) HIP_TRY(c, hipEventRecord(q.t1, s));
   if (q.attr && q.walk != Walk::Hits && q.walk != Walk::ClosestHits) {
@@ -2858,6 +2880,88 @@ int rt_closest_triangle(rt_ctx* c, size_t n, const float* tris12, uint32_t cull_
   Query q; q.walk = Walk::Triangle; q.n = n; q.cull_mask = cull_mask; q.counting = counting != 0;
   return blocking_query(c, q, tris12, tri_bytes, tri_bytes + hit_bytes + par_bytes,
                         {{&Query::hits, tri_bytes, out, hit_bytes}, {&Query::params, tri_bytes + hit_bytes, params, par_bytes}}, stats);
+}
+
+// The world triangles of (inst, prim) references: the checks and ordering of a device query (rt_closest_point_device), then k_refs_expand
+// from the caller's references into the caller's records (enqueue_query, Walk::Expand).
+int rt_scene_triangles_device(rt_ctx* c, size_t n, const void* d_refs4, void* d_tris12, void* hip_stream) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const std::string name = "rt_scene_triangles_device";
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": too many references for one call");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, name + " needs trace_variant 0");
+  if (n) {
+    if (!d_refs4 || !d_tris12) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null reference/triangle pointers");
+    if (((uintptr_t)d_refs4 & 15u) || ((uintptr_t)d_tris12 & 15u)) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": references and triangles must be 16-byte aligned");
+    { int w = check_device_pointers(c, name, "references and triangles", {d_refs4, d_tris12}); if (w) return w; }
+  }
+  Query q; q.walk = Walk::Expand; q.n = n; q.records = d_refs4; q.refs = true; q.tris_out = d_tris12;
+  return device_query(c, q, hip_stream);
+}
+
+// rt_overlap_triangles_device asked about triangles of the scene: its checks and ordering with the references in the place of the
+// triangles, then k_refs_expand into the workspace and k_refs_collide over those records (enqueue_query).
+int rt_overlap_scene_triangles_device(rt_ctx* c, size_t n, const void* d_refs4, uint32_t cull_mask, uint32_t flags, uint32_t max_ids, void* d_ids, void* d_counts,
+                                      void* hip_stream) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const std::string name = "rt_overlap_scene_triangles_device";
+  { int w = overlap_arguments(c, name, n, cull_mask, flags, max_ids, d_ids, d_counts, "references"); if (w) return w; }
+  if (n) {
+    if (!d_refs4) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null reference pointer");
+    if (((uintptr_t)d_refs4 & 15u) || ((uintptr_t)d_ids & 3u) || ((uintptr_t)d_counts & 3u))
+      return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": references must be 16-byte aligned, ids and counts 4-byte aligned");
+    { int w = check_device_pointers(c, name, "references, ids and counts", {d_refs4, d_ids, d_counts}); if (w) return w; }
+  }
+  Query q; q.walk = Walk::Triangles; q.n = n; q.records = d_refs4; q.refs = true; q.cull_mask = cull_mask; q.overlap_any = (flags & RT_OVERLAP_ANY) != 0u;
+  q.max_ids = max_ids; q.ids = d_ids; q.counts = d_counts;
+  return device_query(c, q, hip_stream);
+}
+
+// The blocking host form, as rt_overlap_triangles is to rt_overlap_triangles_device: the references (16 B each), then the counts, then the
+// rows.  The expansion runs inside the timed window.
+int rt_overlap_scene_triangles(rt_ctx* c, size_t n, const rt_tri_ref* refs, uint32_t cull_mask, uint32_t flags, uint32_t max_ids, int32_t* ids, uint32_t* counts,
+                               int counting, rt_stats* stats) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const std::string name = "rt_overlap_scene_triangles";
+  { int w = overlap_arguments(c, name, n, cull_mask, flags, max_ids, ids, counts, "references"); if (w) return w; }
+  if (!refs && n) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null reference pointer");
+  const size_t ref_bytes = n * sizeof(rt_tri_ref), count_bytes = n * sizeof(uint32_t), id_bytes = n * max_ids * 2 * sizeof(int32_t);
+  Query q; q.walk = Walk::Triangles; q.n = n; q.refs = true; q.cull_mask = cull_mask; q.overlap_any = (flags & RT_OVERLAP_ANY) != 0u; q.max_ids = max_ids;
+  q.counting = counting != 0;
+  return blocking_query(c, q, refs, ref_bytes, ref_bytes + count_bytes + id_bytes,
+                        {{&Query::counts, ref_bytes, counts, count_bytes}, {&Query::ids, ref_bytes + count_bytes, ids, id_bytes}}, stats);
+}
+
+// rt_closest_triangle_device asked about triangles of the scene: its checks and ordering with the references in the place of the
+// triangles, then k_refs_expand into the workspace, k_refs_nearest over those records, k_hit_attr and k_triangle_side over them too.
+int rt_closest_scene_triangle_device(rt_ctx* c, size_t n, const void* d_refs4, uint32_t cull_mask, void* d_hits, void* d_attr, void* d_params, void* hip_stream) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const std::string name = "rt_closest_scene_triangle_device";
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": too many references for one call");
+  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": cull_mask is above 0xFF");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, name + " needs trace_variant 0");
+  if (n) {
+    if (!d_refs4 || !d_hits) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null reference/hit pointers");
+    if (((uintptr_t)d_refs4 & 15u) || ((uintptr_t)d_hits & 3u) || ((uintptr_t)d_attr & 15u) || ((uintptr_t)d_params & 3u))
+      return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": references and attributes must be 16-byte aligned, hits and parameters 4-byte aligned");
+    { int w = check_device_pointers(c, name, "references, hits, attributes and parameters", {d_refs4, d_hits, d_attr, d_params}); if (w) return w; }
+  }
+  Query q; q.walk = Walk::Triangle; q.n = n; q.records = d_refs4; q.refs = true; q.cull_mask = cull_mask; q.hits = d_hits; q.attr = d_attr; q.params = d_params;
+  return device_query(c, q, hip_stream);
+}
+
+// The blocking host form, as rt_closest_triangle is to rt_closest_triangle_device: the references (16 B each), then the hits, then the
+// parameters (two floats each).
+int rt_closest_scene_triangle(rt_ctx* c, size_t n, const rt_tri_ref* refs, uint32_t cull_mask, rt_hit* out, float* params, int counting, rt_stats* stats) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const std::string name = "rt_closest_scene_triangle";
+  if ((!refs || !out) && n) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null reference/hit pointers");
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": too many references for one call");
+  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": cull_mask is above 0xFF");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, name + " needs trace_variant 0");
+  const size_t ref_bytes = n * sizeof(rt_tri_ref), hit_bytes = n * sizeof(HitRec), par_bytes = n * 2 * sizeof(float);
+  Query q; q.walk = Walk::Triangle; q.n = n; q.refs = true; q.cull_mask = cull_mask; q.counting = counting != 0;
+  return blocking_query(c, q, refs, ref_bytes, ref_bytes + hit_bytes + par_bytes,
+                        {{&Query::hits, ref_bytes, out, hit_bytes}, {&Query::params, ref_bytes + hit_bytes, params, par_bytes}}, stats);
 }
 
 namespace {

@@ -93,7 +93,7 @@ struct alignas(16) InstanceDev {
   float q_scale[3];
   uint32_t type;        // per-instance object type (rt_set_instance_types) or TYPE_BY_OBJECT_INDEX: the reference's two-way switch
   uint32_t cover_first, cover_count;   // the mesh's frontier boxes in SceneDev::cover_boxes (primary-ray coverage mask, k_cover)
-  uint32_t pad;
+  uint32_t prim_count;  // triangles of the instance's mesh (k_refs_expand checks a reference's prim against it); no walk reads it
 };
 static_assert(sizeof(InstanceDev) == 160, "InstanceDev must be 160 bytes");
 

@@ -247,6 +247,16 @@ void launch_closest_triangle(const SceneDev& sc, const float4* tris, uint32_t cu
                              int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
 // the side of the reported triangle's plane the query's point (P0 + qu (P1 - P0)) + qv (P2 - P0) lies on (launch_closest_side's rule and word)
 void launch_triangle_side(const SceneDev& sc, const float4* tris, const float* params, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s);
+// rt_scene_triangles_device and the expansion in front of the two by-reference walks (kernels_refs.inc): the 48-byte record of every
+// reference (16 bytes: inst, prim, against, r_max) into tris[3 n]: the world image of the source packet, r_max, inst and against in words
+// 3, 7 and 11; nine quiet NaNs for an invalid reference.  n_vert_floats: the floats of sc.verts.
+void launch_refs_expand(const SceneDev& sc, const void* refs, float4* tris, uint32_t n, uint64_t n_vert_floats, hipStream_t s);
+// rt_overlap_scene_triangles_device, rt_closest_scene_triangle_device: launch_collide_triangles and launch_closest_triangle over
+// launch_refs_expand's records, honouring words 7 (the source instance) and 11 (against: -1 every other instance, >= 0 that one only)
+void launch_refs_collide(const SceneDev& sc, const float4* tris, uint32_t cull_mask, const float* inst_scale, bool any, uint32_t k, void* ids, uint32_t* counts,
+                         uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
+void launch_refs_nearest(const SceneDev& sc, const float4* tris, uint32_t cull_mask, const float* inst_scale, HitRec* hits, float* params, uint32_t n,
+                         int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
 // rt_shade_rays_device: k_ray_ingest replaces k_raygen for the caller's n rays (32 bytes each, o.xyz, w3, d.xyz, tmax; sample id = record
 // index): sky colours of the rays that miss the TLAS and (0, 0, 0, 0) for invalid records into f.sample_color, the others into bounce queue 0
 // (workgroup b appends to shard b % 8: f.shard_cap >= 256 * ceil(ray_ingest_block_count(n) / 8)).  f.counters must be zero.

@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void k_inst_records(const RecDev* rec, int n, 
       d.first_float = m.first_float;
       d.first_index = m.first_index;
       d.type = i < n_types ? types[i] : TYPE_BY_OBJECT_INDEX;
-      d.cover_first = m.cover_first; d.cover_count = m.prim_count ? m.cover_count : 0u; d.pad = 0;
+      d.cover_first = m.cover_first; d.cover_count = m.prim_count ? m.cover_count : 0u; d.prim_count = m.prim_count;
       // instance_world_box (rt_api.cpp): 8 transformed corners of the mesh bounds, padded against the binary32 roundings
       if (!(m.lo[0] > m.hi[0])) {
         for (int k = 0; k < 3; k++) { w.lo[k] = 3.0e38f; w.hi[k] = -3.0e38f; }

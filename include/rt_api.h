@@ -792,6 +792,47 @@ int rt_closest_scene_triangle_device(rt_ctx* ctx, size_t n, const void* d_refs4,
 int rt_closest_scene_triangle(rt_ctx* ctx, size_t n, const rt_tri_ref* refs_host, uint32_t cull_mask,
                               rt_hit* out_host, float* params_host, int counting, rt_stats* stats);
 
+/* Overlap lists: every candidate of every record, for the consumers that want all pairs (Embree's rtcCollide, FCL's collide, PhysX's
+ * overlap buffers, voxelisers, cutters), where the three calls above give a count and the 16 smallest.  The result is in CSR form:
+ *   d_offsets   n + 1 uint64, 8-byte aligned.  offsets[i] is the sum of |C(j)| over j < i and offsets[n] the total T.  The offsets
+ *               are always complete: capacity never limits them.  (64 bits: n and every count are below 2^32, their sum is not.)
+ *   d_ids       capacity records of 8 bytes (int32 inst, int32 prim), 4-byte aligned.  Row i is the whole of C(i) in ascending
+ *               (inst, prim) order at ids[offsets[i] .. offsets[i + 1]).  A row is written if and only if offsets[i + 1] <= capacity:
+ *               a row that would cross the capacity, and every row behind it, is not written at all.  No byte at or beyond
+ *               min(T, capacity) records is touched, nor any byte of a row that is not written.  The caller compares offsets[n] with
+ *               capacity and calls again with more room if it has to.  capacity == 0 wants d_ids == NULL and gives the offsets only.
+ * The records, their validity rules (an invalid record has an empty row), the candidates C, the cull mask, the `against` rule of
+ * references and the canonical predicates are exactly those of rt_overlap_boxes_device, rt_overlap_triangles_device and
+ * rt_overlap_scene_triangles_device.  So the first min(|C(i)|, 16) entries of row i are the row of that call with max_ids = 16, byte for
+ * byte, offsets[i + 1] - offsets[i] is its count, and the result is the same bytes whatever the tree.
+ * No flag is defined: RT_OVERLAP_ANY and unknown bits are RT_ERR_INVALID_ARGUMENT, and so are a NULL or misaligned pointer (the
+ * records 16-byte aligned), memory that is not of ctx's GPU, n >= 0xFFFFFF00, capacity >= 0xFFFFFF00 (rows are indexed with 32 bits
+ * once they are known to fit), d_ids == NULL with capacity != 0 or d_ids != NULL with capacity == 0, cull_mask > 0xFF and
+ * trace_variant != 0.
+ * Stream ordering without host synchronisation, the TLAS and scene of the call, RT_ERR_NOT_READY and "queries of one context one
+ * after another" are as for rt_overlap_boxes_device; for n == 0 nothing is enqueued and d_offsets is not written.  A call walks twice:
+ * the count-only walk of the capped call, a scan of the counts, then (capacity != 0) a second walk that writes the rows and a sort of
+ * the longer rows.  The counts, the scan's storage and the sort's worklist (about 8 n bytes) are part of the query workspace;
+ * it grows after the context's earlier queries are done, and an allocation that fails is RT_ERR_OUT_OF_MEMORY and leaves the context as
+ * it was. */
+int rt_overlap_boxes_device_list(rt_ctx* ctx, size_t n, const void* d_boxes8, uint32_t cull_mask, uint32_t flags,
+                                 void* d_offsets, void* d_ids, size_t capacity, void* hip_stream);
+int rt_overlap_triangles_device_list(rt_ctx* ctx, size_t n, const void* d_tris12, uint32_t cull_mask, uint32_t flags,
+                                     void* d_offsets, void* d_ids, size_t capacity, void* hip_stream);
+int rt_overlap_scene_triangles_device_list(rt_ctx* ctx, size_t n, const void* d_refs4, uint32_t cull_mask, uint32_t flags,
+                                           void* d_offsets, void* d_ids, size_t capacity, void* hip_stream);
+/* The blocking host forms, as rt_overlap_boxes is to rt_overlap_boxes_device: offsets_host (n + 1) and ids_host (capacity pairs; NULL
+ * with capacity 0) are host memory, and the entries of ids_host that the call does not write keep their values.  counting != 0 runs the
+ * instrumented walks and returns stats->node_visits and stats->tri_tests: those of both walks together (of the one walk with capacity
+ * 0); stats may be NULL.  stats->ms_trace_closest is the device time of the whole sequence (for references the expansion too); the size
+ * fields as for rt_overlap_boxes. */
+int rt_overlap_boxes_list(rt_ctx* ctx, size_t n, const float* boxes8_host, uint32_t cull_mask, uint32_t flags,
+                          uint64_t* offsets_host, int32_t* ids_host, size_t capacity, int counting, rt_stats* stats);
+int rt_overlap_triangles_list(rt_ctx* ctx, size_t n, const float* tris12_host, uint32_t cull_mask, uint32_t flags,
+                              uint64_t* offsets_host, int32_t* ids_host, size_t capacity, int counting, rt_stats* stats);
+int rt_overlap_scene_triangles_list(rt_ctx* ctx, size_t n, const rt_tri_ref* refs_host, uint32_t cull_mask, uint32_t flags,
+                                    uint64_t* offsets_host, int32_t* ids_host, size_t capacity, int counting, rt_stats* stats);
+
 /* Inside / outside: for every point, is it enclosed by the scene's surfaces (Open3D's compute_occupancy and compute_signed_distance),
  * for signed distance fields, penetration tests, occupancy and voxel filling.  The answer is a vote over the crossing parities of a few
  * rays from the point along a fixed table of generic directions; one ray is not enough, because the canonical triangle test is not

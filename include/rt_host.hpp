@@ -258,6 +258,28 @@ class Renderer {
   void closestSceneTriangleDevice(size_t n, const void* dRefs4, uint32_t cullMask, void* dHits, void* dAttr, void* dParams, void* stream) {
     check(rt_closest_scene_triangle_device(ctx_, n, dRefs4, cullMask, dHits, dAttr, dParams, stream), "rt_closest_scene_triangle_device");
   }
+  // Overlap lists (rt_overlap_*_list): every candidate of every reference in CSR form.  offsets gets refs.size() + 1 entries; ids holds the
+  // pairs (inst, prim) of the rows that end within `capacity` pairs (0: the offsets only).  Returns true when every row was written
+  // (offsets.back() <= capacity); otherwise call again with a capacity of offsets.back().
+  bool overlapSceneTrianglesList(const std::vector<rt_tri_ref>& refs, std::vector<uint64_t>& offsets, std::vector<int32_t>& ids, size_t capacity,
+                                 uint32_t cullMask = 0xFF, rt_stats* stats = nullptr) {
+    offsets.assign(refs.size() + 1, 0);
+    ids.resize(capacity * 2);
+    rt_stats st{};
+    check(rt_overlap_scene_triangles_list(ctx_, refs.size(), refs.data(), cullMask, 0, offsets.data(), capacity ? ids.data() : nullptr, capacity, 0, &st),
+          "rt_overlap_scene_triangles_list");
+    if (stats) *stats = st;
+    return offsets.back() <= capacity;
+  }
+  void overlapBoxesDeviceList(size_t n, const void* dBoxes8, uint32_t cullMask, void* dOffsets, void* dIds, size_t capacity, void* stream) {
+    check(rt_overlap_boxes_device_list(ctx_, n, dBoxes8, cullMask, 0, dOffsets, dIds, capacity, stream), "rt_overlap_boxes_device_list");
+  }
+  void overlapTrianglesDeviceList(size_t n, const void* dTris12, uint32_t cullMask, void* dOffsets, void* dIds, size_t capacity, void* stream) {
+    check(rt_overlap_triangles_device_list(ctx_, n, dTris12, cullMask, 0, dOffsets, dIds, capacity, stream), "rt_overlap_triangles_device_list");
+  }
+  void overlapSceneTrianglesDeviceList(size_t n, const void* dRefs4, uint32_t cullMask, void* dOffsets, void* dIds, size_t capacity, void* stream) {
+    check(rt_overlap_scene_triangles_device_list(ctx_, n, dRefs4, cullMask, 0, dOffsets, dIds, capacity, stream), "rt_overlap_scene_triangles_device_list");
+  }
 
  private:
   void check(int r, const char* fn) { if (r) throwExceptionRtAPI(r, fn, ctx_); }

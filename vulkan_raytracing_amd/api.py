@@ -78,7 +78,7 @@ INSIDE_DIRS = ((0.36, 0.48, 0.8), (-0.8, 0.36, -0.48), (0.48, -0.8, -0.36), (-0.
 
 EXPORTS = ["rt_create", "rt_create_frame_slot", "rt_destroy", "rt_upload_geometry", "rt_build_blas", "rt_set_instances", "rt_set_instances_device", "rt_refit_blas_device", "rt_set_materials", "rt_set_instance_types", "rt_set_uniforms", "rt_set_skybox",
            "rt_trace", "rt_trace_async", "rt_trace_wait", "rt_trace_shard", "rt_set_batch", "rt_trace_shard_batch", "rt_assemble_shards", "rt_shard_rows", "rt_synchronize", "rt_get_stats", "rt_set_timing", "rt_intersect",
-           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_closest_point_device_hits", "rt_closest_point_hits", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_overlap_triangles_device", "rt_overlap_triangles", "rt_sweep_spheres_device", "rt_sweep_spheres", "rt_closest_segment_device", "rt_closest_segment", "rt_closest_triangle_device", "rt_closest_triangle", "rt_scene_triangles_device", "rt_overlap_scene_triangles_device", "rt_overlap_scene_triangles", "rt_closest_scene_triangle_device", "rt_closest_scene_triangle", "rt_point_inside_device", "rt_point_inside", "rt_signed_distance_device", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_host_blas", "rt_debug_snapshot", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
+           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_closest_point_device_hits", "rt_closest_point_hits", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_overlap_triangles_device", "rt_overlap_triangles", "rt_sweep_spheres_device", "rt_sweep_spheres", "rt_closest_segment_device", "rt_closest_segment", "rt_closest_triangle_device", "rt_closest_triangle", "rt_scene_triangles_device", "rt_overlap_scene_triangles_device", "rt_overlap_scene_triangles", "rt_overlap_boxes_device_list", "rt_overlap_boxes_list", "rt_overlap_triangles_device_list", "rt_overlap_triangles_list", "rt_overlap_scene_triangles_device_list", "rt_overlap_scene_triangles_list", "rt_closest_scene_triangle_device", "rt_closest_scene_triangle", "rt_point_inside_device", "rt_point_inside", "rt_signed_distance_device", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_host_blas", "rt_debug_snapshot", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
 
 _LIBS = {}
 
@@ -143,6 +143,9 @@ def lib(variant=None):
         L.rt_scene_triangles_device.argtypes = [vp, C.c_size_t, vp, vp, vp]
         L.rt_overlap_scene_triangles_device.argtypes = L.rt_overlap_boxes_device.argtypes
         L.rt_overlap_scene_triangles.argtypes = L.rt_overlap_boxes.argtypes
+        for name in ("boxes", "triangles", "scene_triangles"):
+            getattr(L, "rt_overlap_%s_device_list" % name).argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_size_t, vp]
+            getattr(L, "rt_overlap_%s_list" % name).argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_size_t, C.c_int, C.POINTER(RtStats)]
         L.rt_closest_scene_triangle_device.argtypes = L.rt_closest_triangle_device.argtypes
         L.rt_closest_scene_triangle.argtypes = L.rt_closest_triangle.argtypes
         L.rt_shade_rays_device.argtypes = [vp, C.c_size_t, C.c_uint32, vp, vp, vp, vp]
@@ -760,6 +763,108 @@ class RtContext:
                   "rt_overlap_scene_triangles")
         return cnt, ids, st
 
+    def overlap_boxes_device_list(self, boxes, capacity=None, cull_mask=0xFF, stream=None, out=None):
+        """rt_overlap_boxes_device_list: every triangle that touches every query box, in CSR form.  `boxes` as for overlap_boxes_device.
+        Returns an OverlapList: offsets, int64 (n + 1,), the row starts (offsets[n]: the total T, always complete); ids, int32
+        (capacity, 2), row i the whole candidate set of box i in ascending (inst, prim) order at ids[offsets[i]:offsets[i + 1]], written
+        if and only if offsets[i + 1] <= capacity (capacity 0: ids is None, offsets only); total, a 0-d view of offsets[n] (reading it
+        is the caller's synchronisation).  out = (offsets, ids) reuses such buffers, and capacity then defaults to the rows of ids.
+        With capacity=None and no out the wrapper makes an offsets-only call, reads the total ON THE HOST (a synchronisation),
+        allocates exactly and calls again: three walks instead of two.  A loop is better served by a persistent ids buffer passed
+        through out, and a second call with a larger one when total exceeds it.  See include/rt_api.h."""
+        return self._overlap_list_device(boxes, "overlap_boxes", 8, "box", capacity, cull_mask, stream, out)
+
+    def overlap_triangles_device_list(self, tris, capacity=None, cull_mask=0xFF, stream=None, out=None):
+        """rt_overlap_triangles_device_list: every triangle of the scene that cuts or touches every query triangle (`tris` as for
+        overlap_triangles_device), as overlap_boxes_device_list returns them."""
+        return self._overlap_list_device(tris, "overlap_triangles", 12, "triangle", capacity, cull_mask, stream, out)
+
+    def overlap_scene_triangles_device_list(self, refs, capacity=None, cull_mask=0xFF, stream=None, out=None):
+        """rt_overlap_scene_triangles_device_list: overlap_triangles_device_list asked about triangles of the scene itself (`refs` as
+        for overlap_scene_triangles_device)."""
+        return self._overlap_list_device(refs, "overlap_scene_triangles", 4, "reference", capacity, cull_mask, stream, out, int32=True)
+
+    def _overlap_list_device(self, records, name, cols, noun, capacity, cull_mask, stream, out, int32=False):
+        """the three *_device_list calls: the checks, the buffers and rt_<name>_device_list on `stream`"""
+        import torch
+        self._check_rays(records, name + "_device_list", cols, noun, int32)
+        fn = getattr(self.L, "rt_%s_device_list" % name)
+        n = records.shape[0]
+        cur = torch.cuda.current_stream(records.device)
+        if stream is None:
+            stream = cur
+        fresh = []
+        if out is None:
+            offsets = torch.zeros(n + 1, dtype=torch.int64, device=records.device) if n == 0 else torch.empty(n + 1, dtype=torch.int64, device=records.device)
+            ids = None
+            fresh.append(offsets)
+        else:
+            offsets, ids = out
+            if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int64 or tuple(offsets.shape) != (n + 1,) or not offsets.is_contiguous() or offsets.device != records.device:
+                raise ValueError("out offsets must be a contiguous int64 (n + 1,) tensor on the records' device")
+            if ids is not None and (not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.dim() != 2 or ids.shape[1] != 2 or not ids.is_contiguous() or ids.device != records.device):
+                raise ValueError("out ids must be a contiguous int32 (capacity, 2) tensor on the records' device, or None")
+            if capacity is None:
+                capacity = ids.shape[0] if ids is not None else 0
+            elif int(capacity) != (ids.shape[0] if ids is not None else 0):
+                raise ValueError("capacity must be the rows of out ids")
+        if stream != cur:   # (allocated for the current stream, written on `stream`)
+            for t in fresh:
+                t.record_stream(stream)
+
+        def run_call(ids_t, cap):
+            def call(run):
+                return fn(self.h, n, C.c_void_p(records.data_ptr()), int(cull_mask) & 0xFFFFFFFF, 0, C.c_void_p(offsets.data_ptr()),
+                          C.c_void_p(ids_t.data_ptr()) if ids_t is not None else None, cap, C.c_void_p(run.cuda_stream))
+            if n:
+                self._on_stream(stream, (records, offsets, ids_t), call, "rt_%s_device_list" % name)
+        if capacity is None:   # the offsets first, the total read on the host, then the exact allocation
+            run_call(None, 0)
+            if n:
+                stream.synchronize()
+            capacity = int(offsets[n].item()) if n else 0
+        capacity = int(capacity)
+        if capacity < 0:
+            raise ValueError("capacity must not be negative")
+        if capacity and ids is None:
+            ids = torch.empty((capacity, 2), dtype=torch.int32, device=records.device)
+            if stream != cur:
+                ids.record_stream(stream)
+        run_call(ids if capacity else None, capacity)
+        return OverlapList(offsets, ids if capacity else None)
+
+    def _overlap_list_host(self, records, name, capacity, cull_mask, counting):
+        """the three blocking *_list forms -> (offsets uint64 (n + 1,), ids int32 (capacity, 2) or None, RtStats); capacity=None: an
+        offsets-only call first, then one with exactly the total"""
+        fn = getattr(self.L, "rt_%s_list" % name)
+        n = len(records)
+        offsets = np.zeros(n + 1, np.uint64)
+        st = RtStats()
+
+        def call(ids, cap):
+            self._chk(fn(self.h, n, _p(records), int(cull_mask) & 0xFFFFFFFF, 0, _p(offsets), _p(ids) if ids is not None else None, cap, int(counting), C.byref(st)),
+                      "rt_%s_list" % name)
+        if capacity is None:
+            call(None, 0)
+            capacity = int(offsets[n])
+        capacity = int(capacity)
+        ids = np.zeros((capacity, 2), np.int32) if capacity else None
+        call(ids, capacity)
+        return offsets, ids, st
+
+    def overlap_boxes_list(self, boxes8, capacity=None, cull_mask=0xFF, counting=False):
+        """rt_overlap_boxes_list: the blocking host form -> (offsets uint64 (n + 1,), ids int32 (capacity, 2) or None, RtStats; with
+        counting its node_visits / tri_tests are those of both walks).  Rows that do not fit `capacity` stay zero."""
+        return self._overlap_list_host(np.ascontiguousarray(boxes8, np.float32).reshape(-1, 8), "overlap_boxes", capacity, cull_mask, counting)
+
+    def overlap_triangles_list(self, tris12, capacity=None, cull_mask=0xFF, counting=False):
+        """rt_overlap_triangles_list: the blocking host form, as overlap_boxes_list"""
+        return self._overlap_list_host(np.ascontiguousarray(tris12, np.float32).reshape(-1, 12), "overlap_triangles", capacity, cull_mask, counting)
+
+    def overlap_scene_triangles_list(self, refs, capacity=None, cull_mask=0xFF, counting=False):
+        """rt_overlap_scene_triangles_list: the blocking host form (refs as for overlap_scene_triangles), as overlap_boxes_list"""
+        return self._overlap_list_host(_host_refs(refs), "overlap_scene_triangles", capacity, cull_mask, counting)
+
     def closest_scene_triangle_device(self, refs, cull_mask=0xFF, attributes=False, params=False, stream=None, out=None):
         """rt_closest_scene_triangle_device: closest_triangle_device asked about triangles of the scene itself.  `refs` is
         scene_triangles_device's tensor (triangle_refs packs it, r_max the search radius).  The RayQuery names the candidate triangle;
@@ -1088,6 +1193,20 @@ class BoxOverlaps:
         """(counts as (n,) uint32, ids as (n, max_ids, 2) int32), None where not asked for; synchronises"""
         return (self.count.cpu().numpy().view(np.uint32) if self.count is not None else None,
                 self.ids.cpu().numpy() if self.ids is not None else None)
+
+
+class OverlapList:
+    """Results of RtContext.overlap_*_device_list: offsets, int64 (n + 1,), and ids, int32 (capacity, 2) rows of (inst, prim) or None;
+    row i is ids[offsets[i]:offsets[i + 1]] if offsets[i + 1] <= capacity.  total is a 0-d view of offsets[n]: reading it (int(),
+    .item()) synchronises."""
+
+    def __init__(self, offsets, ids):
+        self.offsets, self.ids = offsets, ids
+        self.total = offsets[-1]
+
+    def numpy(self):
+        """(offsets as (n + 1,) uint64, ids as (capacity, 2) int32 or None); synchronises"""
+        return self.offsets.cpu().numpy().view(np.uint64), self.ids.cpu().numpy() if self.ids is not None else None
 
 
 def triangle_records(vertices, faces, r_max=0.0):

@@ -2471,6 +2471,8 @@ void launch_resolve_points(const float4* sample_color, float4* out, uint32_t n_p
 
 #include "kernels_refs.inc"   // k_refs_expand, k_refs_collide, k_refs_nearest: the two triangle queries over (inst, prim) references (rt_*_scene_triangle*_device)
 
+#include "kernels_list.inc"   // k_list_boxes, k_list_triangles, k_list_refs, k_list_sort, k_list_scan_*: whole overlap rows in CSR form (rt_overlap_*_device_list)
+
 int tail_blocks_per_cu() {
   // the smallest over the instantiations: any of them may be the one in flight (counting; 4-ary records in the alt build)
   int n = 1 << 30, v = 0;

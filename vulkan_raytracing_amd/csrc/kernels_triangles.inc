@@ -25,6 +25,11 @@ struct CollideArgs {
   uint32_t* cursor;            // chunk cursor (zero before the launch)
   uint32_t* counters;          // the query's counter block (counting form: CNT_NODE_VISITS, CNT_TRI_TESTS)
   int32_t* ovf_stack;          // ovf_stride ints per thread of the grid
+  // the LIST instantiations only (kernels_list.inc); behind everything else, so that the other kernels read their arguments where they did
+  const unsigned long long* offsets;   // n + 1 row starts: row i is ids[offsets[i] .. offsets[i + 1])
+  unsigned long long capacity; // records of ids: a row that ends beyond it is not written
+  uint32_t* worklist;          // the rows left in walk order (longer than RT_LIST_INSERT_MAX), for k_list_sort
+  uint32_t* work_count;        // their number (zero before the launch)
 };
 
 // one axis L: the query projects to 0, L.p1, L.p2 and the candidate to L.a, L.b, L.c (everything centred on P0).  Strict: a tie is not a
@@ -74,13 +79,14 @@ __device__ __forceinline__ bool collide_tri(F3 wlo, F3 whi, F3 P0, F3 P1, F3 P2,
 // REFS (kernels_refs.inc, rt_overlap_scene_triangles_device): the records are k_refs_expand's, words 7 and 11 the source instance and
 // `against`; a valid record with against >= 0 starts at that instance's TLAS leaf with nothing beneath it, so the TLAS is never walked,
 // and with against == -1 the TLAS-leaf branch passes over the source instance.  Everything else is shared.
-template <bool COUNT, bool REFS = false>
+template <bool COUNT, bool REFS = false, bool LIST = false>
 __device__ __forceinline__ void collide_body(const CollideArgs& a) {
   __shared__ int s_stack[4][STACK2_LDS][64];
   WalkStack st(s_stack, a.ovf_stack, a.sc.ovf_stride);
   WalkFeed feed;
   const uint32_t K = a.k;
-  const bool prune = a.counts == nullptr;
+  const bool prune = !LIST && a.counts == nullptr;
+  uint32_t len = 0;                           // LIST: the row's length, from the offsets (0: a row that is not written)
 
   bool need = true;
   uint32_t bx = 0, count = 0;
@@ -116,7 +122,12 @@ __device__ __forceinline__ void collide_body(const CollideArgs& a) {
       cur_inst = -1; count = 0;
       st.reset(); cur = valid ? a.sc.tlas_root : REF_DONE;
       if (REFS && valid && (int)__float_as_uint(r2.w) >= 0) cur = ~(int)__float_as_uint(r2.w);   // (k_refs_expand: below n_inst)
-      row = a.ids + (size_t)bx * K;
+      if (LIST) {   // the row the count walk measured: nothing to do for an empty one or one that ends beyond the capacity
+        const unsigned long long o0 = a.offsets[bx], o1 = a.offsets[bx + 1u];
+        len = o1 > a.capacity ? 0u : (uint32_t)(o1 - o0);
+        if (len == 0u) cur = REF_DONE;
+        row = a.ids + o0;
+      } else row = a.ids + (size_t)bx * K;
       need = false;
     }
     if (__ballot(!need) == 0) break;   // every lane idle and the records used up
@@ -155,6 +166,22 @@ __device__ __forceinline__ void collide_body(const CollideArgs& a) {
         if (prune && full && !id_before(cur_inst, prim, last_inst, last_prim)) continue;   // (it could neither enter the row nor be counted)
         if (COUNT) cnt_tris++;
         if (!collide_tri(wlo, whi, P0, P1, P2, xform_point(m, mk3(T0.x, T0.y, T0.z)), xform_vec(m, mk3(T0.w, T1.x, T1.y)), xform_vec(m, mk3(T1.z, T1.w, T2.x)))) continue;
+        if (LIST) {   // every candidate has its place (never beyond the row, whatever the walk finds): a short row by insertion, a long one in walk order
+          if (count < len) {
+            uint32_t p = count;
+            if (len <= (uint32_t)RT_LIST_INSERT_MAX)
+              while (p > 0u) {
+                const IdRec o = row[p - 1u];
+                if (!id_before(cur_inst, prim, o.inst, o.prim)) break;
+                row[p] = o;
+                p--;
+              }
+            IdRec id; id.inst = cur_inst; id.prim = prim;
+            row[p] = id;
+          }
+          count++;
+          continue;
+        }
         const uint32_t e = count < K ? count : K;   // entries in the row
         count++;
         if (a.any) { done = true; break; }
@@ -200,9 +227,13 @@ __device__ __forceinline__ void collide_body(const CollideArgs& a) {
     }
     if (!need && cur == REF_DONE) {
       // ---- finished: the rest of the row empty, the count
-      IdRec none; none.inst = -1; none.prim = -1;
-      for (uint32_t j = count < K ? count : K; j < K; j++) row[j] = none;
-      if (a.counts) a.counts[bx] = count;
+      if (LIST) {   // (a long row goes to k_list_sort)
+        if (len > (uint32_t)RT_LIST_INSERT_MAX) a.worklist[atomicAdd(a.work_count, 1u)] = bx;
+      } else {
+        IdRec none; none.inst = -1; none.prim = -1;
+        for (uint32_t j = count < K ? count : K; j < K; j++) row[j] = none;
+        if (a.counts) a.counts[bx] = count;
+      }
       need = true;
     }
   }

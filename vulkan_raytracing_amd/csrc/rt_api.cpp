@@ -309,6 +309,9 @@ struct rt_ctx {
   float4* d_q_tris = nullptr;      // rt_overlap_scene_triangles*, rt_closest_scene_triangle*: the 48-byte records k_refs_expand makes of the
                                    // references, which the walk then reads; part of the query workspace
   size_t q_tris_alloc = 0;         // records of d_q_tris
+  char* d_q_list = nullptr;        // rt_overlap_*_list: the counts of the first walk, the worklist of k_list_sort and the scan's tile sums
+                                   // (list_workspace); part of the query workspace
+  size_t q_list_alloc = 0;         // bytes of d_q_list
   hipEvent_t ev_query[2] = {nullptr, nullptr};
   bool ev_query_valid[2] = {false, false};
   int query_last = -1;             // parity of the last query (-1: none since the last host wait)
@@ -1490,6 +1493,7 @@ void rt_destroy(rt_ctx* c) {
   if (c->d_q_scale) hipFree(c->d_q_scale);
   if (c->d_q_words) hipFree(c->d_q_words);
   if (c->d_q_tris) hipFree(c->d_q_tris);
+  if (c->d_q_list) hipFree(c->d_q_list);
   for (int k = 0; k < 2; k++) if (c->ev_query[k]) hipEventDestroy(c->ev_query[k]);
   tlas_gpu_free(c->tgpu);
   for (auto e : c->ev_pool) hipEventDestroy(e);
@@ -2382,6 +2386,10 @@ struct Query {
   bool overlap_any = false;          // Overlap: RT_OVERLAP_ANY
   uint32_t max_hits = 0;             // Hits, ClosestHits: records per row of hits
   uint32_t max_ids = 0;              // Overlap: entries per row of ids
+  bool list = false;                 // Overlap, Triangles: rt_overlap_*_list: the count-only walk into the workspace, the scan into offsets, and
+                                     // with capacity != 0 the fill walk (its chunk cursor initialised again) and k_list_sort into ids
+  void* offsets = nullptr;           // list: n + 1 uint64 row starts
+  uint64_t capacity = 0;             // list: records of ids
   uint32_t n_dirs = 0;               // Inside
   void* hits = nullptr;              // hit records (Hits, ClosestHits: n rows; Overlap: none; Inside: the signed distances, or none)
   void* ids = nullptr;               // Overlap: n rows of (inst, prim)
@@ -2391,6 +2399,17 @@ struct Query {
   void* attr = nullptr;              // the hit attributes (optional)
   bool counting = false;             // the instrumented walk (Hits and Flags have none): its counts start from a zeroed counter block
   hipEvent_t t0 = nullptr, t1 = nullptr;   // recorded around the walk (optional)
+};
+// The list calls' part of the query workspace for n records, as byte offsets into one area: the n counts of the first walk, the worklist
+// of k_list_sort (the number of listed rows, then up to n records) and the scan's tile sums (8-byte aligned).
+struct ListWorkspace {
+  size_t counts = 0, work = 0, sums = 0, bytes = 0;
+  ListWorkspace() = default;
+  explicit ListWorkspace(size_t n) {
+    work = n * sizeof(uint32_t);
+    sums = (work + (1 + n) * sizeof(uint32_t) + 7u) & ~(size_t)7u;
+    bytes = sums + (size_t)list_scan_tiles((uint32_t)n) * sizeof(unsigned long long);
+  }
 };
 int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q) {
   const bool flags = q.walk == Walk::Flags, sweep = q.walk == Walk::Sweep, inside = q.walk == Walk::Inside, segment = q.walk == Walk::Segment;
@@ -2422,6 +2441,19 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q
     }
     words = c->d_q_words;
   }
+  ListWorkspace lw;
+  if (q.list) {   // as the words above: a new area before the old one goes, so that a failure changes nothing
+    lw = ListWorkspace(q.n);
+    if (lw.bytes > c->q_list_alloc) {
+      { int w = wait_queries(c, c); if (w) return w; }
+      char* grown = nullptr;
+      HIP_TRY(c, hipMalloc((void**)&grown, lw.bytes));
+      if (c->d_q_list) (void)hipFree(c->d_q_list);
+      c->d_q_list = grown; c->q_list_alloc = lw.bytes;
+    }
+  }
+  uint32_t* list_counts = (uint32_t*)(c->d_q_list + lw.counts), *list_work = (uint32_t*)(c->d_q_list + lw.work);
+  unsigned long long* list_sums = (unsigned long long*)(c->d_q_list + lw.sums);
   if (q.counting) HIP_TRY(c, hipMemsetAsync(c->d_q_counters, 0, CNT_WORDS * sizeof(uint32_t), s));
   const SceneDev sc = scene_dev(c);
   if (q.t0) HIP_TRY(c, hipEventRecord(q.t0, s));
@@ -2440,9 +2472,24 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q
                           q.counting, cfg, s);
       break;
     case Walk::Overlap:
+      if (q.list) {
+        launch_overlap_boxes(sc, records, q.cull_mask, c->d_q_scale, false, 0u, nullptr, list_counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
+        launch_list_scan(list_counts, n, list_sums, (unsigned long long*)q.offsets, s);
+        if (q.capacity) launch_list_boxes(sc, records, q.cull_mask, c->d_q_scale, (const unsigned long long*)q.offsets, q.ids, q.capacity, list_work, n, c->d_q_ovf,
+                                          c->d_q_counters, q.counting, cfg, s);
+        break;
+      }
       launch_overlap_boxes(sc, records, q.cull_mask, c->d_q_scale, q.overlap_any, q.max_ids, q.ids, (uint32_t*)q.counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
       break;
     case Walk::Triangles:
+      if (q.list) {
+        if (q.refs) launch_refs_collide(sc, records, q.cull_mask, c->d_q_scale, false, 0u, nullptr, list_counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
+        else launch_collide_triangles(sc, records, q.cull_mask, c->d_q_scale, false, 0u, nullptr, list_counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
+        launch_list_scan(list_counts, n, list_sums, (unsigned long long*)q.offsets, s);
+        if (q.capacity) launch_list_triangles(sc, records, q.refs, q.cull_mask, c->d_q_scale, (const unsigned long long*)q.offsets, q.ids, q.capacity, list_work, n,
+                                              c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
+        break;
+      }
       if (q.refs) launch_refs_collide(sc, records, q.cull_mask, c->d_q_scale, q.overlap_any, q.max_ids, q.ids, (uint32_t*)q.counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
       else launch_collide_triangles(sc, records, q.cull_mask, c->d_q_scale, q.overlap_any, q.max_ids, q.ids, (uint32_t*)q.counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
       break;
@@ -2486,12 +2533,12 @@ int device_query(rt_ctx* c, const Query& q, void* hip_stream) {
 
 // One output of a blocking query: its place in the staging buffer, the Query field that points there, and the host memory it is copied
 // to afterwards (NULL: the caller does not want it; the field stays null and nothing is copied).
-struct HostOutput { void* Query::*field; size_t offset; void* host; size_t bytes; };
+struct HostOutput { void* Query::*field; size_t offset; void* host; size_t bytes; bool preload = false; };
 
 // What every blocking host form does after its own checks: a query from host memory, walked on the context's stream like a device
 // query (its workspace and ordering).  One staging allocation of total_bytes: the records (record_bytes, copied in as they are) at its
 // start, the outputs behind them; two events time the walk.  With q.counting the instrumented walk's node visits and triangle tests
-// come back in stats.
+// come back in stats.  An output with preload is copied in first as well: what the query leaves alone comes back as it was.
 int blocking_query(rt_ctx* c, Query q, const void* records, size_t record_bytes, size_t total_bytes, std::initializer_list<HostOutput> outs, rt_stats* stats) {
   HIP_TRY(c, hipSetDevice(c->device));
   { int w = quiesce(c); if (w) return w; }   // not beside a frame of rt_trace_async; a finished pending frame is collected
@@ -2507,11 +2554,12 @@ int blocking_query(rt_ctx* c, Query q, const void* records, size_t record_bytes,
   HIP_TRY(c, hipEventCreate(&st.e0)); HIP_TRY(c, hipEventCreate(&st.e1));
   q.records = st.buf; q.t0 = st.e0; q.t1 = st.e1;
   for (const HostOutput& o : outs) if (o.host) q.*o.field = st.buf + o.offset;
+  for (const HostOutput& o : outs) if (o.host && o.preload && o.bytes) HIP_TRY(c, hipMemcpy(st.buf + o.offset, o.host, o.bytes, hipMemcpyHostToDevice));
   LaunchCfg cfg = c->cfg;
   if (q.walk == Walk::Plain && c->stack_need > 120) cfg.packet = 0;   // (see enqueue_frame)
   r = enqueue_query(c, c->stream, cfg, q); if (r) return r;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (const HostOutput& o : outs) if (o.host) HIP_TRY(c, hipMemcpy(o.host, st.buf + o.offset, o.bytes, hipMemcpyDeviceToHost));
+  for (const HostOutput& o : outs) if (o.host && o.bytes) HIP_TRY(c, hipMemcpy(o.host, st.buf + o.offset, o.bytes, hipMemcpyDeviceToHost));
   if (stats) {
     if (q.counting) {   // (an any-hit walk counts in the shadow words)
       uint32_t cnt[CNT_TAILS];
@@ -2707,13 +2755,18 @@ int rt_closest_point_hits(rt_ctx* c, size_t n, const float* points4, uint32_t cu
 }
 
 namespace {
+// the rules every overlap call has, capped or list: the number of records and the cull mask
+int overlap_record_arguments(rt_ctx* c, const std::string& name, size_t n, uint32_t cull_mask, const char* what) {
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": too many " + what + " for one call");
+  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": cull_mask is above 0xFF");
+  return RT_OK;
+}
 // the argument rules rt_overlap_boxes*, and rt_overlap_triangles* with what = "triangles", share (pointers aside)
 int overlap_arguments(rt_ctx* c, const std::string& name, size_t n, uint32_t cull_mask, uint32_t flags, uint32_t max_ids, const void* ids, const void* counts,
                       const char* what = "boxes") {
-  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": too many " + what + " for one call");
+  { int w = overlap_record_arguments(c, name, n, cull_mask, what); if (w) return w; }
   if (max_ids > 16u) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": max_ids must be 0..16");
   if ((uint64_t)n * max_ids >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": n * max_ids must be below 0xFFFFFF00 (32-bit record indices)");
-  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": cull_mask is above 0xFF");
   if ((flags & ~RT_OVERLAP_ANY) != 0u) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": unknown flag bits");
   if ((flags & RT_OVERLAP_ANY) && max_ids != 0u) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": RT_OVERLAP_ANY needs max_ids 0");
   if (!ids && !counts) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": neither ids nor counts given");
@@ -2722,7 +2775,75 @@ int overlap_arguments(rt_ctx* c, const std::string& name, size_t n, uint32_t cul
   if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, name + " needs trace_variant 0");
   return RT_OK;
 }
+// ... and the rules of the list calls (pointers' alignment and memory aside): no flag is defined for them, ids and capacity go together
+int overlap_list_arguments(rt_ctx* c, const std::string& name, size_t n, uint32_t cull_mask, uint32_t flags, const void* ids, size_t capacity, const char* what) {
+  { int w = overlap_record_arguments(c, name, n, cull_mask, what); if (w) return w; }
+  if (capacity >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": capacity must be below 0xFFFFFF00 (32-bit record indices)");
+  if (flags & RT_OVERLAP_ANY) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": RT_OVERLAP_ANY does not apply to a list");
+  if (flags != 0u) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": unknown flag bits");
+  if (capacity == 0 && ids) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": capacity 0 gives the offsets only: the ids must be NULL");
+  if (capacity != 0 && !ids) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null id pointer with a capacity above 0");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, name + " needs trace_variant 0");
+  return RT_OK;
+}
+
+// What the three rt_overlap_*_device_list calls do: the checks and ordering of their capped call, then (enqueue_query, Query::list) its
+// count-only walk into the workspace, the scan into the caller's offsets and, with a capacity, the fill walk and k_list_sort into the
+// caller's ids.
+int overlap_list_device(rt_ctx* c, const std::string& name, const char* what, Walk walk, bool refs, size_t n, const void* d_records, uint32_t cull_mask, uint32_t flags,
+                        void* d_offsets, void* d_ids, size_t capacity, void* hip_stream) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  { int w = overlap_list_arguments(c, name, n, cull_mask, flags, d_ids, capacity, what); if (w) return w; }
+  if (n) {
+    if (!d_records || !d_offsets) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null record/offset pointers");
+    if (((uintptr_t)d_records & 15u) || ((uintptr_t)d_offsets & 7u) || ((uintptr_t)d_ids & 3u))
+      return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": " + what + " must be 16-byte aligned, offsets 8-byte aligned, ids 4-byte aligned");
+    { int w = check_device_pointers(c, name, "records, offsets and ids", {d_records, d_offsets, d_ids}); if (w) return w; }
+  }
+  Query q; q.walk = walk; q.n = n; q.records = d_records; q.refs = refs; q.cull_mask = cull_mask; q.list = true; q.offsets = d_offsets; q.ids = d_ids; q.capacity = capacity;
+  return device_query(c, q, hip_stream);
+}
+// ... and their blocking host forms: the records (record_bytes each, a multiple of 8), then the offsets, then the ids, which are copied in
+// first so that the rows the call does not write come back as they were.
+int overlap_list_host(rt_ctx* c, const std::string& name, const char* what, Walk walk, bool refs, size_t n, const void* records, size_t record_bytes, uint32_t cull_mask,
+                      uint32_t flags, uint64_t* offsets, int32_t* ids, size_t capacity, int counting, rt_stats* stats) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  { int w = overlap_list_arguments(c, name, n, cull_mask, flags, ids, capacity, what); if (w) return w; }
+  if ((!records || !offsets) && n) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null record/offset pointers");
+  const size_t rec_bytes = n * record_bytes, off_bytes = (n + 1) * sizeof(uint64_t), id_bytes = capacity * 2 * sizeof(int32_t);
+  Query q; q.walk = walk; q.n = n; q.refs = refs; q.cull_mask = cull_mask; q.list = true; q.capacity = capacity; q.counting = counting != 0;
+  return blocking_query(c, q, records, rec_bytes, rec_bytes + off_bytes + id_bytes,
+                        {{&Query::offsets, rec_bytes, offsets, off_bytes}, {&Query::ids, rec_bytes + off_bytes, ids, id_bytes, true}}, stats);
+}
 }  // namespace
+
+int rt_overlap_boxes_device_list(rt_ctx* c, size_t n, const void* d_boxes8, uint32_t cull_mask, uint32_t flags, void* d_offsets, void* d_ids, size_t capacity,
+                                 void* hip_stream) {
+  return overlap_list_device(c, "rt_overlap_boxes_device_list", "boxes", Walk::Overlap, false, n, d_boxes8, cull_mask, flags, d_offsets, d_ids, capacity, hip_stream);
+}
+int rt_overlap_boxes_list(rt_ctx* c, size_t n, const float* boxes8, uint32_t cull_mask, uint32_t flags, uint64_t* offsets, int32_t* ids, size_t capacity, int counting,
+                          rt_stats* stats) {
+  return overlap_list_host(c, "rt_overlap_boxes_list", "boxes", Walk::Overlap, false, n, boxes8, 8 * sizeof(float), cull_mask, flags, offsets, ids, capacity, counting, stats);
+}
+int rt_overlap_triangles_device_list(rt_ctx* c, size_t n, const void* d_tris12, uint32_t cull_mask, uint32_t flags, void* d_offsets, void* d_ids, size_t capacity,
+                                     void* hip_stream) {
+  return overlap_list_device(c, "rt_overlap_triangles_device_list", "triangles", Walk::Triangles, false, n, d_tris12, cull_mask, flags, d_offsets, d_ids, capacity, hip_stream);
+}
+int rt_overlap_triangles_list(rt_ctx* c, size_t n, const float* tris12, uint32_t cull_mask, uint32_t flags, uint64_t* offsets, int32_t* ids, size_t capacity, int counting,
+                              rt_stats* stats) {
+  return overlap_list_host(c, "rt_overlap_triangles_list", "triangles", Walk::Triangles, false, n, tris12, 12 * sizeof(float), cull_mask, flags, offsets, ids, capacity, counting,
+                           stats);
+}
+int rt_overlap_scene_triangles_device_list(rt_ctx* c, size_t n, const void* d_refs4, uint32_t cull_mask, uint32_t flags, void* d_offsets, void* d_ids, size_t capacity,
+                                           void* hip_stream) {
+  return overlap_list_device(c, "rt_overlap_scene_triangles_device_list", "references", Walk::Triangles, true, n, d_refs4, cull_mask, flags, d_offsets, d_ids, capacity,
+                             hip_stream);
+}
+int rt_overlap_scene_triangles_list(rt_ctx* c, size_t n, const rt_tri_ref* refs, uint32_t cull_mask, uint32_t flags, uint64_t* offsets, int32_t* ids, size_t capacity,
+                                    int counting, rt_stats* stats) {
+  return overlap_list_host(c, "rt_overlap_scene_triangles_list", "references", Walk::Triangles, true, n, refs, sizeof(rt_tri_ref), cull_mask, flags, offsets, ids, capacity,
+                           counting, stats);
+}
 
 // The triangles that touch every query box: the checks and ordering of a device query (rt_closest_point_device), then k_closest_scale and
 // k_overlap_boxes over the caller's records into the caller's rows and counts (enqueue_query).

@@ -257,6 +257,24 @@ void launch_refs_collide(const SceneDev& sc, const float4* tris, uint32_t cull_m
                          uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
 void launch_refs_nearest(const SceneDev& sc, const float4* tris, uint32_t cull_mask, const float* inst_scale, HitRec* hits, float* params, uint32_t n,
                          int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
+// rt_overlap_*_device_list (kernels_list.inc; DESIGN.md §5 "Overlap lists").  The two thresholds of a row's length:
+#ifndef RT_LIST_INSERT_MAX
+#define RT_LIST_INSERT_MAX 64   /* a row of at most this many entries is kept sorted by insertion in the walk, as the capped calls keep theirs; a longer one goes to k_list_sort
+                                   (measured: 4, 16, 32, 64, 128, 256 in profiles/overlap_lists.txt) */
+#endif
+#ifndef RT_LIST_LDS_TILE
+#define RT_LIST_LDS_TILE 2048   /* entries k_list_sort sorts in LDS at once (16 KB: eight workgroups share a CU); a longer row is merged tile by tile through global memory */
+#endif
+// the n + 1 uint64 exclusive offsets of n uint32 counts (offsets[n]: their sum); sums: list_scan_tiles(n) words of scratch
+uint32_t list_scan_tiles(uint32_t n);
+void launch_list_scan(const uint32_t* counts, uint32_t n, unsigned long long* sums, unsigned long long* offsets, hipStream_t s);
+// the fill walk behind launch_overlap_boxes' / launch_collide_triangles' (refs: launch_refs_collide's) count-only walk and the scan: row i,
+// the whole candidate set in (inst, prim) order, at ids[offsets[i] .. offsets[i + 1]) if offsets[i + 1] <= capacity, then k_list_sort
+// over the rows longer than RT_LIST_INSERT_MAX.  work: 1 + n words of scratch (the number of such rows, then their records).
+void launch_list_boxes(const SceneDev& sc, const float4* boxes, uint32_t cull_mask, const float* inst_scale, const unsigned long long* offsets, void* ids,
+                       uint64_t capacity, uint32_t* work, uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
+void launch_list_triangles(const SceneDev& sc, const float4* tris, bool refs, uint32_t cull_mask, const float* inst_scale, const unsigned long long* offsets, void* ids,
+                           uint64_t capacity, uint32_t* work, uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
 // rt_shade_rays_device: k_ray_ingest replaces k_raygen for the caller's n rays (32 bytes each, o.xyz, w3, d.xyz, tmax; sample id = record
 // index): sky colours of the rays that miss the TLAS and (0, 0, 0, 0) for invalid records into f.sample_color, the others into bounce queue 0
 // (workgroup b appends to shard b % 8: f.shard_cap >= 256 * ceil(ray_ingest_block_count(n) / 8)).  f.counters must be zero.

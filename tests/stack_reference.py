@@ -20,7 +20,7 @@ Three descent rules, each as its source states it:
          the opposite order, and k_beam walks the rays of a pixel together, ordering children by the beam's entry; tests that go
          through them take a larger margin.  (beam_shadow_body, alt library only, visits the child that reaches farther from the
          light first: not modelled.)
-  BOUND  closest_body: `swap = b1 < b0` on the squared distance from the point to the child's box: the smaller bound first; a child
+  BOUND  nearest_body: `swap = b1 < b0` on the squared distance from the point to the child's box: the smaller bound first; a child
          is entered while its bound does not exceed the search radius squared.
   FIRST  overlap_body: `push(Q1.w); cur = Q1.z`: child 0 first.  A child is entered if its box touches the query box.
 

@@ -2453,10 +2453,12 @@ void launch_resolve_points(const float4* sample_color, float4* out, uint32_t n_p
   hipLaunchKernelGGL(k_resolve_points, dim3((n_points + 255u) / 256u), dim3(256), 0, s, sample_color, out, n_points, n_samples);
 }
 
+#include "walk_nearest.inc"   // nearest_body: the one walk of the nearest-pair family (points, segments, triangles; the shapes are in their own files below)
 #include "kernels_closest.inc"   // k_closest_point, k_closest_side: the nearest surface point of every query point (rt_closest_point_device)
 
 #include "kernels_closest_hits.inc"   // k_closest_hits, k_closest_hits_side: the K nearest triangles of every query point and their count (rt_closest_point_device_hits)
 
+#include "walk_overlap.inc"   // overlap_body: the one walk of the overlap family (boxes, triangles; capped rows and whole lists)
 #include "kernels_overlap.inc"   // k_overlap_boxes: the triangles that touch every query box (rt_overlap_boxes_device)
 
 #include "kernels_triangles.inc"   // k_collide_triangles: the triangles that cut every query triangle (rt_overlap_triangles_device)

@@ -1,35 +1,14 @@
-// kernels_closest.inc — included by kernels.hip (product and alt translation units alike).
-// rt_closest_point_device: for every query point the nearest point of the scene's surface within the record's radius.  A record-level
-// walk of its own (walk_common.inc: the stack, the chunk feed, the trip exit, the counters), one lane per point: no frame kernel and no
-// k_trace instantiation changes.
+// kernels_closest.inc — included by kernels.hip after walk_nearest.inc (product and alt translation units alike).
+// rt_closest_point_device: for every query point the nearest point of the scene's surface within the record's radius.  The point shape
+// of the nearest-pair family (walk_nearest.inc: the walk, the deflation, the key), one lane per point:
 //
-//  * the box test is the point-to-box distance on the dequantised planes: in world space for TLAS nodes, in the instance's object space
-//    for BLAS nodes, there times s_i <= sigma_min(linear part of o2w) (k_closest_scale), which makes it a lower bound on the world
-//    distance under any affine instance;
-//  * the bound is deflated (DESIGN.md §5 "Closest points"): every axis distance by an absolute slack 2^-16 of the magnitudes that enter
-//    the canonical d2 (the point, the planes, the rows of the transforms), the sum of squares by 1 - 2^-13, so that it stays below the
-//    BINARY32 d2 of every triangle under the box; a subtree is skipped only when its bound EXCEEDS the best d2 (ties still arrive);
-//  * the nearer child first, the farther one pushed;
-//  * the triangle test is the canonical sequence of DESIGN.md §5 in world space (closest_tri): it depends on the point, the instance
-//    record and the packet only, so the result is the minimum of the key (d2, inst, prim) whatever the tree.
+//  * the record is 16 bytes, (p.xyz, r_max); the point is held in the space of the tree being walked: in world space for TLAS nodes,
+//    in the instance's object space for BLAS nodes;
+//  * the node test is the deflated point-to-box distance on the dequantised planes (box_bound);
+//  * the triangle test is the canonical sequence of DESIGN.md §5 in world space (closest_tri).
 #ifndef RT_CLOSEST_WAVES_PER_EU
 #define RT_CLOSEST_WAVES_PER_EU 4   /* the record-level walks' budget */
 #endif
-
-struct ClosestArgs {
-  SceneDev sc;
-  const float4* points;        // n records of 16 bytes: (p.xyz, r_max)
-  const float* inst_scale;     // k_closest_scale: [0] the largest row-term magnitude of any instance's o2w, [1 + i] s_i
-  uint32_t cull_mask;
-  uint32_t n;
-  HitRec* hits;                // n records
-  uint32_t* cursor;            // chunk cursor (zero before the launch)
-  uint32_t* counters;          // the query's counter block (counting form: CNT_NODE_VISITS, CNT_TRI_TESTS)
-  int32_t* ovf_stack;          // ovf_stride ints per thread of the grid
-};
-
-constexpr float CP_ABS = 1.52587890625e-05f;       // 2^-16: absolute slack per unit of magnitude
-constexpr float CP_REL = 0.9998779296875f;         // 1 - 2^-13: factor on the squared bound
 
 // s_i of every instance: a lower bound on the smallest singular value of the linear part L of o2w, tight (to 1e-6) for every matrix.
 // G = L^T L in binary64, four cyclic Jacobi sweeps, then Gershgorin on what is left: lambda_min >= min_k (G_kk - sum_j |G_kj|).
@@ -114,134 +93,29 @@ __device__ __forceinline__ float box_bound(uint32_t wx, uint32_t wy, uint32_t wz
   return (dx * dx + dy * dy + dz * dz) * scale2;
 }
 
-// The entry of instance I (s: its scale of k_closest_scale) by the closest-family point walks (k_closest_point, k_closest_hits): the
-// world point wp into object space (q), the dequantisation of the mesh's tree, and the slack of both spaces in object units
-// (w_slack: the walk's world-space slack) with the factor on the squared bound.
-__device__ __forceinline__ void closest_enter_instance(const InstanceDev* I, float s, F3 wp, float w_slack, F3& q, F3& q_lo, F3& q_scale, float& slack, float& scale2) {
-  const float* w = I->w2o; const float* o = I->o2w;
-  q = xform_point(w, wp);
-  q_lo = mk3(I->q_lo[0], I->q_lo[1], I->q_lo[2]); q_scale = mk3(I->q_scale[0], I->q_scale[1], I->q_scale[2]);
-  // magnitudes: the mesh's planes, the terms of q's rows (they may cancel), the terms of o2w's rows over the mesh's bounds
-  const F3 bm = mk3(fmaxf(__builtin_fabsf(q_lo.x), __builtin_fabsf(__builtin_fmaf(65535.0f, q_scale.x, q_lo.x))),
-                    fmaxf(__builtin_fabsf(q_lo.y), __builtin_fabsf(__builtin_fmaf(65535.0f, q_scale.y, q_lo.y))),
-                    fmaxf(__builtin_fabsf(q_lo.z), __builtin_fabsf(__builtin_fmaf(65535.0f, q_scale.z, q_lo.z))));
-  const F3 ap = mk3(__builtin_fabsf(wp.x), __builtin_fabsf(wp.y), __builtin_fabsf(wp.z));
-  float om = fmaxf(fmaxf(bm.x, bm.y), bm.z), wm = w_slack;
-  for (int r = 0; r < 3; r++) {
-    om = fmaxf(om, __builtin_fabsf(w[4 * r]) * ap.x + __builtin_fabsf(w[4 * r + 1]) * ap.y + __builtin_fabsf(w[4 * r + 2]) * ap.z + __builtin_fabsf(w[4 * r + 3]));
-    wm = fmaxf(wm, CP_ABS * (__builtin_fabsf(o[4 * r]) * bm.x + __builtin_fabsf(o[4 * r + 1]) * bm.y + __builtin_fabsf(o[4 * r + 2]) * bm.z + __builtin_fabsf(o[4 * r + 3])));
-  }
-  slack = CP_ABS * om + wm / s;   // (s == 0: an infinite slack, every bound 0)
-  scale2 = CP_REL * (s * s);
-}
-
-template <bool COUNT>
-__device__ __forceinline__ void closest_body(const ClosestArgs& a) {
-  __shared__ int s_stack[4][STACK2_LDS][64];
-  WalkStack st(s_stack, a.ovf_stack, a.sc.ovf_stride);
-  WalkFeed feed;
-  constexpr int NONE = 0x7FFFFFFF;            // best_inst / best_prim before the first candidate: every (inst, prim) precedes it
-
-  bool need = true;
-  uint32_t pt = 0;
+struct NearestPoint {
+  static constexpr uint32_t STRIDE = 1;
+  struct Params {};
   F3 wp = mk3(0, 0, 0), q = wp;               // the point in world space; in the space of the tree being walked
-  float w_slack = 0.f, slack = 0.f, scale2 = CP_REL;
-  F3 q_lo = wp, q_scale = wp;                 // dequantisation of that tree
-  float best = 0.f, best_u = 0.f, best_v = 0.f;
-  int best_prim = NONE, best_inst = NONE;
-  int cur = REF_DONE, cur_inst = -1;
-  unsigned long long cnt_nodes = 0, cnt_tris = 0;
-
-  auto world_space = [&]() { q = wp; slack = w_slack; scale2 = CP_REL; tlas_dequant(a.sc, q_lo, q_scale); };
-
-  for (;;) {
-    // ---- refill: idle lanes take the next points of the wave's chunk
-    const uint32_t rec = feed.take(__ballot(need), a.cursor, a.n);
-    if (need && rec != WALK_NONE) {
-      pt = rec;
-      const float4 r = ld_stream(&a.points[pt]);
-      wp = mk3(r.x, r.y, r.z);
-      const bool valid = finite_bits(r.x) && finite_bits(r.y) && finite_bits(r.z) && r.w >= 0.0f;
-      best = r.w * r.w; best_u = 0.f; best_v = 0.f; best_prim = NONE; best_inst = NONE;
-      const float pmag = fmaxf(fmaxf(__builtin_fabsf(r.x), __builtin_fabsf(r.y)), __builtin_fabsf(r.z));
-      w_slack = CP_ABS * fmaxf(fmaxf(pmag, tlas_magnitude(a.sc, 0.f)), a.inst_scale[0]);
-      world_space();
-      cur_inst = -1;
-      st.reset(); cur = valid ? a.sc.tlas_root : REF_DONE;
-      need = false;
-    }
-    if (__ballot(!need) == 0) break;   // every lane idle and the points used up
-
-    // ---- interior nodes: every lane at one takes a visit; the trip repeats while most live lanes are interior
-    for (;;) {
-      if (cur >= 0) {
-        uint4 Q0, Q1;
-        walk_node(a.sc, cur, Q0, Q1);
-        if (COUNT) cnt_nodes++;
-        const float b0 = box_bound(Q0.x, Q0.y, Q0.z, q, q_lo, q_scale, slack, scale2);
-        const float b1 = box_bound(Q0.w, Q1.x, Q1.y, q, q_lo, q_scale, slack, scale2);
-        // (!(b > best): inclusive, and an unbounded best opens all)
-        const bool h0 = box_present(Q0.x) && !(b0 > best);
-        const bool h1 = box_present(Q0.w) && !(b1 > best);
-        if (h0 && h1) {
-          const bool swap = b1 < b0;
-          st.push(swap ? (int)Q1.z : (int)Q1.w);
-          cur = swap ? (int)Q1.w : (int)Q1.z;
-        } else if (h0) cur = (int)Q1.z;
-        else if (h1) cur = (int)Q1.w;
-        else cur = st.pop();
-      }
-      if (walk_trip_done(need, cur)) break;
-    }
-
-    if (!need && cur < 0 && cur > REF_MARK && cur_inst >= 0) {
-      // ---- BLAS leaf: the canonical test of every packet, in world space; the smallest key (d2, inst, prim) stays
-      uint32_t first, nt;
-      walk_leaf(cur, first, nt);
-      const float* m = a.sc.inst[cur_inst].o2w;
-      for (uint32_t j = 0; j < nt; j++) {
-        const float4* tp = a.sc.tris + (size_t)(first + j) * 3;
-        const float4 T0 = tp[0], T1 = tp[1], T2 = tp[2];
-        if (COUNT) cnt_tris++;
-        float uu, vv;
-        const float d2 = closest_tri(wp, xform_point(m, mk3(T0.x, T0.y, T0.z)), xform_vec(m, mk3(T0.w, T1.x, T1.y)), xform_vec(m, mk3(T1.z, T1.w, T2.x)), uu, vv);
-        const int prim = (int)__float_as_uint(T2.y);
-        if (d2 < best || (d2 == best && (cur_inst < best_inst || (cur_inst == best_inst && prim < best_prim)))) {
-          best = d2; best_u = uu; best_v = vv; best_prim = prim; best_inst = cur_inst;
-        }
-      }
-      cur = st.pop();
-    }
-    if (!need && cur == REF_MARK) {
-      // ---- leave the instance
-      cur_inst = -1;
-      world_space();
-      cur = st.pop();
-    }
-    if (!need && cur < 0 && cur > REF_MARK && cur_inst < 0) {
-      // ---- TLAS leaf: enter the instance if the call's mask lets it (point -> object space, the slack of both spaces in object units)
-      const int ii = ~cur;
-      const InstanceDev* I = a.sc.inst + ii;
-      if (((I->mask >> INST_WORLD_MASK_SHIFT) & a.cull_mask & 0xFFu) != 0u) {
-        closest_enter_instance(I, a.inst_scale[1 + ii], wp, w_slack, q, q_lo, q_scale, slack, scale2);
-        st.push(REF_MARK);
-        cur_inst = ii; cur = I->blas_root;
-      } else cur = st.pop();
-    }
-    if (!need && cur == REF_DONE) {
-      // ---- finished: the record, or the miss form with the radius as given
-      HitRec h;
-      if (best_inst != NONE) { h.t = __builtin_sqrtf(best); h.u = best_u; h.v = best_v; h.prim = best_prim; h.inst = best_inst; }
-      else { h.t = ld_stream(&a.points[pt]).w; h.u = 0.f; h.v = 0.f; h.prim = -1; h.inst = -1; }
-      a.hits[pt] = h;
-      need = true;
-    }
+  __device__ __forceinline__ bool load(const NearestArgs& a, uint32_t pt, float& r_max, float& pmag, int& against) {
+    const float4 r = ld_stream(&a.records[pt]);
+    wp = mk3(r.x, r.y, r.z); r_max = r.w; against = -1;
+    pmag = fmaxf(fmaxf(__builtin_fabsf(r.x), __builtin_fabsf(r.y)), __builtin_fabsf(r.z));
+    return finite_bits(r.x) && finite_bits(r.y) && finite_bits(r.z) && r.w >= 0.0f;
   }
-  if (COUNT) walk_flush_counters(a.counters, cnt_nodes, cnt_tris);
-}
+  __device__ __forceinline__ void to_world() { q = wp; }
+  __device__ __forceinline__ F3 enter(const InstanceDev* I) { q = xform_point(I->w2o, wp); return wp; }
+  __device__ __forceinline__ void reach(float, float) {}   // (the point's node test has no use for it)
+  __device__ __forceinline__ bool open(uint32_t wx, uint32_t wy, uint32_t wz, F3 q_lo, F3 q_scale, float slack, float scale2, float best, float& b) const {
+    b = box_bound(wx, wy, wz, q, q_lo, q_scale, slack, scale2);
+    return !(b > best);   // (inclusive, and an unbounded best opens all)
+  }
+  __device__ __forceinline__ float test(F3 a, F3 ab, F3 ac, float& u, float& v, Params&) const { return closest_tri(wp, a, ab, ac, u, v); }
+  __device__ __forceinline__ static void store(const NearestArgs&, uint32_t, Params) {}
+};
 
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_CLOSEST_WAVES_PER_EU))) void k_closest_point(ClosestArgs a) { closest_body<false>(a); }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_CLOSEST_WAVES_PER_EU))) void k_closest_point_count(ClosestArgs a) { closest_body<true>(a); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_CLOSEST_WAVES_PER_EU))) void k_closest_point(NearestArgs a) { nearest_body<NearestPoint, false>(a); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_CLOSEST_WAVES_PER_EU))) void k_closest_point_count(NearestArgs a) { nearest_body<NearestPoint, true>(a); }
 
 // The side of the reported triangle's plane the query point lies on, into word 7 of its rt_hit_attr (after k_hit_attr): front when
 // s = dot(cross(e1, e2), xform_point(w2o, p) - v0) < 0, e1 / e2 / v0 from the vertex buffer as k_hit_kind forms them, inverted by
@@ -269,13 +143,6 @@ __global__ __launch_bounds__(256) void k_closest_side(SceneDev sc, const float4*
 void launch_closest_scale(const SceneDev& sc, float* inst_scale, hipStream_t s) {
   hipMemsetAsync(inst_scale, 0, sizeof(float), s);
   if (sc.n_inst > 0) hipLaunchKernelGGL(k_closest_scale, dim3(((uint32_t)sc.n_inst + 255u) / 256u), dim3(256), 0, s, sc.inst, inst_scale, (uint32_t)sc.n_inst);
-}
-
-void launch_closest_point(const SceneDev& sc, const float4* points, uint32_t cull_mask, const float* inst_scale, HitRec* hits, uint32_t n, int32_t* ovf_stack,
-                          uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s) {
-  ClosestArgs a{};
-  a.sc = sc; a.points = points; a.inst_scale = inst_scale; a.cull_mask = cull_mask; a.n = n; a.hits = hits; a.counters = counters; a.ovf_stack = ovf_stack;
-  launch_walk(k_closest_point, k_closest_point_count, a, counters, counting, cfg, s);
 }
 
 void launch_closest_side(const SceneDev& sc, const float4* points, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s) {

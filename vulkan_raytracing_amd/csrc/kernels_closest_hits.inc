@@ -3,8 +3,8 @@
 // within it (a contact manifold, PhysX's overlapSphere count, the few nearest triangles to vote over).  k_closest_point's walk with
 // k_query_hits' row in the place of the one best record: a walk of its own, no existing kernel changes.
 //
-//  * the arithmetic is kernels_closest.inc's as it stands: closest_tri, box_bound with CP_ABS / CP_REL, closest_enter_instance, the
-//    scales of k_closest_scale; the deflated bound stays below the binary32 d2 of every triangle under the box, so which triangles
+//  * the arithmetic is k_closest_point's as it stands: closest_tri and box_bound (kernels_closest.inc) with CP_ABS / CP_REL and
+//    closest_enter_instance (walk_nearest.inc), the scales of k_closest_scale; the deflated bound stays below the binary32 d2 of every triangle under the box, so which triangles
 //    arrive at the leaf test does not depend on the tree (DESIGN.md §5 "K nearest triangles");
 //  * candidates: d2 not NaN and d2 <= r_max * r_max — the set k_closest_point takes its minimum from;
 //  * the row: in the lane's own row of the caller's hit array, kept sorted by (d2, inst, prim) by insertion from the back, d2 itself in

@@ -4,7 +4,7 @@
 //  * count: the count-only walk of the capped call (k == 0), unchanged, into n counts of the query workspace;
 //  * scan: k_list_scan_sums, k_list_scan_tops, k_list_scan_offsets turn the uint32 counts into n + 1 uint64 row starts, the last of
 //    them the total.  Every sum is a uint64: n counts below 2^32 each do not fit anything less;
-//  * fill: the LIST instantiations of overlap_body and collide_body (k_list_boxes, k_list_triangles, k_list_refs) walk again and write
+//  * fill: the LIST instantiations of overlap_body (walk_overlap.inc: k_list_boxes, k_list_triangles, k_list_refs) walk again and write
 //    every candidate into its row.  A lane passes over a record whose row is empty or ends beyond the capacity.  A row of at most
 //    RT_LIST_INSERT_MAX entries is kept sorted by insertion, as the capped kernels keep theirs; a longer one is written in walk order
 //    and its record goes onto a worklist.  k_list_sort, one workgroup per listed row, sorts such a row in place by (inst, prim).
@@ -86,12 +86,12 @@ void launch_list_scan(const uint32_t* counts, uint32_t n, unsigned long long* su
 }
 
 // ---- fill: the walks
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_OVERLAP_WAVES_PER_EU))) void k_list_boxes(OverlapArgs a) { overlap_body<false, true>(a); }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_OVERLAP_WAVES_PER_EU))) void k_list_boxes_count(OverlapArgs a) { overlap_body<true, true>(a); }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_OVERLAP_WAVES_PER_EU))) void k_list_triangles(CollideArgs a) { collide_body<false, false, true>(a); }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_OVERLAP_WAVES_PER_EU))) void k_list_triangles_count(CollideArgs a) { collide_body<true, false, true>(a); }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_OVERLAP_WAVES_PER_EU))) void k_list_refs(CollideArgs a) { collide_body<false, true, true>(a); }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_OVERLAP_WAVES_PER_EU))) void k_list_refs_count(CollideArgs a) { collide_body<true, true, true>(a); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_OVERLAP_WAVES_PER_EU))) void k_list_boxes(OverlapArgs a) { overlap_body<OverlapBox, false, false, true>(a); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_OVERLAP_WAVES_PER_EU))) void k_list_boxes_count(OverlapArgs a) { overlap_body<OverlapBox, true, false, true>(a); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_OVERLAP_WAVES_PER_EU))) void k_list_triangles(OverlapArgs a) { overlap_body<OverlapTriangle, false, false, true>(a); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_OVERLAP_WAVES_PER_EU))) void k_list_triangles_count(OverlapArgs a) { overlap_body<OverlapTriangle, true, false, true>(a); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_OVERLAP_WAVES_PER_EU))) void k_list_refs(OverlapArgs a) { overlap_body<OverlapTriangle, false, true, true>(a); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_OVERLAP_WAVES_PER_EU))) void k_list_refs_count(OverlapArgs a) { overlap_body<OverlapTriangle, true, true, true>(a); }
 
 // ---- sort
 constexpr uint32_t LIST_TILE = RT_LIST_LDS_TILE;
@@ -189,35 +189,15 @@ __global__ __launch_bounds__(256) void k_list_sort(ListSortArgs a) {
   }
 }
 
-// ---- launches.  list_counts: n counts (the count walk's), work: 1 + n words (the number of listed rows, then the rows).
-template <class Args>
-static void list_fill_args(Args& a, const unsigned long long* offsets, uint64_t capacity, uint32_t* work) {
-  a.k = 0u; a.any = 0u; a.counts = nullptr;
-  a.offsets = offsets; a.capacity = capacity; a.work_count = work; a.worklist = work + 1;
-}
-static void launch_list_sort(void* ids, const unsigned long long* offsets, uint32_t* work, uint32_t n, const LaunchCfg& cfg, hipStream_t s) {
+// ---- launch.  work: 1 + n words (the number of listed rows, then the rows).
+void launch_overlap_list(OverlapShape shape, const SceneDev& sc, const float4* records, uint32_t cull_mask, const float* inst_scale, const unsigned long long* offsets,
+                         void* ids, uint64_t capacity, uint32_t* work, uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg,
+                         hipStream_t s) {
+  static void (*const kernels[3][2])(OverlapArgs) = {{k_list_boxes, k_list_boxes_count}, {k_list_triangles, k_list_triangles_count}, {k_list_refs, k_list_refs_count}};
+  OverlapArgs a = overlap_args(sc, records, cull_mask, inst_scale, ids, n, ovf_stack, counters);
+  a.offsets = offsets; a.capacity = capacity; a.work_count = work; a.worklist = work + 1;   // (k = 0, any = 0, no counts)
+  hipMemsetAsync(work, 0, sizeof(uint32_t), s);
+  launch_walk(kernels[(int)shape][0], kernels[(int)shape][1], a, counters, counting, cfg, s);
   ListSortArgs t{(IdRec*)ids, offsets, work + 1, work};
-  const uint32_t blocks = min((uint32_t)cfg.trace_blocks, n);
-  hipLaunchKernelGGL(k_list_sort, dim3(blocks), dim3(256), 0, s, t);
-}
-
-void launch_list_boxes(const SceneDev& sc, const float4* boxes, uint32_t cull_mask, const float* inst_scale, const unsigned long long* offsets, void* ids,
-                       uint64_t capacity, uint32_t* work, uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s) {
-  OverlapArgs a{};
-  a.sc = sc; a.boxes = boxes; a.inst_scale = inst_scale; a.cull_mask = cull_mask; a.n = n; a.ids = (IdRec*)ids; a.counters = counters; a.ovf_stack = ovf_stack;
-  list_fill_args(a, offsets, capacity, work);
-  hipMemsetAsync(work, 0, sizeof(uint32_t), s);
-  launch_walk(k_list_boxes, k_list_boxes_count, a, counters, counting, cfg, s);
-  launch_list_sort(ids, offsets, work, n, cfg, s);
-}
-
-void launch_list_triangles(const SceneDev& sc, const float4* tris, bool refs, uint32_t cull_mask, const float* inst_scale, const unsigned long long* offsets, void* ids,
-                           uint64_t capacity, uint32_t* work, uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s) {
-  CollideArgs a{};
-  a.sc = sc; a.tris = tris; a.inst_scale = inst_scale; a.cull_mask = cull_mask; a.n = n; a.ids = (IdRec*)ids; a.counters = counters; a.ovf_stack = ovf_stack;
-  list_fill_args(a, offsets, capacity, work);
-  hipMemsetAsync(work, 0, sizeof(uint32_t), s);
-  if (refs) launch_walk(k_list_refs, k_list_refs_count, a, counters, counting, cfg, s);
-  else launch_walk(k_list_triangles, k_list_triangles_count, a, counters, counting, cfg, s);
-  launch_list_sort(ids, offsets, work, n, cfg, s);
+  hipLaunchKernelGGL(k_list_sort, dim3(min((uint32_t)cfg.trace_blocks, n)), dim3(256), 0, s, t);
 }

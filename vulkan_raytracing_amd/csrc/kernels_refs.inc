@@ -8,8 +8,8 @@
 //    the bits of inst in word 7 and of against in word 11.  An invalid reference gets nine quiet NaNs, which both walks answer as they
 //    answer any record with a non-finite vertex.  Nothing of the scene is indexed with an unchecked value: inst, then against, then prim
 //    against the triangle count of the instance's mesh (InstanceDev::prim_count), then the loads;
-//  * the walks are the REFS instantiations of collide_body and triangle_body (kernels_triangles.inc, kernels_triangle.inc) over the
-//    expanded records, under kernel names of their own.
+//  * the walks are the REFS instantiations of overlap_body and nearest_body (walk_overlap.inc, walk_nearest.inc) with the triangle
+//    shapes (kernels_triangles.inc, kernels_triangle.inc) over the expanded records, under kernel names of their own.
 
 __global__ __launch_bounds__(256) void k_refs_expand(SceneDev sc, const int4* __restrict__ refs, float4* __restrict__ out, uint32_t n, uint32_t n_vert_floats) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -51,28 +51,12 @@ __global__ __launch_bounds__(256) void k_refs_expand(SceneDev sc, const int4* __
   o[2] = make_float4(P2.x, P2.y, P2.z, __int_as_float(against));
 }
 
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_OVERLAP_WAVES_PER_EU))) void k_refs_collide(CollideArgs a) { collide_body<false, true>(a); }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_OVERLAP_WAVES_PER_EU))) void k_refs_collide_count(CollideArgs a) { collide_body<true, true>(a); }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_TRIANGLE_WAVES_PER_EU))) void k_refs_nearest(TriangleArgs a) { triangle_body<false, true>(a); }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_TRIANGLE_WAVES_PER_EU))) void k_refs_nearest_count(TriangleArgs a) { triangle_body<true, true>(a); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_OVERLAP_WAVES_PER_EU))) void k_refs_collide(OverlapArgs a) { overlap_body<OverlapTriangle, false, true>(a); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_OVERLAP_WAVES_PER_EU))) void k_refs_collide_count(OverlapArgs a) { overlap_body<OverlapTriangle, true, true>(a); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_TRIANGLE_WAVES_PER_EU))) void k_refs_nearest(NearestArgs a) { nearest_body<NearestTriangle, false, true>(a); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_TRIANGLE_WAVES_PER_EU))) void k_refs_nearest_count(NearestArgs a) { nearest_body<NearestTriangle, true, true>(a); }
 
 void launch_refs_expand(const SceneDev& sc, const void* refs, float4* tris, uint32_t n, uint64_t n_vert_floats, hipStream_t s) {
   const uint32_t cap = (uint32_t)(n_vert_floats < 0xFFFFFFFFull ? n_vert_floats : 0xFFFFFFFFull);
   hipLaunchKernelGGL(k_refs_expand, dim3((n + 255u) / 256u), dim3(256), 0, s, sc, (const int4*)refs, tris, n, cap);
-}
-
-void launch_refs_collide(const SceneDev& sc, const float4* tris, uint32_t cull_mask, const float* inst_scale, bool any, uint32_t k, void* ids, uint32_t* counts,
-                         uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s) {
-  CollideArgs a{};
-  a.sc = sc; a.tris = tris; a.inst_scale = inst_scale; a.cull_mask = cull_mask; a.n = n; a.k = k; a.any = any ? 1u : 0u; a.ids = (IdRec*)ids; a.counts = counts;
-  a.counters = counters; a.ovf_stack = ovf_stack;
-  launch_walk(k_refs_collide, k_refs_collide_count, a, counters, counting, cfg, s);
-}
-
-void launch_refs_nearest(const SceneDev& sc, const float4* tris, uint32_t cull_mask, const float* inst_scale, HitRec* hits, float* params, uint32_t n,
-                         int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s) {
-  TriangleArgs a{};
-  a.sc = sc; a.tris = tris; a.inst_scale = inst_scale; a.cull_mask = cull_mask; a.n = n; a.hits = hits; a.params = params;
-  a.counters = counters; a.ovf_stack = ovf_stack;
-  launch_walk(k_refs_nearest, k_refs_nearest_count, a, counters, counting, cfg, s);
 }

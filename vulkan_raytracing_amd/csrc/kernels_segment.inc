@@ -1,40 +1,24 @@
 // kernels_segment.inc — included by kernels.hip after kernels_inside.inc (product and alt translation units alike).
 // rt_closest_segment_device: for every segment record (P0, r_max, P1) the nearest pair of a point of the closed segment P0..P1 and a
-// point of the scene's surface within the record's radius.  A record-level walk of its own (walk_common.inc: the stack, the chunk feed,
-// the trip exit, the counters), one lane per segment: no frame kernel and no existing query kernel changes.
+// point of the scene's surface within the record's radius.  The segment shape of the nearest-pair family (walk_nearest.inc), one lane
+// per segment:
 //
 //  * the segment is held as its midpoint m and half vector h in the space of the tree being walked: in world space for TLAS nodes, in
-//    the instance's object space for BLAS nodes (both endpoints through w2o), where distances are multiplied by s_i <= sigma_min(linear
-//    part of o2w) (k_closest_scale), which makes them lower bounds on world distances under any affine instance;
+//    the instance's object space for BLAS nodes (both endpoints through w2o);
 //  * node test (i): the per-axis gap |m - c| - e - |h| between the segment's interval and the box (centre c, half extents e), every axis
-//    shortened by the closest-point walk's absolute slack (2^-16 of the magnitudes that enter the canonical d2: both endpoints, the
-//    planes, the rows of the transforms, word 0 of k_closest_scale's array), the sum of squares times 1 - 2^-13 (DESIGN.md §5 "Closest
-//    points of segments"); it orders the children, nearer first, and a subtree is skipped only when its bound EXCEEDS the best d2;
+//    shortened by the family's absolute slack (the magnitudes: both endpoints, the planes, the rows of the transforms, word 0 of
+//    k_closest_scale's array), the sum of squares times 1 - 2^-13 (DESIGN.md §5 "Closest points of segments"); it orders the children;
 //  * node test (ii) (RT_SEGMENT_SLAB): the slab test of the path m + s h, s in [-1, 1], against the box inflated on every side by
 //    rho = sqrt(best / scale2) (1 + 2^-13) plus the same slack, in its separating-axis form (Ericson, Real-Time Collision Detection
 //    §5.3.3): the three box axes are test (i), the three axes cross(axis, h) are tested here, without a reciprocal direction.  A
 //    segment within rho of a box meets the box inflated by rho on every side.  An unbounded best (rho = +inf) or a NaN opens the box;
-//  * the triangle test is the canonical sequence of DESIGN.md §5 in world space (segment_tri): it depends on the record, the instance
-//    record and the packet only, so the result is the minimum of the key (d2, inst, prim) whatever the tree.
+//  * the triangle test is the canonical sequence of DESIGN.md §5 in world space (segment_tri); the result word is the parameter s.
 #ifndef RT_SEGMENT_WAVES_PER_EU
 #define RT_SEGMENT_WAVES_PER_EU 4   /* the record-level walks' budget */
 #endif
 #ifndef RT_SEGMENT_SLAB
 #define RT_SEGMENT_SLAB 1           /* node test (ii); 0: test (i) alone (tools/closest_segment_cost.py measures both) */
 #endif
-
-struct SegmentArgs {
-  SceneDev sc;
-  const float4* segs;          // n records of 32 bytes: (P0.xyz, r_max), (P1.xyz, ignored)
-  const float* inst_scale;     // k_closest_scale: [0] the largest row-term magnitude of any instance's o2w, [1 + i] s_i
-  uint32_t cull_mask;
-  uint32_t n;
-  HitRec* hits;                // n records
-  float* params;               // n floats: s of the segment's point of the nearest pair (0 on a miss), or null
-  uint32_t* cursor;            // chunk cursor (zero before the launch)
-  uint32_t* counters;          // the query's counter block (counting form: CNT_NODE_VISITS, CNT_TRI_TESTS)
-  int32_t* ovf_stack;          // ovf_stride ints per thread of the grid
-};
 
 // the canonical clamp to [0, 1]: NaN and -0 give +0 (fminf(fmaxf(x, 0), 1) with the sign of a zero result fixed)
 __device__ __forceinline__ float seg_clamp(float x) { return x > 0.0f ? (x < 1.0f ? x : 1.0f) : 0.0f; }
@@ -123,131 +107,40 @@ __device__ __forceinline__ bool segment_box(uint32_t wx, uint32_t wy, uint32_t w
   return open;
 }
 
-template <bool COUNT>
-__device__ __forceinline__ void segment_body(const SegmentArgs& a) {
-  __shared__ int s_stack[4][STACK2_LDS][64];
-  WalkStack st(s_stack, a.ovf_stack, a.sc.ovf_stride);
-  WalkFeed feed;
-  constexpr int NONE = 0x7FFFFFFF;            // best_inst / best_prim before the first candidate: every (inst, prim) precedes it
-
-  bool need = true;
-  uint32_t pt = 0;
+struct NearestSegment {
+  static constexpr uint32_t STRIDE = 2;
+  struct Params { float s = 0.f; };           // the segment's point of the nearest pair
   F3 w0 = mk3(0, 0, 0), w1 = w0;              // the endpoints in world space
   F3 m = w0, h = w0;                          // midpoint and half vector in the space of the tree being walked
-  float w_slack = 0.f, slack = 0.f, scale2 = CP_REL, rho = 0.f;
-  F3 q_lo = w0, q_scale = w0;                 // dequantisation of that tree
-  float best = 0.f, best_u = 0.f, best_v = 0.f, best_s = 0.f;
-  int best_prim = NONE, best_inst = NONE;
-  int cur = REF_DONE, cur_inst = -1;
-  unsigned long long cnt_nodes = 0, cnt_tris = 0;
-
-  // the reach of the best d2 in the units of the tree being walked, rounded up
-  auto reach = [&]() { rho = __builtin_sqrtf(best / scale2) * SW_T_HI; };
-  auto world_space = [&]() {
-    m = mk3(w0.x * 0.5f + w1.x * 0.5f, w0.y * 0.5f + w1.y * 0.5f, w0.z * 0.5f + w1.z * 0.5f);
-    h = mk3(w1.x * 0.5f - w0.x * 0.5f, w1.y * 0.5f - w0.y * 0.5f, w1.z * 0.5f - w0.z * 0.5f);
-    slack = w_slack; scale2 = CP_REL; tlas_dequant(a.sc, q_lo, q_scale);
-    reach();
-  };
-
-  for (;;) {
-    // ---- refill: idle lanes take the next records of the wave's chunk
-    const uint32_t rec = feed.take(__ballot(need), a.cursor, a.n);
-    if (need && rec != WALK_NONE) {
-      pt = rec;
-      const float4 r0 = ld_stream(&a.segs[2u * (size_t)pt]), r1 = ld_stream(&a.segs[2u * (size_t)pt + 1u]);
-      w0 = mk3(r0.x, r0.y, r0.z); w1 = mk3(r1.x, r1.y, r1.z);
-      const bool valid = finite_bits(r0.x) && finite_bits(r0.y) && finite_bits(r0.z) && finite_bits(r1.x) && finite_bits(r1.y) && finite_bits(r1.z) && r0.w >= 0.0f;
-      best = r0.w * r0.w; best_u = 0.f; best_v = 0.f; best_s = 0.f; best_prim = NONE; best_inst = NONE;
-      const float pmag = fmaxf(fmaxf(fmaxf(__builtin_fabsf(r0.x), __builtin_fabsf(r0.y)), __builtin_fabsf(r0.z)),
-                               fmaxf(fmaxf(__builtin_fabsf(r1.x), __builtin_fabsf(r1.y)), __builtin_fabsf(r1.z)));
-      w_slack = CP_ABS * fmaxf(fmaxf(pmag, tlas_magnitude(a.sc, 0.f)), a.inst_scale[0]);
-      world_space();
-      cur_inst = -1;
-      st.reset(); cur = valid ? a.sc.tlas_root : REF_DONE;
-      need = false;
-    }
-    if (__ballot(!need) == 0) break;   // every lane idle and the records used up
-
-    // ---- interior nodes: every lane at one takes a visit; the trip repeats while most live lanes are interior
-    for (;;) {
-      if (cur >= 0) {
-        uint4 Q0, Q1;
-        walk_node(a.sc, cur, Q0, Q1);
-        if (COUNT) cnt_nodes++;
-        float b0, b1;
-        const bool h0 = segment_box(Q0.x, Q0.y, Q0.z, m, h, q_lo, q_scale, slack, scale2, rho, best, b0) && box_present(Q0.x);
-        const bool h1 = segment_box(Q0.w, Q1.x, Q1.y, m, h, q_lo, q_scale, slack, scale2, rho, best, b1) && box_present(Q0.w);
-        if (h0 && h1) {
-          const bool swap = b1 < b0;
-          st.push(swap ? (int)Q1.z : (int)Q1.w);
-          cur = swap ? (int)Q1.w : (int)Q1.z;
-        } else if (h0) cur = (int)Q1.z;
-        else if (h1) cur = (int)Q1.w;
-        else cur = st.pop();
-      }
-      if (walk_trip_done(need, cur)) break;
-    }
-
-    if (!need && cur < 0 && cur > REF_MARK && cur_inst >= 0) {
-      // ---- BLAS leaf: the canonical test of every packet, in world space; the smallest key (d2, inst, prim) stays
-      uint32_t first, nt;
-      walk_leaf(cur, first, nt);
-      const float* o = a.sc.inst[cur_inst].o2w;
-      for (uint32_t j = 0; j < nt; j++) {
-        const float4* tp = a.sc.tris + (size_t)(first + j) * 3;
-        const float4 T0 = tp[0], T1 = tp[1], T2 = tp[2];
-        if (COUNT) cnt_tris++;
-        float uu, vv, ss;
-        const float d2 = segment_tri(w0, w1, xform_point(o, mk3(T0.x, T0.y, T0.z)), xform_vec(o, mk3(T0.w, T1.x, T1.y)), xform_vec(o, mk3(T1.z, T1.w, T2.x)), uu, vv, ss);
-        const int prim = (int)__float_as_uint(T2.y);
-        if (d2 < best || (d2 == best && (cur_inst < best_inst || (cur_inst == best_inst && prim < best_prim)))) {
-          best = d2; best_u = uu; best_v = vv; best_s = ss; best_prim = prim; best_inst = cur_inst;
-        }
-      }
-      reach();
-      cur = st.pop();
-    }
-    if (!need && cur == REF_MARK) {
-      // ---- leave the instance
-      cur_inst = -1;
-      world_space();
-      cur = st.pop();
-    }
-    if (!need && cur < 0 && cur > REF_MARK && cur_inst < 0) {
-      // ---- TLAS leaf: enter the instance if the call's mask lets it (the endpoints -> object space, the slack of both spaces in object units)
-      const int ii = ~cur;
-      const InstanceDev* I = a.sc.inst + ii;
-      if (((I->mask >> INST_WORLD_MASK_SHIFT) & a.cull_mask & 0xFFu) != 0u) {
-        // the closest-point walks' entry with the per-component larger magnitude of the endpoints as the point (its slack formula reads
-        // |wp| only; the object-space point it returns for that argument is not used), then the endpoints themselves through w2o
-        const F3 ap = mk3(fmaxf(__builtin_fabsf(w0.x), __builtin_fabsf(w1.x)), fmaxf(__builtin_fabsf(w0.y), __builtin_fabsf(w1.y)),
-                          fmaxf(__builtin_fabsf(w0.z), __builtin_fabsf(w1.z)));
-        F3 unused;
-        closest_enter_instance(I, a.inst_scale[1 + ii], ap, w_slack, unused, q_lo, q_scale, slack, scale2);
-        const F3 q0 = xform_point(I->w2o, w0), q1 = xform_point(I->w2o, w1);
-        m = mk3(q0.x * 0.5f + q1.x * 0.5f, q0.y * 0.5f + q1.y * 0.5f, q0.z * 0.5f + q1.z * 0.5f);
-        h = mk3(q1.x * 0.5f - q0.x * 0.5f, q1.y * 0.5f - q0.y * 0.5f, q1.z * 0.5f - q0.z * 0.5f);
-        reach();
-        st.push(REF_MARK);
-        cur_inst = ii; cur = I->blas_root;
-      } else cur = st.pop();
-    }
-    if (!need && cur == REF_DONE) {
-      // ---- finished: the record, or the miss form with the radius as given
-      HitRec hr;
-      if (best_inst != NONE) { hr.t = __builtin_sqrtf(best); hr.u = best_u; hr.v = best_v; hr.prim = best_prim; hr.inst = best_inst; }
-      else { hr.t = ld_stream(&a.segs[2u * (size_t)pt]).w; hr.u = 0.f; hr.v = 0.f; hr.prim = -1; hr.inst = -1; best_s = 0.f; }
-      a.hits[pt] = hr;
-      if (a.params) a.params[pt] = best_s;
-      need = true;
-    }
+  float rho = 0.f;                            // the reach of the best d2 in that space's units, rounded up
+  __device__ __forceinline__ bool load(const NearestArgs& a, uint32_t pt, float& r_max, float& pmag, int& against) {
+    const float4 r0 = ld_stream(&a.records[2u * (size_t)pt]), r1 = ld_stream(&a.records[2u * (size_t)pt + 1u]);
+    w0 = mk3(r0.x, r0.y, r0.z); w1 = mk3(r1.x, r1.y, r1.z); r_max = r0.w; against = -1;
+    pmag = fmaxf(fmaxf(fmaxf(__builtin_fabsf(r0.x), __builtin_fabsf(r0.y)), __builtin_fabsf(r0.z)),
+                 fmaxf(fmaxf(__builtin_fabsf(r1.x), __builtin_fabsf(r1.y)), __builtin_fabsf(r1.z)));
+    return finite_bits(r0.x) && finite_bits(r0.y) && finite_bits(r0.z) && finite_bits(r1.x) && finite_bits(r1.y) && finite_bits(r1.z) && r0.w >= 0.0f;
   }
-  if (COUNT) walk_flush_counters(a.counters, cnt_nodes, cnt_tris);
-}
+  __device__ __forceinline__ void hold(F3 p0, F3 p1) {
+    m = mk3(p0.x * 0.5f + p1.x * 0.5f, p0.y * 0.5f + p1.y * 0.5f, p0.z * 0.5f + p1.z * 0.5f);
+    h = mk3(p1.x * 0.5f - p0.x * 0.5f, p1.y * 0.5f - p0.y * 0.5f, p1.z * 0.5f - p0.z * 0.5f);
+  }
+  __device__ __forceinline__ void to_world() { hold(w0, w1); }
+  __device__ __forceinline__ F3 enter(const InstanceDev* I) {
+    hold(xform_point(I->w2o, w0), xform_point(I->w2o, w1));
+    return mk3(fmaxf(__builtin_fabsf(w0.x), __builtin_fabsf(w1.x)), fmaxf(__builtin_fabsf(w0.y), __builtin_fabsf(w1.y)), fmaxf(__builtin_fabsf(w0.z), __builtin_fabsf(w1.z)));
+  }
+  __device__ __forceinline__ void reach(float best, float scale2) { rho = __builtin_sqrtf(best / scale2) * SW_T_HI; }
+  __device__ __forceinline__ bool open(uint32_t wx, uint32_t wy, uint32_t wz, F3 q_lo, F3 q_scale, float slack, float scale2, float best, float& b) const {
+    return segment_box(wx, wy, wz, m, h, q_lo, q_scale, slack, scale2, rho, best, b);
+  }
+  __device__ __forceinline__ float test(F3 a, F3 ab, F3 ac, float& u, float& v, Params& p) const { return segment_tri(w0, w1, a, ab, ac, u, v, p.s); }
+  __device__ __forceinline__ static void store(const NearestArgs& a, uint32_t pt, Params p) {
+    if (a.params) a.params[pt] = p.s;
+  }
+};
 
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SEGMENT_WAVES_PER_EU))) void k_closest_segment(SegmentArgs a) { segment_body<false>(a); }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SEGMENT_WAVES_PER_EU))) void k_closest_segment_count(SegmentArgs a) { segment_body<true>(a); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SEGMENT_WAVES_PER_EU))) void k_closest_segment(NearestArgs a) { nearest_body<NearestSegment, false>(a); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_SEGMENT_WAVES_PER_EU))) void k_closest_segment_count(NearestArgs a) { nearest_body<NearestSegment, true>(a); }
 
 // The side of the reported triangle's plane the segment's point of the nearest pair lies on, into word 7 of its rt_hit_attr (after
 // k_hit_attr): k_closest_side's rule at p = P0 + s d, d = P1 - P0 (per component one product and one sum), 0 on a miss.
@@ -264,13 +157,6 @@ __global__ __launch_bounds__(256) void k_segment_side(SceneDev sc, const float4*
     kind = closest_side_word(sc, &p, hr);
   }
   attr[8u * (size_t)i + 7u] = kind;
-}
-
-void launch_closest_segment(const SceneDev& sc, const float4* segs, uint32_t cull_mask, const float* inst_scale, HitRec* hits, float* params, uint32_t n,
-                            int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s) {
-  SegmentArgs a{};
-  a.sc = sc; a.segs = segs; a.inst_scale = inst_scale; a.cull_mask = cull_mask; a.n = n; a.hits = hits; a.params = params; a.counters = counters; a.ovf_stack = ovf_stack;
-  launch_walk(k_closest_segment, k_closest_segment_count, a, counters, counting, cfg, s);
 }
 
 void launch_segment_side(const SceneDev& sc, const float4* segs, const float* params, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s) {

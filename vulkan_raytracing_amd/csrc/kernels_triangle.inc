@@ -1,40 +1,25 @@
 // kernels_triangle.inc — included by kernels.hip after kernels_segment.inc (product and alt translation units alike).
 // rt_closest_triangle_device: for every triangle record (P0, r_max, P1, w7, P2, w11) the nearest pair of a point of the closed triangle
-// P0 P1 P2 and a point of the scene's surface within the record's radius.  A record-level walk of its own (walk_common.inc: the stack,
-// the chunk feed, the trip exit, the counters), one lane per record: no frame kernel and no existing query kernel changes.
+// P0 P1 P2 and a point of the scene's surface within the record's radius.  The triangle shape of the nearest-pair family
+// (walk_nearest.inc), one lane per record:
 //
 //  * the query triangle is held as the centre m and the half extents eq of its three vertices' bounds in the space of the tree being
-//    walked: in world space for TLAS nodes, in the instance's object space for BLAS nodes (the three vertices through w2o), where
-//    distances are multiplied by s_i <= sigma_min(linear part of o2w) (k_closest_scale);
+//    walked: in world space for TLAS nodes, in the instance's object space for BLAS nodes (the three vertices through w2o);
 //  * node test (i): the per-axis gap |m - c| - e - eq between the triangle's bounds and the box (centre c, half extents e), every axis
-//    shortened by the closest-point walk's absolute slack, the sum of squares times 1 - 2^-13 (DESIGN.md §5 "Closest points of
-//    triangles"): segment_box's test (i) with eq where it has |h|; it orders the children, nearer first, and a subtree is skipped only
-//    when its bound EXCEEDS the best d2;
+//    shortened by the family's absolute slack, the sum of squares times 1 - 2^-13 (DESIGN.md §5 "Closest points of triangles"):
+//    segment_box's test (i) with eq where it has |h|; it orders the children;
 //  * node test (ii) (RT_TRIANGLE_PLANE): the query's plane against the box inflated on every side by rho = sqrt(best / scale2)
 //    (1 + 2^-13) plus the same slack: with n_q = cross(P1 - P0, P2 - P0) in the walked space the box is skipped when
 //    |dot(n_q, c - p0)| > sum_k (e_k + infl) |n_q,k| + E, E = 2^-17 L^3 (L the largest edge component) covering n_q's own rounding, so
 //    that a needle's meaningless normal cannot prune.  An unbounded best (rho = +inf) or a NaN opens the box;
-//  * the triangle test is the canonical sequence of DESIGN.md §5 in world space (triangle_tri): it depends on the record, the instance
-//    record and the packet only, so the result is the minimum of the key (d2, inst, prim) whatever the tree.
+//  * the triangle test is the canonical sequence of DESIGN.md §5 in world space (triangle_tri); the result words are (qu, qv);
+//  * by reference (kernels_refs.inc): words 7 and 11 are the source instance and `against`, read again at every TLAS leaf.
 #ifndef RT_TRIANGLE_WAVES_PER_EU
 #define RT_TRIANGLE_WAVES_PER_EU 4   /* the record-level walks' budget */
 #endif
 #ifndef RT_TRIANGLE_PLANE
 #define RT_TRIANGLE_PLANE 1          /* node test (ii); 0: test (i) alone (tools/closest_triangle_cost.py measures both) */
 #endif
-
-struct TriangleArgs {
-  SceneDev sc;
-  const float4* tris;          // n records of 48 bytes: (P0.xyz, r_max), (P1.xyz, ignored), (P2.xyz, ignored)
-  const float* inst_scale;     // k_closest_scale: [0] the largest row-term magnitude of any instance's o2w, [1 + i] s_i
-  uint32_t cull_mask;
-  uint32_t n;
-  HitRec* hits;                // n records
-  float* params;               // n pairs (qu, qv) of the query's point of the nearest pair (0, 0 on a miss), or null
-  uint32_t* cursor;            // chunk cursor (zero before the launch)
-  uint32_t* counters;          // the query's counter block (counting form: CNT_NODE_VISITS, CNT_TRI_TESTS)
-  int32_t* ovf_stack;          // ovf_stride ints per thread of the grid
-};
 
 // vertex k (0, 1, 2) of a triangle held in registers, by selects (the loops below stay loops)
 __device__ __forceinline__ F3 tri_pick(int k, F3 p0, F3 p1, F3 p2) { return k == 0 ? p0 : (k == 1 ? p1 : p2); }
@@ -158,31 +143,25 @@ __device__ __forceinline__ bool triangle_box(uint32_t wx, uint32_t wy, uint32_t 
   return open;
 }
 
-// REFS (kernels_refs.inc, rt_closest_scene_triangle_device): collide_body's two changes — a valid record with against >= 0 (word 11)
-// starts at that instance's TLAS leaf, one against the others passes over its source instance (word 7).  Everything else is shared.
-template <bool COUNT, bool REFS = false>
-__device__ __forceinline__ void triangle_body(const TriangleArgs& a) {
-  __shared__ int s_stack[4][STACK2_LDS][64];
-  WalkStack st(s_stack, a.ovf_stack, a.sc.ovf_stride);
-  WalkFeed feed;
-  constexpr int NONE = 0x7FFFFFFF;            // best_inst / best_prim before the first candidate: every (inst, prim) precedes it
-
-  bool need = true;
-  uint32_t pt = 0;
+struct NearestTriangle {
+  static constexpr uint32_t STRIDE = 3;
+  struct Params { float qu = 0.f, qv = 0.f; };   // the query's point of the nearest pair
   F3 w0 = mk3(0, 0, 0), w1 = w0, w2 = w0;     // the vertices in world space
   F3 m = w0, eq = w0, nq = w0;                // bounds' centre and half extents, and the normal, in the space of the tree being walked
   float kq = 0.f, eps = 0.f;
-  float w_slack = 0.f, slack = 0.f, scale2 = CP_REL, rho = 0.f;
-  F3 q_lo = w0, q_scale = w0;                 // dequantisation of that tree
-  float best = 0.f, best_u = 0.f, best_v = 0.f, best_qu = 0.f, best_qv = 0.f;
-  int best_prim = NONE, best_inst = NONE;
-  int cur = REF_DONE, cur_inst = -1;
-  unsigned long long cnt_nodes = 0, cnt_tris = 0;
-
-  // the reach of the best d2 in the units of the tree being walked, rounded up
-  auto reach = [&]() { rho = __builtin_sqrtf(best / scale2) * SW_T_HI; };
+  float rho = 0.f;                            // the reach of the best d2 in that space's units, rounded up
+  __device__ __forceinline__ bool load(const NearestArgs& a, uint32_t pt, float& r_max, float& pmag, int& against) {
+    const float4* qp = a.records + 3u * (size_t)pt;
+    const float4 r0 = ld_stream(&qp[0]), r1 = ld_stream(&qp[1]), r2 = ld_stream(&qp[2]);
+    w0 = mk3(r0.x, r0.y, r0.z); w1 = mk3(r1.x, r1.y, r1.z); w2 = mk3(r2.x, r2.y, r2.z); r_max = r0.w; against = (int)__float_as_uint(r2.w);
+    pmag = fmaxf(fmaxf(fmaxf(fmaxf(__builtin_fabsf(r0.x), __builtin_fabsf(r0.y)), __builtin_fabsf(r0.z)),
+                       fmaxf(fmaxf(__builtin_fabsf(r1.x), __builtin_fabsf(r1.y)), __builtin_fabsf(r1.z))),
+                 fmaxf(fmaxf(__builtin_fabsf(r2.x), __builtin_fabsf(r2.y)), __builtin_fabsf(r2.z)));
+    return finite_bits(r0.x) && finite_bits(r0.y) && finite_bits(r0.z) && finite_bits(r1.x) && finite_bits(r1.y) && finite_bits(r1.z) &&
+           finite_bits(r2.x) && finite_bits(r2.y) && finite_bits(r2.z) && r0.w >= 0.0f;
+  }
   // the triangle p0 p1 p2 of the walked space as bounds and plane
-  auto hold = [&](F3 p0, F3 p1, F3 p2) {
+  __device__ __forceinline__ void hold(F3 p0, F3 p1, F3 p2) {
     const F3 lo = mk3(fminf(fminf(p0.x, p1.x), p2.x), fminf(fminf(p0.y, p1.y), p2.y), fminf(fminf(p0.z, p1.z), p2.z));
     const F3 hi = mk3(fmaxf(fmaxf(p0.x, p1.x), p2.x), fmaxf(fmaxf(p0.y, p1.y), p2.y), fmaxf(fmaxf(p0.z, p1.z), p2.z));
     m = mk3(lo.x * 0.5f + hi.x * 0.5f, lo.y * 0.5f + hi.y * 0.5f, lo.z * 0.5f + hi.z * 0.5f);
@@ -193,120 +172,30 @@ __device__ __forceinline__ void triangle_body(const TriangleArgs& a) {
     const float L = 2.0f * fmaxf(fmaxf(eq.x, eq.y), eq.z);
     eps = 7.62939453125e-06f * (L * L * L);   // 2^-17 L^3
 #endif
-  };
-  auto world_space = [&]() {
-    hold(w0, w1, w2);
-    slack = w_slack; scale2 = CP_REL; tlas_dequant(a.sc, q_lo, q_scale);
-    reach();
-  };
-
-  for (;;) {
-    // ---- refill: idle lanes take the next records of the wave's chunk
-    const uint32_t rec = feed.take(__ballot(need), a.cursor, a.n);
-    if (need && rec != WALK_NONE) {
-      pt = rec;
-      const float4* qp = a.tris + 3u * (size_t)pt;
-      const float4 r0 = ld_stream(&qp[0]), r1 = ld_stream(&qp[1]), r2 = ld_stream(&qp[2]);
-      w0 = mk3(r0.x, r0.y, r0.z); w1 = mk3(r1.x, r1.y, r1.z); w2 = mk3(r2.x, r2.y, r2.z);
-      const bool valid = finite_bits(r0.x) && finite_bits(r0.y) && finite_bits(r0.z) && finite_bits(r1.x) && finite_bits(r1.y) && finite_bits(r1.z) &&
-                         finite_bits(r2.x) && finite_bits(r2.y) && finite_bits(r2.z) && r0.w >= 0.0f;
-      best = r0.w * r0.w; best_u = 0.f; best_v = 0.f; best_qu = 0.f; best_qv = 0.f; best_prim = NONE; best_inst = NONE;
-      const float pmag = fmaxf(fmaxf(fmaxf(fmaxf(__builtin_fabsf(r0.x), __builtin_fabsf(r0.y)), __builtin_fabsf(r0.z)),
-                                     fmaxf(fmaxf(__builtin_fabsf(r1.x), __builtin_fabsf(r1.y)), __builtin_fabsf(r1.z))),
-                               fmaxf(fmaxf(__builtin_fabsf(r2.x), __builtin_fabsf(r2.y)), __builtin_fabsf(r2.z)));
-      w_slack = CP_ABS * fmaxf(fmaxf(pmag, tlas_magnitude(a.sc, 0.f)), a.inst_scale[0]);
-      world_space();
-      cur_inst = -1;
-      st.reset(); cur = valid ? a.sc.tlas_root : REF_DONE;
-      if (REFS && valid && (int)__float_as_uint(r2.w) >= 0) cur = ~(int)__float_as_uint(r2.w);   // (k_refs_expand: below n_inst)
-      need = false;
-    }
-    if (__ballot(!need) == 0) break;   // every lane idle and the records used up
-
-    // ---- interior nodes: every lane at one takes a visit; the trip repeats while most live lanes are interior
-    for (;;) {
-      if (cur >= 0) {
-        uint4 Q0, Q1;
-        walk_node(a.sc, cur, Q0, Q1);
-        if (COUNT) cnt_nodes++;
-        float b0, b1;
-        const bool h0 = triangle_box(Q0.x, Q0.y, Q0.z, m, eq, nq, kq, eps, q_lo, q_scale, slack, scale2, rho, best, b0) && box_present(Q0.x);
-        const bool h1 = triangle_box(Q0.w, Q1.x, Q1.y, m, eq, nq, kq, eps, q_lo, q_scale, slack, scale2, rho, best, b1) && box_present(Q0.w);
-        if (h0 && h1) {
-          const bool swap = b1 < b0;
-          st.push(swap ? (int)Q1.z : (int)Q1.w);
-          cur = swap ? (int)Q1.w : (int)Q1.z;
-        } else if (h0) cur = (int)Q1.z;
-        else if (h1) cur = (int)Q1.w;
-        else cur = st.pop();
-      }
-      if (walk_trip_done(need, cur)) break;
-    }
-
-    if (!need && cur < 0 && cur > REF_MARK && cur_inst >= 0) {
-      // ---- BLAS leaf: the canonical test of every packet, in world space; the smallest key (d2, inst, prim) stays
-      uint32_t first, nt;
-      walk_leaf(cur, first, nt);
-      const float* o = a.sc.inst[cur_inst].o2w;
-      for (uint32_t j = 0; j < nt; j++) {
-        const float4* tp = a.sc.tris + (size_t)(first + j) * 3;
-        const float4 T0 = tp[0], T1 = tp[1], T2 = tp[2];
-        if (COUNT) cnt_tris++;
-        float uu, vv, qu, qv;
-        const float d2 = triangle_tri(w0, w1, w2, xform_point(o, mk3(T0.x, T0.y, T0.z)), xform_vec(o, mk3(T0.w, T1.x, T1.y)), xform_vec(o, mk3(T1.z, T1.w, T2.x)),
-                                      uu, vv, qu, qv);
-        const int prim = (int)__float_as_uint(T2.y);
-        if (d2 < best || (d2 == best && (cur_inst < best_inst || (cur_inst == best_inst && prim < best_prim)))) {
-          best = d2; best_u = uu; best_v = vv; best_qu = qu; best_qv = qv; best_prim = prim; best_inst = cur_inst;
-        }
-      }
-      reach();
-      cur = st.pop();
-    }
-    if (!need && cur == REF_MARK) {
-      // ---- leave the instance
-      cur_inst = -1;
-      world_space();
-      cur = st.pop();
-    }
-    if (!need && cur < 0 && cur > REF_MARK && cur_inst < 0) {
-      // ---- TLAS leaf: enter the instance if the call's mask lets it (the vertices -> object space, the slack of both spaces in object units)
-      const int ii = ~cur;
-      const InstanceDev* I = a.sc.inst + ii;
-      bool own = false;   // REFS: the source instance of a record against the others (words 7 and 11, read again)
-      if (REFS) {
-        const float4* qp = a.tris + 3u * (size_t)pt;
-        own = (int)__float_as_uint(qp[2].w) < 0 && ii == (int)__float_as_uint(qp[1].w);
-      }
-      if (((I->mask >> INST_WORLD_MASK_SHIFT) & a.cull_mask & 0xFFu) != 0u && !own) {
-        // the closest-point walks' entry with the per-component largest magnitude of the vertices as the point (its slack formula reads
-        // |wp| only; the object-space point it returns for that argument is not used), then the vertices themselves through w2o
-        const F3 ap = mk3(fmaxf(fmaxf(__builtin_fabsf(w0.x), __builtin_fabsf(w1.x)), __builtin_fabsf(w2.x)),
-                          fmaxf(fmaxf(__builtin_fabsf(w0.y), __builtin_fabsf(w1.y)), __builtin_fabsf(w2.y)),
-                          fmaxf(fmaxf(__builtin_fabsf(w0.z), __builtin_fabsf(w1.z)), __builtin_fabsf(w2.z)));
-        F3 unused;
-        closest_enter_instance(I, a.inst_scale[1 + ii], ap, w_slack, unused, q_lo, q_scale, slack, scale2);
-        hold(xform_point(I->w2o, w0), xform_point(I->w2o, w1), xform_point(I->w2o, w2));
-        reach();
-        st.push(REF_MARK);
-        cur_inst = ii; cur = I->blas_root;
-      } else cur = st.pop();
-    }
-    if (!need && cur == REF_DONE) {
-      // ---- finished: the record, or the miss form with the radius as given
-      HitRec hr;
-      if (best_inst != NONE) { hr.t = __builtin_sqrtf(best); hr.u = best_u; hr.v = best_v; hr.prim = best_prim; hr.inst = best_inst; }
-      else { hr.t = ld_stream(&a.tris[3u * (size_t)pt]).w; hr.u = 0.f; hr.v = 0.f; hr.prim = -1; hr.inst = -1; best_qu = 0.f; best_qv = 0.f; }
-      a.hits[pt] = hr;
-      if (a.params) { a.params[2u * (size_t)pt] = best_qu; a.params[2u * (size_t)pt + 1u] = best_qv; }
-      need = true;
-    }
   }
-  if (COUNT) walk_flush_counters(a.counters, cnt_nodes, cnt_tris);
-}
+  __device__ __forceinline__ void to_world() { hold(w0, w1, w2); }
+  __device__ __forceinline__ F3 enter(const InstanceDev* I) {
+    hold(xform_point(I->w2o, w0), xform_point(I->w2o, w1), xform_point(I->w2o, w2));
+    return mk3(fmaxf(fmaxf(__builtin_fabsf(w0.x), __builtin_fabsf(w1.x)), __builtin_fabsf(w2.x)),
+               fmaxf(fmaxf(__builtin_fabsf(w0.y), __builtin_fabsf(w1.y)), __builtin_fabsf(w2.y)),
+               fmaxf(fmaxf(__builtin_fabsf(w0.z), __builtin_fabsf(w1.z)), __builtin_fabsf(w2.z)));
+  }
+  __device__ __forceinline__ void reach(float best, float scale2) { rho = __builtin_sqrtf(best / scale2) * SW_T_HI; }
+  __device__ __forceinline__ bool open(uint32_t wx, uint32_t wy, uint32_t wz, F3 q_lo, F3 q_scale, float slack, float scale2, float best, float& b) const {
+    return triangle_box(wx, wy, wz, m, eq, nq, kq, eps, q_lo, q_scale, slack, scale2, rho, best, b);
+  }
+  __device__ __forceinline__ float test(F3 a, F3 ab, F3 ac, float& u, float& v, Params& p) const { return triangle_tri(w0, w1, w2, a, ab, ac, u, v, p.qu, p.qv); }
+  __device__ __forceinline__ static void store(const NearestArgs& a, uint32_t pt, Params p) {
+    if (a.params) { a.params[2u * (size_t)pt] = p.qu; a.params[2u * (size_t)pt + 1u] = p.qv; }
+  }
+  __device__ __forceinline__ bool own(const NearestArgs& a, uint32_t pt, int ii) const {
+    const float4* qp = a.records + 3u * (size_t)pt;
+    return (int)__float_as_uint(qp[2].w) < 0 && ii == (int)__float_as_uint(qp[1].w);
+  }
+};
 
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_TRIANGLE_WAVES_PER_EU))) void k_closest_triangle(TriangleArgs a) { triangle_body<false>(a); }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_TRIANGLE_WAVES_PER_EU))) void k_closest_triangle_count(TriangleArgs a) { triangle_body<true>(a); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_TRIANGLE_WAVES_PER_EU))) void k_closest_triangle(NearestArgs a) { nearest_body<NearestTriangle, false>(a); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_TRIANGLE_WAVES_PER_EU))) void k_closest_triangle_count(NearestArgs a) { nearest_body<NearestTriangle, true>(a); }
 
 // The side of the reported triangle's plane the query's point of the nearest pair lies on, into word 7 of its rt_hit_attr (after
 // k_hit_attr): k_closest_side's rule at p = (P0 + qu g0) + qv g2, g0 = P1 - P0, g2 = P2 - P0 (per component), 0 on a miss.
@@ -324,14 +213,6 @@ __global__ __launch_bounds__(256) void k_triangle_side(SceneDev sc, const float4
     kind = closest_side_word(sc, &p, hr);
   }
   attr[8u * (size_t)i + 7u] = kind;
-}
-
-void launch_closest_triangle(const SceneDev& sc, const float4* tris, uint32_t cull_mask, const float* inst_scale, HitRec* hits, float* params, uint32_t n,
-                             int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s) {
-  TriangleArgs a{};
-  a.sc = sc; a.tris = tris; a.inst_scale = inst_scale; a.cull_mask = cull_mask; a.n = n; a.hits = hits; a.params = params;
-  a.counters = counters; a.ovf_stack = ovf_stack;
-  launch_walk(k_closest_triangle, k_closest_triangle_count, a, counters, counting, cfg, s);
 }
 
 void launch_triangle_side(const SceneDev& sc, const float4* tris, const float* params, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s) {

@@ -2459,6 +2459,9 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q
   if (q.t0) HIP_TRY(c, hipEventRecord(q.t0, s));
   if (q.refs) launch_refs_expand(sc, q.records, q.walk == Walk::Expand ? (float4*)q.tris_out : c->d_q_tris, n, c->scene->h_verts.size(), s);
   if (closest || sweep || segment || triangle || q.walk == Walk::ClosestHits || q.walk == Walk::Overlap || q.walk == Walk::Triangles) launch_closest_scale(sc, c->d_q_scale, s);
+  // the two families of walk_nearest.inc and walk_overlap.inc: the shape of the records chooses the kernel, the launch is the family's
+  const NearestShape nearest = segment ? NearestShape::Segment : !triangle ? NearestShape::Point : q.refs ? NearestShape::Refs : NearestShape::Triangle;
+  const OverlapShape overlap = q.walk == Walk::Overlap ? OverlapShape::Boxes : q.refs ? OverlapShape::Refs : OverlapShape::Triangles;
   switch (q.walk) {
     case Walk::Plain: launch_query(sc, records, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, q.any_hit, q.counting, cfg, s); break;
     case Walk::Flags: launch_query_flags(sc, records, (const uint32_t*)q.ray_words, q.query_word, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, cfg, s); break;
@@ -2466,43 +2469,27 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q
       launch_query_hits(sc, records, (const uint32_t*)q.ray_words, q.query_word, n, q.max_hits, (HitRec*)q.hits, (float4*)q.attr, (uint32_t*)q.counts, c->d_q_ovf,
                         c->d_q_counters, cfg, s);
       break;
-    case Walk::Closest: launch_closest_point(sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s); break;
     case Walk::ClosestHits:   // (with k_hit_attr and k_closest_hits_side over the rows for the attributes)
       launch_closest_hits(sc, records, q.cull_mask, c->d_q_scale, n, q.max_hits, (HitRec*)q.hits, (float4*)q.attr, (uint32_t*)q.counts, c->d_q_ovf, c->d_q_counters,
                           q.counting, cfg, s);
       break;
-    case Walk::Overlap:
-      if (q.list) {
-        launch_overlap_boxes(sc, records, q.cull_mask, c->d_q_scale, false, 0u, nullptr, list_counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
-        launch_list_scan(list_counts, n, list_sums, (unsigned long long*)q.offsets, s);
-        if (q.capacity) launch_list_boxes(sc, records, q.cull_mask, c->d_q_scale, (const unsigned long long*)q.offsets, q.ids, q.capacity, list_work, n, c->d_q_ovf,
-                                          c->d_q_counters, q.counting, cfg, s);
-        break;
-      }
-      launch_overlap_boxes(sc, records, q.cull_mask, c->d_q_scale, q.overlap_any, q.max_ids, q.ids, (uint32_t*)q.counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
+    case Walk::Closest: case Walk::Segment: case Walk::Triangle:   // (the point walk has no params)
+      launch_nearest(nearest, sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, segment || triangle ? (float*)words : nullptr, n, c->d_q_ovf, c->d_q_counters,
+                     q.counting, cfg, s);
       break;
-    case Walk::Triangles:
-      if (q.list) {
-        if (q.refs) launch_refs_collide(sc, records, q.cull_mask, c->d_q_scale, false, 0u, nullptr, list_counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
-        else launch_collide_triangles(sc, records, q.cull_mask, c->d_q_scale, false, 0u, nullptr, list_counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
+    case Walk::Overlap: case Walk::Triangles:
+      if (q.list) {   // the count-only walk, the scan and, with room for rows, the fill walk
+        launch_overlap(overlap, sc, records, q.cull_mask, c->d_q_scale, false, 0u, nullptr, list_counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
         launch_list_scan(list_counts, n, list_sums, (unsigned long long*)q.offsets, s);
-        if (q.capacity) launch_list_triangles(sc, records, q.refs, q.cull_mask, c->d_q_scale, (const unsigned long long*)q.offsets, q.ids, q.capacity, list_work, n,
-                                              c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
+        if (q.capacity) launch_overlap_list(overlap, sc, records, q.cull_mask, c->d_q_scale, (const unsigned long long*)q.offsets, q.ids, q.capacity, list_work, n,
+                                            c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
         break;
       }
-      if (q.refs) launch_refs_collide(sc, records, q.cull_mask, c->d_q_scale, q.overlap_any, q.max_ids, q.ids, (uint32_t*)q.counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
-      else launch_collide_triangles(sc, records, q.cull_mask, c->d_q_scale, q.overlap_any, q.max_ids, q.ids, (uint32_t*)q.counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
+      launch_overlap(overlap, sc, records, q.cull_mask, c->d_q_scale, q.overlap_any, q.max_ids, q.ids, (uint32_t*)q.counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
       break;
     case Walk::Sweep: launch_sweep_spheres(sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s); break;
-    case Walk::Segment:
-      launch_closest_segment(sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, (float*)words, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
-      break;
-    case Walk::Triangle:
-      if (q.refs) launch_refs_nearest(sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, (float*)words, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
-      else launch_closest_triangle(sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, (float*)words, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
-      break;
     case Walk::Inside:
-      if (closest) launch_closest_point(sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, n, c->d_q_ovf, c->d_q_counters, false, cfg, s);
+      if (closest) launch_nearest(NearestShape::Point, sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, nullptr, n, c->d_q_ovf, c->d_q_counters, false, cfg, s);
       launch_point_inside(sc, records, q.cull_mask, q.n_dirs, words, (uint32_t*)q.counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
       break;
     case Walk::Expand: break;   // (the expansion above is the whole call)

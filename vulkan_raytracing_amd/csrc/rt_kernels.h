@@ -193,33 +193,44 @@ void launch_hit_kind(const SceneDev& sc, const float4* rays, const HitRec* hits,
 // walk's chunk cursor is a word of `counters`, its stack spills into ovf_stack (sized for cfg.trace_blocks workgroups).
 void launch_query_hits(const SceneDev& sc, const float4* rays, const uint32_t* words, uint32_t query_word, uint32_t n, uint32_t k, HitRec* hits,
                        float4* attr, uint32_t* counts, int32_t* ovf_stack, uint32_t* counters, const LaunchCfg& cfg, hipStream_t s);
-// rt_closest_point_device: the nearest surface point of every query point (16 bytes: p.xyz, r_max) among the instances the cull mask
-// admits, into hits[n] (kernels_closest.inc).  inst_scale: 1 + sc.n_inst floats that launch_closest_scale fills first, in stream
-// order ([0] the largest row-term magnitude of any instance's o2w, [1 + i] a lower bound on the smallest singular value of instance i's).  Chunk cursor, counters (counting: node visits and
-// triangle tests, the caller zeroes the block first) and spill area as for launch_query_hits.
+// The nearest-pair walks (walk_nearest.inc), one launch for the family: for every record the nearest pair of a point of the record and a
+// point of the surface of the instances the cull mask admits, within the record's radius r_max (word 3), into hits[n].
+//   Point     rt_closest_point_device: 16 bytes (p.xyz, r_max); no params (kernels_closest.inc)
+//   Segment   rt_closest_segment_device: 32 bytes (P0.xyz, r_max, P1.xyz, ignored); params[n]: the segment's parameter s (kernels_segment.inc)
+//   Triangle  rt_closest_triangle_device: 48 bytes (P0.xyz, r_max, P1.xyz, ignored, P2.xyz, ignored); params[2 n]: the barycentrics
+//             (qu, qv) of the query's point (kernels_triangle.inc)
+//   Refs      rt_closest_scene_triangle_device: Triangle over launch_refs_expand's records, honouring words 7 (the source instance) and
+//             11 (against: -1 every other instance, >= 0 that one only) (kernels_refs.inc)
+// params is optional (null: not written).  inst_scale: 1 + sc.n_inst floats that launch_closest_scale fills first, in stream order ([0]
+// the largest row-term magnitude of any instance's o2w, [1 + i] a lower bound on the smallest singular value of instance i's).  Chunk
+// cursor, counters (counting: node visits and triangle tests, the caller zeroes the block first) and spill area as for launch_query_hits.
+enum class NearestShape { Point, Segment, Triangle, Refs };
+void launch_nearest(NearestShape shape, const SceneDev& sc, const float4* records, uint32_t cull_mask, const float* inst_scale, HitRec* hits, float* params, uint32_t n,
+                    int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
 void launch_closest_scale(const SceneDev& sc, float* inst_scale, hipStream_t s);
-void launch_closest_point(const SceneDev& sc, const float4* points, uint32_t cull_mask, const float* inst_scale, HitRec* hits, uint32_t n, int32_t* ovf_stack,
-                          uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
 // the side of the reported triangle's plane every point lies on (0xFE front, 0xFF back, 0 miss) into word 7 of its rt_hit_attr (after launch_hit_attr)
 void launch_closest_side(const SceneDev& sc, const float4* points, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s);
-// rt_closest_point_device_hits: the k (0..16) nearest candidates of every point (launch_closest_point's records and candidates), sorted by
+// rt_closest_point_device_hits: the k (0..16) nearest candidates of every point (launch_nearest's Point records and candidates), sorted by
 // (d2, inst, prim), into hits (n * k records, point-major, t = sqrtf(d2); the rest of a row in the miss form), their number into counts
 // (optional: without it the walk prunes by the k-th entry's d2), and with attr (k >= 1) the rt_hit_attr of every record with its side
-// word (kernels_closest_hits.inc).  inst_scale, chunk cursor, counters (counting) and spill area as for launch_closest_point.
+// word (kernels_closest_hits.inc).  inst_scale, chunk cursor, counters (counting) and spill area as for launch_nearest.
 void launch_closest_hits(const SceneDev& sc, const float4* points, uint32_t cull_mask, const float* inst_scale, uint32_t n, uint32_t k, HitRec* hits, float4* attr,
                          uint32_t* counts, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
-// rt_overlap_boxes_device: the triangles that touch every query box (32 bytes: lo.xyz, w3, hi.xyz, w7) among the instances the cull mask
-// admits (kernels_overlap.inc): the k smallest (inst, prim) of each box into ids[n * k] (8 bytes each; k == 0: none), their number into
-// counts[n] (or null: the walk prunes); any: counts of 0 or 1, a box ends at its first candidate.  inst_scale as for launch_closest_point
-// (launch_closest_scale fills it first); chunk cursor, counters (counting) and spill area as for launch_query_hits.
-void launch_overlap_boxes(const SceneDev& sc, const float4* boxes, uint32_t cull_mask, const float* inst_scale, bool any, uint32_t k, void* ids, uint32_t* counts,
-                          uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
-// rt_overlap_triangles_device: the triangles that the canonical triangle-triangle predicate does not separate from every query triangle
-// (48 bytes: P0.xyz, w3, P1.xyz, w7, P2.xyz, w11) (kernels_triangles.inc); every other argument as for launch_overlap_boxes.
-void launch_collide_triangles(const SceneDev& sc, const float4* tris, uint32_t cull_mask, const float* inst_scale, bool any, uint32_t k, void* ids, uint32_t* counts,
-                              uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
+// The overlap walks (walk_overlap.inc), one launch for the family: for every record the triangles its canonical predicate does not
+// separate from it, among the instances the cull mask admits: the k smallest (inst, prim) of each record into ids[n * k] (8 bytes each;
+// k == 0: none), their number into counts[n] (or null: the walk prunes); any: counts of 0 or 1, a record ends at its first candidate.
+//   Boxes      rt_overlap_boxes_device: 32 bytes (lo.xyz, w3, hi.xyz, w7), the triangles that touch the box (kernels_overlap.inc)
+//   Triangles  rt_overlap_triangles_device: 48 bytes (P0.xyz, w3, P1.xyz, w7, P2.xyz, w11), the triangles that cut or touch the query
+//              triangle (kernels_triangles.inc)
+//   Refs       rt_overlap_scene_triangles_device: Triangles over launch_refs_expand's records, honouring words 7 (the source instance)
+//              and 11 (against: -1 every other instance, >= 0 that one only) (kernels_refs.inc)
+// inst_scale as for launch_nearest (launch_closest_scale fills it first); chunk cursor, counters (counting) and spill area as for
+// launch_query_hits.
+enum class OverlapShape { Boxes, Triangles, Refs };
+void launch_overlap(OverlapShape shape, const SceneDev& sc, const float4* records, uint32_t cull_mask, const float* inst_scale, bool any, uint32_t k, void* ids,
+                    uint32_t* counts, uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
 // rt_sweep_spheres_device: the first contact of every moving sphere (32 bytes: o.xyz, r, d.xyz, tmax) with the instances the cull mask
-// admits, into hits[n] (kernels_sweep.inc).  inst_scale as for launch_closest_point (launch_closest_scale fills it first); chunk cursor,
+// admits, into hits[n] (kernels_sweep.inc).  inst_scale as for launch_nearest (launch_closest_scale fills it first); chunk cursor,
 // counters (counting) and spill area as for launch_query_hits.
 void launch_sweep_spheres(const SceneDev& sc, const float4* sweeps, uint32_t cull_mask, const float* inst_scale, HitRec* hits, uint32_t n, int32_t* ovf_stack,
                           uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
@@ -233,30 +244,14 @@ void launch_point_inside(const SceneDev& sc, const float4* points, uint32_t cull
                          int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
 // rt_signed_distance_device: sets the sign bit of hits[i].t where bit 0 of words[i] is set and points[i] was a valid closest-point record
 void launch_sign_distance(const float4* points, const uint32_t* words, HitRec* hits, uint32_t n, hipStream_t s);
-// rt_closest_segment_device: the nearest pair of every segment (32 bytes: P0.xyz, r_max, P1.xyz, ignored) and the surface of the instances
-// the cull mask admits, into hits[n] and, when given, the segment's parameter s into params[n] (kernels_segment.inc).  inst_scale as for
-// launch_closest_point (launch_closest_scale fills it first); chunk cursor, counters (counting) and spill area as for launch_query_hits.
-void launch_closest_segment(const SceneDev& sc, const float4* segs, uint32_t cull_mask, const float* inst_scale, HitRec* hits, float* params, uint32_t n,
-                            int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
 // the side of the reported triangle's plane the segment's point P0 + params[i] (P1 - P0) lies on (launch_closest_side's rule and word)
 void launch_segment_side(const SceneDev& sc, const float4* segs, const float* params, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s);
-// rt_closest_triangle_device: the nearest pair of every query triangle (48 bytes: P0.xyz, r_max, P1.xyz, ignored, P2.xyz, ignored) and the
-// surface of the instances the cull mask admits, into hits[n] and, when given, the barycentrics (qu, qv) of the query's point into
-// params[2 n] (kernels_triangle.inc).  The other arguments as for launch_closest_segment.
-void launch_closest_triangle(const SceneDev& sc, const float4* tris, uint32_t cull_mask, const float* inst_scale, HitRec* hits, float* params, uint32_t n,
-                             int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
 // the side of the reported triangle's plane the query's point (P0 + qu (P1 - P0)) + qv (P2 - P0) lies on (launch_closest_side's rule and word)
 void launch_triangle_side(const SceneDev& sc, const float4* tris, const float* params, const HitRec* hits, float4* attr, uint32_t n, hipStream_t s);
 // rt_scene_triangles_device and the expansion in front of the two by-reference walks (kernels_refs.inc): the 48-byte record of every
 // reference (16 bytes: inst, prim, against, r_max) into tris[3 n]: the world image of the source packet, r_max, inst and against in words
 // 3, 7 and 11; nine quiet NaNs for an invalid reference.  n_vert_floats: the floats of sc.verts.
 void launch_refs_expand(const SceneDev& sc, const void* refs, float4* tris, uint32_t n, uint64_t n_vert_floats, hipStream_t s);
-// rt_overlap_scene_triangles_device, rt_closest_scene_triangle_device: launch_collide_triangles and launch_closest_triangle over
-// launch_refs_expand's records, honouring words 7 (the source instance) and 11 (against: -1 every other instance, >= 0 that one only)
-void launch_refs_collide(const SceneDev& sc, const float4* tris, uint32_t cull_mask, const float* inst_scale, bool any, uint32_t k, void* ids, uint32_t* counts,
-                         uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
-void launch_refs_nearest(const SceneDev& sc, const float4* tris, uint32_t cull_mask, const float* inst_scale, HitRec* hits, float* params, uint32_t n,
-                         int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
 // rt_overlap_*_device_list (kernels_list.inc; DESIGN.md §5 "Overlap lists").  The two thresholds of a row's length:
 #ifndef RT_LIST_INSERT_MAX
 #define RT_LIST_INSERT_MAX 64   /* a row of at most this many entries is kept sorted by insertion in the walk, as the capped calls keep theirs; a longer one goes to k_list_sort
@@ -268,13 +263,12 @@ void launch_refs_nearest(const SceneDev& sc, const float4* tris, uint32_t cull_m
 // the n + 1 uint64 exclusive offsets of n uint32 counts (offsets[n]: their sum); sums: list_scan_tiles(n) words of scratch
 uint32_t list_scan_tiles(uint32_t n);
 void launch_list_scan(const uint32_t* counts, uint32_t n, unsigned long long* sums, unsigned long long* offsets, hipStream_t s);
-// the fill walk behind launch_overlap_boxes' / launch_collide_triangles' (refs: launch_refs_collide's) count-only walk and the scan: row i,
-// the whole candidate set in (inst, prim) order, at ids[offsets[i] .. offsets[i + 1]) if offsets[i + 1] <= capacity, then k_list_sort
-// over the rows longer than RT_LIST_INSERT_MAX.  work: 1 + n words of scratch (the number of such rows, then their records).
-void launch_list_boxes(const SceneDev& sc, const float4* boxes, uint32_t cull_mask, const float* inst_scale, const unsigned long long* offsets, void* ids,
-                       uint64_t capacity, uint32_t* work, uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
-void launch_list_triangles(const SceneDev& sc, const float4* tris, bool refs, uint32_t cull_mask, const float* inst_scale, const unsigned long long* offsets, void* ids,
-                           uint64_t capacity, uint32_t* work, uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
+// the fill walk behind launch_overlap's count-only walk (k == 0, counts) and the scan: row i, the whole candidate set in (inst, prim)
+// order, at ids[offsets[i] .. offsets[i + 1]) if offsets[i + 1] <= capacity, then k_list_sort over the rows longer than
+// RT_LIST_INSERT_MAX.  work: 1 + n words of scratch (the number of such rows, then their records).
+void launch_overlap_list(OverlapShape shape, const SceneDev& sc, const float4* records, uint32_t cull_mask, const float* inst_scale, const unsigned long long* offsets,
+                         void* ids, uint64_t capacity, uint32_t* work, uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg,
+                         hipStream_t s);
 // rt_shade_rays_device: k_ray_ingest replaces k_raygen for the caller's n rays (32 bytes each, o.xyz, w3, d.xyz, tmax; sample id = record
 // index): sky colours of the rays that miss the TLAS and (0, 0, 0, 0) for invalid records into f.sample_color, the others into bounce queue 0
 // (workgroup b appends to shard b % 8: f.shard_cap >= 256 * ceil(ray_ingest_block_count(n) / 8)).  f.counters must be zero.

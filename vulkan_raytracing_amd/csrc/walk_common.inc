@@ -1,7 +1,12 @@
 // walk_common.inc — included by kernels.hip before kernels_hits.inc (product and alt translation units alike).
-// The skeleton of a record-level walk (k_query_hits, k_closest_point, k_closest_hits, k_overlap_boxes, k_sweep_spheres, k_point_inside): one lane per
-// record, the quantised BVH2 of the TLAS and, inside an instance, of its BLAS.  What every such walk does the same way lives here; its
-// node test, child order, leaf body, instance entry and exit, finish step, args struct and register budget stay in its own file.
+// The skeleton of a record-level walk: one lane per record, the quantised BVH2 of the TLAS and, inside an instance, of its BLAS.  What
+// every such walk does the same way lives here.  On top of it:
+//  * k_query_hits, k_closest_hits, k_sweep_spheres and k_point_inside each have a body in their own file: node test, child order, leaf
+//    body, instance entry and exit, finish step, args struct and register budget;
+//  * the nearest-pair walks (k_closest_point, k_closest_segment, k_closest_triangle, k_refs_nearest) share the body, args struct and
+//    launch of walk_nearest.inc, the overlap walks (k_overlap_boxes, k_collide_triangles, k_refs_collide, k_list_*) those of
+//    walk_overlap.inc.  What stays in such a walk's own file is its shape: the record and its validity, the form the node test reads,
+//    the node test (nearest), the canonical leaf test, the result words beside the hit record, and the register budget switch.
 // The frame kernels and k_trace have a stack of their own (the fast_step row) and use none of this.
 
 // The per-lane stack: STACK2_LDS entries in the block's LDS array (entry e at stk[e * 64]), deeper ones in the query's spill area

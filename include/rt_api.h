@@ -833,6 +833,68 @@ int rt_overlap_triangles_list(rt_ctx* ctx, size_t n, const float* tris12_host, u
 int rt_overlap_scene_triangles_list(rt_ctx* ctx, size_t n, const rt_tri_ref* refs_host, uint32_t cull_mask, uint32_t flags,
                                     uint64_t* offsets_host, int32_t* ids_host, size_t capacity, int counting, rt_stats* stats);
 
+/* Instance pairs: the two by-reference queries one level up, per pair of bodies (FCL's distance and collide, PhysX's computePenetration,
+ * Bullet's closest points, Embree's rtcCollide): "the clearance between link 3 and link 7 and where", "does body 5 touch anything".  A
+ * record stands for every triangle of its source instance; the caller builds no reference per triangle, keeps no n x P records and
+ * reduces nothing.  Both calls are defined entirely through rt_closest_scene_triangle_device and rt_overlap_scene_triangles_device, so
+ * their results are the same bytes whatever the tree.
+ * Records: d_irefs4 holds n records of 16 B, 16-B aligned, memory of ctx's GPU; one buffer feeds both calls. */
+typedef struct rt_inst_ref {
+  int32_t inst;      /* source instance: index into the context's current instance array */
+  int32_t against;   /* RT_REF_AGAINST_OTHERS (-1) or a candidate instance, as in rt_tri_ref */
+  float   r_max;     /* search radius of the distance query; ignored by the overlap query */
+  uint32_t reserved; /* ignored */
+} rt_inst_ref;
+/* Validity: a record is valid when inst is in [0, n_instances) and against is in [-1, n_instances); the distance query also wants
+ * r_max >= 0 and not NaN.  An invalid record is no error, and neither is a source mesh without triangles or a source all of whose
+ * triangles are invalid references (BAD TRIANGLES, a non-finite transform): the distance query answers the miss form, the overlap
+ * query count 0 and first (-1, -1, -1, 0).  Everything else is the by-reference calls': against == inst is not special, cull_mask
+ * admits candidates only (the source's mask plays no part), void and non-invertible records behave as they do there.
+ *
+ * rt_closest_instances_device.  For a valid record let R_p be the record rt_closest_scene_triangle_device gives the reference
+ * (inst, p, against, r_max) under the same cull_mask, p = 0 .. P - 1 (P the triangles of the source's mesh), and d2_p its canonical d2
+ * (the key is d2, not the rounded t, as everywhere in the family).  The answer is R_p*, p* the smallest p among those with the smallest
+ * d2_p:
+ *   d_hits[i]       that hit (4-B aligned): the candidate's inst and prim, its u and v, t = sqrtf(d2);
+ *   d_src_prims[i]  p* (int32, 4-B aligned, required);
+ *   d_params        (optional, n x 2 floats, 4-B aligned) its (qu, qv), on the world image of source triangle p*;
+ *   d_attr          (optional, n rt_hit_attr, 16-B aligned) its attributes, the side word included;
+ * all of them byte for byte what rt_closest_scene_triangle_device returns for (inst, p*, against, r_max).  When no source triangle has a
+ * candidate: the miss record with t = r_max as given (bit pattern kept), src_prim -1, parameters 0, attributes of a miss.
+ *
+ * rt_overlap_instances_device.
+ *   d_counts64[i]   (uint64, 8-B aligned, required) the sum over p of the count rt_overlap_scene_triangles_device gives (inst, p, against):
+ *                   the number of intersecting triangle pairs (64 bits: every count is below 2^32, their sum is not);
+ *   d_first4        (optional, n x 4 int32, 4-B aligned) (p, inst, prim, 0): p the smallest source primitive with a non-empty row,
+ *                   (inst, prim) the first entry of that row; (-1, -1, -1, 0) when there is none.
+ * RT_OVERLAP_ANY in flags makes d_counts64[i] 0 or 1, and the walk of a whole record ends at the first contact any of its source
+ * triangles finds; d_first4 must then be NULL, because which pair ends the walk is not deterministic.
+ *
+ * Stream ordering without host synchronisation, the TLAS and scene of the call, queries and shading calls of one context one after
+ * another, RT_ERR_NOT_READY and n == 0 (nothing is enqueued): as for rt_closest_point_device.  A call plans (the work items of every
+ * record and a scan of them; their total stays on the device), walks every source triangle as one work item, the items of a record
+ * sharing one bound (distance) or one flag (RT_OVERLAP_ANY), and finishes with the by-reference call over one reference per record.
+ * The plan, the keys and those references (about 50 n bytes, and n x 48 B of expanded records) are part of the query workspace; it
+ * grows after the context's earlier queries are done, and an allocation that fails is RT_ERR_OUT_OF_MEMORY and leaves the context as it
+ * was.
+ * RT_ERR_INVALID_ARGUMENT: a NULL pointer (d_attr, d_params and d_first4 aside), a misaligned pointer, memory that is not of ctx's GPU,
+ * n >= 0xFFFFFF00 or n x (the largest triangle count of any mesh of the scene) >= 0xFFFFFF00 (work items are indexed with 32 bits and
+ * the records live on the device, so the check is conservative), unknown flag bits, d_first4 with RT_OVERLAP_ANY, cull_mask > 0xFF,
+ * trace_variant != 0. */
+int rt_closest_instances_device(rt_ctx* ctx, size_t n, const void* d_irefs4, uint32_t cull_mask,
+                                void* d_hits, void* d_src_prims, void* d_attr, void* d_params, void* hip_stream);
+int rt_overlap_instances_device(rt_ctx* ctx, size_t n, const void* d_irefs4, uint32_t cull_mask, uint32_t flags,
+                                void* d_counts64, void* d_first4, void* hip_stream);
+/* The blocking host forms, as rt_closest_scene_triangle and rt_overlap_scene_triangles are to their device calls: out_host,
+ * src_prims_host and counts_host are required, params_host and first4_host optional.  counting != 0 runs the instrumented walks and
+ * returns stats->node_visits and stats->tri_tests summed over all walks of the call (the finish included); stats->ms_trace_closest is
+ * the device time of the whole sequence.  The visits of a shared-bound or shared-flag walk depend on the order in which the lanes of a
+ * record publish, that is on timing: the counts are for measurement, not for tests of equality.  The results never depend on it. */
+int rt_closest_instances(rt_ctx* ctx, size_t n, const rt_inst_ref* irefs_host, uint32_t cull_mask,
+                         rt_hit* out_host, int32_t* src_prims_host, float* params_host, int counting, rt_stats* stats);
+int rt_overlap_instances(rt_ctx* ctx, size_t n, const rt_inst_ref* irefs_host, uint32_t cull_mask, uint32_t flags,
+                         uint64_t* counts_host, int32_t* first4_host, int counting, rt_stats* stats);
+
 /* Inside / outside: for every point, is it enclosed by the scene's surfaces (Open3D's compute_occupancy and compute_signed_distance),
  * for signed distance fields, penetration tests, occupancy and voxel filling.  The answer is a vote over the crossing parities of a few
  * rays from the point along a fixed table of generic directions; one ray is not enough, because the canonical triangle test is not

@@ -72,13 +72,16 @@ HIT_KIND_BACK_FACING = 0xFF
 TRI_REF_DTYPE = np.dtype([("inst", np.int32), ("prim", np.int32), ("against", np.int32), ("r_max", np.float32)])
 assert TRI_REF_DTYPE.itemsize == 16
 REF_AGAINST_OTHERS = -1
+# rt_inst_ref (include/rt_api.h): a whole instance as the query of closest_instances* / overlap_instances*
+INST_REF_DTYPE = np.dtype([("inst", np.int32), ("against", np.int32), ("r_max", np.float32), ("reserved", np.uint32)])
+assert INST_REF_DTYPE.itemsize == 16
 OVERLAP_ANY = 0x1   # rt_overlap_boxes_device: occupancy (counts of 0 or 1)
 # rt_point_inside_device: the direction table (RT_INSIDE_DIRS of include/rt_api.h; rounded to binary32, not normalised)
 INSIDE_DIRS = ((0.36, 0.48, 0.8), (-0.8, 0.36, -0.48), (0.48, -0.8, -0.36), (-0.6, -0.64, 0.48), (0.64, -0.48, 0.6))
 
 EXPORTS = ["rt_create", "rt_create_frame_slot", "rt_destroy", "rt_upload_geometry", "rt_build_blas", "rt_set_instances", "rt_set_instances_device", "rt_refit_blas_device", "rt_set_materials", "rt_set_instance_types", "rt_set_uniforms", "rt_set_skybox",
            "rt_trace", "rt_trace_async", "rt_trace_wait", "rt_trace_shard", "rt_set_batch", "rt_trace_shard_batch", "rt_assemble_shards", "rt_shard_rows", "rt_synchronize", "rt_get_stats", "rt_set_timing", "rt_intersect",
-           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_closest_point_device_hits", "rt_closest_point_hits", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_overlap_triangles_device", "rt_overlap_triangles", "rt_sweep_spheres_device", "rt_sweep_spheres", "rt_closest_segment_device", "rt_closest_segment", "rt_closest_triangle_device", "rt_closest_triangle", "rt_scene_triangles_device", "rt_overlap_scene_triangles_device", "rt_overlap_scene_triangles", "rt_overlap_boxes_device_list", "rt_overlap_boxes_list", "rt_overlap_triangles_device_list", "rt_overlap_triangles_list", "rt_overlap_scene_triangles_device_list", "rt_overlap_scene_triangles_list", "rt_closest_scene_triangle_device", "rt_closest_scene_triangle", "rt_point_inside_device", "rt_point_inside", "rt_signed_distance_device", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_host_blas", "rt_debug_snapshot", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
+           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_closest_point_device_hits", "rt_closest_point_hits", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_overlap_triangles_device", "rt_overlap_triangles", "rt_sweep_spheres_device", "rt_sweep_spheres", "rt_closest_segment_device", "rt_closest_segment", "rt_closest_triangle_device", "rt_closest_triangle", "rt_scene_triangles_device", "rt_overlap_scene_triangles_device", "rt_overlap_scene_triangles", "rt_overlap_boxes_device_list", "rt_overlap_boxes_list", "rt_overlap_triangles_device_list", "rt_overlap_triangles_list", "rt_overlap_scene_triangles_device_list", "rt_overlap_scene_triangles_list", "rt_closest_scene_triangle_device", "rt_closest_scene_triangle", "rt_closest_instances_device", "rt_closest_instances", "rt_overlap_instances_device", "rt_overlap_instances", "rt_point_inside_device", "rt_point_inside", "rt_signed_distance_device", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_host_blas", "rt_debug_snapshot", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
 
 _LIBS = {}
 
@@ -148,6 +151,10 @@ def lib(variant=None):
             getattr(L, "rt_overlap_%s_list" % name).argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_size_t, C.c_int, C.POINTER(RtStats)]
         L.rt_closest_scene_triangle_device.argtypes = L.rt_closest_triangle_device.argtypes
         L.rt_closest_scene_triangle.argtypes = L.rt_closest_triangle.argtypes
+        L.rt_closest_instances_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, vp, vp, vp, vp]
+        L.rt_closest_instances.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, vp, vp, C.c_int, C.POINTER(RtStats)]
+        L.rt_overlap_instances_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
+        L.rt_overlap_instances.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_int, C.POINTER(RtStats)]
         L.rt_shade_rays_device.argtypes = [vp, C.c_size_t, C.c_uint32, vp, vp, vp, vp]
         L.rt_last_error.argtypes = [vp]
         L.rt_last_error.restype = C.c_char_p
@@ -905,6 +912,108 @@ class RtContext:
                                                    int(counting), C.byref(st)), "rt_closest_scene_triangle")
         return (out, quv, st) if params else (out, st)
 
+    def closest_instances_device(self, irefs, cull_mask=0xFF, attributes=False, params=False, stream=None, out=None):
+        """rt_closest_instances_device: the nearest pair of every pair of bodies.  `irefs` is a contiguous int32 torch tensor (n, 4) on
+        this context's GPU (inst, against, the bits of r_max, ignored per row; instance_refs packs it): instance `inst` against every
+        other instance (against = -1) or against that one, within r_max.  Returns a RayQuery that names the candidate triangle as
+        closest_scene_triangle_device does for the winning source triangle; its `src_prim` is an int32 (n,) tensor, that source
+        triangle (-1 on a miss); quv (params=True) and hit_kind refer to its world image.  out = (hits, attr, src_prim) or
+        (hits, attr, src_prim, quv) reuses buffers.  See include/rt_api.h."""
+        import torch
+        self._check_rays(irefs, "closest_instances_device", 4, "record", True)
+        n = irefs.shape[0]
+        src = quv = None
+        if out is not None:
+            if len(out) not in (3, 4):
+                raise ValueError("out is (hits, attr, src_prim) or (hits, attr, src_prim, quv)")
+            src, quv, out = out[2], (out[3] if len(out) == 4 else None), tuple(out[:2])
+            if src is None or src.dtype != torch.int32 or tuple(src.shape) != (n,) or not src.is_contiguous() or src.device != irefs.device:
+                raise ValueError("out src_prim must be a contiguous int32 (n,) tensor on the records' device")
+            if params and (quv is None or quv.dtype != torch.float32 or tuple(quv.shape) != (n, 2) or not quv.is_contiguous() or quv.device != irefs.device):
+                raise ValueError("out quv must be a contiguous float32 (n, 2) tensor on the records' device")
+        else:
+            src = torch.empty((n,), dtype=torch.int32, device=irefs.device)
+        if not params:
+            quv = None
+        elif quv is None:
+            quv = torch.empty((n, 2), dtype=torch.float32, device=irefs.device)
+
+        def call(run, hits, attr):
+            src.record_stream(run)
+            if quv is not None:
+                quv.record_stream(run)
+            return self.L.rt_closest_instances_device(self.h, n, C.c_void_p(irefs.data_ptr()), int(cull_mask) & 0xFFFFFFFF, C.c_void_p(hits.data_ptr()),
+                                                      C.c_void_p(src.data_ptr()), C.c_void_p(attr.data_ptr()) if attr is not None else None,
+                                                      C.c_void_p(quv.data_ptr()) if quv is not None else None, C.c_void_p(run.cuda_stream))
+        hits, attr = self._device_query(irefs, attributes, stream, out, (), call, "rt_closest_instances_device", cols=4, checked=True)
+        res = RayQuery(hits, attr, hit_kind=True)
+        res.src_prim = src
+        res.quv = quv
+        return res
+
+    def closest_instances(self, irefs, cull_mask=0xFF, params=False, counting=False):
+        """rt_closest_instances: the blocking host form (irefs: INST_REF_DTYPE records or (n, 4) int32 rows) -> (HIT_DTYPE records,
+        src_prim int32 (n,), RtStats; with counting its node_visits / tri_tests are filled: a measurement, they depend on timing), or
+        with params=True (records, src_prim, (qu, qv) float32 (n, 2), RtStats)"""
+        irefs = _host_irefs(irefs)
+        n = len(irefs)
+        out = np.zeros(n, HIT_DTYPE)
+        src = np.zeros(n, np.int32)
+        quv = np.zeros((n, 2), np.float32) if params else None
+        st = RtStats()
+        self._chk(self.L.rt_closest_instances(self.h, n, _p(irefs), int(cull_mask) & 0xFFFFFFFF, _p(out), _p(src), _p(quv) if quv is not None else None,
+                                              int(counting), C.byref(st)), "rt_closest_instances")
+        return (out, src, quv, st) if params else (out, src, st)
+
+    def overlap_instances_device(self, irefs, cull_mask=0xFF, any=False, first=False, stream=None, out=None):
+        """rt_overlap_instances_device: the intersecting triangle pairs of every pair of bodies.  `irefs` as for
+        closest_instances_device (r_max is ignored).  Returns (count, first4): count an int64 (n,) tensor, the number of pairs (with
+        any=True 0 or 1, and every record stops at its first contact); first4, with first=True (not with any), an int32 (n, 4)
+        tensor (p, inst, prim, 0): the smallest source primitive with a contact and the smallest triangle it touches, -1s when there
+        is none; else None.  out = (count, first4) reuses such buffers.  See include/rt_api.h."""
+        import torch
+        self._check_rays(irefs, "overlap_instances_device", 4, "record", True)
+        if any and first:
+            raise ValueError("any=True stops at any contact: first must be False")
+        n = irefs.shape[0]
+        cur = torch.cuda.current_stream(irefs.device)
+        if stream is None:
+            stream = cur
+        if out is None:
+            count = torch.empty((n,), dtype=torch.int64, device=irefs.device)
+            first4 = torch.empty((n, 4), dtype=torch.int32, device=irefs.device) if first else None
+            if stream != cur:   # (allocated for the current stream, written on `stream`)
+                count.record_stream(stream)
+                if first4 is not None:
+                    first4.record_stream(stream)
+        else:
+            count, first4 = out
+            if count is None or count.dtype != torch.int64 or tuple(count.shape) != (n,) or not count.is_contiguous() or count.device != irefs.device:
+                raise ValueError("out count must be a contiguous int64 (n,) tensor on the records' device")
+            if first and (first4 is None or first4.dtype != torch.int32 or tuple(first4.shape) != (n, 4) or not first4.is_contiguous() or first4.device != irefs.device):
+                raise ValueError("out first4 must be a contiguous int32 (n, 4) tensor on the records' device")
+            first4 = first4 if first else None
+
+        def call(run):
+            return self.L.rt_overlap_instances_device(self.h, n, C.c_void_p(irefs.data_ptr()), int(cull_mask) & 0xFFFFFFFF, OVERLAP_ANY if any else 0,
+                                                      C.c_void_p(count.data_ptr()), C.c_void_p(first4.data_ptr()) if first4 is not None else None,
+                                                      C.c_void_p(run.cuda_stream))
+        if n:
+            self._on_stream(stream, (irefs, count, first4), call, "rt_overlap_instances_device")
+        return count, first4
+
+    def overlap_instances(self, irefs, cull_mask=0xFF, any=False, first=False, counting=False):
+        """rt_overlap_instances: the blocking host form (irefs as for closest_instances) -> (counts uint64 (n,), first4 int32 (n, 4) or
+        None, RtStats; with counting its node_visits / tri_tests are filled: a measurement, they depend on timing)"""
+        irefs = _host_irefs(irefs)
+        n = len(irefs)
+        cnt = np.zeros(n, np.uint64)
+        first4 = np.zeros((n, 4), np.int32) if first else None
+        st = RtStats()
+        self._chk(self.L.rt_overlap_instances(self.h, n, _p(irefs), int(cull_mask) & 0xFFFFFFFF, OVERLAP_ANY if any else 0, _p(cnt),
+                                              _p(first4) if first4 is not None else None, int(counting), C.byref(st)), "rt_overlap_instances")
+        return cnt, first4, st
+
     def intersect_device_hits(self, rays, max_hits, ray_flags=0, cull_mask=0xFF, words=None, attributes=False, counts=True, stream=None, out=None):
         """rt_intersect_device_hits: every candidate along each ray, the first max_hits of them in (t, inst, prim) order, and their number.
         rays and words as for intersect_device_flags; max_hits 1..16, or 0 for counts only.  Read and written in the order of `stream`
@@ -1240,6 +1349,39 @@ def _host_refs(refs):
     if refs.dtype != np.int32:
         raise ValueError("references must be TRI_REF_DTYPE records or int32 rows, not %s" % refs.dtype)
     return np.ascontiguousarray(refs).reshape(-1, 4)
+
+
+def _host_irefs(irefs):
+    """host instance-pair records as contiguous (n, 4) int32 rows: INST_REF_DTYPE records or anything instance_refs returns for numpy input"""
+    irefs = np.asarray(irefs)
+    if irefs.dtype == INST_REF_DTYPE:
+        return np.ascontiguousarray(irefs).view(np.int32).reshape(-1, 4)
+    if irefs.dtype != np.int32:
+        raise ValueError("records must be INST_REF_DTYPE records or int32 rows, not %s" % irefs.dtype)
+    return np.ascontiguousarray(irefs).reshape(-1, 4)
+
+
+def instance_refs(inst, against=REF_AGAINST_OTHERS, r_max=float("inf")):
+    """the (n, 4) int32 rows (rt_inst_ref: inst, against, the bits of r_max, 0) of closest_instances* and overlap_instances*: instance
+    `inst` as the query, against every other instance (against = -1) or against that instance only.  inst, against and r_max broadcast
+    against each other ((n,) or scalars).  torch tensors stay on their device; anything else goes through numpy (the rows then view as
+    INST_REF_DTYPE)."""
+    try:
+        import torch
+        dev = next((x.device for x in (inst, against, r_max) if isinstance(x, torch.Tensor)), None)
+    except ImportError:
+        dev = None
+    if dev is not None:
+        i, a, r = torch.broadcast_tensors(*(torch.as_tensor(x, device=dev).reshape(-1) for x in (inst, against, r_max)))
+        rec = torch.zeros((i.shape[0], 4), dtype=torch.int32, device=dev)
+        rec[:, 0] = i.to(torch.int32); rec[:, 1] = a.to(torch.int32)
+        rec[:, 2] = r.to(torch.float32).contiguous().view(torch.int32)
+        return rec
+    i, a, r = np.broadcast_arrays(*(np.asarray(x).reshape(-1) for x in (inst, against, r_max)))
+    rec = np.zeros((len(i), 4), np.int32)
+    rec[:, 0] = i.astype(np.int64).astype(np.int32); rec[:, 1] = a.astype(np.int64).astype(np.int32)
+    rec[:, 2] = np.ascontiguousarray(r, np.float32).view(np.int32)
+    return rec
 
 
 def triangle_refs(inst, prim, against=REF_AGAINST_OTHERS, r_max=float("inf")):

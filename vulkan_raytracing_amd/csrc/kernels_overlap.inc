@@ -52,8 +52,9 @@ struct OverlapBox {
     against = -1;   // (no by-reference form)
     return valid;
   }
+  using Item = NoItem;
   struct Leaf {   // (the bounds are the whole record)
-    __device__ __forceinline__ Leaf(const OverlapArgs&, uint32_t) {}
+    __device__ __forceinline__ Leaf(const OverlapArgs&, uint32_t, const Item&) {}
     __device__ __forceinline__ bool touches(F3 wlo, F3 whi, F3 A, F3 ab, F3 ac) const { return overlap_tri(wlo, whi, A, ab, ac); }
   };
 };

@@ -11,15 +11,12 @@
 //  * the walks are the REFS instantiations of overlap_body and nearest_body (walk_overlap.inc, walk_nearest.inc) with the triangle
 //    shapes (kernels_triangles.inc, kernels_triangle.inc) over the expanded records, under kernel names of their own.
 
-__global__ __launch_bounds__(256) void k_refs_expand(SceneDev sc, const int4* __restrict__ refs, float4* __restrict__ out, uint32_t n, uint32_t n_vert_floats) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  const int4 r = refs[i];
-  const int inst = r.x, prim = r.y, against = r.z;
-  const float QNAN = __uint_as_float(0x7FC00000u);
-  F3 P0 = mk3(QNAN, QNAN, QNAN), P1 = P0, P2 = P0;
-  if (inst >= 0 && inst < sc.n_inst && against >= -1 && against < sc.n_inst) {
-    const InstanceDev* I = sc.inst + inst;
+// The world image (P0, P1, P2) of triangle `prim` of instance I (a checked instance of the scene), or nothing: prim outside the mesh, a
+// bad triangle, an image that is not finite.  k_refs_expand's loads, checks and arithmetic, which the instance-pair walks
+// (kernels_pairs.inc) repeat for their work items: one function, so that both make the same bytes.
+__device__ __forceinline__ bool refs_world_triangle(const SceneDev& sc, const InstanceDev* I, int prim, uint32_t n_vert_floats, F3& P0, F3& P1, F3& P2) {
+  bool made = false;
+  {
     if (prim >= 0 && (uint32_t)prim < I->prim_count) {
       const uint32_t* ip = sc.idx + I->first_index + 3ull * (uint32_t)prim;
       const uint32_t i0 = ip[0], i1 = ip[1], i2 = ip[2];
@@ -40,11 +37,22 @@ __global__ __launch_bounds__(256) void k_refs_expand(SceneDev sc, const int4* __
         const F3 B = add3(A, xform_vec(I->o2w, sub3(v1, v0))), Cc = add3(A, xform_vec(I->o2w, sub3(v2, v0)));
         if (good && finite_bits(A.x) && finite_bits(A.y) && finite_bits(A.z) && finite_bits(B.x) && finite_bits(B.y) && finite_bits(B.z) &&
             finite_bits(Cc.x) && finite_bits(Cc.y) && finite_bits(Cc.z)) {
-          P0 = A; P1 = B; P2 = Cc;
+          P0 = A; P1 = B; P2 = Cc; made = true;
         }
       }
     }
   }
+  return made;
+}
+
+__global__ __launch_bounds__(256) void k_refs_expand(SceneDev sc, const int4* __restrict__ refs, float4* __restrict__ out, uint32_t n, uint32_t n_vert_floats) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const int4 r = refs[i];
+  const int inst = r.x, prim = r.y, against = r.z;
+  const float QNAN = __uint_as_float(0x7FC00000u);
+  F3 P0 = mk3(QNAN, QNAN, QNAN), P1 = P0, P2 = P0;
+  if (inst >= 0 && inst < sc.n_inst && against >= -1 && against < sc.n_inst) refs_world_triangle(sc, sc.inst + inst, prim, n_vert_floats, P0, P1, P2);
   float4* o = out + 3u * (size_t)i;
   o[0] = make_float4(P0.x, P0.y, P0.z, __int_as_float(r.w));
   o[1] = make_float4(P1.x, P1.y, P1.z, __int_as_float(inst));

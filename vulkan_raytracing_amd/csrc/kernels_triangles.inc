@@ -67,9 +67,10 @@ struct OverlapTriangle {
     return finite_bits(r0.x) && finite_bits(r0.y) && finite_bits(r0.z) && finite_bits(r1.x) && finite_bits(r1.y) && finite_bits(r1.z) &&
            finite_bits(r2.x) && finite_bits(r2.y) && finite_bits(r2.z);
   }
+  using Item = NoItem;
   struct Leaf {   // the record read again
     F3 P0, P1, P2;
-    __device__ __forceinline__ Leaf(const OverlapArgs& a, uint32_t bx) {
+    __device__ __forceinline__ Leaf(const OverlapArgs& a, uint32_t bx, const Item&) {
       const float4* qp = a.records + 3u * (size_t)bx;
       const float4 r0 = qp[0], r1 = qp[1], r2 = qp[2];
       P0 = mk3(r0.x, r0.y, r0.z); P1 = mk3(r1.x, r1.y, r1.z); P2 = mk3(r2.x, r2.y, r2.z);

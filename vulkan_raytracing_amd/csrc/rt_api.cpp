@@ -312,6 +312,9 @@ struct rt_ctx {
   char* d_q_list = nullptr;        // rt_overlap_*_list: the counts of the first walk, the worklist of k_list_sort and the scan's tile sums
                                    // (list_workspace); part of the query workspace
   size_t q_list_alloc = 0;         // bytes of d_q_list
+  char* d_q_pairs = nullptr;       // rt_*_instances*: the finish references, the work items' offsets, the keys (or the rows of one), the
+                                   // scan's tile sums, the item counts and the first-p words (PairsWorkspace); part of the query workspace
+  size_t q_pairs_alloc = 0;        // bytes of d_q_pairs
   hipEvent_t ev_query[2] = {nullptr, nullptr};
   bool ev_query_valid[2] = {false, false};
   int query_last = -1;             // parity of the last query (-1: none since the last host wait)
@@ -1494,6 +1497,7 @@ void rt_destroy(rt_ctx* c) {
   if (c->d_q_words) hipFree(c->d_q_words);
   if (c->d_q_tris) hipFree(c->d_q_tris);
   if (c->d_q_list) hipFree(c->d_q_list);
+  if (c->d_q_pairs) hipFree(c->d_q_pairs);
   for (int k = 0; k < 2; k++) if (c->ev_query[k]) hipEventDestroy(c->ev_query[k]);
   tlas_gpu_free(c->tgpu);
   for (auto e : c->ev_pool) hipEventDestroy(e);
@@ -2370,7 +2374,11 @@ enum class Walk {
   Triangle,  // rt_closest_triangle*: the nearest pair of every query triangle and the surface, and its (qu, qv) (the same scales first)
   Inside,    // rt_point_inside*: the inside / outside vote; with hits, rt_signed_distance_device: the closest-point walk into hits (and
              // attr) first, the vote with the counter block's cursor initialised again, then the sign pass over hits
-  Expand     // rt_scene_triangles_device: k_refs_expand alone, the references' 48-byte records into tris_out
+  Expand,    // rt_scene_triangles_device: k_refs_expand alone, the references' 48-byte records into tris_out
+  Pairs,     // rt_closest_instances*: the records are n rt_inst_ref.  k_pairs_plan and the scan, the shared-bound walk into the workspace's
+             // keys, k_pairs_refs, then the by-reference Triangle walk over those n references into hits (and params, attr)
+  PairsOverlap // rt_overlap_instances*: the same plan, the count-only walk into counts (uint64) and, with first4, k_pairs_refs, the capped
+             // by-reference walk with rows of one, and k_pairs_first
 };
 struct Query {
   Walk walk = Walk::Plain;
@@ -2397,6 +2405,9 @@ struct Query {
   void* words = nullptr;             // Inside: n vote words (null with hits: the workspace's)
   void* params = nullptr;            // Segment: n parameters s; Triangle: n pairs (qu, qv) (optional; null with attr: the workspace's words hold them)
   void* attr = nullptr;              // the hit attributes (optional)
+  void* src_prims = nullptr;         // Pairs: n int32, the source primitive of the nearest pair
+  void* first4 = nullptr;            // PairsOverlap: n rows (p, inst, prim, 0) (optional)
+  uint64_t max_items = 0;            // Pairs, PairsOverlap: n * the largest triangle count of a mesh, which bounds the work items
   bool counting = false;             // the instrumented walk (Hits and Flags have none): its counts start from a zeroed counter block
   hipEvent_t t0 = nullptr, t1 = nullptr;   // recorded around the walk (optional)
 };
@@ -2411,14 +2422,30 @@ struct ListWorkspace {
     bytes = sums + (size_t)list_scan_tiles((uint32_t)n) * sizeof(unsigned long long);
   }
 };
+// The instance-pair calls' part of the query workspace for n records, as byte offsets into one area: the n finish references (16-byte
+// aligned), the n + 1 offsets of the work items, n 8-byte words (Pairs: the keys; PairsOverlap: the rows of one), the scan's tile sums,
+// the n item counts and the n first-p words.
+struct PairsWorkspace {
+  size_t refs = 0, offsets = 0, keys = 0, sums = 0, items = 0, first = 0, bytes = 0;
+  PairsWorkspace() = default;
+  explicit PairsWorkspace(size_t n) {
+    offsets = n * 16;
+    keys = offsets + (n + 1) * sizeof(uint64_t);
+    sums = keys + n * sizeof(uint64_t);
+    items = sums + (size_t)list_scan_tiles((uint32_t)n) * sizeof(unsigned long long);
+    first = items + n * sizeof(uint32_t);
+    bytes = first + n * sizeof(uint32_t);
+  }
+};
 int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q) {
   const bool flags = q.walk == Walk::Flags, sweep = q.walk == Walk::Sweep, inside = q.walk == Walk::Inside, segment = q.walk == Walk::Segment;
-  const bool triangle = q.walk == Walk::Triangle;
+  const bool pairs = q.walk == Walk::Pairs, pairs_overlap = q.walk == Walk::PairsOverlap;
+  const bool triangle = q.walk == Walk::Triangle || pairs;   // (Pairs ends in the by-reference Triangle walk over its finish references)
   const bool closest = q.walk == Walk::Closest || (inside && q.hits);
   const uint32_t n = (uint32_t)q.n;
   const float4* records = (const float4*)q.records;
   { int r = query_workspace(c, s); if (r) return r; }
-  if (q.refs && q.walk != Walk::Expand) {   // the expanded records: a new area before the old one goes, so that a failure changes nothing
+  if ((q.refs && q.walk != Walk::Expand) || pairs || (pairs_overlap && q.first4)) {   // the expanded records: a new area before the old one goes, so that a failure changes nothing
     if (q.n > c->q_tris_alloc) {
       { int w = wait_queries(c, c); if (w) return w; }
       float4* grown = nullptr;
@@ -2452,13 +2479,25 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q
       c->d_q_list = grown; c->q_list_alloc = lw.bytes;
     }
   }
+  PairsWorkspace pw;
+  if (pairs || pairs_overlap) {   // as the list area
+    pw = PairsWorkspace(q.n);
+    if (pw.bytes > c->q_pairs_alloc) {
+      { int w = wait_queries(c, c); if (w) return w; }
+      char* grown = nullptr;
+      HIP_TRY(c, hipMalloc((void**)&grown, pw.bytes));
+      if (c->d_q_pairs) (void)hipFree(c->d_q_pairs);
+      c->d_q_pairs = grown; c->q_pairs_alloc = pw.bytes;
+    }
+  }
+  char* const pa = c->d_q_pairs;
   uint32_t* list_counts = (uint32_t*)(c->d_q_list + lw.counts), *list_work = (uint32_t*)(c->d_q_list + lw.work);
   unsigned long long* list_sums = (unsigned long long*)(c->d_q_list + lw.sums);
   if (q.counting) HIP_TRY(c, hipMemsetAsync(c->d_q_counters, 0, CNT_WORDS * sizeof(uint32_t), s));
   const SceneDev sc = scene_dev(c);
   if (q.t0) HIP_TRY(c, hipEventRecord(q.t0, s));
   if (q.refs) launch_refs_expand(sc, q.records, q.walk == Walk::Expand ? (float4*)q.tris_out : c->d_q_tris, n, c->scene->h_verts.size(), s);
-  if (closest || sweep || segment || triangle || q.walk == Walk::ClosestHits || q.walk == Walk::Overlap || q.walk == Walk::Triangles) launch_closest_scale(sc, c->d_q_scale, s);
+  if (closest || sweep || segment || triangle || q.walk == Walk::ClosestHits || q.walk == Walk::Overlap || q.walk == Walk::Triangles || pairs_overlap) launch_closest_scale(sc, c->d_q_scale, s);
   // the two families of walk_nearest.inc and walk_overlap.inc: the shape of the records chooses the kernel, the launch is the family's
   const NearestShape nearest = segment ? NearestShape::Segment : !triangle ? NearestShape::Point : q.refs ? NearestShape::Refs : NearestShape::Triangle;
   const OverlapShape overlap = q.walk == Walk::Overlap ? OverlapShape::Boxes : q.refs ? OverlapShape::Refs : OverlapShape::Triangles;
@@ -2493,6 +2532,29 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q
       launch_point_inside(sc, records, q.cull_mask, q.n_dirs, words, (uint32_t*)q.counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
       break;
     case Walk::Expand: break;   // (the expansion above is the whole call)
+    case Walk::Pairs:   // the shared-bound walk names every record's source triangle; the by-reference call over those makes the answer
+      launch_pairs_plan(sc, q.records, n, true, (uint32_t*)(pa + pw.items), (unsigned long long*)(pa + pw.sums), (unsigned long long*)(pa + pw.offsets),
+                        (unsigned long long*)(pa + pw.keys), nullptr, nullptr, s);
+      launch_pairs_nearest(sc, q.records, (const unsigned long long*)(pa + pw.offsets), (unsigned long long*)(pa + pw.keys), q.cull_mask, c->d_q_scale, n, q.max_items,
+                           c->scene->h_verts.size(), c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
+      launch_pairs_refs(q.records, (const uint32_t*)(pa + pw.keys), 2u, n, true, pa + pw.refs, (int32_t*)q.src_prims, s);
+      launch_refs_expand(sc, pa + pw.refs, c->d_q_tris, n, c->scene->h_verts.size(), s);
+      launch_nearest(NearestShape::Refs, sc, records, q.cull_mask, c->d_q_scale, (HitRec*)q.hits, (float*)words, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
+      break;
+    case Walk::PairsOverlap: {
+      uint32_t* first_p = q.first4 ? (uint32_t*)(pa + pw.first) : nullptr;
+      launch_pairs_plan(sc, q.records, n, false, (uint32_t*)(pa + pw.items), (unsigned long long*)(pa + pw.sums), (unsigned long long*)(pa + pw.offsets), nullptr,
+                        (unsigned long long*)q.counts, first_p, s);
+      launch_pairs_collide(sc, q.records, (const unsigned long long*)(pa + pw.offsets), (unsigned long long*)q.counts, first_p, q.overlap_any, q.cull_mask, c->d_q_scale, n,
+                           q.max_items, c->scene->h_verts.size(), c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
+      if (first_p) {   // the first entry of the first non-empty row: the capped by-reference walk with rows of one (it prunes)
+        launch_pairs_refs(q.records, first_p, 1u, n, false, pa + pw.refs, nullptr, s);
+        launch_refs_expand(sc, pa + pw.refs, c->d_q_tris, n, c->scene->h_verts.size(), s);
+        launch_overlap(OverlapShape::Refs, sc, records, q.cull_mask, c->d_q_scale, false, 1u, pa + pw.keys, nullptr, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
+        launch_pairs_first(first_p, pa + pw.keys, n, q.first4, s);
+      }
+      break;
+    }
   }
   if (q.t1) HIP_TRY(c, hipEventRecord(q.t1, s));
   if (q.attr && q.walk != Walk::Hits && q.walk != Walk::ClosestHits) {
@@ -3070,6 +3132,92 @@ int rt_closest_scene_triangle(rt_ctx* c, size_t n, const rt_tri_ref* refs, uint3
   Query q; q.walk = Walk::Triangle; q.n = n; q.refs = true; q.cull_mask = cull_mask; q.counting = counting != 0;
   return blocking_query(c, q, refs, ref_bytes, ref_bytes + hit_bytes + par_bytes,
                         {{&Query::hits, ref_bytes, out, hit_bytes}, {&Query::params, ref_bytes + hit_bytes, params, par_bytes}}, stats);
+}
+
+namespace {
+// the argument rules the four rt_*_instances* calls share (pointers aside): the number of records against the work items they can stand
+// for (every record the largest mesh of the scene: conservative, the records live on the device), the cull mask and the traversal
+int instances_arguments(rt_ctx* c, const std::string& name, size_t n, uint32_t cull_mask, uint64_t& max_items) {
+  uint64_t largest = 0;
+  for (const Mesh& m : c->scene->meshes) largest = std::max<uint64_t>(largest, m.range.prim_count);
+  if (n >= 0xFFFFFF00ull || (largest != 0 && (uint64_t)n >= (0xFFFFFF00ull + largest - 1) / largest))
+    return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": n * the largest triangle count of a mesh must be below 0xFFFFFF00 (32-bit work-item indices)");
+  max_items = (uint64_t)n * largest;
+  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": cull_mask is above 0xFF");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, name + " needs trace_variant 0");
+  return RT_OK;
+}
+// ... and the overlap pair's own: the flags, and no first entries with RT_OVERLAP_ANY
+int overlap_instances_arguments(rt_ctx* c, const std::string& name, uint32_t flags, const void* counts, const void* first4, size_t n) {
+  if ((flags & ~RT_OVERLAP_ANY) != 0u) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": unknown flag bits");
+  if ((flags & RT_OVERLAP_ANY) && first4) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": RT_OVERLAP_ANY gives no first entries: they must be NULL");
+  if (n && !counts) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null count pointer");
+  return RT_OK;
+}
+}  // namespace
+
+// The nearest pair of every pair of bodies: the checks and ordering of a device query (rt_closest_point_device), then (enqueue_query,
+// Walk::Pairs) k_pairs_plan and the scan, k_pairs_nearest, k_pairs_refs and rt_closest_scene_triangle_device's kernels over the n
+// references it wrote.
+int rt_closest_instances_device(rt_ctx* c, size_t n, const void* d_irefs4, uint32_t cull_mask, void* d_hits, void* d_src_prims, void* d_attr, void* d_params,
+                                void* hip_stream) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const std::string name = "rt_closest_instances_device";
+  Query q; q.walk = Walk::Pairs; q.n = n; q.records = d_irefs4; q.cull_mask = cull_mask; q.hits = d_hits; q.src_prims = d_src_prims; q.attr = d_attr; q.params = d_params;
+  { int w = instances_arguments(c, name, n, cull_mask, q.max_items); if (w) return w; }
+  if (n) {
+    if (!d_irefs4 || !d_hits || !d_src_prims) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null record/hit/source-primitive pointers");
+    if (((uintptr_t)d_irefs4 & 15u) || ((uintptr_t)d_hits & 3u) || ((uintptr_t)d_src_prims & 3u) || ((uintptr_t)d_attr & 15u) || ((uintptr_t)d_params & 3u))
+      return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": records and attributes must be 16-byte aligned, hits, source primitives and parameters 4-byte aligned");
+    { int w = check_device_pointers(c, name, "records, hits, source primitives, attributes and parameters", {d_irefs4, d_hits, d_src_prims, d_attr, d_params}); if (w) return w; }
+  }
+  return device_query(c, q, hip_stream);
+}
+
+// The blocking host form, as rt_closest_scene_triangle is to rt_closest_scene_triangle_device: the records (16 B each), then the hits, the
+// source primitives and the parameters (two floats each).  The whole sequence runs inside the timed window.
+int rt_closest_instances(rt_ctx* c, size_t n, const rt_inst_ref* irefs, uint32_t cull_mask, rt_hit* out, int32_t* src_prims, float* params, int counting, rt_stats* stats) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const std::string name = "rt_closest_instances";
+  Query q; q.walk = Walk::Pairs; q.n = n; q.cull_mask = cull_mask; q.counting = counting != 0;
+  if ((!irefs || !out || !src_prims) && n) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null record/hit/source-primitive pointers");
+  { int w = instances_arguments(c, name, n, cull_mask, q.max_items); if (w) return w; }
+  const size_t ref_bytes = n * sizeof(rt_inst_ref), hit_bytes = n * sizeof(HitRec), src_bytes = n * sizeof(int32_t), par_bytes = n * 2 * sizeof(float);
+  return blocking_query(c, q, irefs, ref_bytes, ref_bytes + hit_bytes + src_bytes + par_bytes,
+                        {{&Query::hits, ref_bytes, out, hit_bytes}, {&Query::src_prims, ref_bytes + hit_bytes, src_prims, src_bytes},
+                         {&Query::params, ref_bytes + hit_bytes + src_bytes, params, par_bytes}}, stats);
+}
+
+// The intersecting triangle pairs of every pair of bodies: the same checks and ordering, then (enqueue_query, Walk::PairsOverlap)
+// k_pairs_plan and the scan, k_pairs_collide into the caller's sums and, with d_first4, k_pairs_refs, k_refs_collide with rows of one
+// and k_pairs_first.
+int rt_overlap_instances_device(rt_ctx* c, size_t n, const void* d_irefs4, uint32_t cull_mask, uint32_t flags, void* d_counts64, void* d_first4, void* hip_stream) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const std::string name = "rt_overlap_instances_device";
+  Query q; q.walk = Walk::PairsOverlap; q.n = n; q.records = d_irefs4; q.cull_mask = cull_mask; q.overlap_any = (flags & RT_OVERLAP_ANY) != 0u;
+  q.counts = d_counts64; q.first4 = d_first4;
+  { int w = instances_arguments(c, name, n, cull_mask, q.max_items); if (w) return w; }
+  { int w = overlap_instances_arguments(c, name, flags, d_counts64, d_first4, n); if (w) return w; }
+  if (n) {
+    if (!d_irefs4) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null record pointer");
+    if (((uintptr_t)d_irefs4 & 15u) || ((uintptr_t)d_counts64 & 7u) || ((uintptr_t)d_first4 & 3u))
+      return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": records must be 16-byte aligned, counts 8-byte aligned, first entries 4-byte aligned");
+    { int w = check_device_pointers(c, name, "records, counts and first entries", {d_irefs4, d_counts64, d_first4}); if (w) return w; }
+  }
+  return device_query(c, q, hip_stream);
+}
+
+// The blocking host form: the records (16 B each), then the counts (uint64), then the first entries (16 B each).
+int rt_overlap_instances(rt_ctx* c, size_t n, const rt_inst_ref* irefs, uint32_t cull_mask, uint32_t flags, uint64_t* counts, int32_t* first4, int counting, rt_stats* stats) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const std::string name = "rt_overlap_instances";
+  Query q; q.walk = Walk::PairsOverlap; q.n = n; q.cull_mask = cull_mask; q.overlap_any = (flags & RT_OVERLAP_ANY) != 0u; q.counting = counting != 0;
+  if (!irefs && n) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null record pointer");
+  { int w = instances_arguments(c, name, n, cull_mask, q.max_items); if (w) return w; }
+  { int w = overlap_instances_arguments(c, name, flags, counts, first4, n); if (w) return w; }
+  const size_t ref_bytes = n * sizeof(rt_inst_ref), count_bytes = n * sizeof(uint64_t), first_bytes = first4 ? n * 4 * sizeof(int32_t) : 0;
+  return blocking_query(c, q, irefs, ref_bytes, ref_bytes + count_bytes + first_bytes,
+                        {{&Query::counts, ref_bytes, counts, count_bytes}, {&Query::first4, ref_bytes + count_bytes, first4, first_bytes}}, stats);
 }
 
 namespace {

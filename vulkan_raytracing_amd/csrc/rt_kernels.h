@@ -269,6 +269,27 @@ void launch_list_scan(const uint32_t* counts, uint32_t n, unsigned long long* su
 void launch_overlap_list(OverlapShape shape, const SceneDev& sc, const float4* records, uint32_t cull_mask, const float* inst_scale, const unsigned long long* offsets,
                          void* ids, uint64_t capacity, uint32_t* work, uint32_t n, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg,
                          hipStream_t s);
+// rt_closest_instances_device, rt_overlap_instances_device (kernels_pairs.inc; DESIGN.md §5 "Instance pairs"): the by-reference triangle
+// queries per record (16 bytes: inst, against, r_max, reserved), every triangle of the source instance a work item of the walk.
+//   plan      items[n]: the work items of every record (0: invalid), offsets[n + 1] their starts (launch_list_scan; sums_scratch its
+//             scratch), and the start values: keys[n] (nearest), or sums[n] and first_p[n] (overlap; first_p optional)
+//   nearest   the shared-bound walk: keys[i] becomes bits(d2) << 32 | p of the record's nearest pair, its low word 0xFFFFFFFF on a miss
+//   collide   the count-only walk: sums[i] the number of triangle pairs, first_p[i] the smallest source primitive with one (or
+//             0xFFFFFFFF); any: sums[i] 0 or 1 and no first_p
+//   refs      one rt_tri_ref per record from `word` (stride words apart: the keys' low words, or first_p): (inst, p, against, r_max or 0),
+//             or (-1, -1, -1, r_max or 0); src_prims (optional): p or -1
+//   first     (p, inst, prim, 0) from first_p and the capped by-reference call's rows of one
+// max_items bounds the work items (their number stays on the device) and with it the grid; inst_scale, chunk cursor, counters
+// (counting) and spill area as for launch_nearest; n_vert_floats as for launch_refs_expand.
+void launch_pairs_plan(const SceneDev& sc, const void* irefs, uint32_t n, bool nearest, uint32_t* items, unsigned long long* sums_scratch, unsigned long long* offsets,
+                       unsigned long long* keys, unsigned long long* sums, uint32_t* first_p, hipStream_t s);
+void launch_pairs_nearest(const SceneDev& sc, const void* irefs, const unsigned long long* offsets, unsigned long long* keys, uint32_t cull_mask, const float* inst_scale,
+                          uint32_t n, uint64_t max_items, uint64_t n_vert_floats, int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
+void launch_pairs_collide(const SceneDev& sc, const void* irefs, const unsigned long long* offsets, unsigned long long* sums, uint32_t* first_p, bool any, uint32_t cull_mask,
+                          const float* inst_scale, uint32_t n, uint64_t max_items, uint64_t n_vert_floats, int32_t* ovf_stack, uint32_t* counters, bool counting,
+                          const LaunchCfg& cfg, hipStream_t s);
+void launch_pairs_refs(const void* irefs, const uint32_t* word, uint32_t stride, uint32_t n, bool keep_radius, void* refs, int32_t* src_prims, hipStream_t s);
+void launch_pairs_first(const uint32_t* first_p, const void* ids, uint32_t n, void* first4, hipStream_t s);
 // rt_shade_rays_device: k_ray_ingest replaces k_raygen for the caller's n rays (32 bytes each, o.xyz, w3, d.xyz, tmax; sample id = record
 // index): sky colours of the rays that miss the TLAS and (0, 0, 0, 0) for invalid records into f.sample_color, the others into bounce queue 0
 // (workgroup b appends to shard b % 8: f.shard_cap >= 256 * ceil(ray_ingest_block_count(n) / 8)).  f.counters must be zero.

@@ -30,7 +30,10 @@
 //  * the leaf test depends on the record, the instance record and the packet only, so the result is the minimum of the key
 //    (d2, inst, prim) whatever the tree;
 //  * REFS (kernels_refs.inc): the records are k_refs_expand's; a valid record with against >= 0 (word 11) starts at that instance's TLAS
-//    leaf, one against the others passes over its source instance (word 7).
+//    leaf, one against the others passes over its source instance (word 7);
+//  * PAIRS (kernels_pairs.inc): a lane's item is one source triangle of an instance-pair record, and the bound is shared: `best` is the
+//    smaller of the lane's own best d2 and the smallest d2 any lane of the record has published (PairNearest::shared).  No hit is
+//    kept: the key names the winning source triangle, and the by-reference call over it makes the answer.
 
 struct NearestArgs {
   SceneDev sc;
@@ -43,6 +46,11 @@ struct NearestArgs {
   uint32_t* cursor;            // chunk cursor (zero before the launch)
   uint32_t* counters;          // the query's counter block (counting form: CNT_NODE_VISITS, CNT_TRI_TESTS)
   int32_t* ovf_stack;          // ovf_stride ints per thread of the grid
+  // the PAIRS instantiations only; behind everything else, so that the other kernels read their arguments where they did
+  const int4* irefs;           // n instance-pair records (rt_inst_ref)
+  const unsigned long long* offsets;   // n + 1 starts of the records' work items (offsets[n]: their number)
+  unsigned long long* keys;    // n keys: the bits of the smallest published d2 << 32 | its smallest source primitive
+  uint32_t n_vert_floats;      // the floats of sc.verts
 };
 
 constexpr float CP_ABS = 1.52587890625e-05f;       // 2^-16: absolute slack per unit of magnitude
@@ -69,7 +77,7 @@ __device__ __forceinline__ void closest_enter_instance(const InstanceDev* I, flo
   scale2 = CP_REL * (s * s);
 }
 
-template <class Shape, bool COUNT, bool REFS = false>
+template <class Shape, bool COUNT, bool REFS = false, bool PAIRS = false>
 __device__ __forceinline__ void nearest_body(const NearestArgs& a) {
   __shared__ int s_stack[4][STACK2_LDS][64];
   WalkStack st(s_stack, a.ovf_stack, a.sc.ovf_stride);
@@ -86,6 +94,8 @@ __device__ __forceinline__ void nearest_body(const NearestArgs& a) {
   int best_prim = NONE, best_inst = NONE;
   int cur = REF_DONE, cur_inst = -1;
   unsigned long long cnt_nodes = 0, cnt_tris = 0;
+  uint32_t n_items = a.n;                     // PAIRS: the work items of all records, from the device
+  if constexpr (PAIRS) n_items = (uint32_t)a.offsets[a.n];
 
   auto world_space = [&]() {
     sh.to_world();
@@ -95,13 +105,15 @@ __device__ __forceinline__ void nearest_body(const NearestArgs& a) {
 
   for (;;) {
     // ---- refill: idle lanes take the next records of the wave's chunk
-    const uint32_t rec = feed.take(__ballot(need), a.cursor, a.n);
+    const uint32_t rec = feed.take(__ballot(need), a.cursor, n_items);
     if (need && rec != WALK_NONE) {
       pt = rec;
       float r_max, pmag;
       int against;
       const bool valid = sh.load(a, pt, r_max, pmag, against);
-      best = r_max * r_max; best_u = 0.f; best_v = 0.f; best_p = typename Shape::Params(); best_prim = NONE; best_inst = NONE;
+      best = r_max * r_max;
+      if constexpr (PAIRS) best = fminf(best, sh.shared(a));   // (never above r_max * r_max: the key starts there)
+      best_u = 0.f; best_v = 0.f; best_p = typename Shape::Params(); best_prim = NONE; best_inst = NONE;
       w_slack = CP_ABS * fmaxf(fmaxf(pmag, tlas_magnitude(a.sc, 0.f)), a.inst_scale[0]);
       world_space();
       cur_inst = -1;
@@ -136,6 +148,7 @@ __device__ __forceinline__ void nearest_body(const NearestArgs& a) {
       uint32_t first, nt;
       walk_leaf(cur, first, nt);
       const float* o = a.sc.inst[cur_inst].o2w;
+      bool mine = false;   // PAIRS: best is a d2 of this leaf, to be published
       for (uint32_t j = 0; j < nt; j++) {
         const float4* tp = a.sc.tris + (size_t)(first + j) * 3;
         const float4 T0 = tp[0], T1 = tp[1], T2 = tp[2];
@@ -144,9 +157,17 @@ __device__ __forceinline__ void nearest_body(const NearestArgs& a) {
         typename Shape::Params pp;
         const float d2 = sh.test(xform_point(o, mk3(T0.x, T0.y, T0.z)), xform_vec(o, mk3(T0.w, T1.x, T1.y)), xform_vec(o, mk3(T1.z, T1.w, T2.x)), uu, vv, pp);
         const int prim = (int)__float_as_uint(T2.y);
+        if constexpr (PAIRS) {   // no farther than the record's bound (a tie too: this source primitive may be the smaller one)
+          if (d2 <= best) { best = d2; mine = true; }
+          continue;
+        }
         if (d2 < best || (d2 == best && (cur_inst < best_inst || (cur_inst == best_inst && prim < best_prim)))) {
           best = d2; best_u = uu; best_v = vv; best_p = pp; best_prim = prim; best_inst = cur_inst;
         }
+      }
+      if constexpr (PAIRS) {
+        if (mine) sh.publish(a, best);
+        best = fminf(best, sh.shared(a));
       }
       sh.reach(best, scale2);
       cur = st.pop();
@@ -167,6 +188,7 @@ __device__ __forceinline__ void nearest_body(const NearestArgs& a) {
         // (the object-space point closest_enter_instance returns for the magnitudes is not used: the shape holds itself)
         F3 unused;
         closest_enter_instance(I, a.inst_scale[1 + ii], sh.enter(I), w_slack, unused, q_lo, q_scale, slack, scale2);
+        if constexpr (PAIRS) best = fminf(best, sh.shared(a));
         sh.reach(best, scale2);
         st.push(REF_MARK);
         cur_inst = ii; cur = I->blas_root;
@@ -174,6 +196,7 @@ __device__ __forceinline__ void nearest_body(const NearestArgs& a) {
     }
     if (!need && cur == REF_DONE) {
       // ---- finished: the record, or the miss form with the radius as given (read again)
+      if constexpr (PAIRS) { need = true; continue; }   // (what the item found is in the record's key)
       HitRec h;
       if (best_inst != NONE) { h.t = __builtin_sqrtf(best); h.u = best_u; h.v = best_v; h.prim = best_prim; h.inst = best_inst; }
       else { h.t = ld_stream(&a.records[Shape::STRIDE * (size_t)pt]).w; h.u = 0.f; h.v = 0.f; h.prim = -1; h.inst = -1; best_p = typename Shape::Params(); }

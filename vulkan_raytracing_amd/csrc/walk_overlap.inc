@@ -24,7 +24,10 @@
 //  * REFS (kernels_refs.inc): the records are k_refs_expand's, words 7 and 11 the source instance and `against`; a valid record with
 //    against >= 0 starts at that instance's TLAS leaf with nothing beneath it, so the TLAS is never walked, and with against == -1 the
 //    TLAS-leaf branch passes over the source instance;
-//  * LIST (kernels_list.inc): every candidate into the row the offsets give, a short row by insertion, a long one in walk order.
+//  * LIST (kernels_list.inc): every candidate into the row the offsets give, a short row by insertion, a long one in walk order;
+//  * PAIRS (kernels_pairs.inc): a lane's item is one source triangle of an instance-pair record, held in the lane (Shape::Item); count
+//    only, the count added to the record's 64-bit sum and the source primitive offered as its first; with `any` the record's word is the
+//    flag that ends every item of the record.
 #ifndef RT_OVERLAP_WAVES_PER_EU
 #define RT_OVERLAP_WAVES_PER_EU 4   /* the record-level walks' budget */
 #endif
@@ -49,7 +52,13 @@ struct OverlapArgs {
   unsigned long long capacity; // records of ids: a row that ends beyond it is not written
   uint32_t* worklist;          // the rows left in walk order (longer than RT_LIST_INSERT_MAX), for k_list_sort
   uint32_t* work_count;        // their number (zero before the launch)
+  // the PAIRS instantiations only (offsets: the n + 1 starts of the records' work items)
+  const int4* irefs;           // n instance-pair records (rt_inst_ref)
+  unsigned long long* sums;    // n sums of counts; any: n words 0 or 1, the flag of the record
+  uint32_t* first_p;           // n words: the smallest source primitive with a candidate (0xFFFFFFFF: none), or null
+  uint32_t n_vert_floats;      // the floats of sc.verts
 };
+struct NoItem {};
 
 constexpr float OB_ABS = 1.220703125e-04f;          // 2^-13: absolute slack per unit of magnitude
 
@@ -93,13 +102,13 @@ __device__ __forceinline__ void overlap_enter_instance(const InstanceDev* I, flo
   }
 }
 
-template <class Shape, bool COUNT, bool REFS = false, bool LIST = false>
+template <class Shape, bool COUNT, bool REFS = false, bool LIST = false, bool PAIRS = false>
 __device__ __forceinline__ void overlap_body(const OverlapArgs& a) {
   __shared__ int s_stack[4][STACK2_LDS][64];
   WalkStack st(s_stack, a.ovf_stack, a.sc.ovf_stride);
   WalkFeed feed;
-  const uint32_t K = a.k;
-  const bool prune = !LIST && a.counts == nullptr;
+  const uint32_t K = PAIRS ? 0u : a.k;
+  const bool prune = !LIST && !PAIRS && a.counts == nullptr;
   uint32_t len = 0;                           // LIST: the row's length, from the offsets (0: a row that is not written)
 
   bool need = true;
@@ -112,6 +121,9 @@ __device__ __forceinline__ void overlap_body(const OverlapArgs& a) {
   int cur = REF_DONE, cur_inst = -1;
   IdRec* row = nullptr;
   unsigned long long cnt_nodes = 0, cnt_tris = 0;
+  uint32_t n_items = a.n;                     // PAIRS: the work items of all records, from the device
+  if constexpr (PAIRS) n_items = (uint32_t)a.offsets[a.n];
+  typename Shape::Item item;                  // PAIRS: the source triangle and its record
 
   auto world_space = [&]() {
     qlo = mk3(wlo.x - w_slack, wlo.y - w_slack, wlo.z - w_slack); qhi = mk3(whi.x + w_slack, whi.y + w_slack, whi.z + w_slack);
@@ -120,12 +132,14 @@ __device__ __forceinline__ void overlap_body(const OverlapArgs& a) {
 
   for (;;) {
     // ---- refill: idle lanes take the next records of the wave's chunk
-    const uint32_t rec = feed.take(__ballot(need), a.cursor, a.n);
+    const uint32_t rec = feed.take(__ballot(need), a.cursor, n_items);
     if (need && rec != WALK_NONE) {
       bx = rec;
       float mag;
       int against;
-      const bool valid = Shape::load(a, bx, wlo, whi, mag, against);
+      bool valid;
+      if constexpr (PAIRS) valid = Shape::load(a, bx, item, wlo, whi, mag, against) && !Shape::ended(a, item);
+      else valid = Shape::load(a, bx, wlo, whi, mag, against);
       w_slack = OB_ABS * fmaxf(tlas_magnitude(a.sc, mag), a.inst_scale[0]);
       world_space();
       cur_inst = -1; count = 0;
@@ -163,8 +177,9 @@ __device__ __forceinline__ void overlap_body(const OverlapArgs& a) {
       uint32_t first, nt;
       walk_leaf(cur, first, nt);
       const float* m = a.sc.inst[cur_inst].o2w;
-      const typename Shape::Leaf leaf(a, bx);
+      const typename Shape::Leaf leaf(a, bx, item);
       bool done = false;
+      if constexpr (PAIRS) if (Shape::ended(a, item)) { done = true; nt = 0u; }   // (another item of the record found a contact)
       for (uint32_t j = 0; j < nt; j++) {
         const float4* tp = a.sc.tris + (size_t)(first + j) * 3;
         const float4 T0 = tp[0], T1 = tp[1], T2 = tp[2];
@@ -222,7 +237,8 @@ __device__ __forceinline__ void overlap_body(const OverlapArgs& a) {
       const int ii = ~cur;
       const InstanceDev* I = a.sc.inst + ii;
       bool own = false;   // REFS: the source instance of a record against the others (the record read again)
-      if constexpr (REFS) own = Shape::own(a, bx, ii);
+      if constexpr (PAIRS) own = Shape::own(a, item, ii);
+      else if constexpr (REFS) own = Shape::own(a, bx, ii);
       if (((I->mask >> INST_WORLD_MASK_SHIFT) & a.cull_mask & 0xFFu) != 0u && !(prune && K != 0u && count >= K && ii > last_inst) && !own) {
         overlap_enter_instance(I, a.inst_scale[1 + ii], qlo, qhi, q_lo, q_scale);
         st.push(REF_MARK);
@@ -231,7 +247,9 @@ __device__ __forceinline__ void overlap_body(const OverlapArgs& a) {
     }
     if (!need && cur == REF_DONE) {
       // ---- finished: the rest of the row empty, the count
-      if (LIST) {   // (a long row goes to k_list_sort)
+      if constexpr (PAIRS) {
+        if (count != 0u) Shape::finish(a, item, count);
+      } else if (LIST) {   // (a long row goes to k_list_sort)
         if (len > (uint32_t)RT_LIST_INSERT_MAX) a.worklist[atomicAdd(a.work_count, 1u)] = bx;
       } else {
         IdRec none; none.inst = -1; none.prim = -1;

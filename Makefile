@@ -20,7 +20,7 @@ $(OBJDIR)/%.o: $(CSRC)/%.hip $(DEVHDRS)
 $(OBJDIR)/%.o: $(CSRC)/%.cpp $(DEVHDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-$(OBJDIR)/kernels.o: $(CSRC)/kernels_beam.inc $(CSRC)/walk_common.inc $(CSRC)/kernels_hits.inc $(CSRC)/walk_nearest.inc $(CSRC)/kernels_closest.inc $(CSRC)/kernels_closest_hits.inc $(CSRC)/walk_overlap.inc $(CSRC)/kernels_overlap.inc $(CSRC)/kernels_triangles.inc $(CSRC)/kernels_sweep.inc $(CSRC)/kernels_inside.inc $(CSRC)/kernels_segment.inc $(CSRC)/kernels_triangle.inc $(CSRC)/kernels_refs.inc $(CSRC)/kernels_list.inc $(CSRC)/kernels_pairs.inc
+$(OBJDIR)/kernels.o: $(CSRC)/kernels_beam.inc $(CSRC)/walk_common.inc $(CSRC)/kernels_hits.inc $(CSRC)/walk_nearest.inc $(CSRC)/kernels_closest.inc $(CSRC)/kernels_closest_hits.inc $(CSRC)/walk_overlap.inc $(CSRC)/kernels_overlap.inc $(CSRC)/kernels_triangles.inc $(CSRC)/kernels_sweep.inc $(CSRC)/kernels_inside.inc $(CSRC)/kernels_segment.inc $(CSRC)/kernels_triangle.inc $(CSRC)/kernels_refs.inc $(CSRC)/kernels_list.inc $(CSRC)/kernels_pairs.inc $(CSRC)/kernels_ipairs.inc
 PRODUCT_OBJS := $(OBJDIR)/kernels.o $(OBJDIR)/bvh_gpu.o $(OBJDIR)/tlas_gpu.o $(OBJDIR)/blas_refit.o $(OBJDIR)/rt_api.o $(OBJDIR)/bvh_build.o
 $(PKG)/librt_mi355x.so: $(PRODUCT_OBJS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(PRODUCT_OBJS)
@@ -28,7 +28,7 @@ $(PKG)/librt_mi355x.so: $(PRODUCT_OBJS)
 # the alternatives that measured slower (k_packet, the quad/BVH4 kernel, 4-ary records: csrc/kernels_alt.inc; tile blobs: csrc/kernels_tile.inc;
 # shadow beams: k_beam_shadow in csrc/kernels_beam.inc) are NOT in the product library; `make alt` builds librt_mi355x_alt.so with them
 # (-DRT_ALT_KERNELS) for the identity tests (RtContext(variant="alt") / RT_LIB_VARIANT=alt)
-$(OBJDIR)/kernels_alt.o: $(CSRC)/kernels.hip $(CSRC)/kernels_alt.inc $(CSRC)/kernels_tile.inc $(CSRC)/kernels_beam.inc $(CSRC)/walk_common.inc $(CSRC)/kernels_hits.inc $(CSRC)/walk_nearest.inc $(CSRC)/kernels_closest.inc $(CSRC)/kernels_closest_hits.inc $(CSRC)/walk_overlap.inc $(CSRC)/kernels_overlap.inc $(CSRC)/kernels_triangles.inc $(CSRC)/kernels_sweep.inc $(CSRC)/kernels_inside.inc $(CSRC)/kernels_segment.inc $(CSRC)/kernels_triangle.inc $(CSRC)/kernels_refs.inc $(CSRC)/kernels_list.inc $(CSRC)/kernels_pairs.inc $(DEVHDRS)
+$(OBJDIR)/kernels_alt.o: $(CSRC)/kernels.hip $(CSRC)/kernels_alt.inc $(CSRC)/kernels_tile.inc $(CSRC)/kernels_beam.inc $(CSRC)/walk_common.inc $(CSRC)/kernels_hits.inc $(CSRC)/walk_nearest.inc $(CSRC)/kernels_closest.inc $(CSRC)/kernels_closest_hits.inc $(CSRC)/walk_overlap.inc $(CSRC)/kernels_overlap.inc $(CSRC)/kernels_triangles.inc $(CSRC)/kernels_sweep.inc $(CSRC)/kernels_inside.inc $(CSRC)/kernels_segment.inc $(CSRC)/kernels_triangle.inc $(CSRC)/kernels_refs.inc $(CSRC)/kernels_list.inc $(CSRC)/kernels_pairs.inc $(CSRC)/kernels_ipairs.inc $(DEVHDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -DRT_ALT_KERNELS -c -o $@ $(CSRC)/kernels.hip
 $(PKG)/librt_mi355x_alt.so: $(OBJDIR)/kernels_alt.o $(OBJDIR)/bvh_gpu.o $(OBJDIR)/tlas_gpu.o $(OBJDIR)/blas_refit.o $(OBJDIR)/rt_api.o $(OBJDIR)/bvh_build.o

@@ -895,6 +895,47 @@ int rt_closest_instances(rt_ctx* ctx, size_t n, const rt_inst_ref* irefs_host, u
 int rt_overlap_instances(rt_ctx* ctx, size_t n, const rt_inst_ref* irefs_host, uint32_t cull_mask, uint32_t flags,
                          uint64_t* counts_host, int32_t* first4_host, int counting, rt_stats* stats);
 
+/* Instance broad phase: which bodies can be within a margin of which (the sweep-and-prune or grid in front of FCL's collide, PhysX's
+ * broad phase), asked of the TLAS the context already holds and answered in the record format the two calls above read: one buffer
+ * feeds the next call.  The caller computes no world box of a mesh the library holds.
+ * Records: n rt_inst_ref as they are.  r_max is the margin m: the search radius a later rt_closest_instances_device will use, 0 for
+ * contact, +inf allowed.  reserved is ignored.  A source record is valid when inst is in [0, n_instances), against is in
+ * [-1, n_instances), r_max >= 0 and not NaN, the source instance is not void (rt_set_instances) and its mesh has an active triangle.
+ * An invalid record has an empty row and is no error.  The source's own mask plays no part; a non-invertible record with a finite
+ * transform is valid, as in the world-space queries.
+ * The canonical box of instance i depends on its record and its mesh only, never on a tree or on another instance.  [lo, hi] are the
+ * exact binary32 bounds of the vertices of the mesh's active triangles and M is the record's transform.  The eight corners of [lo, hi]
+ * are mapped in binary64, M_r0 p0 + M_r1 p1 + M_r2 p2 + M_r3 in that order, each coordinate rounded once to binary32; blo and bhi are
+ * their bounds.  With bm_k = max(|lo_k|, |hi_k|) and mw = max_r (|M_r0| bm_0 + |M_r1| bm_1 + |M_r2| bm_2 + |M_r3|) in binary32, unfused,
+ * left to right, Box(i) = [blo - e, bhi + e], e = 2^-13 mw, every bound rounded once.  An instance one of whose three row sums is not
+ * finite has no box: it is in no row and its own rows are empty.
+ * Candidates of record (i, against, m): instance j when it has a box, (its mask & cull_mask) != 0 (a void record and an instance of
+ * an empty mesh have mask 0), j != i when against == -1, j == against when against >= 0 (against == inst is not special), j > i with
+ * RT_INSTANCE_PAIRS_ABOVE in flags, and on every axis k both !(Box(i).lo_k - m > Box(j).hi_k) and !(Box(i).hi_k + m < Box(j).lo_k),
+ * the two inflated values rounded once in binary32.  The test is closed: touching boxes count.
+ * Output, in CSR form with the rules of rt_overlap_*_device_list: d_offsets is n + 1 uint64, 8-byte aligned, always complete; d_pairs4 is
+ * capacity records of 16 B, 16-byte aligned.  Row i holds (inst of record i, j, r_max of record i with its bit pattern kept, 0) for
+ * every candidate j in ascending j, and is written if and only if offsets[i + 1] <= capacity.  No byte of a row that is not written, or
+ * at or beyond min(T, capacity) records, is touched.  capacity == 0 wants d_pairs4 == NULL and gives the offsets only.  The rows are
+ * valid input of rt_closest_instances_device and rt_overlap_instances_device as they are.
+ * GUARANTEE: under the same cull_mask, every j for which rt_overlap_instances_device counts a pair for (i, j), or for which
+ * rt_closest_instances_device returns a hit for (i, j, m), is in the row of (i, -1, m) (DESIGN.md §5 "Instance broad phase": the slack e
+ * covers the rounding of every world vertex the narrow phase makes).  With RT_INSTANCE_PAIRS_ABOVE and every instance asking, every
+ * unordered pair is listed once.
+ * Stream ordering without host synchronisation, the TLAS and scene of the call, "queries of one context one after another", the
+ * workspace (the list calls' and 32 bytes per instance) and RT_ERR_OUT_OF_MEMORY, RT_ERR_NOT_READY and n == 0 (nothing is enqueued,
+ * d_offsets is not written) are as for the list calls.  RT_ERR_INVALID_ARGUMENT: a NULL or misaligned pointer, memory that is not of
+ * ctx's GPU, n or capacity >= 0xFFFFFF00, d_pairs4 == NULL with capacity != 0 or the reverse, unknown flag bits, cull_mask > 0xFF,
+ * trace_variant != 0. */
+#define RT_INSTANCE_PAIRS_ABOVE 0x1u   /* list only candidates j > inst: every unordered pair once when every instance asks */
+int rt_instance_pairs_device(rt_ctx* ctx, size_t n, const void* d_irefs4, uint32_t cull_mask, uint32_t flags,
+                             void* d_offsets, void* d_pairs4, size_t capacity, void* hip_stream);
+/* The blocking host form, as rt_overlap_boxes_list is to its device call: the entries of pairs_host that the call does not write keep
+ * their values.  counting != 0 returns stats->node_visits (TLAS node visits) and stats->tri_tests (exact box-pair tests) of all walks;
+ * stats->ms_trace_closest is the device time of the whole sequence. */
+int rt_instance_pairs(rt_ctx* ctx, size_t n, const rt_inst_ref* irefs_host, uint32_t cull_mask, uint32_t flags,
+                      uint64_t* offsets_host, rt_inst_ref* pairs_host, size_t capacity, int counting, rt_stats* stats);
+
 /* Inside / outside: for every point, is it enclosed by the scene's surfaces (Open3D's compute_occupancy and compute_signed_distance),
  * for signed distance fields, penetration tests, occupancy and voxel filling.  The answer is a vote over the crossing parities of a few
  * rays from the point along a fixed table of generic directions; one ray is not enough, because the canonical triangle test is not

@@ -280,6 +280,23 @@ class Renderer {
   void overlapSceneTrianglesDeviceList(size_t n, const void* dRefs4, uint32_t cullMask, void* dOffsets, void* dIds, size_t capacity, void* stream) {
     check(rt_overlap_scene_triangles_device_list(ctx_, n, dRefs4, cullMask, 0, dOffsets, dIds, capacity, stream), "rt_overlap_scene_triangles_device_list");
   }
+  // rt_instance_pairs: the broad phase over the scene's instances.  offsets (n + 1) is always complete; pairs receives the rows
+  // (inst, j, r_max, 0) that end within `capacity` records (0: the offsets only): the input of rt_closest_instances /
+  // rt_overlap_instances as they are.  Returns true when every row was written; otherwise call again with a capacity of offsets.back().
+  bool instancePairs(const std::vector<rt_inst_ref>& irefs, std::vector<uint64_t>& offsets, std::vector<rt_inst_ref>& pairs, size_t capacity,
+                     uint32_t cullMask = 0xFF, bool above = false, rt_stats* stats = nullptr) {
+    offsets.assign(irefs.size() + 1, 0);
+    pairs.resize(capacity);
+    rt_stats st{};
+    check(rt_instance_pairs(ctx_, irefs.size(), irefs.data(), cullMask, above ? RT_INSTANCE_PAIRS_ABOVE : 0u, offsets.data(), capacity ? pairs.data() : nullptr,
+                            capacity, 0, &st),
+          "rt_instance_pairs");
+    if (stats) *stats = st;
+    return offsets.back() <= capacity;
+  }
+  void instancePairsDevice(size_t n, const void* dIrefs4, uint32_t cullMask, bool above, void* dOffsets, void* dPairs4, size_t capacity, void* stream) {
+    check(rt_instance_pairs_device(ctx_, n, dIrefs4, cullMask, above ? RT_INSTANCE_PAIRS_ABOVE : 0u, dOffsets, dPairs4, capacity, stream), "rt_instance_pairs_device");
+  }
 
  private:
   void check(int r, const char* fn) { if (r) throwExceptionRtAPI(r, fn, ctx_); }

@@ -76,12 +76,13 @@ REF_AGAINST_OTHERS = -1
 INST_REF_DTYPE = np.dtype([("inst", np.int32), ("against", np.int32), ("r_max", np.float32), ("reserved", np.uint32)])
 assert INST_REF_DTYPE.itemsize == 16
 OVERLAP_ANY = 0x1   # rt_overlap_boxes_device: occupancy (counts of 0 or 1)
+INSTANCE_PAIRS_ABOVE = 0x1   # rt_instance_pairs_device: only candidates above the source instance
 # rt_point_inside_device: the direction table (RT_INSIDE_DIRS of include/rt_api.h; rounded to binary32, not normalised)
 INSIDE_DIRS = ((0.36, 0.48, 0.8), (-0.8, 0.36, -0.48), (0.48, -0.8, -0.36), (-0.6, -0.64, 0.48), (0.64, -0.48, 0.6))
 
 EXPORTS = ["rt_create", "rt_create_frame_slot", "rt_destroy", "rt_upload_geometry", "rt_build_blas", "rt_set_instances", "rt_set_instances_device", "rt_refit_blas_device", "rt_set_materials", "rt_set_instance_types", "rt_set_uniforms", "rt_set_skybox",
            "rt_trace", "rt_trace_async", "rt_trace_wait", "rt_trace_shard", "rt_set_batch", "rt_trace_shard_batch", "rt_assemble_shards", "rt_shard_rows", "rt_synchronize", "rt_get_stats", "rt_set_timing", "rt_intersect",
-           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_closest_point_device_hits", "rt_closest_point_hits", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_overlap_triangles_device", "rt_overlap_triangles", "rt_sweep_spheres_device", "rt_sweep_spheres", "rt_closest_segment_device", "rt_closest_segment", "rt_closest_triangle_device", "rt_closest_triangle", "rt_scene_triangles_device", "rt_overlap_scene_triangles_device", "rt_overlap_scene_triangles", "rt_overlap_boxes_device_list", "rt_overlap_boxes_list", "rt_overlap_triangles_device_list", "rt_overlap_triangles_list", "rt_overlap_scene_triangles_device_list", "rt_overlap_scene_triangles_list", "rt_closest_scene_triangle_device", "rt_closest_scene_triangle", "rt_closest_instances_device", "rt_closest_instances", "rt_overlap_instances_device", "rt_overlap_instances", "rt_point_inside_device", "rt_point_inside", "rt_signed_distance_device", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_host_blas", "rt_debug_snapshot", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
+           "rt_trace_counting", "rt_intersect_device", "rt_intersect_device_flags", "rt_intersect_device_hits", "rt_closest_point_device", "rt_closest_point", "rt_closest_point_device_hits", "rt_closest_point_hits", "rt_overlap_boxes_device", "rt_overlap_boxes", "rt_overlap_triangles_device", "rt_overlap_triangles", "rt_sweep_spheres_device", "rt_sweep_spheres", "rt_closest_segment_device", "rt_closest_segment", "rt_closest_triangle_device", "rt_closest_triangle", "rt_scene_triangles_device", "rt_overlap_scene_triangles_device", "rt_overlap_scene_triangles", "rt_overlap_boxes_device_list", "rt_overlap_boxes_list", "rt_overlap_triangles_device_list", "rt_overlap_triangles_list", "rt_overlap_scene_triangles_device_list", "rt_overlap_scene_triangles_list", "rt_closest_scene_triangle_device", "rt_closest_scene_triangle", "rt_closest_instances_device", "rt_closest_instances", "rt_overlap_instances_device", "rt_overlap_instances", "rt_instance_pairs_device", "rt_instance_pairs", "rt_point_inside_device", "rt_point_inside", "rt_signed_distance_device", "rt_shade_rays_device", "rt_set_param", "rt_debug_check_builders", "rt_debug_host_blas", "rt_debug_snapshot", "rt_debug_sizing", "rt_last_error", "rt_device_info", "rt_abi_version"]
 
 _LIBS = {}
 
@@ -155,6 +156,8 @@ def lib(variant=None):
         L.rt_closest_instances.argtypes = [vp, C.c_size_t, vp, C.c_uint32, vp, vp, vp, C.c_int, C.POINTER(RtStats)]
         L.rt_overlap_instances_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
         L.rt_overlap_instances.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_int, C.POINTER(RtStats)]
+        L.rt_instance_pairs_device.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_size_t, vp]
+        L.rt_instance_pairs.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_size_t, C.c_int, C.POINTER(RtStats)]
         L.rt_shade_rays_device.argtypes = [vp, C.c_size_t, C.c_uint32, vp, vp, vp, vp]
         L.rt_last_error.argtypes = [vp]
         L.rt_last_error.restype = C.c_char_p
@@ -791,11 +794,12 @@ class RtContext:
         for overlap_scene_triangles_device)."""
         return self._overlap_list_device(refs, "overlap_scene_triangles", 4, "reference", capacity, cull_mask, stream, out, int32=True)
 
-    def _overlap_list_device(self, records, name, cols, noun, capacity, cull_mask, stream, out, int32=False):
-        """the three *_device_list calls: the checks, the buffers and rt_<name>_device_list on `stream`"""
+    def _overlap_list_device(self, records, name, cols, noun, capacity, cull_mask, stream, out, int32=False, width=2, flags=0, suffix="_device_list"):
+        """the three *_device_list calls and instance_pairs_device (rows of `width` int32, `flags`): the checks, the buffers and
+        rt_<name><suffix> on `stream`"""
         import torch
-        self._check_rays(records, name + "_device_list", cols, noun, int32)
-        fn = getattr(self.L, "rt_%s_device_list" % name)
+        self._check_rays(records, name + suffix, cols, noun, int32)
+        fn = getattr(self.L, "rt_%s%s" % (name, suffix))
         n = records.shape[0]
         cur = torch.cuda.current_stream(records.device)
         if stream is None:
@@ -809,8 +813,8 @@ class RtContext:
             offsets, ids = out
             if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int64 or tuple(offsets.shape) != (n + 1,) or not offsets.is_contiguous() or offsets.device != records.device:
                 raise ValueError("out offsets must be a contiguous int64 (n + 1,) tensor on the records' device")
-            if ids is not None and (not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.dim() != 2 or ids.shape[1] != 2 or not ids.is_contiguous() or ids.device != records.device):
-                raise ValueError("out ids must be a contiguous int32 (capacity, 2) tensor on the records' device, or None")
+            if ids is not None and (not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.dim() != 2 or ids.shape[1] != width or not ids.is_contiguous() or ids.device != records.device):
+                raise ValueError("out rows must be a contiguous int32 (capacity, %d) tensor on the records' device, or None" % width)
             if capacity is None:
                 capacity = ids.shape[0] if ids is not None else 0
             elif int(capacity) != (ids.shape[0] if ids is not None else 0):
@@ -821,10 +825,10 @@ class RtContext:
 
         def run_call(ids_t, cap):
             def call(run):
-                return fn(self.h, n, C.c_void_p(records.data_ptr()), int(cull_mask) & 0xFFFFFFFF, 0, C.c_void_p(offsets.data_ptr()),
+                return fn(self.h, n, C.c_void_p(records.data_ptr()), int(cull_mask) & 0xFFFFFFFF, flags, C.c_void_p(offsets.data_ptr()),
                           C.c_void_p(ids_t.data_ptr()) if ids_t is not None else None, cap, C.c_void_p(run.cuda_stream))
             if n:
-                self._on_stream(stream, (records, offsets, ids_t), call, "rt_%s_device_list" % name)
+                self._on_stream(stream, (records, offsets, ids_t), call, "rt_%s%s" % (name, suffix))
         if capacity is None:   # the offsets first, the total read on the host, then the exact allocation
             run_call(None, 0)
             if n:
@@ -834,7 +838,7 @@ class RtContext:
         if capacity < 0:
             raise ValueError("capacity must not be negative")
         if capacity and ids is None:
-            ids = torch.empty((capacity, 2), dtype=torch.int32, device=records.device)
+            ids = torch.empty((capacity, width), dtype=torch.int32, device=records.device)
             if stream != cur:
                 ids.record_stream(stream)
         run_call(ids if capacity else None, capacity)
@@ -1013,6 +1017,40 @@ class RtContext:
         self._chk(self.L.rt_overlap_instances(self.h, n, _p(irefs), int(cull_mask) & 0xFFFFFFFF, OVERLAP_ANY if any else 0, _p(cnt),
                                               _p(first4) if first4 is not None else None, int(counting), C.byref(st)), "rt_overlap_instances")
         return cnt, first4, st
+
+    def instance_pairs_device(self, irefs, capacity=None, cull_mask=0xFF, above=False, stream=None, out=None):
+        """rt_instance_pairs_device: the broad phase over the scene's instances.  `irefs` as for closest_instances_device, r_max the
+        margin: row i lists every instance whose canonical box comes within r_max of the box of instance `inst` (against = -1: of
+        the others; against >= 0: that one or nothing; above=True: only instances above inst, every unordered pair once).  Returns
+        an InstancePairs that unpacks as (offsets, pairs, total): offsets int64 (n + 1,), always complete; pairs int32
+        (capacity, 4), row i the records (inst, j, the bits of r_max, 0) in ascending j at pairs[offsets[i]:offsets[i + 1]], written
+        if and only if offsets[i + 1] <= capacity (capacity 0: None); total a 0-d view of offsets[n] (reading it is the caller's
+        synchronisation).  pairs[:total] is the `irefs` of closest_instances_device and overlap_instances_device as it is.
+        capacity=None and out=(offsets, pairs) behave as for overlap_boxes_device_list: a loop keeps one pair buffer and passes it
+        through out.  See include/rt_api.h."""
+        res = self._overlap_list_device(irefs, "instance_pairs", 4, "record", capacity, cull_mask, stream, out, int32=True, width=4,
+                                        flags=INSTANCE_PAIRS_ABOVE if above else 0, suffix="_device")
+        return InstancePairs(res.offsets, res.ids)
+
+    def instance_pairs(self, irefs, capacity=None, cull_mask=0xFF, above=False, counting=False):
+        """rt_instance_pairs: the blocking host form (irefs as for closest_instances) -> (offsets uint64 (n + 1,), pairs int32
+        (capacity, 4) or None, RtStats; with counting its node_visits are TLAS node visits and its tri_tests exact box tests, of
+        both walks).  capacity=None: an offsets-only call first, then one with exactly the total.  Rows that do not fit stay zero."""
+        irefs = _host_irefs(irefs)
+        n = len(irefs)
+        offsets = np.zeros(n + 1, np.uint64)
+        st = RtStats()
+
+        def call(pairs, cap):
+            self._chk(self.L.rt_instance_pairs(self.h, n, _p(irefs), int(cull_mask) & 0xFFFFFFFF, INSTANCE_PAIRS_ABOVE if above else 0, _p(offsets),
+                                               _p(pairs) if pairs is not None else None, cap, int(counting), C.byref(st)), "rt_instance_pairs")
+        if capacity is None:
+            call(None, 0)
+            capacity = int(offsets[n])
+        capacity = int(capacity)
+        pairs = np.zeros((capacity, 4), np.int32) if capacity else None
+        call(pairs, capacity)
+        return offsets, pairs, st
 
     def intersect_device_hits(self, rays, max_hits, ray_flags=0, cull_mask=0xFF, words=None, attributes=False, counts=True, stream=None, out=None):
         """rt_intersect_device_hits: every candidate along each ray, the first max_hits of them in (t, inst, prim) order, and their number.
@@ -1316,6 +1354,22 @@ class OverlapList:
     def numpy(self):
         """(offsets as (n + 1,) uint64, ids as (capacity, 2) int32 or None); synchronises"""
         return self.offsets.cpu().numpy().view(np.uint64), self.ids.cpu().numpy() if self.ids is not None else None
+
+
+class InstancePairs:
+    """Results of RtContext.instance_pairs_device: offsets, int64 (n + 1,); pairs, int32 (capacity, 4) rows of (inst, against, the bits
+    of r_max, 0) or None; total, a 0-d view of offsets[n] (reading it synchronises).  Unpacks as (offsets, pairs, total)."""
+
+    def __init__(self, offsets, pairs):
+        self.offsets, self.pairs = offsets, pairs
+        self.total = offsets[-1]
+
+    def __iter__(self):
+        return iter((self.offsets, self.pairs, self.total))
+
+    def numpy(self):
+        """(offsets as (n + 1,) uint64, pairs as (capacity, 4) int32 or None); synchronises"""
+        return self.offsets.cpu().numpy().view(np.uint64), self.pairs.cpu().numpy() if self.pairs is not None else None
 
 
 def triangle_records(vertices, faces, r_max=0.0):

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rt_kernels.h"
+#include "tlas_gpu.h"                 // TlasMeshDev (kernels_ipairs.inc)
 #include "../../include/rt_api.h"   // RT_INSIDE_DIRS (kernels_inside.inc)
 
 namespace rt {
@@ -2476,6 +2477,8 @@ void launch_resolve_points(const float4* sample_color, float4* out, uint32_t n_p
 #include "kernels_list.inc"   // k_list_boxes, k_list_triangles, k_list_refs, k_list_sort, k_list_scan_*: whole overlap rows in CSR form (rt_overlap_*_device_list)
 
 #include "kernels_pairs.inc"   // k_pairs_plan, k_pairs_nearest, k_pairs_collide, k_pairs_refs, k_pairs_first: the two by-reference queries per pair of bodies (rt_*_instances_device)
+
+#include "kernels_ipairs.inc"   // k_ipairs_boxes, k_ipairs_size, k_ipairs_fill, k_ipairs_sort: the broad phase over the scene's instances (rt_instance_pairs_device)
 
 int tail_blocks_per_cu() {
   // the smallest over the instantiations: any of them may be the one in flight (counting; 4-ary records in the alt build)

@@ -14,7 +14,8 @@
 // length is sorted without padding: a comparator with a partner beyond the row is passed over.  A row of at most RT_LIST_LDS_TILE
 // entries is sorted in LDS; a longer one tile by tile in LDS, the steps whose distance reaches across tiles on the row in global memory
 // (the workgroup's own writes, read back behind a barrier).  Keys are unique within a row, so the sorted row is unique whatever order
-// the walk wrote.
+// the walk wrote.  The network is list_sort_body, a template over what a row's records and keys are: k_list_sort instantiates it for
+// (inst, prim) rows, k_ipairs_sort (kernels_ipairs.inc) for the `against` words of rt_inst_ref rows.
 
 // ---- scan
 constexpr uint32_t LIST_SCAN_ITEMS = 8u, LIST_SCAN_TILE = 256u * LIST_SCAN_ITEMS;   // counts per thread and per workgroup
@@ -98,15 +99,24 @@ constexpr uint32_t LIST_TILE = RT_LIST_LDS_TILE;
 static_assert(LIST_TILE >= 512u && (LIST_TILE & (LIST_TILE - 1u)) == 0u, "RT_LIST_LDS_TILE: a power of two, two entries per thread at the least");
 static_assert(RT_LIST_INSERT_MAX >= 1 && (uint32_t)RT_LIST_INSERT_MAX < LIST_TILE, "RT_LIST_INSERT_MAX: below the tile");
 
-// (inst, prim), both non-negative, as one key in (inst, prim) order
-__device__ __forceinline__ unsigned long long list_key(const IdRec* ids, size_t i) {
-  const int32_t* w = reinterpret_cast<const int32_t*>(ids + i);   // (rows are 4-byte aligned)
-  return ((unsigned long long)(uint32_t)w[0] << 32) | (unsigned long long)(uint32_t)w[1];
-}
-__device__ __forceinline__ void list_put(IdRec* ids, size_t i, unsigned long long key) {
-  int32_t* w = reinterpret_cast<int32_t*>(ids + i);
-  w[0] = (int32_t)(uint32_t)(key >> 32); w[1] = (int32_t)(uint32_t)key;
-}
+// What k_list_sort permutes is a shape of its own (a sibling kernel sorts other rows with the same network: kernels_ipairs.inc):
+//    Rec                       the records of a row
+//    Key                       what orders them, unique within a row
+//    static Key key(rows, i)   the key of record i
+//    static void put(rows, i, key)   record i takes the key (and nothing else of it changes)
+// The rows of the overlap lists: (inst, prim), both non-negative, as one key in (inst, prim) order
+struct ListIds {
+  typedef IdRec Rec;
+  typedef unsigned long long Key;
+  __device__ __forceinline__ static Key key(const IdRec* ids, size_t i) {
+    const int32_t* w = reinterpret_cast<const int32_t*>(ids + i);   // (rows are 4-byte aligned)
+    return ((unsigned long long)(uint32_t)w[0] << 32) | (unsigned long long)(uint32_t)w[1];
+  }
+  __device__ __forceinline__ static void put(IdRec* ids, size_t i, Key key) {
+    int32_t* w = reinterpret_cast<int32_t*>(ids + i);
+    w[0] = (int32_t)(uint32_t)(key >> 32); w[1] = (int32_t)(uint32_t)key;
+  }
+};
 // pair p of a step: the lower index of the p-th pair whose members differ in the bit h (a power of two)
 __device__ __forceinline__ uint32_t list_pair(uint32_t p, uint32_t h) { return ((p & ~(h - 1u)) << 1) | (p & (h - 1u)); }
 // the smallest power of two that is no less than m (m >= 2)
@@ -114,34 +124,78 @@ __device__ __forceinline__ uint32_t list_pow2(uint32_t m) { return 1u << (32 - _
 
 // One step over the m keys of s (LDS): pairs (i, i ^ (k - 1)) of blocks of k when flip, (i, i | h) otherwise; then the barrier.
 // pairs: half the power of two that holds m; a pair beyond it has no member below m.
-__device__ __forceinline__ void list_lds_step(unsigned long long* s, uint32_t m, uint32_t pairs, uint32_t h, bool flip) {
+template <class R>
+__device__ __forceinline__ void list_lds_step(typename R::Key* s, uint32_t m, uint32_t pairs, uint32_t h, bool flip) {
   for (uint32_t p = threadIdx.x; p < pairs; p += 256u) {
     const uint32_t i = list_pair(p, h), q = flip ? (i ^ (2u * h - 1u)) : (i | h);
     if (q < m) {
-      const unsigned long long x = s[i], y = s[q];
+      const typename R::Key x = s[i], y = s[q];
       if (x > y) { s[i] = y; s[q] = x; }
     }
   }
   __syncthreads();
 }
 // the same step over the len keys of a row in global memory (distances of a tile and more)
-__device__ __forceinline__ void list_global_step(IdRec* row, uint32_t len, uint32_t pairs, uint32_t h, bool flip) {
+template <class R>
+__device__ __forceinline__ void list_global_step(typename R::Rec* row, uint32_t len, uint32_t pairs, uint32_t h, bool flip) {
   for (uint32_t p = threadIdx.x; p < pairs; p += 256u) {
     const uint32_t i = list_pair(p, h), q = flip ? (i ^ (2u * h - 1u)) : (i | h);
     if (q < len) {
-      const unsigned long long x = list_key(row, i), y = list_key(row, q);
-      if (x > y) { list_put(row, i, y); list_put(row, q, x); }
+      const typename R::Key x = R::key(row, i), y = R::key(row, q);
+      if (x > y) { R::put(row, i, y); R::put(row, q, x); }
     }
   }
   __syncthreads();
 }
-__device__ __forceinline__ void list_tile_load(unsigned long long* s, const IdRec* row, uint32_t m) {
-  for (uint32_t i = threadIdx.x; i < m; i += 256u) s[i] = list_key(row, i);
+template <class R>
+__device__ __forceinline__ void list_tile_load(typename R::Key* s, const typename R::Rec* row, uint32_t m) {
+  for (uint32_t i = threadIdx.x; i < m; i += 256u) s[i] = R::key(row, i);
   __syncthreads();
 }
-__device__ __forceinline__ void list_tile_store(const unsigned long long* s, IdRec* row, uint32_t m) {
-  for (uint32_t i = threadIdx.x; i < m; i += 256u) list_put(row, i, s[i]);
+template <class R>
+__device__ __forceinline__ void list_tile_store(const typename R::Key* s, typename R::Rec* row, uint32_t m) {
+  for (uint32_t i = threadIdx.x; i < m; i += 256u) R::put(row, i, s[i]);
   __syncthreads();   // (the next load of this LDS, the next reader of the row)
+}
+
+// the sort of every listed row, one workgroup per row; s_keys: LIST_TILE keys of LDS
+template <class R>
+__device__ __forceinline__ void list_sort_body(typename R::Rec* rows, const unsigned long long* offsets, const uint32_t* worklist, const uint32_t* work_count,
+                                               typename R::Key* s_keys) {
+  const uint32_t n_work = *work_count;
+  for (uint32_t w = blockIdx.x; w < n_work; w += gridDim.x) {
+    const uint32_t rec = worklist[w];
+    const unsigned long long o0 = offsets[rec];
+    const uint32_t len = (uint32_t)(offsets[rec + 1u] - o0);
+    if (len < 2u) continue;
+    typename R::Rec* row = rows + o0;
+    // every tile sorted by itself (a row that fits: the whole sort)
+    for (uint32_t b = 0; b < len; b += LIST_TILE) {
+      const uint32_t m = min(LIST_TILE, len - b);
+      list_tile_load<R>(s_keys, row + b, m);
+      if (m >= 2u) {
+        const uint32_t P = list_pow2(m);
+        for (uint32_t k = 2u; k <= P; k <<= 1) {
+          list_lds_step<R>(s_keys, m, P >> 1, k >> 1, true);
+          for (uint32_t h = k >> 2; h > 0u; h >>= 1) list_lds_step<R>(s_keys, m, P >> 1, h, false);
+        }
+      }
+      list_tile_store<R>(s_keys, row + b, m);
+    }
+    if (len <= LIST_TILE) continue;
+    // merges of two, four, ... tiles: the steps that reach across tiles on the row itself, the rest tile by tile in LDS
+    const uint32_t P = list_pow2(len);
+    for (uint32_t k = 2u * LIST_TILE; k <= P; k <<= 1) {
+      list_global_step<R>(row, len, P >> 1, k >> 1, true);
+      for (uint32_t h = k >> 2; h >= LIST_TILE; h >>= 1) list_global_step<R>(row, len, P >> 1, h, false);
+      for (uint32_t b = 0; b < len; b += LIST_TILE) {
+        const uint32_t m = min(LIST_TILE, len - b);
+        list_tile_load<R>(s_keys, row + b, m);
+        for (uint32_t h = LIST_TILE >> 1; h > 0u; h >>= 1) list_lds_step<R>(s_keys, m, LIST_TILE >> 1, h, false);
+        list_tile_store<R>(s_keys, row + b, m);
+      }
+    }
+  }
 }
 
 struct ListSortArgs {
@@ -153,40 +207,7 @@ struct ListSortArgs {
 
 __global__ __launch_bounds__(256) void k_list_sort(ListSortArgs a) {
   __shared__ unsigned long long s_keys[LIST_TILE];
-  const uint32_t n_work = *a.work_count;
-  for (uint32_t w = blockIdx.x; w < n_work; w += gridDim.x) {
-    const uint32_t rec = a.worklist[w];
-    const unsigned long long o0 = a.offsets[rec];
-    const uint32_t len = (uint32_t)(a.offsets[rec + 1u] - o0);
-    if (len < 2u) continue;
-    IdRec* row = a.ids + o0;
-    // every tile sorted by itself (a row that fits: the whole sort)
-    for (uint32_t b = 0; b < len; b += LIST_TILE) {
-      const uint32_t m = min(LIST_TILE, len - b);
-      list_tile_load(s_keys, row + b, m);
-      if (m >= 2u) {
-        const uint32_t P = list_pow2(m);
-        for (uint32_t k = 2u; k <= P; k <<= 1) {
-          list_lds_step(s_keys, m, P >> 1, k >> 1, true);
-          for (uint32_t h = k >> 2; h > 0u; h >>= 1) list_lds_step(s_keys, m, P >> 1, h, false);
-        }
-      }
-      list_tile_store(s_keys, row + b, m);
-    }
-    if (len <= LIST_TILE) continue;
-    // merges of two, four, ... tiles: the steps that reach across tiles on the row itself, the rest tile by tile in LDS
-    const uint32_t P = list_pow2(len);
-    for (uint32_t k = 2u * LIST_TILE; k <= P; k <<= 1) {
-      list_global_step(row, len, P >> 1, k >> 1, true);
-      for (uint32_t h = k >> 2; h >= LIST_TILE; h >>= 1) list_global_step(row, len, P >> 1, h, false);
-      for (uint32_t b = 0; b < len; b += LIST_TILE) {
-        const uint32_t m = min(LIST_TILE, len - b);
-        list_tile_load(s_keys, row + b, m);
-        for (uint32_t h = LIST_TILE >> 1; h > 0u; h >>= 1) list_lds_step(s_keys, m, LIST_TILE >> 1, h, false);
-        list_tile_store(s_keys, row + b, m);
-      }
-    }
-  }
+  list_sort_body<ListIds>(a.ids, a.offsets, a.worklist, a.work_count, s_keys);
 }
 
 // ---- launch.  work: 1 + n words (the number of listed rows, then the rows).

@@ -315,6 +315,9 @@ struct rt_ctx {
   char* d_q_pairs = nullptr;       // rt_*_instances*: the finish references, the work items' offsets, the keys (or the rows of one), the
                                    // scan's tile sums, the item counts and the first-p words (PairsWorkspace); part of the query workspace
   size_t q_pairs_alloc = 0;        // bytes of d_q_pairs
+  float4* d_q_ibox = nullptr;      // rt_instance_pairs*: the canonical box and the flags of every instance (k_ipairs_boxes: two float4 each); part
+                                   // of the query workspace
+  size_t q_ibox_alloc = 0;         // instances of d_q_ibox
   hipEvent_t ev_query[2] = {nullptr, nullptr};
   bool ev_query_valid[2] = {false, false};
   int query_last = -1;             // parity of the last query (-1: none since the last host wait)
@@ -1498,6 +1501,7 @@ void rt_destroy(rt_ctx* c) {
   if (c->d_q_tris) hipFree(c->d_q_tris);
   if (c->d_q_list) hipFree(c->d_q_list);
   if (c->d_q_pairs) hipFree(c->d_q_pairs);
+  if (c->d_q_ibox) hipFree(c->d_q_ibox);
   for (int k = 0; k < 2; k++) if (c->ev_query[k]) hipEventDestroy(c->ev_query[k]);
   tlas_gpu_free(c->tgpu);
   for (auto e : c->ev_pool) hipEventDestroy(e);
@@ -2377,8 +2381,10 @@ enum class Walk {
   Expand,    // rt_scene_triangles_device: k_refs_expand alone, the references' 48-byte records into tris_out
   Pairs,     // rt_closest_instances*: the records are n rt_inst_ref.  k_pairs_plan and the scan, the shared-bound walk into the workspace's
              // keys, k_pairs_refs, then the by-reference Triangle walk over those n references into hits (and params, attr)
-  PairsOverlap // rt_overlap_instances*: the same plan, the count-only walk into counts (uint64) and, with first4, k_pairs_refs, the capped
+  PairsOverlap, // rt_overlap_instances*: the same plan, the count-only walk into counts (uint64) and, with first4, k_pairs_refs, the capped
              // by-reference walk with rows of one, and k_pairs_first
+  InstancePairs // rt_instance_pairs*: the records are n rt_inst_ref.  k_closest_scale and k_ipairs_boxes, the count walk into the workspace
+             // (Query::list's area), the scan into offsets and, with capacity != 0, the fill walk and k_ipairs_sort into ids
 };
 struct Query {
   Walk walk = Walk::Plain;
@@ -2398,6 +2404,7 @@ struct Query {
                                      // with capacity != 0 the fill walk (its chunk cursor initialised again) and k_list_sort into ids
   void* offsets = nullptr;           // list: n + 1 uint64 row starts
   uint64_t capacity = 0;             // list: records of ids
+  bool pairs_above = false;          // InstancePairs: RT_INSTANCE_PAIRS_ABOVE
   uint32_t n_dirs = 0;               // Inside
   void* hits = nullptr;              // hit records (Hits, ClosestHits: n rows; Overlap: none; Inside: the signed distances, or none)
   void* ids = nullptr;               // Overlap: n rows of (inst, prim)
@@ -2490,6 +2497,16 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q
       c->d_q_pairs = grown; c->q_pairs_alloc = pw.bytes;
     }
   }
+  if (q.walk == Walk::InstancePairs) {   // as the list area
+    const size_t need = (size_t)std::max(scene_dev(c).n_inst, 1);
+    if (need > c->q_ibox_alloc) {
+      { int w = wait_queries(c, c); if (w) return w; }
+      float4* grown = nullptr;
+      HIP_TRY(c, hipMalloc((void**)&grown, need * 2 * sizeof(float4)));
+      if (c->d_q_ibox) (void)hipFree(c->d_q_ibox);
+      c->d_q_ibox = grown; c->q_ibox_alloc = need;
+    }
+  }
   char* const pa = c->d_q_pairs;
   uint32_t* list_counts = (uint32_t*)(c->d_q_list + lw.counts), *list_work = (uint32_t*)(c->d_q_list + lw.work);
   unsigned long long* list_sums = (unsigned long long*)(c->d_q_list + lw.sums);
@@ -2497,7 +2514,9 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q
   const SceneDev sc = scene_dev(c);
   if (q.t0) HIP_TRY(c, hipEventRecord(q.t0, s));
   if (q.refs) launch_refs_expand(sc, q.records, q.walk == Walk::Expand ? (float4*)q.tris_out : c->d_q_tris, n, c->scene->h_verts.size(), s);
-  if (closest || sweep || segment || triangle || q.walk == Walk::ClosestHits || q.walk == Walk::Overlap || q.walk == Walk::Triangles || pairs_overlap) launch_closest_scale(sc, c->d_q_scale, s);
+  if (closest || sweep || segment || triangle || q.walk == Walk::ClosestHits || q.walk == Walk::Overlap || q.walk == Walk::Triangles || pairs_overlap ||
+      q.walk == Walk::InstancePairs)
+    launch_closest_scale(sc, c->d_q_scale, s);
   // the two families of walk_nearest.inc and walk_overlap.inc: the shape of the records chooses the kernel, the launch is the family's
   const NearestShape nearest = segment ? NearestShape::Segment : !triangle ? NearestShape::Point : q.refs ? NearestShape::Refs : NearestShape::Triangle;
   const OverlapShape overlap = q.walk == Walk::Overlap ? OverlapShape::Boxes : q.refs ? OverlapShape::Refs : OverlapShape::Triangles;
@@ -2555,6 +2574,13 @@ int enqueue_query(rt_ctx* c, hipStream_t s, const LaunchCfg& cfg, const Query& q
       }
       break;
     }
+    case Walk::InstancePairs:   // the boxes, the count walk, the scan and, with room for rows, the fill walk
+      launch_ipairs_boxes(sc, c->scene->d_mesh_table, (uint32_t)c->scene->meshes.size(), c->d_q_ibox, s);
+      launch_ipairs_size(sc, q.records, c->d_q_ibox, c->d_q_scale, q.cull_mask, q.pairs_above, list_counts, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
+      launch_list_scan(list_counts, n, list_sums, (unsigned long long*)q.offsets, s);
+      if (q.capacity) launch_ipairs_fill(sc, q.records, c->d_q_ibox, c->d_q_scale, q.cull_mask, q.pairs_above, (const unsigned long long*)q.offsets, q.ids, q.capacity,
+                                         list_work, n, c->d_q_ovf, c->d_q_counters, q.counting, cfg, s);
+      break;
   }
   if (q.t1) HIP_TRY(c, hipEventRecord(q.t1, s));
   if (q.attr && q.walk != Walk::Hits && q.walk != Walk::ClosestHits) {
@@ -3218,6 +3244,55 @@ int rt_overlap_instances(rt_ctx* c, size_t n, const rt_inst_ref* irefs, uint32_t
   const size_t ref_bytes = n * sizeof(rt_inst_ref), count_bytes = n * sizeof(uint64_t), first_bytes = first4 ? n * 4 * sizeof(int32_t) : 0;
   return blocking_query(c, q, irefs, ref_bytes, ref_bytes + count_bytes + first_bytes,
                         {{&Query::counts, ref_bytes, counts, count_bytes}, {&Query::first4, ref_bytes + count_bytes, first4, first_bytes}}, stats);
+}
+
+namespace {
+// the argument rules rt_instance_pairs_device and rt_instance_pairs share (pointers' alignment and memory aside): those of the list calls
+// with a flag of their own
+int instance_pairs_arguments(rt_ctx* c, const std::string& name, size_t n, uint32_t cull_mask, uint32_t flags, const void* pairs, size_t capacity) {
+  if (n >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": too many records for one call");
+  if (capacity >= 0xFFFFFF00ull) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": capacity must be below 0xFFFFFF00 (32-bit record indices)");
+  if (cull_mask > 0xFFu) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": cull_mask is above 0xFF");
+  if ((flags & ~RT_INSTANCE_PAIRS_ABOVE) != 0u) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": unknown flag bits");
+  if (capacity == 0 && pairs) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": capacity 0 gives the offsets only: the pairs must be NULL");
+  if (capacity != 0 && !pairs) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null pair pointer with a capacity above 0");
+  if (c->cfg.variant != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, name + " needs trace_variant 0");
+  return RT_OK;
+}
+}  // namespace
+
+// The broad phase over the scene's instances: the checks and ordering of a list call (overlap_list_device), then (enqueue_query,
+// Walk::InstancePairs) k_closest_scale, k_ipairs_boxes, the count walk into the workspace, the scan into the caller's offsets and, with
+// a capacity, the fill walk and k_ipairs_sort into the caller's rows.
+int rt_instance_pairs_device(rt_ctx* c, size_t n, const void* d_irefs4, uint32_t cull_mask, uint32_t flags, void* d_offsets, void* d_pairs4, size_t capacity,
+                             void* hip_stream) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const std::string name = "rt_instance_pairs_device";
+  { int w = instance_pairs_arguments(c, name, n, cull_mask, flags, d_pairs4, capacity); if (w) return w; }
+  if (n) {
+    if (!d_irefs4 || !d_offsets) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null record/offset pointers");
+    if (((uintptr_t)d_irefs4 & 15u) || ((uintptr_t)d_offsets & 7u) || ((uintptr_t)d_pairs4 & 15u))
+      return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": records and pairs must be 16-byte aligned, offsets 8-byte aligned");
+    { int w = check_device_pointers(c, name, "records, offsets and pairs", {d_irefs4, d_offsets, d_pairs4}); if (w) return w; }
+  }
+  Query q; q.walk = Walk::InstancePairs; q.n = n; q.records = d_irefs4; q.cull_mask = cull_mask; q.pairs_above = (flags & RT_INSTANCE_PAIRS_ABOVE) != 0u;
+  q.list = true; q.offsets = d_offsets; q.ids = d_pairs4; q.capacity = capacity;
+  return device_query(c, q, hip_stream);
+}
+
+// The blocking host form, as rt_overlap_boxes_list is to its device call: the records (16 B each), then the pairs (16 B each, copied in
+// first so that the rows the call does not write come back as they were), then the offsets.
+int rt_instance_pairs(rt_ctx* c, size_t n, const rt_inst_ref* irefs, uint32_t cull_mask, uint32_t flags, uint64_t* offsets, rt_inst_ref* pairs, size_t capacity,
+                      int counting, rt_stats* stats) {
+  if (!c) return RT_ERR_INVALID_ARGUMENT;
+  const std::string name = "rt_instance_pairs";
+  { int w = instance_pairs_arguments(c, name, n, cull_mask, flags, pairs, capacity); if (w) return w; }
+  if ((!irefs || !offsets) && n) return fail(c, RT_ERR_INVALID_ARGUMENT, name + ": null record/offset pointers");
+  const size_t rec_bytes = n * sizeof(rt_inst_ref), pair_bytes = capacity * sizeof(rt_inst_ref), off_bytes = (n + 1) * sizeof(uint64_t);
+  Query q; q.walk = Walk::InstancePairs; q.n = n; q.cull_mask = cull_mask; q.pairs_above = (flags & RT_INSTANCE_PAIRS_ABOVE) != 0u; q.list = true; q.capacity = capacity;
+  q.counting = counting != 0;
+  return blocking_query(c, q, irefs, rec_bytes, rec_bytes + pair_bytes + off_bytes,
+                        {{&Query::ids, rec_bytes, pairs, pair_bytes, true}, {&Query::offsets, rec_bytes + pair_bytes, offsets, off_bytes}}, stats);
 }
 
 namespace {

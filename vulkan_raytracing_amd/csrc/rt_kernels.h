@@ -290,6 +290,21 @@ void launch_pairs_collide(const SceneDev& sc, const void* irefs, const unsigned 
                           const LaunchCfg& cfg, hipStream_t s);
 void launch_pairs_refs(const void* irefs, const uint32_t* word, uint32_t stride, uint32_t n, bool keep_radius, void* refs, int32_t* src_prims, hipStream_t s);
 void launch_pairs_first(const uint32_t* first_p, const void* ids, uint32_t n, void* first4, hipStream_t s);
+// rt_instance_pairs_device (kernels_ipairs.inc; DESIGN.md §5 "Instance broad phase"): the instances whose canonical boxes come within a
+// record's margin of its source's, as rows of rt_inst_ref records in CSR form.
+//   boxes   two float4 per instance of sc into `boxes` (the canonical box and its flags), from the n_meshes entries of the scene's device
+//           mesh table (TlasMeshDev)
+//   size    the count walk: counts[n], the rows' lengths (launch_list_scan makes the offsets of them)
+//   fill    the fill walk: row i at pairs[offsets[i] .. offsets[i + 1]) if offsets[i + 1] <= capacity, in ascending `against`, then
+//           k_ipairs_sort over the rows longer than RT_LIST_INSERT_MAX.  work: 1 + n words of scratch, as for launch_overlap_list
+// inst_scale (launch_closest_scale fills it first: word 0 bounds every box's widening), chunk cursor, counters (counting: node visits
+// and exact box tests) and spill area as for launch_overlap.
+void launch_ipairs_boxes(const SceneDev& sc, const void* mesh_table, uint32_t n_meshes, float4* boxes, hipStream_t s);
+void launch_ipairs_size(const SceneDev& sc, const void* irefs, const float4* boxes, const float* inst_scale, uint32_t cull_mask, bool above, uint32_t* counts, uint32_t n,
+                        int32_t* ovf_stack, uint32_t* counters, bool counting, const LaunchCfg& cfg, hipStream_t s);
+void launch_ipairs_fill(const SceneDev& sc, const void* irefs, const float4* boxes, const float* inst_scale, uint32_t cull_mask, bool above,
+                        const unsigned long long* offsets, void* pairs, uint64_t capacity, uint32_t* work, uint32_t n, int32_t* ovf_stack, uint32_t* counters,
+                        bool counting, const LaunchCfg& cfg, hipStream_t s);
 // rt_shade_rays_device: k_ray_ingest replaces k_raygen for the caller's n rays (32 bytes each, o.xyz, w3, d.xyz, tmax; sample id = record
 // index): sky colours of the rays that miss the TLAS and (0, 0, 0, 0) for invalid records into f.sample_color, the others into bounce queue 0
 // (workgroup b appends to shard b % 8: f.shard_cap >= 256 * ceil(ray_ingest_block_count(n) / 8)).  f.counters must be zero.

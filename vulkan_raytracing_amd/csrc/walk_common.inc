@@ -7,6 +7,7 @@
 //    launch of walk_nearest.inc, the overlap walks (k_overlap_boxes, k_collide_triangles, k_refs_collide, k_list_*) those of
 //    walk_overlap.inc.  What stays in such a walk's own file is its shape: the record and its validity, the form the node test reads,
 //    the node test (nearest), the canonical leaf test, the result words beside the hit record, and the register budget switch.
+//  * k_ipairs_size and k_ipairs_fill (kernels_ipairs.inc) walk the TLAS only, a record's box against the instances' boxes.
 // The frame kernels and k_trace have a stack of their own (the fast_step row) and use none of this.
 
 // The per-lane stack: STACK2_LDS entries in the block's LDS array (entry e at stk[e * 64]), deeper ones in the query's spill area

@@ -133,8 +133,14 @@ __device__ __forceinline__ F3 ambient_of(const SceneDev& sc, uint32_t mat) {
 // non-temporal hint so that it does not push the acceleration structure out of the 4-MB L2 of its XCD (experiment: -DRT_NT_STREAMS).
 typedef float rt_v4f __attribute__((ext_vector_type(4)));
 #ifndef RT_NT_STREAMS
-#define RT_NT_STREAMS 1   /* bit 0: loads (default), bit 1: stores, bit 2: the cube-map taps */
+/* bit 0: loads (default), bit 1: stores, bit 2: the cube-map taps, bit 3: the jitter table, bit 4: the finished pixels (default).
+   Bits 1 and 2 measured slower in round 3 (a queue's consumer is the next kernel; the cube map is re-read), bit 3 in round 8 (+1.9 %:
+   the frames in flight read the SAME table, so it is not a read-once stream for the chip), bit 4 faster (-1.8 %); profiles/r08_experiments.txt. */
+#define RT_NT_STREAMS 17
 #endif
+typedef float rt_v2f __attribute__((ext_vector_type(2)));
+typedef uint32_t rt_v2u __attribute__((ext_vector_type(2)));
+typedef rt_v2u rt_v2u_a4 __attribute__((aligned(4)));   // two adjacent 4-byte words at 4-byte alignment: still one global_load_dwordx2
 __device__ __forceinline__ float4 ld_stream(const float4* p) {
   if (RT_NT_STREAMS & 1) { const rt_v4f v = __builtin_nontemporal_load(reinterpret_cast<const rt_v4f*>(p)); return make_float4(v.x, v.y, v.z, v.w); }
   return *p;
@@ -144,6 +150,11 @@ __device__ __forceinline__ void st_stream(float4* p, float4 v) {
   else *p = v;
 }
 __device__ __forceinline__ int ld_stream(const int* p) { return (RT_NT_STREAMS & 1) ? __builtin_nontemporal_load(p) : *p; }
+// the jitter table: 8 bytes per sample, read once per frame by k_raygen (bit 3)
+__device__ __forceinline__ float2 ld_stream(const float2* p) {
+  if (RT_NT_STREAMS & 8) { const rt_v2f v = __builtin_nontemporal_load(reinterpret_cast<const rt_v2f*>(p)); return make_float2(v.x, v.y); }
+  return *p;
+}
 __device__ __forceinline__ void st_stream(int* p, int v) { if (RT_NT_STREAMS & 2) __builtin_nontemporal_store(v, p); else *p = v; }
 __device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 __device__ __forceinline__ uint32_t prefix_rank(uint64_t mask) {  // # set bits below this lane
@@ -322,7 +333,7 @@ __device__ __forceinline__ float div255(float x) {
 // Cube-map lookup (LINEAR on a cube view, RGBA8 UNORM, src/main.cpp:2393-2406) — same arithmetic as oracle sample_sky.
 // Footprint texels that fall off the selected face come from the neighbouring face (Vulkan cube map edge handling); the
 // tap beyond a corner is the mean of the other three.  Only ~1/W of all lookups touch an edge, so that path lives in its
-// own function and the common path stays four plain loads.
+// own function and the common path is two 8-byte loads, one per footprint row.
 struct SkyTap { int layer, x, y; };
 __device__ __forceinline__ SkyTap sky_neighbour(int layer, int x, int y, int W) {
   const int S = 2 * x + 1 - W, T = 2 * y + 1 - W;
@@ -381,8 +392,19 @@ __device__ __forceinline__ F3 sample_sky(const SceneDev& sc, F3 r) {
     if (RT_NT_STREAMS & 4) { const uint32_t w = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(sc.sky) + i); uchar4 r; r.x = w & 255u; r.y = (w >> 8) & 255u; r.z = (w >> 16) & 255u; r.w = w >> 24; return r; }
     return sc.sky[i];
   };
-  const uchar4 a = tap(i00 == SKY_CORNER ? 0u : i00), b = tap(i10 == SKY_CORNER ? 0u : i10);
-  const uchar4 c = tap(i01 == SKY_CORNER ? 0u : i01), d = tap(i11 == SKY_CORNER ? 0u : i11);
+  // off the edges the two taps of a footprint row are neighbours in memory: 8 bytes, 4-byte aligned (x0 may be odd), ONE load per row
+  // (x0 + 1 < W and y0 + 1 < H: a pair ends on its row's last texel at the latest, the second pair on the layer's)
+  auto pair = [&](uint32_t i, uchar4& lo, uchar4& hi) {
+    const rt_v2u_a4* p = reinterpret_cast<const rt_v2u_a4*>(reinterpret_cast<const uint32_t*>(sc.sky) + i);
+    const rt_v2u w = (RT_NT_STREAMS & 4) ? __builtin_nontemporal_load(p) : *p;
+    lo.x = w.x & 255u; lo.y = (w.x >> 8) & 255u; lo.z = (w.x >> 16) & 255u; lo.w = w.x >> 24;
+    hi.x = w.y & 255u; hi.y = (w.y >> 8) & 255u; hi.z = (w.y >> 16) & 255u; hi.w = w.y >> 24;
+  };
+  uchar4 a, b, c, d;
+  if (edge) {
+    a = tap(i00 == SKY_CORNER ? 0u : i00); b = tap(i10 == SKY_CORNER ? 0u : i10);
+    c = tap(i01 == SKY_CORNER ? 0u : i01); d = tap(i11 == SKY_CORNER ? 0u : i11);
+  } else { pair(i00, a, b); pair(i01, c, d); }
   float c00x = (float)a.x, c00y = (float)a.y, c00z = (float)a.z, c10x = (float)b.x, c10y = (float)b.y, c10z = (float)b.z;
   float c01x = (float)c.x, c01y = (float)c.y, c01z = (float)c.z, c11x = (float)d.x, c11y = (float)d.y, c11z = (float)d.z;
   if (edge) {
@@ -405,7 +427,12 @@ __device__ __forceinline__ F3 sample_sky(const SceneDev& sc, F3 r) {
 __device__ __forceinline__ void store_pixel(const FrameDev& f, uint32_t p, float4 px) {
   if (f.out_rgba8) {
     auto q = [](float v) -> unsigned char { v = fminf(fmaxf(v, 0.0f), 1.0f); return (unsigned char)(v * 255.0f + 0.5f); };
-    reinterpret_cast<uchar4*>(f.out)[p] = f.out_rgba8 == 2 ? make_uchar4(q(px.z), q(px.y), q(px.x), q(px.w)) : make_uchar4(q(px.x), q(px.y), q(px.z), q(px.w));
+    const uchar4 c = f.out_rgba8 == 2 ? make_uchar4(q(px.z), q(px.y), q(px.x), q(px.w)) : make_uchar4(q(px.x), q(px.y), q(px.z), q(px.w));
+    // (bit 4: no kernel of the frame reads a finished pixel again)
+    if (RT_NT_STREAMS & 16) __builtin_nontemporal_store((uint32_t)c.x | (uint32_t)c.y << 8 | (uint32_t)c.z << 16 | (uint32_t)c.w << 24, reinterpret_cast<uint32_t*>(f.out) + p);
+    else reinterpret_cast<uchar4*>(f.out)[p] = c;
+  } else if (RT_NT_STREAMS & 16) {
+    rt_v4f w; w.x = px.x; w.y = px.y; w.z = px.z; w.w = px.w; __builtin_nontemporal_store(w, reinterpret_cast<rt_v4f*>(f.out + p));
   } else {
     f.out[p] = px;
   }
@@ -857,7 +884,7 @@ __global__ __launch_bounds__(256) void k_raygen(SceneDev sc, FrameDev f, Uniform
       // chain jitter -> direction -> four taps of a sample does not overlap the next sample's.)
       float4 col = make_float4(0.f, 0.f, 0.f, 0.f);
       if (live) {
-        const float2 uv = f.jitter != nullptr ? f.jitter[jitter_index(tile1, i, spp, lane)] : sample_uv(x, fy, i, spp, f.width, f.height);
+        const float2 uv = f.jitter != nullptr ? ld_stream(&f.jitter[jitter_index(tile1, i, spp, lane)]) : sample_uv(x, fy, i, spp, f.width, f.height);
         const F3 d = normalize3(fma3(2.5f, fwd, fma3(uv.y, up, mul3(right, uv.x))));
         const F3 c = sample_sky(sc, mk3(d.x, d.y, -d.z));
         col = make_float4(c.x, c.y, c.z, 1.0f);
@@ -870,7 +897,7 @@ __global__ __launch_bounds__(256) void k_raygen(SceneDev sc, FrameDev f, Uniform
       // more samples than a workgroup holds: the first wave of the tile's first workgroup walks all of them, a lane per pixel
       if (threadIdx.y != 0u || blockIdx.z != 0u || x >= (uint32_t)f.width || ly >= (uint32_t)f.rows) return;
       for (uint32_t k = 0; k < spp; k++) {
-        const float2 uv = f.jitter != nullptr ? f.jitter[jitter_index(tile1, k, spp, lane)] : sample_uv(x, fy, k, spp, f.width, f.height);
+        const float2 uv = f.jitter != nullptr ? ld_stream(&f.jitter[jitter_index(tile1, k, spp, lane)]) : sample_uv(x, fy, k, spp, f.width, f.height);
         const F3 d = normalize3(fma3(2.5f, fwd, fma3(uv.y, up, mul3(right, uv.x))));
         const F3 c = sample_sky(sc, mk3(d.x, d.y, -d.z));
         r += c.x; g += c.y; b += c.z; al += 1.0f;
@@ -889,7 +916,7 @@ __global__ __launch_bounds__(256) void k_raygen(SceneDev sc, FrameDev f, Uniform
   float4 miss_col = make_float4(0.f, 0.f, 0.f, 0.f);
   if (live) {
     // (the table of this frame size and shard layout, when the host has one: rt_api jitter tables)
-    const float2 uv = f.jitter != nullptr ? f.jitter[jitter_index(tile1, i, spp, lane)] : sample_uv(x, frame_row(f, ly), i, spp, f.width, f.height);
+    const float2 uv = f.jitter != nullptr ? ld_stream(&f.jitter[jitter_index(tile1, i, spp, lane)]) : sample_uv(x, frame_row(f, ly), i, spp, f.width, f.height);
     const float ux = uv.x, uy = uv.y;
     F3 right = mk3(u.right[0], u.right[1], u.right[2]), up = mk3(u.up[0], u.up[1], u.up[2]), fwd = mk3(u.forward[0], u.forward[1], u.forward[2]);
     if (f.batch_k > 1) { right = mk3(bt.right[fi][0], bt.right[fi][1], bt.right[fi][2]); up = mk3(bt.up[fi][0], bt.up[fi][1], bt.up[fi][2]); fwd = mk3(bt.forward[fi][0], bt.forward[fi][1], bt.forward[fi][2]); }
